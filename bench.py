@@ -9,16 +9,24 @@ N = 1 runs in this process.  N > 1 without torchrun's environment starts N ranks
 
 One "step" = train_D + train_G (reference train.py:398-523) on one synthetic JetNet-30-like batch
 resident in HBM, fresh generator noise and dropout masks every step, optimizer updates included.
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times the K steps,
+writes the outputs of the last step if ``--dump-outputs DIR`` is given and prints the line: nothing else.
+``--full`` adds the legs that take runs of their own, as extra objects on the line:
   roofline      -- the dominant kernel's algorithmic FLOP (or byte) rate vs the MI355X peak, from HIP-event timings
                    taken in this process on the launch stream
   cpu_baseline  -- the CPU oracle (own port of the reference step) timed on this box's host cores
                    on a bounded sample (rank 0, N = 1 only)
-  secondary     -- (default run, --gpus 1) the two other single-GPU workloads of BASELINE.json, 20 warm-up + 100 timed
-                   iterations each in the same process: GAPT B = 512 (config 4) and MPGAN N = 150, B = 16 (config 5's
+  secondary     -- (headline workload, --gpus 1) the two other single-GPU workloads of BASELINE.json, 20 warm-up + 100
+                   timed iterations each in the same process: GAPT B = 512 (config 4) and MPGAN N = 150, B = 16 (config 5's
                    per-GPU shard), each with its own value / ms_per_step / roofline
+(``--no-roofline``, ``--no-cpu-baseline``, ``--no-secondary`` leave single legs out of a ``--full`` run.)
 Other workloads (``--model gapt``, ``--particles 150 --batch 16``) can also be run as the line itself: same fields under
 their own metric name.
+
+``--dump-outputs DIR``: after the timed steps, what the last step left to its caller -- both networks' parameters and
+RMSprop square averages (flat, in ``module.parameters()`` order) and the two losses -- as ``DIR/<name>.npy`` (float32;
+about 6 MB at the headline sizes).  Inputs (weights, data, noise and dropout streams) are seeded, so the same arguments
+give the same inputs in every run and two builds can be compared output for output.
 """
 import argparse
 import json
@@ -121,6 +129,10 @@ def parse_args():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the GAPT B=512 and MPGAN N=150 B=16 legs that follow the headline run at --gpus 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline, CPU-baseline and secondary-workload legs (off: the timed steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
 
 
@@ -187,10 +199,12 @@ def main():
             out["config"]["rccl_version"] = None
     out["config"]["graph_collectives"] = bool(ts.graph_collectives)
     out["config"]["graphs_per_step"] = len(ts._graphs) if ts._graphs else 0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(ts, args.dump_outputs)
 
     # ------------------------------------------------------------------ roofline of the dominant kernel
     # rank 0 only, after the timed region, with the collectives switched off (the other ranks are not taking part)
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         ts.world, ts.pg = 1, None
         out["roofline"], out["kernels"] = roofline(torch, ts, args.model, dev, measured_traffic=headline)
         log("roofline leg done", out["roofline"]["kernel"], out["roofline"]["frac"])
@@ -199,7 +213,7 @@ def main():
     # ------------------------------------------------------------------ the other single-GPU workloads of BASELINE.json
     # (config 4: GAPT B = 512; config 5's per-GPU shard: MPGAN N = 150, B = 16), same process, after the headline legs:
     # their own value / ms_per_step / roofline under one extra key -- metric, value and config above stay the headline's
-    if rank == 0 and world == 1 and headline and not args.no_secondary:
+    if rank == 0 and world == 1 and headline and args.full and not args.no_secondary:
         out["secondary"] = {}
         for key, (model2, B2, N2) in {"gapt_n30_b512": ("gapt", 512, 30), "mpgan_n150_b16": ("mpgan", 16, 150)}.items():
             torch.cuda.empty_cache()
@@ -240,7 +254,7 @@ def main():
         log("secondary", "mpgan_n30_b256_gp", f"{o3['value']:.0f} jets/s")
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N = 1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(torch, args.model, N, B)
 
     if rank == 0:
@@ -248,6 +262,17 @@ def main():
     if world > 1:
         dist.barrier()  # rank 0 arrives after its extra legs; nobody tears the group down under it
         dist.destroy_process_group()
+
+
+def dump_outputs(ts, out_dir):
+    """The state the last step left to its caller (before any further leg runs the step again), as float32 ``.npy`` files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"D_params": ts.fD.flat, "G_params": ts.fG.flat, "D_rmsprop_sq": ts.fD.sq, "G_rmsprop_sq": ts.fG.sq,
+              "D_loss": ts.D_loss.reshape(1), "G_loss": ts.G_loss.reshape(1)}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
+    log(f"outputs of the last step written to {out_dir}: {', '.join(arrays)}")
 
 
 LOSS_NAME = {"ls": "LSGAN", "og": "BCE GAN", "w": "Wasserstein", "hinge": "hinge"}

@@ -33,7 +33,14 @@ def pytest_collection_modifyitems(config, items):
 
 
 def load_golden(name):
-    return dict(np.load(os.path.join(GOLDEN, name), allow_pickle=False))
+    """``tests/golden/<name>``, merged with its parts ``<stem>.part1.npz``, ... where a fixture is larger than one committed
+    file may be (tests/gen_golden.py: save_parts)."""
+    d = dict(np.load(os.path.join(GOLDEN, name), allow_pickle=False))
+    stem, k = os.path.splitext(name)[0], 1
+    while os.path.isfile(os.path.join(GOLDEN, f"{stem}.part{k}.npz")):
+        d.update(np.load(os.path.join(GOLDEN, f"{stem}.part{k}.npz"), allow_pickle=False))
+        k += 1
+    return d
 
 
 def summarize(name, t):

@@ -12,6 +12,7 @@ summaries (sum, L2 norm, 64 sampled entries per tensor) to keep the fixtures sma
 gradients and outputs are stored in full.
 
 Run:  python tests/gen_golden.py          (no-op with a message if /root/reference is absent)
+      python tests/gen_golden.py fixtures (published weights, drop-in records: see ``fixtures``)
 """
 import json
 import os
@@ -341,7 +342,7 @@ def main():
                 rec[f"{bname}_dx"] = x.grad.numpy()
                 for k, p in blk.named_parameters():
                     rec[f"{bname}_grad__{k}"] = summarize(k, p.grad)
-            np.savez_compressed(os.path.join(OUT, f"gapt_blocks_{name}_{dt_name}.npz"), **rec)
+            save_parts(f"gapt_blocks_{name}_{dt_name}", rec)
             print("gapt blocks", name, dt_name)
 
         # 4b. SAB with LayerNorm (layer_norm=True: gapt/model.py:118-120, :131-136), fp64 only
@@ -556,5 +557,104 @@ def main():
     return 0
 
 
+PART_BYTES = 900 * 1024   # a committed file stays below 1 MiB: larger fixtures are split into <stem>.npz, <stem>.part1.npz, ...
+
+
+def save_parts(stem, arrays):
+    """``arrays`` (name -> ndarray, in order) as compressed ``.npz`` parts of at most ~PART_BYTES of raw data each;
+    ``conftest.load_golden(stem + ".npz")`` merges them back."""
+    parts, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        if cur and size + v.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += v.nbytes
+    parts.append(cur)
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(OUT, stem + (".npz" if i == 0 else f".part{i}.npz")), **p)
+
+
+def fixtures():
+    """Fixtures that let the drop-in and published-weight tests run without the reference:
+      * published_mp_{g,q,t}_weights.npz (+ parts): the published generator checkpoints' state dicts (fp32);
+      * reference_setup.json: class, repr and state-dict shapes of the four networks the reference's ``setup_training``
+        builds from its default arguments with OUR packages installed as ``mpgan`` / ``gapt``;
+      * reference_augment.npz: the reference's ``augment`` / ``mask_manual`` outputs on a stored input under fixed seeds.
+    Runs in a process of its own (``python tests/gen_golden.py fixtures``): ``mpgan`` must resolve to our package here."""
+    import importlib.util
+    if not os.path.isdir(REF):
+        print(f"reference not found at {REF}; nothing generated")
+        return 0
+    import mpgan_amd
+    os.makedirs(OUT, exist_ok=True)
+
+    for jets in ("g", "q", "t"):
+        sd = torch.load(os.path.join(REF, "trained_models", f"mp_{jets}", "G_best_epoch.pt"), map_location="cpu")
+        save_parts(f"published_mp_{jets}_weights", {k: v.numpy() for k, v in sd.items()})
+        print("weights", jets, sum(v.numel() for v in sd.values()))
+
+    saved = {k: sys.modules.get(k) for k in ("mpgan", "gapt", "setup_training")}
+    mpgan_amd.install_as_reference_packages()
+    sys.path.insert(0, REF)
+    try:
+        import setup_training as st  # reference
+        argv = sys.argv
+        sys.argv = ["train.py", "--name", "t", "--no-save-zero"]
+        try:
+            args = st.parse_args()
+        finally:
+            sys.argv = argv
+        args.device = "cpu"
+        args = st.process_args(args) if hasattr(st, "process_args") else args
+        nets = {"mpgan_G": st.setup_mpgan(args, gen=True), "mpgan_D": st.setup_mpgan(args, gen=False),
+                "gapt_G": st.setup_gapt(args, gen=True), "gapt_D": st.setup_gapt(args, gen=False)}
+    finally:
+        sys.path.remove(REF)
+        for k, v in saved.items():
+            if v is None:
+                sys.modules.pop(k, None)
+            else:
+                sys.modules[k] = v
+    rec = {k: {"class": f"{type(m).__module__}.{type(m).__qualname__}", "repr": repr(m),
+               "state_dict": {n: list(t.shape) for n, t in m.state_dict().items()}} for k, m in nets.items()}
+    with open(os.path.join(OUT, "reference_setup.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+
+    def load(name, path):
+        spec = importlib.util.spec_from_file_location(name, path)
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        return mod
+    ref_aug = load("_ref_augment", os.path.join(REF, "mpgan", "augment.py"))
+    ref_mask = load("_ref_mask_utils", os.path.join(REF, "mpgan", "mask_utils.py"))
+
+    class Args:   # (tests/test_reference_dropin_cpu.py: _Args)
+        device = "cpu"
+        num_hits = 30
+        aug_r90 = aug_f = aug_t = aug_s = True
+        translate_ratio = 0.125
+        translate_pn_ratio = 0.05
+        scale_sd = 0.125
+        mask_real_only = False
+        mask_exp = False
+    X = (seeded((16, 30, 3), 31) * 0.3).float()
+    out = {"X": X.numpy()}
+    for p in (0.3, 0.8, 1):
+        torch.manual_seed(11)
+        out[f"augment_p{p}"] = ref_aug.augment(Args(), X.clone(), p).numpy()
+    for fn in ("rand_flip", "rand_90_rotation", "rand_translate", "rand_translate_per_node", "rand_scale"):
+        torch.manual_seed(5)
+        out[fn] = getattr(ref_aug, fn)(Args(), X.clone()).numpy()
+    for tag, flags in (("plain", {}), ("mask_exp", {"mask_exp": True}), ("mask_real_only", {"mask_real_only": True})):
+        a = Args()
+        for k, v in flags.items():
+            setattr(a, k, v)
+        out[f"mask_manual_{tag}"] = ref_mask.mask_manual(a, X, -0.2).numpy()
+    np.savez_compressed(os.path.join(OUT, "reference_augment.npz"), **out)
+    print("reference setup and augment records written")
+    return 0
+
+
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(fixtures() if sys.argv[1:] == ["fixtures"] else main())

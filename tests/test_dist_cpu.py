@@ -99,7 +99,7 @@ import pytest
 
 
 @pytest.mark.parametrize("world,port", [(2, 29517), (4, 29541)])
-def test_multi_rank_trainstep_equals_global_batch(world, port):
+def test_multi_rank_trainstep_equals_global_batch(world, port, monkeypatch):
     """world 2 and 4 (the driver's scaling points below 8; eight ranks of 1 jet each would only repeat the protocol)."""
     mgr = mp.get_context("spawn").Manager()
     out = mgr.dict()
@@ -110,6 +110,9 @@ def test_multi_rank_trainstep_equals_global_batch(world, port):
         assert torch.equal(d0, dr) and torch.equal(g0, gr_)   # broadcast + identical averaged updates on every rank
         assert torch.equal(gr0, grr)                          # the all-reduced (summed) gradient buffer
     sys.path.insert(0, ROOT)
+    from mpgan_amd import train
+    # (_run puts the torch RMSprop in place of the fused step: in THIS process only for the length of the test)
+    monkeypatch.setattr(train.FlatParams, "step", _torch_rmsprop)
     sD, sG, sgr, sl, _ = _run(1, 0, None)
     assert torch.allclose(sD, d0, rtol=1e-4, atol=1e-6), float((sD - d0).abs().max())
     assert torch.allclose(sG, g0, rtol=1e-4, atol=1e-6), float((sG - g0).abs().max())
@@ -193,13 +196,13 @@ class ToyD2(torch.nn.Module):
         return torch.sigmoid(self.net(x.reshape(x.shape[0], -1)))
 
 
-def test_gradient_penalty_host_logic_on_a_plain_torch_discriminator():
+def test_gradient_penalty_host_logic_on_a_plain_torch_discriminator(monkeypatch):
     """``TrainStep(gp_lambda=...)`` with a discriminator that is plain torch (twice differentiable as it is): the D step's
     gradients are those of  D_loss + gp_lambda * mean_b (||dD/dx_b|| - 1)^2  (train.py:286-324) written out directly --
     the host logic of the penalty (interpolation, detached generated jets, create_graph, what is added to the loss)."""
     sys.path.insert(0, ROOT)
     from mpgan_amd import train
-    train.FlatParams.step = _torch_rmsprop
+    monkeypatch.setattr(train.FlatParams, "step", _torch_rmsprop)   # (restored when the test ends: later tests use the fused step)
     torch.manual_seed(5)
     G, D = ToyG(), ToyD2()
     B = 6

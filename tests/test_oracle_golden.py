@@ -93,15 +93,17 @@ def test_manifests():
     assert sum(int(np.prod(v)) for v in m["gapt_D"].values()) == 62785
 
 
+def published_weights(jets):
+    """The published ``trained_models/mp_<jets>/G_best_epoch.pt`` generator state dict (fp32 tensors, checkpoint key order)."""
+    return {k: torch.from_numpy(v) for k, v in load_golden(f"published_mp_{jets}_weights.npz").items()}
+
+
 @pytest.mark.parametrize("jets", ["g", "q", "t"])
 def test_published_weights(jets):
-    """Published generator weights: the oracle reproduces the reference's outputs.  The
-    weights themselves are not committed, so this runs only where /root/reference exists."""
-    path = f"/root/reference/trained_models/mp_{jets}/G_best_epoch.pt"
-    if not os.path.isfile(path):
-        pytest.skip("reference checkpoints not present on this machine")
+    """Published generator weights: the oracle reproduces the reference's outputs.  The weights are the published
+    checkpoints' state dicts, stored under tests/golden/ (tests/gen_golden.py: fixtures)."""
     g = load_golden(f"published_mp_{jets}.npz")
-    sd = torch.load(path, map_location="cpu")
+    sd = published_weights(jets)
     assert {k: tuple(v.shape) for k, v in sd.items()} == T.mpgan_param_shapes(True)
     out = oracle.mpgen_forward(sd, torch.from_numpy(g["noise"]), torch.from_numpy(g["labels"]))
     assert rel_err(out.numpy(), g["out"]) < 3e-5

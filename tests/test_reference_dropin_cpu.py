@@ -1,49 +1,21 @@
-"""Drop-in boundary, checked against the reference where it can be imported
-(the build container; skipped on the GPU box, where /root/reference does not exist):
+"""Drop-in boundary, checked against records of the reference stored under tests/golden/
+(tests/gen_golden.py: fixtures, generated where the reference can be imported):
 
-* ``install_as_reference_packages()`` makes the reference's ``setup_training`` build OUR classes, with its own
-  default arguments, and the import line of the reference's ``train.py:7`` resolves;
+* the reference's ``setup_training`` with ``install_as_reference_packages()`` in force builds OUR classes, with its own
+  default arguments (reference_setup.json: class, structure and state-dict shapes of the four networks it built), and the
+  import line of the reference's ``train.py:7`` resolves;
 * the published ``trained_models/mp_g`` generator checkpoint loads (all keys matched);
-* ``augment`` / ``mask_manual`` reproduce the reference functions under the same RNG state.
+* ``augment`` / ``mask_manual`` reproduce the reference functions under the same RNG state (reference_augment.npz).
 """
+import json
 import os
 import sys
 import types
 
-import pytest
 import torch
 
-REF = "/root/reference"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
-
-
-@pytest.fixture
-def as_reference_packages():
-    import mpgan_amd
-    saved = {k: sys.modules.get(k) for k in ("mpgan", "gapt", "setup_training")}
-    mpgan_amd.install_as_reference_packages()
-    sys.path.insert(0, REF)
-    sys.modules.pop("setup_training", None)
-    try:
-        yield
-    finally:
-        sys.path.remove(REF)
-        for k, v in saved.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
-
-
-def _default_args(setup_training, extra=()):
-    argv = sys.argv
-    sys.argv = ["train.py", "--name", "t", "--no-save-zero"] + list(extra)
-    try:
-        args = setup_training.parse_args()
-    finally:
-        sys.argv = argv
-    args.device = "cpu"
-    return setup_training.process_args(args) if hasattr(setup_training, "process_args") else args
+from conftest import GOLDEN, load_golden
+from test_oracle_golden import published_weights
 
 
 def test_train_py_import_line_resolves():
@@ -66,27 +38,24 @@ def test_train_py_import_line_resolves():
                 sys.modules[k] = v
 
 
-@needs_ref
-def test_reference_setup_builds_our_classes_and_loads_published_weights(as_reference_packages):
-    import setup_training
+def test_reference_setup_builds_our_classes_and_loads_published_weights():
+    """What the reference's ``setup_mpgan`` / ``setup_gapt`` built from their default arguments with our packages installed
+    (recorded) is what ``train.default_mpgan`` / ``default_gapt`` build: the same classes, module structure and state-dict
+    shapes; the published generator checkpoint loads into it with every key matched."""
     import mpgan_amd
-    try:
-        args = _default_args(setup_training)
-    except SystemExit:
-        pytest.skip("reference argument parser needs options this environment cannot supply")
-    G = setup_training.setup_mpgan(args, gen=True)
-    D = setup_training.setup_mpgan(args, gen=False)
+    from mpgan_amd import train
+    with open(os.path.join(GOLDEN, "reference_setup.json")) as f:
+        rec = json.load(f)
+    G, D = train.default_mpgan(30, device="cpu")
+    Gg, Dg = train.default_gapt(30, device="cpu")
     assert type(G) is mpgan_amd.MPGenerator and type(D) is mpgan_amd.MPDiscriminator
-    Gg = setup_training.setup_gapt(args, gen=True)
-    Dg = setup_training.setup_gapt(args, gen=False)
     assert type(Gg) is mpgan_amd.GAPT_G and type(Dg) is mpgan_amd.GAPT_D
-    ck = os.path.join(REF, "trained_models", "mp_g", "G_best_epoch.pt")
-    if not os.path.isfile(ck):
-        cands = [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(REF, "trained_models", "mp_g")) for f in fs
-                 if f.endswith(".pt")]
-        assert cands, "no published generator checkpoint found"
-        ck = cands[0]
-    res = G.load_state_dict(torch.load(ck, map_location="cpu"))
+    for key, m in (("mpgan_G", G), ("mpgan_D", D), ("gapt_G", Gg), ("gapt_D", Dg)):
+        r = rec[key]
+        assert f"{type(m).__module__}.{type(m).__qualname__}" == r["class"], key
+        assert repr(m) == r["repr"], key
+        assert {k: list(v.shape) for k, v in m.state_dict().items()} == r["state_dict"], key
+    res = G.load_state_dict(published_weights("g"))
     assert not res.missing_keys and not res.unexpected_keys
 
 
@@ -101,37 +70,24 @@ class _Args:
     mask_exp = False
 
 
-@needs_ref
 def test_augment_and_mask_manual_match_reference():
-    import importlib.util
     from mpgan_amd.mpgan import augment as ours, mask_manual as ours_mask
-
-    def load(name, path):
-        spec = importlib.util.spec_from_file_location(name, path)
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        return mod
-    ref_aug = load("_ref_augment", os.path.join(REF, "mpgan", "augment.py"))
-    ref_mask = load("_ref_mask_utils", os.path.join(REF, "mpgan", "mask_utils.py"))
+    ref = load_golden("reference_augment.npz")
     args = _Args()
-    X = torch.randn(16, 30, 3) * 0.3
+    X = torch.from_numpy(ref["X"])
     for p in (0.3, 0.8, 1):
         torch.manual_seed(11)
         a = ours.augment(args, X.clone(), p)
-        torch.manual_seed(11)
-        b = ref_aug.augment(args, X.clone(), p)
-        assert torch.allclose(a, b, atol=1e-6), p
+        assert torch.allclose(a, torch.from_numpy(ref[f"augment_p{p}"]), atol=1e-6), p
     for fn in ("rand_flip", "rand_90_rotation", "rand_translate", "rand_translate_per_node", "rand_scale"):
         torch.manual_seed(5)
         a = getattr(ours, fn)(args, X.clone())
-        torch.manual_seed(5)
-        b = getattr(ref_aug, fn)(args, X.clone())
-        assert torch.allclose(a, b, atol=1e-6), fn
-    for flags in ({}, {"mask_exp": True}, {"mask_real_only": True}):
+        assert torch.allclose(a, torch.from_numpy(ref[fn]), atol=1e-6), fn
+    for tag, flags in (("plain", {}), ("mask_exp", {"mask_exp": True}), ("mask_real_only", {"mask_real_only": True})):
         a2 = _Args()
         for k, v in flags.items():
             setattr(a2, k, v)
-        assert torch.equal(ours_mask(a2, X, -0.2), ref_mask.mask_manual(a2, X, -0.2)), flags
+        assert torch.equal(ours_mask(a2, X, -0.2), torch.from_numpy(ref[f"mask_manual_{tag}"])), flags
 
 
 def test_augment_without_reference():

@@ -11,11 +11,11 @@ python3 -c "import sys; sys.path.insert(0, '$R'); from mpgan_amd import _lib; pr
 cd /tmp && export TMPDIR=/tmp
 out=$R/gpurun_out/final/bench_stats
 rm -rf $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o b -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $R/gpurun_out/final/bench_under_rocprof.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o b -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > ${out%/*}/bench_under_rocprof.log 2>&1 || exit 1
 python3 $R/tools/prof_summary.py $out 40 > $R/gpurun_out/final/bench_stats_summary.txt
 out=$R/gpurun_out/final/gapt_stats
 rm -rf $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o b -- python3 $R/bench.py --model gapt --steps 20 --warmup 5 --no-cpu-baseline > $R/gpurun_out/final/gapt_under_rocprof.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o b -- python3 $R/bench.py --full --model gapt --steps 20 --warmup 5 --no-cpu-baseline > ${out%/*}/gapt_under_rocprof.log 2>&1 || exit 1
 python3 $R/tools/prof_summary.py $out 40 > $R/gpurun_out/final/gapt_stats_summary.txt
 echo "stats done"
 KERNELS=("edge_fwd1_fn_kernel<0" "edge_fwd1_fn_kernel<2" "edge_bwd1_fn_kernel<0, true" "edge_bwd1_fn_kernel<0, false" "edge_bwd1_fn_kernel<2, true" "edge_bwd1_fn_kernel<2, false" "edge_dw12_kernel<0" "edge_dw12_kernel<2" chain2_kernel gemm_group_kernel)

@@ -7,6 +7,6 @@ timeout -k 10 1000 python -m pytest tests -m gpu -q -x --durations=15 > $O/pytes
 tail -25 $O/pytest.txt; cp gpurun_out/parity_bars.txt $O/ 2>/dev/null
 if [ $rc -ge 124 ]; then echo "pytest killed rc=$rc"; exit $rc; fi
 echo "pytest rc=$rc"
-timeout -k 10 900 python bench.py > $O/bench.json 2> $O/bench.log; rc2=$?
+timeout -k 10 900 python bench.py --full > $O/bench.json 2> $O/bench.log; rc2=$?
 tail -3 $O/bench.log; head -c 1500 $O/bench.json
 exit $(( rc + rc2 ))

@@ -11,7 +11,7 @@ if [ $rc2 -ge 124 ]; then echo "pytest killed rc=$rc2"; exit $rc2; fi
 echo "pytest (two-term) rc=$rc2"
 for rep in 1 2; do
   for tt in 0 1; do
-    MPG_FWD_TWO_TERM=$tt timeout -k 10 300 python bench.py --steps 300 --warmup 20 --no-secondary --no-cpu-baseline > $O/bench_tt${tt}_$rep.json 2> $O/bench_tt${tt}_$rep.log || exit 1
+    MPG_FWD_TWO_TERM=$tt timeout -k 10 300 python bench.py --full --steps 300 --warmup 20 --no-secondary --no-cpu-baseline > $O/bench_tt${tt}_$rep.json 2> $O/bench_tt${tt}_$rep.log || exit 1
     python - <<PY
 import json; d=json.load(open("$O/bench_tt${tt}_$rep.json")); print("two_term=$tt rep $rep:", round(d["value"]), "jets/s", d["roofline"]["kernel"], round(d["roofline"]["frac"],4), d["kernels"]["mpg_edge_fwd_fn"])
 PY

@@ -1,7 +1,7 @@
 #!/bin/bash
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; O=gpurun_out/r06_w128; mkdir -p $O
 run() { name=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --steps 300 --warmup 20 --no-secondary --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.log || { tail -3 $O/bench_$name.log; return 1; }
+  env "$@" timeout -k 10 300 python bench.py --full --steps 300 --warmup 20 --no-secondary --no-cpu-baseline > $O/bench_$name.json 2> $O/bench_$name.log || { tail -3 $O/bench_$name.log; return 1; }
   python -c "import json; d=json.load(open('$O/bench_$name.json')); k=d['kernels']; print('$name: %.0f jets/s %.4f ms  wgrad %.1f us  reduce %.1f us' % (d['value'], d['ms_per_step'], k['mpg_gemm_wgrad_group']['avg_ms']*1e3, k['mpg_splitk_reduce_group_dw']['avg_ms']*1e3))"
 }
 for rep in 1 2; do
