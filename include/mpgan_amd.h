@@ -503,6 +503,27 @@ int mpg_adam(float* p, float* g, float* m, float* v, float* step, uint64_t n, fl
 int mpg_adadelta(float* p, float* g, float* v, float* u, uint64_t n, float lr, float rho, float eps,
                  float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, void* stream);
 
+/* ---- evaluation metrics --------------------------------------------------------------------------
+ * mpg_jet_obs: per-jet observables of the metrics the reference's evaluate (train.py:543-606) draws from jetnet / energyflow:
+ * jetnet.utils.jet_features (for w1m) and the EFPs of jetnet.evaluation.w1efp (energyflow ("n==",4), ("d==",4), ("p==",1)).
+ * Particle p of jet b is (eta_rel, phi_rel, pt_rel) at jets[b*ld_jet + p*ld_part + 0..2] ([n, N, 3] or [n, N, 4] in place);
+ * padding particles have pt_rel = 0, anywhere in the jet.  Each particle is a massless four-vector:
+ *   kin[b] = (pt, eta, phi, mass) of their sum: pt = hypot(px, py), eta = asinh(pz / pt) (0 when pt = 0), phi = atan2(py, px),
+ *            mass^2 = sum_{i,j} pT_i pT_j (cosh(eta_i - eta_j) - cos(phi_i - phi_j)) (not E^2 - |p|^2, which cancels in fp32);
+ *   efp[b, k] (flags bit 0), hadronic measure, beta = 1: theta_ij = sqrt(d_eta^2 + d_phi^2), z_i = pT_i / sum pT (flags bit 1)
+ *            or pT_i; sums over all index tuples; w = Theta z, u = (Theta o Theta) z, M = Theta diag(z) Theta:
+ *            k = 0  a=b-c-d          sum_{b,c} z_b u_b theta_bc z_c w_c
+ *            k = 1  a-b=c-d          sum_{b,c} z_b w_b theta_bc^2 z_c w_c
+ *            k = 2  3-star, 1 double sum_c z_c u_c w_c^2
+ *            k = 3  triangle+pendant sum_{a,c} z_a z_c w_c theta_ac M_ac
+ *            k = 4  4-cycle          sum_{a,c} z_a z_c M_ac^2
+ *            (this column order is the project's, not necessarily energyflow's).  A jet whose pT sum is 0 gives zeros.
+ * 1 <= N <= MPG_JET_OBS_MAX_N (else -1).  fp32; fixed-order reductions: the same input gives the same bits. */
+#define MPG_JET_OBS_MAX_N 160
+#define MPG_JET_OBS_EFP 1
+#define MPG_JET_OBS_NORMED 2
+int mpg_jet_obs(const float* jets, int ld_jet, int ld_part, int n, int N, int flags, float* kin, float* efp, void* stream);
+
 /* mpg_normal: out[i] = mean + std * z_i with z ~ N(0, 1) -- the generator's input noise (get_gen_noise, train.py:100-141:
  * torch.randn * sd) from a counter-based stream keyed by the device-resident 64-bit `seed` (the dropout seed, advanced
  * once per iteration) and a site `tag`: a captured hipGraph draws fresh values on every replay, and torch's generator

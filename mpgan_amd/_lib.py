@@ -247,6 +247,7 @@ SIGNATURES = {
     "mpg_normal": (C.c_int, [_fp, C.c_uint64, _fp, C.c_uint32, C.c_float, C.c_float, C.c_void_p]),
     "mpg_normal_rank_mask": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_uint32, C.c_float, C.c_float, _fp, C.c_int, _fp, _fp,
                                        C.c_void_p]),
+    "mpg_jet_obs": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_void_p]),
 }
 
 

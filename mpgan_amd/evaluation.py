@@ -1,0 +1,275 @@
+"""Evaluation metrics of a training run without jetnet / energyflow: W1 of the jet mass (``w1m``), of the particle features
+(``w1p``) and of five energy-flow polynomials (``w1efp``), as the reference's ``evaluate`` (train.py:543-606) appends them
+to its ``losses`` dict after every epoch.
+
+The names follow ``jetnet.utils`` / ``jetnet.evaluation`` so a caller can swap those modules for this one.  Jets are
+``[n, N, >=3]`` un-normalised ``(eta_rel, phi_rel, pt_rel[, mask])`` with ``pt_rel = 0`` on padding particles (what
+``gen.generate_jets`` returns).  The per-jet observables run on the GPU through ``mpg_jet_obs`` (fp32) for CUDA tensors,
+and through a torch fp64 statement of the same formulas for CPU tensors and numpy arrays; the W1 distances are computed
+in fp64 on the inputs' device.
+
+The sampling semantics of ``w1m`` / ``w1p`` / ``w1efp`` (per batch ``rng.choice(len(real), k)`` then
+``rng.choice(len(gen), k)``, with replacement; mean and population std over batches; ``exclude_zeros`` drops particles
+whose feature norm is 0) are restated from memory of jetnet 0.2; jetnet is not available to check them against.  The same
+holds for jetnet's EFP normalisation: ``normed=True`` (z_i = pT_i / sum pT) is energyflow's documented default, not a
+checked property of ``jetnet.utils.efps``.
+
+EFP columns (``efps``), hadronic measure with beta = 1 (theta_ij = sqrt(d_eta^2 + d_phi^2)), sums over all index tuples,
+w = Theta z, u = (Theta o Theta) z, M = Theta diag(z) Theta -- the five connected multigraphs with 4 vertices and 4 edges
+(energyflow's ``("n==", 4), ("d==", 4), ("p==", 1)`` set), in this project's order:
+
+    0  a=b-c-d (end edge doubled)     sum_{b,c} z_b u_b theta_bc z_c w_c
+    1  a-b=c-d (middle edge doubled)  sum_{b,c} z_b w_b theta_bc^2 z_c w_c
+    2  3-star, one edge doubled       sum_c z_c u_c w_c^2
+    3  triangle + pendant             sum_{a,c} z_a z_c w_c theta_ac M_ac
+    4  4-cycle                        sum_{a,c} z_a z_c M_ac^2
+
+FPD (energyflow's ``d<=4`` set, whose membership and order cannot be checked here) and FPND (jetnet's pretrained
+ParticleNet) are not provided.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+
+NUM_EFPS = 5
+MAX_PARTICLES = 160          # MPG_JET_OBS_MAX_N of include/mpgan_amd.h
+_FLAG_EFP, _FLAG_NORMED = 1, 2
+_CPU_CHUNK = 1 << 22         # fp64 pair elements per chunk of the CPU path (jets x N x N)
+
+
+def _as_tensor(x):
+    return (torch.from_numpy(np.ascontiguousarray(x)), True) if isinstance(x, np.ndarray) else (x, False)
+
+
+def _out(t, numpy_in):
+    return t.cpu().numpy() if numpy_in else t
+
+
+# ------------------------------------------------------------------------------------- per-jet observables
+def _obs_cuda(jets: torch.Tensor, with_efps: bool, normed: bool):
+    n, N = jets.shape[0], jets.shape[1]
+    if jets.dtype != torch.float32 or jets.stride(2) != 1:
+        jets = jets.float().contiguous()
+    kin = torch.empty((n, 4), device=jets.device, dtype=torch.float32)
+    efp = torch.empty((n, NUM_EFPS), device=jets.device, dtype=torch.float32) if with_efps else None
+    if n == 0:
+        return kin, efp
+    flags = (_FLAG_EFP if with_efps else 0) | (_FLAG_NORMED if normed else 0)
+    with torch.cuda.device(jets.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mpg_jet_obs(jets.data_ptr(), jets.stride(0), jets.stride(1), n, N, flags, kin.data_ptr(),
+                                          None if efp is None else efp.data_ptr(), stream), "mpg_jet_obs")
+    return kin, efp
+
+
+def _obs_cpu(jets: torch.Tensor, with_efps: bool, normed: bool):
+    """fp64 statement of mpg_jet_obs, chunked over jets (the pair tensors are jets x N x N)."""
+    x = jets[..., :3].double()
+    n, N = x.shape[0], x.shape[1]
+    kin = torch.empty((n, 4), dtype=torch.float64)
+    efp = torch.empty((n, NUM_EFPS), dtype=torch.float64) if with_efps else None
+    step = max(1, _CPU_CHUNK // max(1, N * N))
+    for s in range(0, n, step):
+        eta, phi, pt = x[s:s + step].unbind(-1)
+        px, py, pz = (pt * phi.cos()).sum(1), (pt * phi.sin()).sum(1), (pt * eta.sinh()).sum(1)
+        jpt = torch.hypot(px, py)
+        deta = eta[:, :, None] - eta[:, None, :]
+        dphi = phi[:, :, None] - phi[:, None, :]
+        # cosh(d_eta) - cos(d_phi) = 2 sinh^2(d_eta / 2) + 2 sin^2(d_phi / 2)
+        pair = 2 * ((0.5 * deta).sinh() ** 2 + (0.5 * dphi).sin() ** 2)
+        m2 = torch.einsum("bi,bij,bj->b", pt, pair, pt)
+        kin[s:s + step, 0] = jpt
+        kin[s:s + step, 1] = torch.where(jpt > 0, torch.asinh(pz / torch.where(jpt > 0, jpt, 1.0)), 0.0)
+        kin[s:s + step, 2] = torch.atan2(py, px)
+        kin[s:s + step, 3] = m2.clamp(min=0).sqrt()
+        if with_efps:
+            if normed:
+                spt = pt.sum(1, keepdim=True)
+                z = pt / torch.where(spt != 0, spt, 1.0)
+            else:
+                z = pt
+            th = (deta ** 2 + dphi ** 2).sqrt()
+            w = torch.einsum("bij,bj->bi", th, z)
+            u = torch.einsum("bij,bj->bi", th * th, z)
+            M = torch.einsum("bij,bj,bjk->bik", th, z, th)
+            zw = z * w
+            efp[s:s + step, 0] = torch.einsum("bi,bij,bj->b", z * u, th, zw)
+            efp[s:s + step, 1] = torch.einsum("bi,bij,bj->b", zw, th * th, zw)
+            efp[s:s + step, 2] = (z * u * w * w).sum(1)
+            efp[s:s + step, 3] = torch.einsum("bi,bij,bj->b", z, th * M, zw)
+            efp[s:s + step, 4] = torch.einsum("bi,bij,bj->b", z, M * M, z)
+    return kin, efp
+
+
+def _observables(jets, with_efps: bool, normed: bool = True):
+    """(kin [n, 4] = (pt, eta, phi, mass), efp [n, 5] or None) on the jets' device; numpy in, numpy out."""
+    t, numpy_in = _as_tensor(jets)
+    if t.dim() != 3 or t.shape[2] < 3:
+        raise ValueError(f"expected jets [n, N, >=3] = (eta_rel, phi_rel, pt_rel, ...), got {tuple(t.shape)}")
+    if t.is_cuda:
+        if not 1 <= t.shape[1] <= MAX_PARTICLES:
+            raise ValueError(f"mpg_jet_obs takes 1 <= N <= {MAX_PARTICLES} particles per jet (got {t.shape[1]})")
+        kin, efp = _obs_cuda(t, with_efps, normed)
+    else:
+        kin, efp = _obs_cpu(t, with_efps, normed)
+    return _out(kin, numpy_in), (None if efp is None else _out(efp, numpy_in))
+
+
+def jet_features(jets) -> Dict[str, object]:
+    """``jetnet.utils.jet_features``: ``{"pt", "eta", "phi", "mass"}`` of each jet's summed massless four-vectors."""
+    kin, _ = _observables(jets, with_efps=False)
+    return {k: kin[:, i] for i, k in enumerate(("pt", "eta", "phi", "mass"))}
+
+
+def efps(jets, normed: bool = True):
+    """``[n, 5]`` EFPs of each jet in the column order of the module docstring (``jetnet.utils.efps`` with the
+    ``("n==", 4), ("d==", 4), ("p==", 1)`` set).  ``normed``: z_i = pT_i / sum pT (else pT_i)."""
+    return _observables(jets, with_efps=True, normed=normed)[1]
+
+
+# ------------------------------------------------------------------------------------- W1
+def wasserstein_1d(u, v) -> torch.Tensor:
+    """``scipy.stats.wasserstein_distance(u, v)`` (the integral of |CDF_u - CDF_v|) in fp64 on the inputs' device:
+    a 0-d tensor.  Samples may differ in size and hold ties."""
+    u = torch.as_tensor(u).reshape(-1).double()
+    v = torch.as_tensor(v, device=u.device).reshape(-1).double()
+    us, vs = u.sort().values, v.sort().values
+    allv = torch.cat([us, vs]).sort().values
+    deltas = allv[1:] - allv[:-1]
+    ucdf = torch.searchsorted(us, allv[:-1], right=True).double() / us.numel()
+    vcdf = torch.searchsorted(vs, allv[:-1], right=True).double() / vs.numel()
+    return ((ucdf - vcdf).abs() * deltas).sum()
+
+
+def _draws(rng, n1: int, n2: int, k: int, device):
+    rng = np.random if rng is None else rng
+    i1 = rng.choice(n1, k)
+    i2 = rng.choice(n2, k)
+    return torch.from_numpy(np.asarray(i1)).to(device), torch.from_numpy(np.asarray(i2)).to(device)
+
+
+def _batched_w1(x1: torch.Tensor, x2: torch.Tensor, num_eval_samples: int, num_batches: int, rng, per_column: bool):
+    """W1 of ``num_batches`` random draws of ``x1`` against ``x2`` ([n, C] observables): [num_batches, C] float64."""
+    out = []
+    for _ in range(num_batches):
+        i1, i2 = _draws(rng, x1.shape[0], x2.shape[0], num_eval_samples, x1.device)
+        a, b = x1[i1], x2[i2]
+        out.append(torch.stack([wasserstein_1d(a[:, c], b[:, c]) for c in range(a.shape[1])]) if per_column
+                   else wasserstein_1d(a, b).reshape(1))
+    return torch.stack(out).cpu().numpy()
+
+
+def _mean_std(w1s: np.ndarray, average: bool, return_std: bool):
+    means, stds = np.mean(w1s, axis=0), np.std(w1s, axis=0)
+    if average:
+        means, stds = np.mean(means), np.linalg.norm(stds)
+    return (means, stds) if return_std else means
+
+
+def _obs_tensor(x, like=None):
+    t, _ = _as_tensor(x)
+    return t.to(like.device) if like is not None else t
+
+
+def w1m(jets1, jets2, num_eval_samples: int = 50000, num_batches: int = 5, return_std: bool = True, rng=None):
+    """``jetnet.evaluation.w1m``: W1 of the jet mass, mean (and std) over ``num_batches`` draws of
+    ``num_eval_samples`` jets from each set.  ``rng``: anything with numpy's ``choice`` (default: ``np.random``)."""
+    m1 = _obs_tensor(jet_features(_obs_tensor(jets1))["mass"])
+    m2 = _obs_tensor(jet_features(_obs_tensor(jets2, m1))["mass"])
+    w1s = _batched_w1(m1[:, None], m2[:, None], num_eval_samples, num_batches, rng, per_column=False)[:, 0]
+    return (float(np.mean(w1s)), float(np.std(w1s))) if return_std else float(np.mean(w1s))
+
+
+def w1p(jets1, jets2, mask1=None, mask2=None, exclude_zeros: bool = True, num_particle_features: int = 0,
+        num_eval_samples: int = 50000, num_batches: int = 5, average_over_features: bool = True, return_std: bool = True,
+        rng=None):
+    """``jetnet.evaluation.w1p``: W1 of each particle feature over the particles of ``num_eval_samples`` drawn jets per
+    set and batch.  ``exclude_zeros`` drops particles whose feature vector has norm 0; ``mask1`` / ``mask2`` [n, N]
+    select particles instead.  ``average_over_features=False``: per-feature means and stds (as the reference calls it)."""
+    j1 = _obs_tensor(jets1)
+    j2 = _obs_tensor(jets2, j1)
+    F = num_particle_features if num_particle_features > 0 else j1.shape[2]
+    j1, j2 = j1[:, :, :F], j2[:, :, :F]
+    if mask1 is not None or mask2 is not None:
+        mask1 = _obs_tensor(mask1, j1).bool().reshape(j1.shape[:2]) if mask1 is not None else torch.ones(j1.shape[:2], dtype=torch.bool, device=j1.device)
+        mask2 = _obs_tensor(mask2, j1).bool().reshape(j2.shape[:2]) if mask2 is not None else torch.ones(j2.shape[:2], dtype=torch.bool, device=j1.device)
+    elif exclude_zeros:
+        mask1 = j1.double().norm(dim=2) != 0
+        mask2 = j2.double().norm(dim=2) != 0
+    w1s = []
+    for _ in range(num_batches):
+        i1, i2 = _draws(rng, j1.shape[0], j2.shape[0], num_eval_samples, j1.device)
+        p1 = j1[i1][mask1[i1]] if mask1 is not None else j1[i1].reshape(-1, F)
+        p2 = j2[i2][mask2[i2]] if mask2 is not None else j2[i2].reshape(-1, F)
+        if p1.shape[0] == 0 or p2.shape[0] == 0:
+            w1s.append(np.full(F, np.inf))
+        else:
+            w1s.append(torch.stack([wasserstein_1d(p1[:, f], p2[:, f]) for f in range(F)]).cpu().numpy())
+    return _mean_std(np.stack(w1s), average_over_features, return_std)
+
+
+def w1efp(jets1, jets2, use_particle_masses: bool = False, num_eval_samples: int = 50000, num_batches: int = 5,
+          average_over_efps: bool = True, return_std: bool = True, efp_jobs=None, normed: bool = True, rng=None):
+    """``jetnet.evaluation.w1efp`` with its default EFP set: W1 of each of the five EFPs (``efps``).  Massless particles
+    only (``use_particle_masses=True`` raises); ``efp_jobs`` is accepted and unused (the EFPs run on the jets' device)."""
+    if use_particle_masses:
+        raise NotImplementedError("mpgan_amd.evaluation computes EFPs of massless particles only")
+    e1 = _obs_tensor(efps(_obs_tensor(jets1), normed=normed))
+    e2 = _obs_tensor(efps(_obs_tensor(jets2, e1), normed=normed))
+    w1s = _batched_w1(e1, e2, num_eval_samples, num_batches, rng, per_column=True)
+    return _mean_std(w1s, average_over_efps, return_std)
+
+
+# ------------------------------------------------------------------------------------- the reference's evaluate
+def evaluate(losses: dict, real_jets, gen_jets, jet_type: str, num_particles: int = 30, num_w1_eval_samples: int = 10000,
+             num_cov_mmd_eval_samples: int = 100, num_fpnd_eval_samples: int = 50000, fpnd_batch_size: int = 16,
+             efp_jobs=None, real_efps=None, gen_efps=None, rng=None):
+    """train.py:543-606: append ``w1p`` (means(3) then stds(3)), ``w1m`` ([mean, std]) and ``w1efp`` (means(5) then
+    stds(5)) to the lists of ``losses`` that hold those keys, with ``len(real_jets) // num_w1_eval_samples`` batches.
+    ``"fpd"`` is left alone (the reference's evaluate leaves it too); ``"fpnd"`` raises ``NotImplementedError``.
+    The draws come from ``rng`` (default ``np.random``) in the reference's order: w1p, w1m, w1efp."""
+    if "fpnd" in losses:
+        raise NotImplementedError("fpnd needs jetnet's pretrained ParticleNet, which mpgan_amd does not provide")
+    num_batches = len(real_jets) // num_w1_eval_samples
+    if "w1p" in losses:
+        m, s = w1p(real_jets, gen_jets, exclude_zeros=True, num_eval_samples=num_w1_eval_samples, num_batches=num_batches,
+                   average_over_features=False, return_std=True, rng=rng)
+        losses["w1p"].append(np.concatenate((m, s)))
+    if "w1m" in losses:
+        m, s = w1m(real_jets, gen_jets, num_eval_samples=num_w1_eval_samples, num_batches=num_batches, return_std=True,
+                   rng=rng)
+        losses["w1m"].append(np.array([m, s]))
+    if "w1efp" in losses:
+        m, s = w1efp(real_jets, gen_jets, use_particle_masses=False, num_eval_samples=num_w1_eval_samples,
+                     num_batches=num_batches, average_over_efps=False, return_std=True, efp_jobs=efp_jobs, rng=rng)
+        losses["w1efp"].append(np.concatenate((m, s)))
+    return losses
+
+
+def evaluate_generator(G: torch.nn.Module, real_jets, jet_type: str, num_samples: int = 50000,
+                       keys: Sequence[str] = ("w1p", "w1m"), losses: Optional[dict] = None, num_particles: int = 30,
+                       num_w1_eval_samples: int = 10000, labels: Optional[torch.Tensor] = None, model: str = "mpgan",
+                       model_args: Optional[dict] = None, batch_size: int = 4096, rng=None) -> dict:
+    """Generate ``num_samples`` jets with ``gen.generate_jets`` and ``evaluate`` them against ``real_jets`` ([n, N, >=3]
+    un-normalised), all on G's device.  ``labels`` (num_particles / N per generated jet) default to the multiplicities of
+    the real jets, taken in order and repeated as needed -- the reference conditions on the test set's ``jet_data``
+    (train.py:712-723).  Returns ``losses`` (a new ``{key: []}`` for ``keys`` when not given) with one entry appended."""
+    from .gen import generate_jets
+    device = next(G.parameters()).device
+    real, _ = _as_tensor(real_jets)
+    real = real.to(device)
+    N = real.shape[1]
+    if labels is None:
+        idx = torch.arange(num_samples, device=device) % real.shape[0]
+        labels = ((real[idx, :, 2] != 0).sum(1).float() * np.float32(1.0 / N)).reshape(-1, 1)
+    gen_jets = generate_jets(G, num_samples, num_particles=N, labels=labels, jet_type=jet_type, model=model,
+                             model_args=model_args, batch_size=batch_size)
+    if losses is None:
+        losses = {k: [] for k in keys}
+    return evaluate(losses, real[..., :3], gen_jets, jet_type, num_particles=num_particles,
+                    num_w1_eval_samples=num_w1_eval_samples, rng=rng)
