@@ -14,7 +14,7 @@
 //     whose bounds check drops what must not be written, the dropout mode is a template parameter.
 //
 // The schedule itself lives in chain2_impl.h (c2_body): this file is the stand-alone kernel -- rows staged from memory --
-// and the entry point's shape table; edge_fwd2_impl.h runs the same body as the epilogue of the fused edge forward.
+// and the entry point's shape table; edge_fwd1_impl.h / edge_bwd1_impl.h run the same body as the epilogues of the fused edge kernels.
 #include "chain2_impl.h"
 #include "chain_int.h"
 #include <stdlib.h>

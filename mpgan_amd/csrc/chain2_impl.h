@@ -1,6 +1,6 @@
 // The schedule of chain2.hip as a device function, shared by the stand-alone kernel (chain2_kernel: rows staged from
-// memory) and by the fused edge forward (edge_fwd2_impl.h, FN: the node network fn runs as the epilogue of the workgroup
-// that has just aggregated its 32 receivers -- their rows are staged straight from the LDS reduction).
+// memory) and by the fused edge kernels' epilogues (edge_fwd1_impl.h, FN: the node network fn runs as the epilogue of the workgroup
+// that has just aggregated its 32 receivers -- their rows are staged straight from the LDS reduction; edge_bwd1_impl.h, EPI).
 // See chain2.hip for the description of the schedule itself.
 #pragma once
 #include "common.h"

@@ -1,6 +1,7 @@
-// mpg_edge_fwd (the fused edge network's forward: edge_fwd2_impl.h holds the kernel; this unit has the entry point and the
-// no-dropout variants, the variants with dropout are edge_fwd_d1.hip / edge_fwd_d2.hip so that the three parts of the
-// slow-to-compile template build side by side) and mpg_pack_weights (the weight images every fused kernel takes).
+// mpg_edge_fwd, the fused edge network's forward: the entry point.  Launches without edge scalars take the eight-wave kernel
+// (edge_fwd1_impl.h): this unit holds its no-dropout variants, edge_fwd_d1.hip / edge_fwd_d2.hip those with dropout, so that
+// the three parts of the slow-to-compile template build side by side.  Launches with edge scalars take the four-wave kernel
+// (edge_fwd2_impl.h): edge_fwd_q{0,1,2}.hip.  And mpg_pack_weights (the weight images every fused kernel takes).
 #include "edge_fwd1_impl.h"
 
 int mpg_edge_fwd_d1(const MpgEdgeFwd* p, hipStream_t st);   // edge_fwd_d1.hip: byte-threshold dropout
@@ -63,7 +64,7 @@ extern "C" int mpg_edge_fwd(const MpgEdgeFwd* p, void* stream) {
     if (p->stageE2 != nullptr && (long long)p->B * ((p->N + 31) / 32) * p->N * 10240LL > 0x7fffffffLL) return -7;
     hipStream_t st = (hipStream_t)stream;
 #ifdef MPG_SINGLE_VARIANT  // tools/ubench/fwd_bench.hip: one dropout mode, seconds to compile
-#ifdef MPG_FWD1   // (-DMPG_FWD1: the eight-wave form, edge_fwd1_impl.h)
+#ifdef MPG_FWD1   // (-DMPG_FWD1: the eight-wave form, edge_fwd1_impl.h; without it the four-wave one, no edge scalars)
     return f1_launch<MPG_SINGLE_VARIANT>(p, st);
 #else
     return f2_launch<MPG_SINGLE_VARIANT>(p, st);

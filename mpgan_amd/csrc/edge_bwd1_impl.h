@@ -14,10 +14,11 @@
 // rate: tools/ubench/valu_rate2.hip), and with 256 registers the accumulators are VGPRs the gates read in place: no
 // v_accvgpr_read / _write (a tenth of the four-wave kernel's instructions).  Peak registers: phase B  dacc 48 + accB 80 + the
 // first E2 fragments 12 + build 24; phase C  dacc 48 + dZ2 fragments 40 + accC 48 + ring 72.
-// Plain form only (no edge scalars, no epilogue chains): mpg_edge_bwd; mpg_edge_bwd_fn answers MPG_FN_NA in this mode and the
-// caller launches the chains itself.
+// Two kernels: edge_bwd1_kernel is what mpg_edge_bwd launches without edge scalars (with them: the four-wave kernel,
+// edge_bwd2_impl.h), edge_bwd1_fn_kernel -- the same body with epilogue chains, EPI below -- is what mpg_edge_bwd_fn launches.
 #pragma once
 #include "edge_bwd2_impl.h"
+#include "chain2_impl.h"
 #include <stdlib.h>
 
 #ifdef MPG_B1_STAMP   // diagnostic build (tools/ubench/bwd2_bench.hip): s_memtime per section of a wave's senders, summed per wave
@@ -34,8 +35,18 @@ static_assert(B1_NW * H1 * 4 == B2_C_BYTES, "one row of c per wave in the four-w
 static_assert(T3 * 4 * 64 == 3 * 512 && T1 * 4 * 64 == 512 + 256, "the prologue's register sets");
 static_assert(B1_NW * T1 * 16 * 64 * 4 <= B2_W_BYTES, "the final reduction reuses the weight area");
 
-// EPI / cdxp / cnxp: the epilogue chains of edge_bwd_body (the layer's dx chain and the lower layer's node-network input-gradient
-// chain on this workgroup's own jet), run by c2_body's eight-wave form
+// EPI: what the workgroup does BEHIND its data-gradient work, as an epilogue on its own 32 nodes (a whole jet per workgroup:
+// N <= 32, SC = 1 -- then the jet's rows of da AND dc are this workgroup's own stores):
+//   0  nothing;
+//   1 / 2 / 3  the layer's input gradient  dx = [da | dc] [W1a ; W1c] + dx(node path)  (the chain `cdxp`: mpg_chain's "dx from da | dc"
+//      call) and -- 1, 2, when `cnxp` has layers -- the NEXT-LOWER MPLayer's node-network input-gradient chain on those dx rows
+//      (the backward of its fn, mpgan/model.py:279, as mpg_chain takes it: dz2 = gate(V3^T dy), dz1 = gate(V2^T dz2),
+//      [dagg | dx] = V1^T dz1), with chain2's schedule in its eight-wave form (chain2_impl.h).  2: that chain's last rows are not
+//      whole 16-byte groups (a 195-column [dagg | dx]); 3: dx's own rows are not (3 features) and nothing follows.
+// A workgroup whose jet has few senders does this while the fullest jets' workgroups are still in their sender loops: the
+// launch is as long as its slowest workgroup, and the chains of most jets hide in its tail (measured for the forward's epilogue:
+// +2.8 %; as a PROLOGUE -- on every workgroup's critical path -- the same chain was 1.2 % slower than its own launch).
+static_assert(C2_LDS <= B2_LDS_BYTES, "the chains' buffers must fit the data-gradient kernel's LDS");
 template <int DROP, bool NEEDW, int EPI>
 MPG_DEV void edge_bwd1_body(const MpgEdgeBwd& p, const MpgChain* const cdxp = nullptr, const MpgChain* const cnxp = nullptr) {
     typedef f16x8 V;
@@ -181,10 +192,6 @@ MPG_DEV void edge_bwd1_body(const MpgEdgeBwd& p, const MpgChain* const cdxp = nu
 #ifdef MPG_B1_STAMP
     unsigned long long b1_acc[6] = {}, b1_t = __builtin_amdgcn_s_memtime();
     const unsigned long long b1_l0 = b1_t;
-#endif
-#ifdef MPG_B1_STAGGER   // experiment: waves 4..7 (the SIMD partners of waves 0..3) start this many s_sleep(16) (~1k clk each) late
-    if (w >= 4)
-        for (int t = 0; t < MPG_B1_STAGGER; ++t) __builtin_amdgcn_s_sleep(16);
 #endif
     for (int s = w; s < nvalid; s += B1_NW) {
         B1_STAMP(5)
@@ -442,8 +449,8 @@ MPG_DEV void edge_bwd1_body(const MpgEdgeBwd& p, const MpgChain* const cdxp = nu
         if (ii < p.N) *reinterpret_cast<float4*>(out + (size_t)ii * H1 + 32 * q + 8 * g + 4 * (ln >> 5)) = v;
     }
     if constexpr (EPI != 0) {
-        // ---- epilogue chains on this jet's nodes (edge_bwd2_impl.h): the rows of da (just written) and of dc (written sender by
-        //      sender in the loop, zeros for masked senders in the prologue) are this workgroup's own stores
+        // ---- epilogue chains on this jet's nodes.  The rows of da (just written above) and of dc (written sender by sender in
+        //      the loop, zeros for masked senders in the prologue) are this workgroup's own stores: ordered within the workgroup.
         const int m0 = b * p.N + rb * 32, nrows = min(32, p.N - rb * 32);
         {
             const MpgChain& c = *cdxp;
@@ -486,7 +493,7 @@ __global__ __launch_bounds__(512) void edge_bwd1_fn_kernel(const MpgEdgeBwd p, c
     edge_bwd1_body<DROP, NEEDW, EPI>(p, &cdx, &cnx);
 }
 
-// the epilogue forms of one dropout mode / NEEDW (edge_bwd_fn_*.hip); epi = 1, 2, 3 as in edge_bwd2_impl.h
+// the epilogue forms of one dropout mode / NEEDW (edge_bwd_fn_*.hip: one translation unit each); epi = 1, 2, 3 as above
 template <int D, bool NEEDW>
 int b1_launch_fn(const MpgEdgeBwd* p, const MpgChain* cdx, const MpgChain* cnx, int epi, hipStream_t st) {
     const int RB = (p->N + 31) / 32;

@@ -1,5 +1,9 @@
 // Backward of the fused edge network, data-gradient path (see edge_fwd2_impl.h for the forward and the chain layout).
 //
+// This header holds the FOUR-WAVE kernel, edge_bwd_kernel -- what mpg_edge_bwd launches when the edges carry scalars
+// (NQ = MPG_EDGE_SCALARS: edge_bwd2_q{0,1,2}.hip); it has no epilogue -- and the LDS plan and helpers it shares with the
+// eight-wave kernels of edge_bwd1_impl.h, which take every other launch (mpg_edge_bwd without edge scalars, mpg_edge_bwd_fn).
+//
 //   dZ3 = m_j * dagg_i * keep3 * phi'(Z3)      phi'(Z3) from the forward's saved sign words
 //   dE2 = W3'^T dZ3 ;  dZ2 = dE2 * keep2 * phi'(Z2)     phi'(Z2) from the SIGN of the E2 fragments the forward parked
 //   dE1 = W2'^T dZ2 ;  dZ1 = dE1 * keep1 * phi'(Z1) ;  da_i = sum_j dZ1 ;  dc_j = sum_i dZ1     (Z1 = a_i + c_j, one add)
@@ -33,7 +37,6 @@
 // the images' operand scales and 2^e), and gexp[(b, rb)] = e tells mpg_edge_dw the unit of the staged dZ2.
 #pragma once
 #include "edge_common.h"
-#include "chain2_impl.h"
 
 #ifndef MPG_B2EXP
 #define MPG_B2EXP 0  // experiment bits (tools/ubench/bwd2_bench.hip): 1 streamed fragments all from k-step 0 (L1 hits), 2 no parking stores
@@ -98,20 +101,8 @@ MPG_DEV f32x16 mma(const f16x8 a, const f16x8 b, const f32x16 c) { return __buil
 
 // DROP: 0 off, 1 byte mode, 2 bit mode (see common.h); NQ: edge scalars (0 or MPG_EDGE_SCALARS): Z1 = a_i + c_j + sum_q es wq[q],
 // and the kernel also returns des = dZ1 . wq[q] per edge and daq = sum_j es dZ1 per receiver
-// EPI: what the workgroup does BEHIND its data-gradient work, as an epilogue on its own 32 nodes (a whole jet per workgroup:
-// N <= 32, SC = 1 -- then the jet's rows of da AND dc are this workgroup's own stores):
-//   0  nothing;
-//   1 / 2 / 3  the layer's input gradient  dx = [da | dc] [W1a ; W1c] + dx(node path)  (the chain `cdx`: mpg_chain's "dx from da | dc"
-//      call) and -- 1, 2, when `cnx` has layers -- the NEXT-LOWER MPLayer's node-network input-gradient chain on those dx rows
-//      (the backward of its fn, mpgan/model.py:279, as mpg_chain takes it: dz2 = gate(V3^T dy), dz1 = gate(V2^T dz2),
-//      [dagg | dx] = V1^T dz1), with chain2's schedule (chain2_impl.h).  2: that chain's last rows are not whole 16-byte groups
-//      (a 195-column [dagg | dx]); 3: dx's own rows are not (3 features) and nothing follows.
-// A workgroup whose jet has few senders does this while the fullest jets' workgroups are still in their sender loops: the
-// launch is as long as its slowest workgroup, and the chains of most jets hide in its tail (measured for the forward's epilogue,
-// edge_fwd2_impl.h: +2.8 %; as a PROLOGUE -- on every workgroup's critical path -- the same chain was 1.2 % slower than its own launch).
-static_assert(C2_LDS <= B2_LDS_BYTES, "the chains' buffers must fit the data-gradient kernel's LDS");
-template <int DROP, bool NEEDW, int NQ, int EPI>
-MPG_DEV void edge_bwd_body(const MpgEdgeBwd& p, const MpgChain* const cdxp, const MpgChain* const cnxp) {
+template <int DROP, bool NEEDW, int NQ>
+MPG_DEV void edge_bwd_body(const MpgEdgeBwd& p) {
     constexpr int QB = NQ > 0 ? B2_Q_BYTES : B2_B2_BYTES;   // bytes between the a tile and the rows of c
     typedef f16x8 V;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -636,64 +627,13 @@ MPG_DEV void edge_bwd_body(const MpgEdgeBwd& p, const MpgChain* const cdxp, cons
             }
         });
     }
-    if constexpr (EPI != 0) {
-        // ---- epilogue chains on this jet's nodes.  The rows of da (just written above) and of dc (written sender by sender in
-        //      the loop, zeros for masked senders in the prologue) are this workgroup's own stores: ordered within the workgroup.
-        const int m0 = b * p.N + rb * 32, nrows = min(32, p.N - rb * 32);
-        {
-            const MpgChain& c = *cdxp;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __syncthreads();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            auto stage = [&](auto&& first_tile, auto&& bias_request, auto&& bias_store, const uint32_t s_lo, const uint32_t s_hi, const float ascale) {
-                c2_stage_rows<false, 12, 0>(c, m0, nrows, smem, first_tile, bias_request, bias_store, s_lo, s_hi, ascale);
-            };
-            c2_body<false, 12, 0, 0, 0, 0, 1, EPI == 3>(c, m0, nrows, smem, smem + C2_FB, reinterpret_cast<float*>(smem + 2 * C2_FB), stage);
-        }
-        if constexpr (EPI != 3) {
-            if (cnxp->nlayers > 0) {
-                const MpgChain& c = *cnxp;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __syncthreads();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                auto stage = [&](auto&& first_tile, auto&& bias_request, auto&& bias_store, const uint32_t s_lo, const uint32_t s_hi, const float ascale) {
-                    c2_stage_rows<false, 2, DROP>(c, m0, nrows, smem, first_tile, bias_request, bias_store, s_lo, s_hi, ascale);
-                };
-                c2_body<false, 2, 16, 16, DROP, 3, 0, EPI == 2>(c, m0, nrows, smem, smem + C2_FB, reinterpret_cast<float*>(smem + 2 * C2_FB), stage);
-            }
-        }
-    }
 }
 
 template <int DROP, bool NEEDW, int NQ>
-__global__ __launch_bounds__(256, 1) void edge_bwd_kernel(const MpgEdgeBwd p) { edge_bwd_body<DROP, NEEDW, NQ, 0>(p, nullptr, nullptr); }
+__global__ __launch_bounds__(256, 1) void edge_bwd_kernel(const MpgEdgeBwd p) { edge_bwd_body<DROP, NEEDW, NQ>(p); }
 
-template <int DROP, bool NEEDW, int EPI>
-__global__ __launch_bounds__(256, 1) void edge_bwd_fn_kernel(const MpgEdgeBwd p, const MpgChain cdx, const MpgChain cnx) {
-    edge_bwd_body<DROP, NEEDW, 0, EPI>(p, &cdx, &cnx);
-}
-
-// the epilogue forms of one dropout mode / NEEDW (edge_bwd_fn_*.hip: one translation unit each); epi = 1, 2, 3 as above
-template <int D, bool NEEDW>
-int b2_launch_fn(const MpgEdgeBwd* p, const MpgChain* cdx, const MpgChain* cnx, int epi, hipStream_t st) {
-    const int RB = (p->N + 31) / 32;
-    dim3 grid(p->B * RB), block(256);
-    MpgChain none = {};   // nlayers = 0: no second chain
-    if (cnx == nullptr) cnx = &none;
-#define MPG_B2FN(E)                                                                                        \
-    do {                                                                                                   \
-        MPG_ENSURE_LDS((edge_bwd_fn_kernel<D, NEEDW, E>), B2_LDS_BYTES);                                   \
-        hipLaunchKernelGGL((edge_bwd_fn_kernel<D, NEEDW, E>), grid, block, B2_LDS_BYTES, st, *p, *cdx, *cnx); \
-    } while (0)
-    if (epi == 1) MPG_B2FN(1);
-    else if (epi == 2) MPG_B2FN(2);
-    else MPG_B2FN(3);
-#undef MPG_B2FN
-    return (int)hipGetLastError();
-}
-
-// the NEEDW pair of one dropout mode (the three modes compile as separate translation units: edge_bwd2.hip, edge_bwd2_d1.hip,
-// edge_bwd2_d2.hip -- this template is slow to compile)
+// the NEEDW pair of one dropout mode and edge-scalar count (the library's are edge_bwd2_q{0,1,2}.hip, one translation unit per
+// dropout mode: this template is slow to compile; NQ = 0 is built by tools/ubench/bwd2_bench.hip only)
 template <int D, int NQ = 0>
 int b2_launch(const MpgEdgeBwd* p, hipStream_t st) {
     const int RB = (p->N + 31) / 32;

@@ -1,8 +1,8 @@
 // mpg_edge_bwd_fn: the fused edge network's data-gradient kernel WITH epilogue chains on every workgroup's own jet: the
 // layer's input gradient dx (from da | dc and the node path) and, optionally, the next-lower MPLayer's node-network
 // input-gradient chain on those rows -- the backward of mpgan/model.py:256-279 from dagg down to dx, and on through the fn of
-// the layer below, in one launch.  The kernel is edge_bwd2_impl.h's (EPI variants, chain2_impl.h's schedule for the chains);
-// its instantiations compile side by side in edge_bwd_fn_d{0,1,2}w{0,1}.hip.  This unit holds the entry point: argument
+// the layer below, in one launch.  The kernel is edge_bwd1_impl.h's edge_bwd1_fn_kernel (eight waves; EPI variants,
+// chain2_impl.h's schedule for the chains); its instantiations compile side by side in edge_bwd_fn_d{0,1,2}w{0,1}.hip.  This unit holds the entry point: argument
 // checks and the variant table.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

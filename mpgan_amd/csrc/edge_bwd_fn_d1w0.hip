@@ -1,4 +1,4 @@
-// The data-gradient kernel with its epilogue chains (mpg_edge_bwd_fn, see edge_bwd_fn.hip),
+// The eight-wave data-gradient kernel with its epilogue chains (mpg_edge_bwd_fn, see edge_bwd_fn.hip),
 // dropout mode 1, data path only.
 #include "edge_bwd1_impl.h"
 

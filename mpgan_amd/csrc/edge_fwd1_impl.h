@@ -1,4 +1,7 @@
 // Fused edge network, forward -- the EIGHT-WAVE form: two waves per SIMD, every wave one sender at a time.
+// Two kernels: edge_fwd1_kernel is what mpg_edge_fwd launches without edge scalars (with them: the four-wave kernel,
+// edge_fwd2_impl.h), edge_fwd1_fn_kernel -- the same body with the node network as epilogue, FN below -- is what mpg_edge_fwd_fn
+// launches.
 //
 // Same function, same memory formats (a | c rows in, agg rows, sign words and parked E2 fragments out) and the same
 // per-element arithmetic as edge_fwd2_impl.h (bias first, then per k-step lo*hi, hi*lo, hi*hi, k ascending); what changes
@@ -13,11 +16,8 @@
 // spends 500 of its 2,700 vector instructions per pair on v_accvgpr_read / _write).
 #pragma once
 #include "edge_fwd2_impl.h"
+#include "chain2_impl.h"
 #include <stdlib.h>
-
-#ifndef MPG_F1_STAGGER
-#define MPG_F1_STAGGER 0   // experiment (tools/ubench/fwd_bench.hip): waves 4..7 start this many s_sleep(16) (~1k clk each) late
-#endif
 
 #ifdef MPG_F1_STAMP   // diagnostic build (tools/ubench/fwd_bench.hip): s_memtime per section of a wave's senders, summed per wave
 __device__ unsigned long long f1_stamps[4096 * 8 * 8];
@@ -34,11 +34,7 @@ namespace {
 constexpr int F1_W2L_OFF = F2_LDS_BYTES, F1_W2L_N = 21;
 constexpr int F1_LDS_BYTES = F1_W2L_OFF + F1_W2L_N * 1024;
 static_assert(F1_LDS_BYTES <= 163840, "LDS plan exceeds 160 KiB");
-#ifdef MPG_F1_NO_W2L   // (experiment: everything of W2 streamed)
-constexpr bool f1_w2_in_lds(int, int) { return false; }
-#else
 constexpr bool f1_w2_in_lds(int m, int k) { return m < 3 || (m == 3 && k < 3); }
-#endif
 constexpr int f1_w2_slot(int m, int k) { return m < 3 ? m * (T1 * 2) + k : 3 * (T1 * 2) + k; }
 
 constexpr int F1_NW = 8;
@@ -51,8 +47,19 @@ MPG_DEV void fill_lds_dma8(void* dst, const void* src, int bytes, int tid) {
                                          (__attribute__((address_space(3))) void*)(static_cast<char*>(dst) + c * 1024), 16, 0, 0);
 }
 
-// FN / cp / cp2: as edge_fwd_body's (the node network and the next layer's a | c projection as the workgroup's epilogue), run
-// by c2_body's eight-wave form.
+// FN: 0 = agg goes to memory; 1 / 2 = the node network fn (mpgan/model.py:268-279: cat((agg, x)) -> three layers, the chain
+// ``cp``) runs as this workgroup's EPILOGUE on the 32 receivers it has just aggregated -- their agg rows never leave the CU as
+// operands (agg itself is still written when a backward will need it) -- with chain2's schedule in its eight-wave form
+// (chain2_impl.h; 2: the last layer's rows are not whole 16-byte groups).  With sender chunks (SC > 1) the workgroup that
+// finishes a (jet, receiver block) last adds the chunks' sums up and runs the epilogue (see below).
+constexpr int F2_RED_BYTES = 4 * T3 * 16 * 64 * 4;      // four waves' partial sums (the eight waves' are folded 8 -> 4 first): 98,304
+constexpr int F2_FN_FB0 = F2_RED_BYTES;                 // fn's input fragments are laid down beside them ...
+constexpr int F2_FN_BIAS = F2_FN_FB0 + C2_FB;           // ... its second fragment buffer over them, once they are dead
+static_assert(F2_FN_BIAS + C2_BIAS * 4 <= F2_LDS_BYTES, "fn's buffers must fit the edge kernel's LDS");
+
+// ``cp2`` (FN only; nlayers = 0: none): one more chain on the rows fn has just written -- the NEXT MPLayer's layer-1 node terms
+// a | c = [W1a ; W1c] y + [b1 ; 0] (its mpg_chain call, with fn's output rows as input) -- so that the next layer starts with
+// its edge launch.
 // LT: which of the hi/lo cross terms the two dense layers issue (the sender loop is bound by MFMA issue:
 // 270 MFMAs per sender in the three-term form, two waves to a SIMD).  0 = all three terms in both layers (fp32-level products).
 // Bit 0: layer 3 on TWO terms -- E2 as the ONE fp16 value that is parked anyway times W3 hi + lo (the E2 lo fragments, their
@@ -180,10 +187,6 @@ MPG_DEV void edge_fwd1_body(const MpgEdgeFwd& p, const MpgChain* const cp = null
         }
     };
     prefetch(w);
-#if MPG_F1_STAGGER
-    if (w >= 4)
-        for (int t = 0; t < MPG_F1_STAGGER; ++t) __builtin_amdgcn_s_sleep(16);
-#endif
 #ifdef MPG_F1_STAMP
     unsigned long long f1_acc[8] = {}, f1_t = __builtin_amdgcn_s_memtime();
     const unsigned long long f1_t0 = f1_t;
@@ -297,7 +300,7 @@ MPG_DEV void edge_fwd1_body(const MpgEdgeFwd& p, const MpgChain* const cp = null
             static_for<0, KS>([&](auto kc) {
                 MPG_CI(k, kc);
                 if constexpr (k + 1 < KS) load_a(std::integral_constant<int, k + 1>{});
-                const V bh0 = eh[k & 1], bl0 = el[k & 1];
+                const V bh0 = eh[k & 1];
                 static_for<0, T2>([&](auto mc) {
                     MPG_CI(m, mc);
                     auto slot = [&](auto slc) {
@@ -312,7 +315,7 @@ MPG_DEV void edge_fwd1_body(const MpgEdgeFwd& p, const MpgChain* const cp = null
                     if constexpr (f1_w2_in_lds(m, k)) a_h = whl[m & 1]; else a_h = wh[m];
                     const V a_l = wl[m];
                     acc[m] = f2_mma(a_l, bh0, acc[m]); slot(std::integral_constant<int, 3 * m + 0>{});
-                    if constexpr (!(LT & 2)) acc[m] = f2_mma(a_h, bl0, acc[m]);
+                    if constexpr (!(LT & 2)) acc[m] = f2_mma(a_h, el[k & 1], acc[m]);   // (el is not written with LT & 2)
                     slot(std::integral_constant<int, 3 * m + 1>{});
                     acc[m] = f2_mma(a_h, bh0, acc[m]);
                     if constexpr (k + 1 < KS) load_w(std::integral_constant<int, k + 1>{}, mc);
@@ -391,7 +394,7 @@ MPG_DEV void edge_fwd1_body(const MpgEdgeFwd& p, const MpgChain* const cp = null
                         ah[(k + 1) & 1] = lds_frag<V>(lb3hi, (m * KS + k + 1) * 1024);
                         al[(k + 1) & 1] = lds_frag<V>(lb3lo, (m * KS + k + 1) * 1024);
                     }
-                    const V bh0 = __builtin_bit_cast(V, e2h[k]), bl0 = __builtin_bit_cast(V, e2l[(LT & 1) ? 0 : k]);
+                    const V bh0 = __builtin_bit_cast(V, e2h[k]);
                     auto slot = [&](auto slc) {
                         MPG_CI(SL, slc);   // 3 KS - 3 slots: the last k-step's are left to the next tile's bias load
                         if constexpr (m > 0) f2_slot<16, 3 * KS - 3, SL>([&](auto uc) { epi3(std::integral_constant<int, m - 1>{}, uc); });
@@ -399,7 +402,7 @@ MPG_DEV void edge_fwd1_body(const MpgEdgeFwd& p, const MpgChain* const cp = null
                     };
                     const V a_h = ah[k & 1], a_l = al[k & 1];
                     a3[m & 1] = f2_mma(a_l, bh0, a3[m & 1]); slot(std::integral_constant<int, 3 * k + 0>{});
-                    if constexpr (!(LT & 1)) a3[m & 1] = f2_mma(a_h, bl0, a3[m & 1]);
+                    if constexpr (!(LT & 1)) a3[m & 1] = f2_mma(a_h, __builtin_bit_cast(V, e2l[k]), a3[m & 1]);   // (no lo fragments with LT & 1)
                     slot(std::integral_constant<int, 3 * k + 1>{});
                     a3[m & 1] = f2_mma(a_h, bh0, a3[m & 1]); slot(std::integral_constant<int, 3 * k + 2>{});
                     if constexpr (k == KS - 1 && m + 1 < T3) {
@@ -475,11 +478,11 @@ MPG_DEV void edge_fwd1_body(const MpgEdgeFwd& p, const MpgChain* const cp = null
             if (ii < p.N) *reinterpret_cast<float4*>(out + (size_t)ii * H3 + 32 * m + 8 * g + 4 * (ln >> 5)) = v;
         }
     } else {
-        // ---- the node network on these 32 receivers (edge_fwd2_impl.h: registers 8s .. 8s+7 of accumulator tile m ARE the B
-        //      fragment of k-step 2m + s of fn's first layer).  Eight waves: wave w sums k-steps w and w + 8 (< 12) of the four
-        //      slabs -- in the plain path's order, times agg_scale: the values that path writes -- and lays them down as hi/lo
-        //      fragments beside the slabs; waves 4, 5 also stage the x columns (k-steps 12, 13).
-        static_assert(F2_FN_BIAS + C2_BIAS * 4 <= F2_LDS_BYTES, "fn's buffers must fit the edge kernel's LDS");
+        // ---- the node network on these 32 receivers.  Registers 8s .. 8s+7 of accumulator tile m ARE the B fragment of k-step
+        //      2m + s of fn's first layer (same chain layout): wave w sums k-steps w and w + 8 (< 12) of the four slabs -- in the
+        //      plain path's order, times agg_scale: the very fp32 values that path writes and chain2 reads back, so both routes
+        //      give the same bits -- and lays them down as hi/lo fragments beside the slabs; waves 4, 5 also stage the x columns
+        //      (k-steps 12, 13) from memory.
         const MpgChain& c = *cp;
         const int m0 = b * p.N + rb * 32, nrows = min(32, p.N - rb * 32);
         if (p.SC > 1) {
@@ -553,6 +556,8 @@ MPG_DEV void edge_fwd1_body(const MpgEdgeFwd& p, const MpgChain* const cp = null
                         av8[j] = sum * red_scale;
                         v[j] = av8[j] * ascale;
                     }
+                    // features 32 mm + 16 s2 + 4 h + {0..3} and + 8: two 16-byte stores of the receiver's agg row (kept for the
+                    // backward: fn.net.0's weight gradient; a NULL agg has an empty descriptor and the stores are dropped)
 #pragma unroll
                     for (int half = 0; half < 2; ++half)
                         __builtin_amdgcn_raw_buffer_store_b128(

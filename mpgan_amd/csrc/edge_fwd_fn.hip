@@ -1,7 +1,7 @@
 // mpg_edge_fwd_fn: the fused edge network's forward WITH the node network fn as the epilogue of every workgroup
-// (mpgan/model.py:256-279 in one launch: fe + mask + sum/mean + cat((agg, x)) + fn).  The kernel is edge_fwd2_impl.h's
-// (FN variants, chain2_impl.h's schedule for the three node layers); its six instantiation pairs compile side by side in
-// edge_fwd_fn_d{0,1,2}s{0,1}.hip.  This unit holds the entry point: argument checks and the variant table.
+// (mpgan/model.py:256-279 in one launch: fe + mask + sum/mean + cat((agg, x)) + fn).  The kernel is edge_fwd1_impl.h's
+// edge_fwd1_fn_kernel (eight waves; FN variants, chain2_impl.h's schedule for the three node layers); its instantiations compile
+// side by side in edge_fwd_fn_d{0,1,2}s{0,1}.hip.  This unit holds the entry point: argument checks and the variant table.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mpgan_amd.h"
@@ -16,8 +16,7 @@ extern "C" int mpg_edge_fwd_fn(const MpgEdgeFwd* p, const MpgChain* c, const Mpg
     if (!p->f16 || !c->f16 || (p->two_term != 0 && p->two_term != 1)) return -8;
     if (p->stageE2 != nullptr && (long long)p->B * ((p->N + 31) / 32) * p->N * 10240LL > 0x7fffffffLL) return -7;
     // what the epilogue form covers -- anything else: MPG_FN_NA, and the caller runs mpg_edge_fwd + mpg_chain
-    // (sender chunks: only with arrival counters -- the last workgroup of a (jet, receiver block) adds the chunks up -- and
-    // only in the eight-wave form: the per-mode units answer MPG_FN_NA otherwise)
+    // (sender chunks: only with arrival counters -- the last workgroup of a (jet, receiver block) adds the chunks up)
     if (p->SC < 1 || (p->SC != 1 && p->tickets == nullptr) || p->N > 160 * p->SC || p->es != nullptr) return MPG_FN_NA;
     if ((p->N + p->SC - 1) / p->SC > 160) return MPG_FN_NA;
     if (c->nlayers != 3 || c->M != p->B * p->N || c->A2 == nullptr || c->in_thr != 0 || c->in_out != nullptr || c->seed != p->seed) return MPG_FN_NA;

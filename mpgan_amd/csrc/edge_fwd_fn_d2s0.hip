@@ -1,4 +1,4 @@
-// The fused edge forward + node network (mpg_edge_fwd_fn, see edge_fwd_fn.hip), dropout mode 2, without the backward's by-products.
+// The eight-wave edge forward + node network (mpg_edge_fwd_fn, see edge_fwd_fn.hip), dropout mode 2, without the backward's by-products.
 #include "edge_fwd1_impl.h"
 
 int mpg_edge_fwd_fn_d2s0(const MpgEdgeFwd* p, const MpgChain* c, const MpgChain* c2, bool sl, hipStream_t st) {

@@ -48,16 +48,12 @@ MPG_DEV V mab_wfrag(WImg w, int frag, int lane16) {
     return *reinterpret_cast<const V*>(w + frag * 1024 + lane16);
 }
 // (LDS-DMA: 1 KiB per wave-instruction straight into LDS, no register staging, all of a wave's pieces in flight at once.
-// Every workgroup of a launch wants the same image at the same moment; walking it from the same end they would all stand
-// at the same few L2 channels, so each starts at a piece of its own; -DMPG_MAB_NOROT builds the A/B.)
+// Every workgroup of a launch wants the same image at the same moment; each starts at a piece of its own so that they do not
+// all walk it from the same end -- measured to make no difference: the fill is not bound by L2 channels)
 MPG_DEV void mab_fill(char* dst, const void* src, int bytes) {
     const int wave = threadIdx.x >> 6, nwav = blockDim.x >> 6, lane = threadIdx.x & 63;
     const int n = bytes / 1024;
-#ifdef MPG_MAB_NOROT
-    const int rot = 0;
-#else
     const int rot = ((int)(blockIdx.x >> 3) * 5) % n;      // (workgroups 8 apart share an XCD and its L2)
-#endif
     for (int c = wave; c < n; c += nwav) {
         int cc = c + rot;
         cc = cc >= n ? cc - n : cc;

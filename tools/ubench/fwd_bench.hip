@@ -1,6 +1,6 @@
 // Stand-alone timing of edge_fwd_kernel<DROP, f16, sign> at B=256, N=30 on random data (no torch):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -fno-slp-vectorize -DMPG_SINGLE_VARIANT=<0|2> [-DMPG_EXP=n] tools/ubench/fwd_bench.hip -o fwd_bench
-//   -DMPG_FWD1 [-DMPG_F1_STAGGER=n]: the eight-wave form (edge_fwd1_impl.h) in place of the four-wave one; the checksums of agg,
+//   -DMPG_FWD1: the eight-wave form (edge_fwd1_impl.h) in place of the four-wave one; the checksums of agg,
 //   of the sign words and of the parked E2 fragments printed at the end must agree between the two (agg up to the order of its sums)
 #include "../../mpgan_amd/csrc/edge.hip"
 #include <stdio.h>
