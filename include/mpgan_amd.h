@@ -524,6 +524,28 @@ int mpg_adadelta(float* p, float* g, float* v, float* u, uint64_t n, float lr, f
 #define MPG_JET_OBS_NORMED 2
 int mpg_jet_obs(const float* jets, int ld_jet, int ld_part, int n, int N, int flags, float* kin, float* efp, void* stream);
 
+/* mpg_jet_emd: out[i, j] = the energy mover's distance between jets a[i] and b[j] (i < na, j < nb), the pairwise distances
+ * that jetnet.evaluation.cov_mmd takes from energyflow's emd (beta = 1, norm = False, no phi wrap).  Jets are laid out as for
+ * mpg_jet_obs (particle p of jet i at a[i*ld_jet_a + p*ld_part + 0..2] = (eta_rel, phi_rel, pt_rel)); only particles with
+ * pt_rel > 0 take part, wherever they sit in the jet.  With weights w_i = pT of a's particles, w'_j = pT of b's,
+ * theta_ij = sqrt(d_eta^2 + d_phi^2) / R and d = sum w - sum w', the lighter jet gets one slack particle of weight |d| whose
+ * cost to every particle of the other jet is exactly 1 (none when d == 0), and
+ *   EMD(a, b) = min_{f >= 0} sum_ij f_ij cost_ij   subject to   sum_j f_ij = w_i,  sum_i f_ij = w'_j.
+ * A jet without a particle of positive pT is all slack: EMD = sum pT of the other jet; two such jets give 0.
+ * The solver is exact (successive shortest paths with potentials, csrc/jet_emd.hip), one launch for the whole matrix, fp32,
+ * and out[i, j] depends on the values of a[i] and b[j] alone: equal jets give equal bits, in any position and on every launch.
+ * status[i, j] (or NULL): 0, or 1 when the pair reached the solver's cap of 32 (N + 1) augmentations, 2 when a search found no
+ * path (non-finite coordinates); out then holds the cost of a feasible plan, an upper bound.
+ * 1 <= N <= MPG_JET_OBS_MAX_N, na, nb >= 1, R > 0, ld_part >= 3 (else -1). */
+int mpg_jet_emd(const float* a, int ld_jet_a, const float* b, int ld_jet_b, int ld_part, int na, int nb, int N, float R,
+                float* out, int* status, void* stream);
+/* mpg_jet_emd_host: the same solver (the same code) in fp64 on host pointers, on min(threads, 16) std::threads; no HIP call.
+ * mpg_jet_emd_host_iters also writes the augmentations each pair took (iters [na, nb] or NULL; the cap is 32 (N + 1)). */
+int mpg_jet_emd_host(const float* a, int ld_jet_a, const float* b, int ld_jet_b, int ld_part, int na, int nb, int N, float R,
+                     double* out, int* status, int threads);
+int mpg_jet_emd_host_iters(const float* a, int ld_jet_a, const float* b, int ld_jet_b, int ld_part, int na, int nb, int N, float R,
+                           double* out, int* status, int* iters, int threads);
+
 /* mpg_normal: out[i] = mean + std * z_i with z ~ N(0, 1) -- the generator's input noise (get_gen_noise, train.py:100-141:
  * torch.randn * sd) from a counter-based stream keyed by the device-resident 64-bit `seed` (the dropout seed, advanced
  * once per iteration) and a site `tag`: a captured hipGraph draws fresh values on every replay, and torch's generator

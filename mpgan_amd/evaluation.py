@@ -24,6 +24,17 @@ w = Theta z, u = (Theta o Theta) z, M = Theta diag(z) Theta -- the five connecte
     3  triangle + pendant             sum_{a,c} z_a z_c w_c theta_ac M_ac
     4  4-cycle                        sum_{a,c} z_a z_c M_ac^2
 
+Coverage and MMD (``cov_mmd``) come from the exact pairwise energy mover's distances of ``emds``: energyflow's ``emd`` with
+``beta = 1``, ``norm = False``, no phi wrap, ``R = 1`` -- the transportation problem between the particles of positive pT of two
+jets with cost theta_ij / R, the lighter jet completed by one slack particle of weight |sum pT_A - sum pT_B| at cost exactly 1
+(``include/mpgan_amd.h`` has the statement in full).  Per batch ``i_real = rng.choice(len(real), k)`` then
+``i_gen = rng.choice(len(gen), k)``, ``D[g, r] = EMD(gen[i_gen[g]], real[i_real[r]])``, ``mmd = mean_r min_g D[g, r]``,
+``cov = |unique_g argmin_r D[g, r]| / k`` (argmin = first index of the minimum); the means over ``num_batches`` batches are
+returned as ``(coverage, mmd)``.  Like the W1 sampling semantics above, the EMD conventions and the cov / mmd definition are
+restated from memory of energyflow, jetnet 0.2 and the MPGAN paper; neither library is available to check them against (the
+solver itself is checked against a linear-programming statement of the definition).  CUDA tensors run ``mpg_jet_emd`` (one
+launch per distance matrix, fp32); CPU tensors and numpy arrays run the same solver in fp64 on up to 16 host threads.
+
 FPD (energyflow's ``d<=4`` set, whose membership and order cannot be checked here) and FPND (jetnet's pretrained
 ParticleNet) are not provided.
 """
@@ -225,6 +236,81 @@ def w1efp(jets1, jets2, use_particle_masses: bool = False, num_eval_samples: int
     return _mean_std(w1s, average_over_efps, return_std)
 
 
+# ------------------------------------------------------------------------------------- EMD, coverage and MMD
+_HOST_THREADS = 16
+
+
+def _emd_input(t: torch.Tensor, width: int) -> torch.Tensor:
+    """fp32, contiguous [n, N, width] (width 3, or the callers' common width: a fourth mask column is stepped over)."""
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[2] != width:
+        t = t[..., :3].float().contiguous()
+    return t
+
+
+def _emds(a: torch.Tensor, b: torch.Tensor, R: float) -> torch.Tensor:
+    """[n1, n2] distances on a's device (fp32 through mpg_jet_emd on a GPU, fp64 through mpg_jet_emd_host otherwise);
+    raises when a pair did not finish inside the solver's cap."""
+    for t in (a, b):
+        if t.dim() != 3 or t.shape[2] < 3:
+            raise ValueError(f"expected jets [n, N, >=3] = (eta_rel, phi_rel, pt_rel, ...), got {tuple(t.shape)}")
+    if a.shape[1] != b.shape[1]:
+        raise ValueError(f"both sets must hold the same number of particle slots per jet (got {a.shape[1]} and {b.shape[1]})")
+    width = a.shape[2] if a.shape[2] == b.shape[2] else 3
+    a, b = _emd_input(a, width), _emd_input(b.to(a.device), width)
+    n1, n2, N, ld = a.shape[0], b.shape[0], a.shape[1], a.shape[2]
+    if not 1 <= N <= MAX_PARTICLES:
+        raise ValueError(f"mpg_jet_emd takes 1 <= N <= {MAX_PARTICLES} particles per jet (got {N})")
+    if not R > 0:
+        raise ValueError(f"R must be positive (got {R})")
+    out = torch.empty((n1, n2), device=a.device, dtype=torch.float32 if a.is_cuda else torch.float64)
+    if n1 == 0 or n2 == 0:
+        return out
+    status = torch.empty((n1, n2), device=a.device, dtype=torch.int32)
+    if a.is_cuda:
+        with torch.cuda.device(a.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            _lib.check(_lib.lib().mpg_jet_emd(a.data_ptr(), N * ld, b.data_ptr(), N * ld, ld, n1, n2, N, float(R),
+                                              out.data_ptr(), status.data_ptr(), stream), "mpg_jet_emd")
+    else:
+        _lib.check(_lib.lib().mpg_jet_emd_host(a.data_ptr(), N * ld, b.data_ptr(), N * ld, ld, n1, n2, N, float(R),
+                                               out.data_ptr(), status.data_ptr(), _HOST_THREADS), "mpg_jet_emd_host")
+    bad = int((status != 0).sum())
+    if bad:
+        raise RuntimeError(f"mpg_jet_emd: {bad} of {n1 * n2} pairs did not reach the optimum (status "
+                           f"{sorted(set(status[status != 0].flatten().tolist()))}: 1 = augmentation cap, 2 = no path, "
+                           f"non-finite input)")
+    return out
+
+
+def emds(jets1, jets2, R: float = 1.0):
+    """``[n1, n2]`` energy mover's distances ``EMD(jets1[i], jets2[j])`` (module docstring): fp32 on the GPU for CUDA tensors,
+    fp64 on the host for CPU tensors and numpy arrays (numpy in, numpy out)."""
+    a, numpy_in = _as_tensor(jets1)
+    b, _ = _as_tensor(jets2)
+    return _out(_emds(a, b, R), numpy_in)
+
+
+def cov_mmd(real_jets, gen_jets, num_eval_samples: int = 100, num_batches: int = 10, rng=None):
+    """``jetnet.evaluation.cov_mmd``: ``(coverage, mmd)`` as floats, means over ``num_batches`` batches of
+    ``num_eval_samples`` jets drawn from each set (module docstring).  ``rng``: anything with numpy's ``choice``."""
+    real = _obs_tensor(real_jets)
+    gen = _obs_tensor(gen_jets, real)
+    covs, mmds = [], []
+    for _ in range(num_batches):
+        i_real, i_gen = _draws(rng, real.shape[0], gen.shape[0], num_eval_samples, real.device)
+        D = _emds(gen[i_gen], real[i_real], 1.0)              # [gen, real]
+        mmds.append(D.min(dim=0).values.double().mean())
+        covs.append(torch.unique(_first_argmin(D)).numel() / num_eval_samples)
+    return float(np.mean(covs)), float(torch.stack(mmds).mean())
+
+
+def _first_argmin(D: torch.Tensor) -> torch.Tensor:
+    """numpy's argmin along the rows of D: the first index of each row's minimum."""
+    n = D.shape[1]
+    idx = torch.arange(n, device=D.device).expand_as(D)
+    return torch.where(D == D.min(dim=1, keepdim=True).values, idx, n).min(dim=1).values
+
+
 # ------------------------------------------------------------------------------------- the reference's evaluate
 def evaluate(losses: dict, real_jets, gen_jets, jet_type: str, num_particles: int = 30, num_w1_eval_samples: int = 10000,
              num_cov_mmd_eval_samples: int = 100, num_fpnd_eval_samples: int = 50000, fpnd_batch_size: int = 16,
@@ -232,7 +318,9 @@ def evaluate(losses: dict, real_jets, gen_jets, jet_type: str, num_particles: in
     """train.py:543-606: append ``w1p`` (means(3) then stds(3)), ``w1m`` ([mean, std]) and ``w1efp`` (means(5) then
     stds(5)) to the lists of ``losses`` that hold those keys, with ``len(real_jets) // num_w1_eval_samples`` batches.
     ``"fpd"`` is left alone (the reference's evaluate leaves it too); ``"fpnd"`` raises ``NotImplementedError``.
-    The draws come from ``rng`` (default ``np.random``) in the reference's order: w1p, w1m, w1efp."""
+    The draws come from ``rng`` (default ``np.random``) in the reference's order: w1p, w1m, w1efp.  ``"coverage"`` and
+    ``"mmd"`` (``cov_mmd`` with ``num_cov_mmd_eval_samples`` samples, 10 batches) are appended after those three, so the draws
+    of a caller without these keys are what they were."""
     if "fpnd" in losses:
         raise NotImplementedError("fpnd needs jetnet's pretrained ParticleNet, which mpgan_amd does not provide")
     num_batches = len(real_jets) // num_w1_eval_samples
@@ -248,13 +336,20 @@ def evaluate(losses: dict, real_jets, gen_jets, jet_type: str, num_particles: in
         m, s = w1efp(real_jets, gen_jets, use_particle_masses=False, num_eval_samples=num_w1_eval_samples,
                      num_batches=num_batches, average_over_efps=False, return_std=True, efp_jobs=efp_jobs, rng=rng)
         losses["w1efp"].append(np.concatenate((m, s)))
+    if "coverage" in losses or "mmd" in losses:
+        cov, mmd = cov_mmd(real_jets, gen_jets, num_eval_samples=num_cov_mmd_eval_samples, rng=rng)
+        if "coverage" in losses:
+            losses["coverage"].append(cov)
+        if "mmd" in losses:
+            losses["mmd"].append(mmd)
     return losses
 
 
 def evaluate_generator(G: torch.nn.Module, real_jets, jet_type: str, num_samples: int = 50000,
                        keys: Sequence[str] = ("w1p", "w1m"), losses: Optional[dict] = None, num_particles: int = 30,
                        num_w1_eval_samples: int = 10000, labels: Optional[torch.Tensor] = None, model: str = "mpgan",
-                       model_args: Optional[dict] = None, batch_size: int = 4096, rng=None) -> dict:
+                       model_args: Optional[dict] = None, batch_size: int = 4096, rng=None,
+                       num_cov_mmd_eval_samples: int = 100) -> dict:
     """Generate ``num_samples`` jets with ``gen.generate_jets`` and ``evaluate`` them against ``real_jets`` ([n, N, >=3]
     un-normalised), all on G's device.  ``labels`` (num_particles / N per generated jet) default to the multiplicities of
     the real jets, taken in order and repeated as needed -- the reference conditions on the test set's ``jet_data``
@@ -272,4 +367,4 @@ def evaluate_generator(G: torch.nn.Module, real_jets, jet_type: str, num_samples
     if losses is None:
         losses = {k: [] for k in keys}
     return evaluate(losses, real[..., :3], gen_jets, jet_type, num_particles=num_particles,
-                    num_w1_eval_samples=num_w1_eval_samples, rng=rng)
+                    num_w1_eval_samples=num_w1_eval_samples, num_cov_mmd_eval_samples=num_cov_mmd_eval_samples, rng=rng)
