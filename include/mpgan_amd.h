@@ -524,6 +524,43 @@ int mpg_adadelta(float* p, float* g, float* v, float* u, uint64_t n, float lr, f
 #define MPG_JET_OBS_NORMED 2
 int mpg_jet_obs(const float* jets, int ld_jet, int ld_part, int n, int N, int flags, float* kin, float* efp, void* stream);
 
+/* mpg_jet_efps_d4: efp[b, 0..20] = the 21 connected ("prime") energy-flow polynomials of degree <= 4 of jet b, the features of
+ * FPD and KPD (jetnet.evaluation.fpd / kpd on jetnet.utils.efps(jets, efpset_args=[("d<=", 4)])).  energyflow's d<=4 set is
+ * every loopless multigraph with at most 4 edges and no isolated vertex, up to isomorphism, the empty graph included: 36
+ * graphs, of which these 21 are connected; the other 15 are disjoint unions, whose EFPs are the products of their components'
+ * -- the caller multiplies (mpgan_amd/evaluation.py: EFP_D4_GRAPHS).  Input contract, measure and index conventions as for
+ * mpg_jet_obs (theta_ij = sqrt(d_eta^2 + d_phi^2), z_i = pT_i / sum pT with MPG_JET_OBS_NORMED in flags, else pT_i; sums over
+ * ALL index tuples, theta_ii = 0 removing the repeated ones; any other flag bit: -2).  With T_k = (Theta^{o k}) z, the row
+ * sums of the k-th elementwise power (T_1 = w, T_2 = u), zw = z o w, v = Theta zw, q = (Theta o Theta) zw and
+ * M = Theta diag(z) Theta:
+ *   col  d  graph                                    closed form
+ *    0   0  one vertex, no edge                      sum z            (1 when normed; 0 for a jet without pT)
+ *    1   1  edge a-b                                 sum z w
+ *    2   2  double edge a=b                          sum z T_2
+ *    3   2  wedge a-b-c                              sum z w^2
+ *    4   3  triple edge                              sum z T_3
+ *    5   3  a=b-c                                    sum z T_2 w
+ *    6   3  triangle                                 sum_{a,c} z_a z_c theta_ac M_ac
+ *    7   3  path a-b-c-d                             sum zw v
+ *    8   3  3-star                                   sum z w^3
+ *    9   4  quadruple edge                           sum z T_4
+ *   10   4  triple edge a-b + edge b-c               sum z T_3 w
+ *   11   4  two double edges sharing b (a=b=c)       sum z T_2^2
+ *   12   4  triangle, one edge doubled               sum_{a,c} z_a z_c theta_ac^2 M_ac
+ *   13   4  a=b-c-d (end edge doubled)               sum z T_2 v            (= efp[b, 0] of mpg_jet_obs)
+ *   14   4  a-b=c-d (middle edge doubled)            sum zw q               (= 1)
+ *   15   4  3-star, one edge doubled                 sum z T_2 w^2          (= 2)
+ *   16   4  triangle + pendant                       sum_{a,c} z_a z_c w_c theta_ac M_ac   (= 3)
+ *   17   4  4-cycle                                  sum_{a,c} z_a z_c M_ac^2              (= 4)
+ *   18   4  path of 5 vertices                       sum z v^2
+ *   19   4  4-star                                   sum z w^4
+ *   20   4  fork (3-star, one leg extended)          sum z w^2 v
+ * (the column order is the project's; FPD and KPD do not depend on it).  Every summand is non-negative.  One launch, one
+ * workgroup per jet, M one 32 x 32 tile at a time as in mpg_jet_obs; fp32; fixed-order reductions: the same input gives the
+ * same bits.  1 <= N <= MPG_JET_OBS_MAX_N, n >= 1, ld_part >= 3 (else -1); jets, efp non-NULL (else -2). */
+#define MPG_JET_EFPS_D4_PRIMES 21
+int mpg_jet_efps_d4(const float* jets, int ld_jet, int ld_part, int n, int N, int flags, float* efp, void* stream);
+
 /* mpg_jet_emd: out[i, j] = the energy mover's distance between jets a[i] and b[j] (i < na, j < nb), the pairwise distances
  * that jetnet.evaluation.cov_mmd takes from energyflow's emd (beta = 1, norm = False, no phi wrap).  Jets are laid out as for
  * mpg_jet_obs (particle p of jet i at a[i*ld_jet_a + p*ld_part + 0..2] = (eta_rel, phi_rel, pt_rel)); only particles with

@@ -248,6 +248,7 @@ SIGNATURES = {
     "mpg_normal_rank_mask": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_uint32, C.c_float, C.c_float, _fp, C.c_int, _fp, _fp,
                                        C.c_void_p]),
     "mpg_jet_obs": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_void_p]),
+    "mpg_jet_efps_d4": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_void_p]),
     "mpg_jet_emd": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, C.c_void_p]),
     "mpg_jet_emd_host": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, C.c_int]),
     "mpg_jet_emd_host_iters": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp,

@@ -68,14 +68,31 @@ def load_optimizers(D_optimizer, G_optimizer, models_path: str, epoch: int, map_
 # metrics holding several values per evaluation.  The reference's list (setup_training.py:1551) leaves out "fpd",
 # whose entries are (value, error) pairs as well (train.py:633): a history with a single evaluation then comes
 # back as two scalar entries there; here it keeps its shape.
-MULTI_VALUE_KEYS = ("w1p", "w1m", "w1efp", "fpd")
+MULTI_VALUE_KEYS = ("w1p", "w1m", "w1efp", "fpd", "kpd")
 
 
-def loss_keys(gp: bool = False, fpnd: bool = False, fpd: bool = True, efp: bool = False) -> Tuple[List[str], List[str]]:
-    """(all keys, evaluation keys) of the ``losses`` dict for a flag combination (setup_training.py:1540-1562)."""
+def loss_keys(gp: bool = False, fpnd: bool = False, fpd: bool = True, efp: bool = False,
+              kpd: bool = False) -> Tuple[List[str], List[str]]:
+    """(all keys, evaluation keys) of the ``losses`` dict for a flag combination (setup_training.py:1540-1562); ``kpd`` (not a
+    key of the reference) adds ``evaluation.kpd``'s (median, error) pairs."""
     keys = ["D", "Dr", "Df", "G"] + (["gp"] if gp else [])
     eval_keys = ["w1p", "w1m"] + (["w1efp"] if efp else []) + (["fpnd"] if fpnd else []) + (["fpd"] if fpd else [])
+    eval_keys += ["kpd"] if kpd else []
     return keys + eval_keys, eval_keys
+
+
+def best_epoch_update(best_epoch: list, epoch: int, losses: Dict[str, list]) -> bool:
+    """train.py:794-797: is this epoch the best so far by ``fpd value + fpd error``?  ``best_epoch`` is the history of
+    ``[epoch, score]`` records (the reference starts it at ``[[0, 10.0]]``); when ``epoch > 0`` and the last ``losses["fpd"]``
+    entry's sum is below the last record's score, ``[epoch, score]`` is appended and True returned -- the caller then saves
+    ``G_best_epoch.pt`` and the generated jets."""
+    if "fpd" not in losses or not len(losses["fpd"]):
+        return False
+    score = float(losses["fpd"][-1][0] + losses["fpd"][-1][1])
+    if epoch > 0 and score < best_epoch[-1][1]:
+        best_epoch.append([epoch, score])
+        return True
+    return False
 
 
 def save_losses(losses: Dict[str, Iterable], losses_path: str):

@@ -1,6 +1,7 @@
 """Evaluation metrics of a training run without jetnet / energyflow: W1 of the jet mass (``w1m``), of the particle features
-(``w1p``) and of five energy-flow polynomials (``w1efp``), as the reference's ``evaluate`` (train.py:543-606) appends them
-to its ``losses`` dict after every epoch.
+(``w1p``) and of five energy-flow polynomials (``w1efp``), coverage and MMD (``cov_mmd``), and the Frechet and kernel physics
+distances (``fpd``, ``kpd``), as the reference's ``evaluate`` (train.py:543-606) appends them to its ``losses`` dict after every
+epoch.
 
 The names follow ``jetnet.utils`` / ``jetnet.evaluation`` so a caller can swap those modules for this one.  Jets are
 ``[n, N, >=3]`` un-normalised ``(eta_rel, phi_rel, pt_rel[, mask])`` with ``pt_rel = 0`` on padding particles (what
@@ -35,8 +36,18 @@ restated from memory of energyflow, jetnet 0.2 and the MPGAN paper; neither libr
 solver itself is checked against a linear-programming statement of the definition).  CUDA tensors run ``mpg_jet_emd`` (one
 launch per distance matrix, fp32); CPU tensors and numpy arrays run the same solver in fp64 on up to 16 host threads.
 
-FPD (energyflow's ``d<=4`` set, whose membership and order cannot be checked here) and FPND (jetnet's pretrained
-ParticleNet) are not provided.
+FPD and KPD (``fpd``, ``kpd``; the reference picks its best epoch by ``fpd value + error``, train.py:794-809) are computed from
+the 36 EFPs of degree <= 4, ``efps(jets, efpset_args=[("d<=", 4)])``.  The set is a definition, not a convention of energyflow:
+every loopless multigraph with at most 4 edges and no isolated vertex, up to isomorphism, the graph of one vertex included --
+1, 1, 3, 8, 23 graphs of degree 0 .. 4 (``EFP_D4_GRAPHS``; tests enumerate them from the definition).  21 of them are connected:
+``mpg_jet_efps_d4`` (one launch, fp32; closed forms over row sums of powers of Theta and over M, table in
+``include/mpgan_amd.h``) computes those for CUDA tensors, an fp64 torch statement of the same forms for CPU tensors and numpy
+arrays; the other 15 are disjoint unions, whose EFPs are products of the connected ones' (``EFP_D4_FACTORS``), formed in fp64.
+The column order is this project's; both metrics and the per-column normalisation they apply first are invariant under
+permutations of the columns, so energyflow's order is not needed.  The sampling and extrapolation procedure of ``fpd`` and
+``kpd`` is restated from memory of jetnet (their docstrings), like the W1 sampling semantics above.
+
+FPND (jetnet's pretrained ParticleNet) is not provided.
 """
 from __future__ import annotations
 
@@ -137,10 +148,133 @@ def jet_features(jets) -> Dict[str, object]:
     return {k: kin[:, i] for i, k in enumerate(("pt", "eta", "phi", "mass"))}
 
 
-def efps(jets, normed: bool = True):
-    """``[n, 5]`` EFPs of each jet in the column order of the module docstring (``jetnet.utils.efps`` with the
-    ``("n==", 4), ("d==", 4), ("p==", 1)`` set).  ``normed``: z_i = pT_i / sum pT (else pT_i)."""
-    return _observables(jets, with_efps=True, normed=normed)[1]
+_EFPSET_DEFAULT = (("n==", 4), ("d==", 4), ("p==", 1))
+_EFPSET_D4 = (("d<=", 4),)
+
+
+def efps(jets, normed: bool = True, efpset_args=None, efp_jobs=None):
+    """``jetnet.utils.efps``.  ``efpset_args`` ``None`` or ``[("n==", 4), ("d==", 4), ("p==", 1)]`` (jetnet's default): ``[n, 5]``
+    in the column order of the module docstring; ``[("d<=", 4)]`` (the set of ``fpd`` / ``kpd``): ``[n, 36]`` in the order of
+    ``EFP_D4_GRAPHS``; any other set raises ``NotImplementedError``.  ``normed``: z_i = pT_i / sum pT (else pT_i);
+    ``efp_jobs`` is accepted and unused (the EFPs run on the jets' device)."""
+    spec = _EFPSET_DEFAULT if efpset_args is None else tuple(tuple(a) for a in efpset_args)
+    if spec == _EFPSET_DEFAULT:
+        return _observables(jets, with_efps=True, normed=normed)[1]
+    if spec != _EFPSET_D4:
+        raise NotImplementedError(f"mpgan_amd.evaluation has the EFP sets {list(_EFPSET_DEFAULT)} and {list(_EFPSET_D4)} "
+                                  f"(got {list(spec)})")
+    t, numpy_in = _as_tensor(jets)
+    _check_jets(t)
+    return _out(_efps_d4(t, normed), numpy_in)
+
+
+# ------------------------------------------------------------------------------------- the 36 EFPs of degree <= 4
+# The connected loopless multigraphs with at most 4 edges, in the column order of mpg_jet_efps_d4 (include/mpgan_amd.h)
+_PRIME_GRAPHS = (
+    (),                                      # 0  d = 0: one vertex
+    ((0, 1),),                               # 1  edge
+    ((0, 1), (0, 1)),                        # 2  double edge
+    ((0, 1), (1, 2)),                        # 3  wedge
+    ((0, 1), (0, 1), (0, 1)),                # 4  triple edge
+    ((0, 1), (0, 1), (1, 2)),                # 5  a=b-c
+    ((0, 1), (1, 2), (0, 2)),                # 6  triangle
+    ((0, 1), (1, 2), (2, 3)),                # 7  path of 4 vertices
+    ((0, 1), (0, 2), (0, 3)),                # 8  3-star
+    ((0, 1), (0, 1), (0, 1), (0, 1)),        # 9  quadruple edge
+    ((0, 1), (0, 1), (0, 1), (1, 2)),        # 10 triple edge + edge
+    ((0, 1), (0, 1), (1, 2), (1, 2)),        # 11 two double edges sharing a vertex
+    ((0, 1), (0, 1), (1, 2), (0, 2)),        # 12 triangle, one edge doubled
+    ((0, 1), (0, 1), (1, 2), (2, 3)),        # 13 a=b-c-d            (column 0 of the five-EFP set)
+    ((0, 1), (1, 2), (1, 2), (2, 3)),        # 14 a-b=c-d            (1)
+    ((0, 1), (0, 1), (0, 2), (0, 3)),        # 15 3-star, one doubled (2)
+    ((0, 1), (1, 2), (0, 2), (2, 3)),        # 16 triangle + pendant  (3)
+    ((0, 1), (1, 2), (2, 3), (3, 0)),        # 17 4-cycle             (4)
+    ((0, 1), (1, 2), (2, 3), (3, 4)),        # 18 path of 5 vertices
+    ((0, 1), (0, 2), (0, 3), (0, 4)),        # 19 4-star
+    ((0, 1), (0, 2), (0, 3), (3, 4)),        # 20 fork
+)
+NUM_EFP_D4_PRIMES = len(_PRIME_GRAPHS)       # MPG_JET_EFPS_D4_PRIMES of include/mpgan_amd.h
+# the disconnected graphs of the set: multisets of the primes 1 .. 8 with at least two members and at most 4 edges in all
+_COMPOSITE_FACTORS = ((1, 1), (1, 1, 1), (1, 2), (1, 3), (1, 1, 1, 1), (1, 1, 2), (1, 1, 3), (2, 2), (2, 3), (3, 3),
+                      (1, 4), (1, 5), (1, 6), (1, 7), (1, 8))
+
+
+def _disjoint_union(factors):
+    edges, base = [], 0
+    for f in factors:
+        edges += [(a + base, b + base) for a, b in _PRIME_GRAPHS[f]]
+        base += 1 + max(max(e) for e in _PRIME_GRAPHS[f])
+    return tuple(edges)
+
+
+# column k of ``efps(jets, efpset_args=[("d<=", 4)])`` is the EFP of the multigraph EFP_D4_GRAPHS[k] (a tuple of edges, pairs
+# of vertex indices; () is the graph of one vertex and no edge) and the product of the prime columns EFP_D4_FACTORS[k]
+EFP_D4_FACTORS = tuple((k,) for k in range(NUM_EFP_D4_PRIMES)) + _COMPOSITE_FACTORS
+EFP_D4_GRAPHS = _PRIME_GRAPHS + tuple(_disjoint_union(f) for f in _COMPOSITE_FACTORS)
+NUM_EFPS_D4 = len(EFP_D4_GRAPHS)
+
+
+def _check_jets(t: torch.Tensor):
+    if t.dim() != 3 or t.shape[2] < 3:
+        raise ValueError(f"expected jets [n, N, >=3] = (eta_rel, phi_rel, pt_rel, ...), got {tuple(t.shape)}")
+    if t.is_cuda and not 1 <= t.shape[1] <= MAX_PARTICLES:
+        raise ValueError(f"mpg_jet_efps_d4 takes 1 <= N <= {MAX_PARTICLES} particles per jet (got {t.shape[1]})")
+
+
+def _efp_primes_cuda(jets: torch.Tensor, normed: bool) -> torch.Tensor:
+    """[n, 21] fp32 from mpg_jet_efps_d4."""
+    n, N = jets.shape[0], jets.shape[1]
+    if jets.dtype != torch.float32 or jets.stride(2) != 1:
+        jets = jets.float().contiguous()
+    out = torch.empty((n, NUM_EFP_D4_PRIMES), device=jets.device, dtype=torch.float32)
+    if n == 0:
+        return out
+    with torch.cuda.device(jets.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().mpg_jet_efps_d4(jets.data_ptr(), jets.stride(0), jets.stride(1), n, N,
+                                              _FLAG_NORMED if normed else 0, out.data_ptr(), stream), "mpg_jet_efps_d4")
+    return out
+
+
+def _efp_primes_cpu(jets: torch.Tensor, normed: bool) -> torch.Tensor:
+    """fp64 statement of mpg_jet_efps_d4 (the closed forms of include/mpgan_amd.h), chunked over jets."""
+    x = jets[..., :3].double()
+    n, N = x.shape[0], x.shape[1]
+    out = torch.empty((n, NUM_EFP_D4_PRIMES), dtype=torch.float64)
+    step = max(1, _CPU_CHUNK // max(1, N * N))
+    for s in range(0, n, step):
+        eta, phi, pt = x[s:s + step].unbind(-1)
+        if normed:
+            spt = pt.sum(1, keepdim=True)
+            z = pt / torch.where(spt != 0, spt, 1.0)
+        else:
+            z = pt
+        th = ((eta[:, :, None] - eta[:, None, :]) ** 2 + (phi[:, :, None] - phi[:, None, :]) ** 2).sqrt()
+        th2 = th * th
+        row = lambda A, y: torch.einsum("bij,bj->bi", A, y)
+        w, T2, T3, T4 = row(th, z), row(th2, z), row(th2 * th, z), row(th2 * th2, z)
+        zw = z * w
+        v, q = row(th, zw), row(th2, zw)
+        M = torch.einsum("bij,bj,bjk->bik", th, z, th)
+        zMz = z[:, :, None] * M * z[:, None, :]
+        cols = (z, zw, z * T2, zw * w, z * T3, z * T2 * w, None, zw * v, zw * w * w, z * T4, z * T3 * w, z * T2 * T2, None,
+                z * T2 * v, zw * q, z * T2 * w * w, None, None, z * v * v, zw * w * w * w, zw * w * v)
+        o = out[s:s + step]
+        for k, c in enumerate(cols):
+            if c is not None:
+                o[:, k] = c.sum(1)
+        o[:, 6] = (zMz * th).sum((1, 2))
+        o[:, 12] = (zMz * th2).sum((1, 2))
+        o[:, 16] = (zMz * th * w[:, None, :]).sum((1, 2))
+        o[:, 17] = (zMz * M).sum((1, 2))
+    return out
+
+
+def _efps_d4(jets: torch.Tensor, normed: bool = True) -> torch.Tensor:
+    """[n, 36] fp64 on the jets' device: the primes (fp32 from the kernel on a GPU, fp64 on the host), then their products."""
+    primes = (_efp_primes_cuda(jets, normed) if jets.is_cuda else _efp_primes_cpu(jets, normed)).double()
+    comps = [primes[:, list(f)].prod(1, keepdim=True) for f in _COMPOSITE_FACTORS]
+    return torch.cat([primes] + comps, 1)
 
 
 # ------------------------------------------------------------------------------------- W1
@@ -311,13 +445,148 @@ def _first_argmin(D: torch.Tensor) -> torch.Tensor:
     return torch.where(D == D.min(dim=1, keepdim=True).values, idx, n).min(dim=1).values
 
 
+# ------------------------------------------------------------------------------------- FPD and KPD
+def _np64(x) -> np.ndarray:
+    return x.detach().cpu().double().numpy() if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)
+
+
+def _psd_sqrt(s: np.ndarray) -> np.ndarray:
+    lam, V = np.linalg.eigh(0.5 * (s + s.T))
+    return (V * np.sqrt(np.clip(lam, 0, None))) @ V.T
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2) -> float:
+    """|mu1 - mu2|^2 + Tr(S1) + Tr(S2) - 2 Tr sqrt(S1 S2) between two Gaussians, in fp64 on the host.  The eigenvalues of S1 S2
+    are those of the symmetric positive semi-definite S1^{1/2} S2 S1^{1/2} = A A^T with A = S1^{1/2} S2^{1/2} (symmetric roots
+    from ``eigh``, eigenvalues clamped at 0), so Tr sqrt(S1 S2) is the sum of A's singular values: no complex parts, no scipy.
+    They are taken from an SVD of A rather than as square roots of computed eigenvalues of A A^T: the covariances of the 36
+    EFPs have eigenvalues down to 1e-10 of the largest, an eigen-solver leaves an absolute error of 1e-16 |A A^T| in each
+    eigenvalue, and the square root of an eigenvalue below that is noise of 1e-8 |A| -- the SVD's error is 1e-16 |A|.
+    A column whose variance is exactly 0 in either set (the degree-0 EFP of normed jets) has a zero row and column in that
+    covariance and hence in A A^T: it is left out of the roots, which changes nothing but the rounding."""
+    mu1, mu2 = _np64(mu1).reshape(-1), _np64(mu2).reshape(-1)
+    s1, s2 = np.atleast_2d(_np64(sigma1)), np.atleast_2d(_np64(sigma2))
+    d = mu1 - mu2
+    keep = (np.diag(s1) > 0) & (np.diag(s2) > 0)
+    tr_sqrt = 0.0
+    if keep.any():
+        A = _psd_sqrt(s1[np.ix_(keep, keep)]) @ _psd_sqrt(s2[np.ix_(keep, keep)])
+        tr_sqrt = float(np.linalg.svd(A, compute_uv=False).sum())
+    return float(d @ d + np.trace(s1) + np.trace(s2) - 2 * tr_sqrt)
+
+
+def _mean_cov(x: torch.Tensor):
+    """Mean and covariance (``np.cov(x, rowvar=False)``: divided by rows - 1) of fp64 rows, on their device."""
+    mu = x.mean(0)
+    c = x - mu
+    return mu, c.T @ c / (x.shape[0] - 1)
+
+
+def _feature_pair(real_features, gen_features, normalise: bool):
+    """Both sets as fp64 tensors on the real features' device; ``normalise`` divides both by max |real| of each column (jetnet's
+    ``_normalise_features``; a column that is 0 throughout is left as it is instead of becoming NaN)."""
+    X = _obs_tensor(real_features).double()
+    Y = _obs_tensor(gen_features, X).double()
+    if X.dim() != 2 or Y.dim() != 2 or X.shape[1] != Y.shape[1]:
+        raise ValueError(f"expected features [n, F] and [m, F], got {tuple(X.shape)} and {tuple(Y.shape)}")
+    if normalise:
+        top = X.abs().max(0).values
+        top = torch.where(top > 0, top, torch.ones_like(top))
+        X, Y = X / top, Y / top
+    return X, Y
+
+
+def _bounded_line_fit(x: np.ndarray, y: np.ndarray):
+    """Least squares of ``y = intercept + slope * x`` with both parameters >= 0: (intercept, slope, standard error of the
+    intercept).  The objective is a convex quadratic in two variables, so the minimum over the quadrant is the unconstrained
+    one when that lies inside, else the better of the two one-parameter fits on the boundary.  The error is what
+    ``scipy.optimize.curve_fit`` reports: the square root of RSS / (points - 2) (J^T J)^{-1}[0, 0] with J = [1, x]."""
+    A = np.stack([np.ones_like(x), x], 1)
+    (a, b), *_ = np.linalg.lstsq(A, y, rcond=None)
+    if a < 0 or b < 0:
+        cands = [(max(float(y.mean()), 0.0), 0.0), (0.0, max(float(x @ y / (x @ x)), 0.0))]
+        a, b = min(cands, key=lambda ab: float(((y - ab[0] - ab[1] * x) ** 2).sum()))
+    rss = float(((y - a - b * x) ** 2).sum())
+    dof = len(x) - 2
+    err = float(np.sqrt(rss / dof * np.linalg.inv(A.T @ A)[0, 0])) if dof > 0 else float("inf")
+    return float(a), float(b), err
+
+
+def fpd(real_features, gen_features, min_samples: int = 20000, max_samples: int = 50000, num_batches: int = 20,
+        num_points: int = 10, normalise: bool = True, seed: int = 42, rng=None):
+    """``jetnet.evaluation.fpd`` (Frechet physics distance, Kansal et al. 2022) of two feature sets ``[n, F]``, e.g.
+    ``efps(jets, efpset_args=[("d<=", 4)])``: ``(value, error)``, the Frechet distance between Gaussians fitted to the two sets
+    extrapolated to infinite sample size.  Restated from memory of jetnet: batch sizes
+    ``(1 / linspace(1 / min_samples, 1 / max_samples, num_points)).astype(int32)``; for each size the mean over ``num_batches``
+    of ``frechet_distance`` between ``real[rng.choice(len(real), size)]`` and ``gen[rng.choice(len(gen), size)]`` (real drawn
+    first, with replacement); a least-squares line ``intercept + slope / size`` with both parameters >= 0; the intercept and
+    its standard error are returned.  jetnet reseeds numpy's GLOBAL stream with ``seed``; here the draws come from a private
+    ``np.random.RandomState(seed)`` -- the same numbers, without disturbing the draws of other metrics -- or from ``rng`` when
+    given.  Means and covariances are computed in fp64 on the features' device, the F x F eigenproblems on the host."""
+    X, Y = _feature_pair(real_features, gen_features, normalise)
+    rng = np.random.RandomState(seed) if rng is None else rng
+    sizes = (1 / np.linspace(1.0 / min_samples, 1.0 / max_samples, num_points)).astype("int32")
+    vals = []
+    for size in sizes:
+        points = []
+        for _ in range(num_batches):
+            i1, i2 = _draws(rng, X.shape[0], Y.shape[0], int(size), X.device)
+            points.append(frechet_distance(*_mean_cov(X[i1]), *_mean_cov(Y[i2])))
+        vals.append(np.mean(points))
+    intercept, _, err = _bounded_line_fit(1.0 / sizes.astype(np.float64), np.asarray(vals, dtype=np.float64))
+    return intercept, err
+
+
+_KPD_ROWS = 1024             # rows per chunk of a kernel matrix (1024 x 5000 fp64: 41 MB)
+
+
+def _poly_kernel_sum(A: torch.Tensor, B: torch.Tensor, degree: int) -> torch.Tensor:
+    """sum_ij (A_i . B_j / F + 1)^degree in fp64, the kernel matrix formed ``_KPD_ROWS`` rows at a time."""
+    F = A.shape[1]
+    return torch.stack([((A[s:s + _KPD_ROWS] @ B.T / F + 1.0) ** degree).sum() for s in range(0, A.shape[0], _KPD_ROWS)]).sum()
+
+
+def _mmd_poly_unbiased(X: torch.Tensor, Y: torch.Tensor, degree: int) -> float:
+    m, n, F = X.shape[0], Y.shape[0], X.shape[1]
+    diag = lambda A: (((A * A).sum(1) / F + 1.0) ** degree).sum()
+    xx = (_poly_kernel_sum(X, X, degree) - diag(X)) / (m * (m - 1))
+    yy = (_poly_kernel_sum(Y, Y, degree) - diag(Y)) / (n * (n - 1))
+    xy = _poly_kernel_sum(X, Y, degree) / (m * n)
+    return float(xx + yy - 2 * xy)
+
+
+def kpd(real_features, gen_features, num_batches: int = 10, batch_size: int = 5000, degree: int = 4, normalise: bool = True,
+        seed: int = 42, rng=None):
+    """``jetnet.evaluation.kpd`` (kernel physics distance): ``(median, error)`` over ``num_batches`` batches of the unbiased
+    quadratic MMD ``(sum K_XX - tr K_XX) / (m (m - 1)) + (sum K_YY - tr K_YY) / (m (m - 1)) - 2 mean K_XY`` between
+    ``batch_size`` rows drawn from each set (real first, with replacement), with the polynomial kernel
+    ``K(x, y) = (x . y / F + 1)^degree``, F the number of columns; the error is half the 16.275 - 83.725 percentile range
+    (numpy's linear interpolation).  Restated from memory of jetnet, like ``fpd``: the paper describes the kernel as cubic, the
+    code as remembered has ``degree = 4``, which is therefore the default here; pass ``degree=3`` for the paper's.  Draws come
+    from a private ``np.random.RandomState(seed)`` or from ``rng`` (see ``fpd``).  fp64 on the features' device: the three sums
+    cancel to 1e-3 .. 1e-6 of their size."""
+    X, Y = _feature_pair(real_features, gen_features, normalise)
+    rng = np.random.RandomState(seed) if rng is None else rng
+    vals = []
+    for _ in range(num_batches):
+        i1, i2 = _draws(rng, X.shape[0], Y.shape[0], batch_size, X.device)
+        vals.append(_mmd_poly_unbiased(X[i1], Y[i2], degree))
+    lo, hi = np.percentile(vals, [16.275, 83.725])
+    return float(np.median(vals)), float(hi - lo) / 2
+
+
 # ------------------------------------------------------------------------------------- the reference's evaluate
 def evaluate(losses: dict, real_jets, gen_jets, jet_type: str, num_particles: int = 30, num_w1_eval_samples: int = 10000,
              num_cov_mmd_eval_samples: int = 100, num_fpnd_eval_samples: int = 50000, fpnd_batch_size: int = 16,
-             efp_jobs=None, real_efps=None, gen_efps=None, rng=None):
+             efp_jobs=None, real_efps=None, gen_efps=None, rng=None, *, fpd_args: Optional[dict] = None,
+             kpd_args: Optional[dict] = None):
     """train.py:543-606: append ``w1p`` (means(3) then stds(3)), ``w1m`` ([mean, std]) and ``w1efp`` (means(5) then
     stds(5)) to the lists of ``losses`` that hold those keys, with ``len(real_jets) // num_w1_eval_samples`` batches.
-    ``"fpd"`` is left alone (the reference's evaluate leaves it too); ``"fpnd"`` raises ``NotImplementedError``.
+    ``"fpd"`` and ``"kpd"`` get ``np.array([value, error])`` of ``fpd`` / ``kpd`` only when ``real_efps`` and ``gen_efps`` (the
+    ``[n, 36]`` of ``efps(jets, efpset_args=[("d<=", 4)])``) are given -- the reference's evaluate carries that line commented
+    out and train.py:604-606 appends after it; without them both keys are left alone.  They come last and draw from their own
+    ``RandomState(seed)`` (``fpd_args`` / ``kpd_args`` are passed on as keyword arguments), so every other key's draws are
+    what they are without them.  ``"fpnd"`` raises ``NotImplementedError``.
     The draws come from ``rng`` (default ``np.random``) in the reference's order: w1p, w1m, w1efp.  ``"coverage"`` and
     ``"mmd"`` (``cov_mmd`` with ``num_cov_mmd_eval_samples`` samples, 10 batches) are appended after those three, so the draws
     of a caller without these keys are what they were."""
@@ -342,6 +611,11 @@ def evaluate(losses: dict, real_jets, gen_jets, jet_type: str, num_particles: in
             losses["coverage"].append(cov)
         if "mmd" in losses:
             losses["mmd"].append(mmd)
+    if real_efps is not None and gen_efps is not None:
+        if "fpd" in losses:
+            losses["fpd"].append(np.array(fpd(real_efps, gen_efps, **(fpd_args or {}))))
+        if "kpd" in losses:
+            losses["kpd"].append(np.array(kpd(real_efps, gen_efps, **(kpd_args or {}))))
     return losses
 
 
@@ -349,11 +623,14 @@ def evaluate_generator(G: torch.nn.Module, real_jets, jet_type: str, num_samples
                        keys: Sequence[str] = ("w1p", "w1m"), losses: Optional[dict] = None, num_particles: int = 30,
                        num_w1_eval_samples: int = 10000, labels: Optional[torch.Tensor] = None, model: str = "mpgan",
                        model_args: Optional[dict] = None, batch_size: int = 4096, rng=None,
-                       num_cov_mmd_eval_samples: int = 100) -> dict:
+                       num_cov_mmd_eval_samples: int = 100, real_efps=None, fpd_args: Optional[dict] = None,
+                       kpd_args: Optional[dict] = None) -> dict:
     """Generate ``num_samples`` jets with ``gen.generate_jets`` and ``evaluate`` them against ``real_jets`` ([n, N, >=3]
     un-normalised), all on G's device.  ``labels`` (num_particles / N per generated jet) default to the multiplicities of
     the real jets, taken in order and repeated as needed -- the reference conditions on the test set's ``jet_data``
-    (train.py:712-723).  Returns ``losses`` (a new ``{key: []}`` for ``keys`` when not given) with one entry appended."""
+    (train.py:712-723).  With ``"fpd"`` or ``"kpd"`` among the keys the 36 EFPs of degree <= 4 of the generated jets are computed
+    on the device, and those of the real jets unless ``real_efps`` carries them (train.py:744-755 keeps them in a file per jet
+    type).  Returns ``losses`` (a new ``{key: []}`` for ``keys`` when not given) with one entry appended."""
     from .gen import generate_jets
     device = next(G.parameters()).device
     real, _ = _as_tensor(real_jets)
@@ -366,5 +643,11 @@ def evaluate_generator(G: torch.nn.Module, real_jets, jet_type: str, num_samples
                              model_args=model_args, batch_size=batch_size)
     if losses is None:
         losses = {k: [] for k in keys}
+    gen_efps = None
+    if "fpd" in losses or "kpd" in losses:
+        gen_efps = _efps_d4(gen_jets)
+        real_efps = _efps_d4(real) if real_efps is None else _obs_tensor(real_efps, gen_efps)
     return evaluate(losses, real[..., :3], gen_jets, jet_type, num_particles=num_particles,
-                    num_w1_eval_samples=num_w1_eval_samples, num_cov_mmd_eval_samples=num_cov_mmd_eval_samples, rng=rng)
+                    num_w1_eval_samples=num_w1_eval_samples, num_cov_mmd_eval_samples=num_cov_mmd_eval_samples, rng=rng,
+                    real_efps=real_efps if gen_efps is not None else None, gen_efps=gen_efps, fpd_args=fpd_args,
+                    kpd_args=kpd_args)

@@ -2,7 +2,7 @@
 and without the EFPs (HIP events), the whole ``evaluate`` with the default keys on 50k + 50k jets (host clock around a
 device synchronise), and the fp64 CPU path for comparison.  One JSON object per line on stdout and in --out.
 
-    python tools/eval_bench.py [--jets 50000] [--reps 20] [--out profiles/eval_bench.jsonl] [--section all|w1|emd30|emd150]
+    python tools/eval_bench.py [--jets 50000] [--reps 20] [--out profiles/eval_bench.jsonl] [--section all|w1|emd30|emd150|fpd]
 
 The ``emd30`` / ``emd150`` sections time the exact pairwise jet EMDs behind coverage and MMD (mpg_jet_emd): at N = 30 the
 default ``cov_mmd`` problem, 10 batches of 100 x 100 pairs (ten launches between two HIP events, median of --reps after a
@@ -10,6 +10,11 @@ warm-up), the same ten matrices through the fp64 host build of the solver on 16 
 yardstick, there being no earlier GPU code -- their ratio, the whole ``cov_mmd`` on the device, and the augmentations per
 pair against the solver's cap; at N = 150 one batch of 100 x 100.  ``--section all`` runs each of the two in a child
 process of its own under a time limit (--emd-timeout seconds), so a kernel that does not come back ends that step alone.
+
+The ``fpd`` section (a run of its own; it APPENDS to --out) times mpg_jet_efps_d4, the 21 connected EFPs of degree <= 4 behind FPD
+and KPD, on the same 50k jets at N = 30 and 150 (HIP events, median of --reps after warm-ups), beside it in the same process
+mpg_jet_obs with its five EFPs -- the same tile pass over M, so the yardstick --, the fp64 host path of the 36 columns once on a
+slice, and whole ``fpd`` and ``kpd`` calls with their defaults on 50k + 50k rows of device features.
 
 The floor beside each kernel time is the FLOP count of the full N^3 product M = Theta diag(z) Theta (2 N^3 per jet,
 3.4e11 FLOP for 50k jets at N = 150) over the 157.3 TFLOP/s fp32 peak; the kernel forms only the tiles of one triangle of M and
@@ -99,6 +104,49 @@ def emd_section(N, batches, reps, out, k=100):
           "s_median_rest": float(np.median(times[1:])), "coverage": cov, "mmd": mmd}, out)
 
 
+def time_events(fn, reps):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+
+
+def fpd_section(a):
+    dev = torch.device("cuda:0")
+    feats = {}
+    for N in (30, 150):
+        cpu_jets = jets_of(a.jets, N, seed=N)
+        jets = cpu_jets.to(dev)
+        old = time_events(lambda: ev._obs_cuda(jets, True, True), a.reps)
+        new = time_events(lambda: ev._efp_primes_cuda(jets, True), a.reps)
+        emit({"what": "mpg_jet_efps_d4", "N": N, "jets": a.jets, "ms_median": new[0], "ms_min": new[1], "ms_max": new[2],
+              "mpg_jet_obs_efps_ms_median": old[0], "mpg_jet_obs_efps_ms_min": old[1], "over_mpg_jet_obs": new[0] / old[0]}, a.out)
+        k = min(a.cpu_jets, a.jets)
+        t0 = time.perf_counter()
+        ev.efps(cpu_jets[:k], efpset_args=[("d<=", 4)])
+        dt = time.perf_counter() - t0
+        emit({"what": "cpu_fp64_efps_d4", "N": N, "jets_timed": k, "threads": torch.get_num_threads(), "s": dt,
+              "s_scaled_to_jets": dt * a.jets / k}, a.out)
+        if N == 30:
+            feats["real"] = ev.efps(jets, efpset_args=[("d<=", 4)])
+            feats["gen"] = ev.efps(jets_of(a.jets, N, seed=2, law="quark").to(dev), efpset_args=[("d<=", 4)])
+    for name, fn in (("fpd", ev.fpd), ("kpd", ev.kpd)):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        val, err = fn(feats["real"], feats["gen"])
+        torch.cuda.synchronize()
+        emit({"what": name, "rows": [a.jets, a.jets], "columns": 36, "defaults": True, "s": time.perf_counter() - t0,
+              "value": val, "error": err}, a.out)
+
+
 def emit(rec, out):
     line = json.dumps(rec)
     print(line, flush=True)
@@ -113,13 +161,16 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--cpu-jets", type=int, default=2000, help="jets the fp64 CPU path is timed on (scaled to --jets)")
     ap.add_argument("--out", default="")
-    ap.add_argument("--section", default="all", choices=("all", "w1", "emd30", "emd150"))
+    ap.add_argument("--section", default="all", choices=("all", "w1", "emd30", "emd150", "fpd"))
     ap.add_argument("--emd-timeout", type=int, default=300, help="seconds each EMD section may take as a child of --section all")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("eval_bench: no GPU visible; these timings are only meaningful on one")
     if a.section in ("emd30", "emd150"):
         emd_section(30, 10, a.reps, a.out) if a.section == "emd30" else emd_section(150, 1, max(3, a.reps // 4), a.out)
+        return
+    if a.section == "fpd":
+        fpd_section(a)
         return
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
