@@ -307,7 +307,9 @@ int mpg_splitk_reduce_group_dw(const MpgReduceJob* jobs, int n, const MpgEdgeDw*
  * i.e. what nn.MultiheadAttention does between its in- and out-projection as called by MAB.forward
  * (gapt/model.py:127-129).  q [B*L, ldq], k/v [B*S, ldk/ldv], o [B*L, ldo] hold the H heads side by
  * side (head h = columns h*d .. h*d+d-1); P (B*H*L*S floats, layout private to the pair of kernels) is written by fwd and read by bwd;
- * ignore [B*S] floats (1 = padded key) or NULL.  bwd takes d_o = dL/do and writes dq, dk, dv. */
+ * ignore [B*S] floats (1 = padded key) or NULL.  bwd takes d_o = dL/do and writes dq, dk, dv.
+ * A query whose keys are all ignored gets zero attention weights (torch's _safe_softmax meaning); all outputs and gradients
+ * stay finite. */
 typedef struct MpgAttn {
     const float* q; const float* k; const float* v; int ldq, ldk, ldv;
     const float* ignore;
@@ -426,7 +428,9 @@ int mpg_bridge_bwd(const MpgBridgeBwd* p, void* stream);
  * bwd recomputes q, k, v, P and u from x, y and save_z, and writes the input gradients dx (dy when y != x) and the three
  * pre-activation gradients whose products with (x | y, save_o, save_z) are the weight gradients:
  *   dq [B*L, :E] / dk, dv [B*S] (row strides lddq / lddkv), dza, du [B*L, E].
- * WinT / WoT / WfT: bf16 images of the transposed weights ([E, 3E], [E, E], [E, E], scale 1). */
+ * WinT / WoT / WfT: bf16 images of the transposed weights ([E, 3E], [E, E], [E, E], scale 1).
+ * A query whose keys are all ignored gets zero attention weights (o = 0, za = x + bo) on every kernel behind these entry
+ * points, mpg_mab_chain_fwd included; all outputs and gradients stay finite (tests/test_gpu_mab_masks.py). */
 typedef struct MpgMab {
     const float* x; int ldx;
     const float* y; int ldy;

@@ -74,10 +74,11 @@ __global__ __launch_bounds__(256) void attn_fwd_fast(const MpgAttn p) {
         sc[s] = x;
         mx = fmaxf(mx, x);
     }
+    const float msafe = mx == -INFINITY ? 0.f : mx;   // (a query whose keys are all ignored: every term below is 0)
     float den = 0.f;
 #pragma unroll
-    for (int s = 0; s < AT_S; ++s) { sc[s] = __expf(sc[s] - mx); den += sc[s]; }
-    const float inv = 1.f / den;
+    for (int s = 0; s < AT_S; ++s) { sc[s] = __expf(sc[s] - msafe); den += sc[s]; }
+    const float inv = den > 0.f ? 1.f / den : 0.f;     // (... and gets zero attention weights)
     float o[D];
 #pragma unroll
     for (int c = 0; c < D; ++c) o[c] = 0.f;
@@ -224,13 +225,14 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const MpgAttn p) {
             prow[s] = sc;
             mx = fmaxf(mx, sc);
         }
+        const float msafe = mx == -INFINITY ? 0.f : mx;   // (all keys ignored: zero attention weights)
         float den = 0.f;
         for (int s = 0; s < p.S; ++s) {
-            const float e = __expf(prow[s] - mx);
+            const float e = __expf(prow[s] - msafe);
             prow[s] = e;
             den += e;
         }
-        const float inv = 1.f / den;
+        const float inv = den > 0.f ? 1.f / den : 0.f;
         float o[DMAX];
         for (int c = 0; c < d; ++c) o[c] = 0.f;
         for (int s = 0; s < p.S; ++s) {

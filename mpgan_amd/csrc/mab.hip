@@ -383,11 +383,12 @@ MPG_DEV void mab_fwd_jet(const MpgMab& p, f32x16 (&xt)[NT], const f32x16* yt, co
 #pragma unroll
             for (int i = 0; i < 16; ++i) { s[i] = s[i] * sc2 + kneg[i]; mx = fmaxf(mx, s[i]); }
             mx = fmaxf(mx, other_half(mx));
+            const float msafe = mx == -INFINITY ? 0.f : mx;   // (a query whose keys are all ignored: every term below is 0)
             float den = 0.f;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { s[i] = __builtin_amdgcn_exp2f(s[i] - mx); den += s[i]; }
+            for (int i = 0; i < 16; ++i) { s[i] = __builtin_amdgcn_exp2f(s[i] - msafe); den += s[i]; }
             den += other_half(den);
-            const float pn = MAB_SP / den;
+            const float pn = den > 0.f ? MAB_SP / den : 0.f;   // (... and gets zero attention weights)
             V ph[2], pl[2];
             tile_frag(s, 0, pn, ph[0], pl[0]);
             tile_frag(s, 1, pn, ph[1], pl[1]);
@@ -722,11 +723,12 @@ MPG_DEV void mab_fwd_half(const MpgMab& p, f16x8* xh, f16x8* xl, const f16x8* yh
 #pragma unroll
             for (int i = 0; i < 16; ++i) { sc[i] = sc[i] * sc2 + kneg[i]; mx = fmaxf(mx, sc[i]); }
             mx = fmaxf(mx, other_half(mx));
+            const float msafe = mx == -INFINITY ? 0.f : mx;   // (a query whose keys are all ignored: every term below is 0)
             float den = 0.f;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { sc[i] = __builtin_amdgcn_exp2f(sc[i] - mx); den += sc[i]; }
+            for (int i = 0; i < 16; ++i) { sc[i] = __builtin_amdgcn_exp2f(sc[i] - msafe); den += sc[i]; }
             den += other_half(den);
-            const float pn = MAB_SP / den;
+            const float pn = den > 0.f ? MAB_SP / den : 0.f;   // (... and gets zero attention weights)
             V ph[2], pl[2];
             tile_frag(sc, 0, pn, ph[0], pl[0]);
             tile_frag(sc, 1, pn, ph[1], pl[1]);
@@ -1199,11 +1201,13 @@ __global__ __launch_bounds__(256) void mab_bwd_kernel(const MpgMab p) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) { s[i] = s[i] * sc2 + kneg[i]; mx = fmaxf(mx, s[i]); }
             mx = fmaxf(mx, other_half(mx));
+            const float msafe = mx == -INFINITY ? 0.f : mx;   // (a query whose keys are all ignored: zero weights, as in mab_bwdS_kernel)
             float den = 0.f;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { s[i] = __builtin_amdgcn_exp2f(s[i] - mx); den += s[i]; }
+            for (int i = 0; i < 16; ++i) { s[i] = __builtin_amdgcn_exp2f(s[i] - msafe); den += s[i]; }
             den += other_half(den);
-            const float inv_den = 1.f / den, cq = mx + __builtin_amdgcn_logf(den);   // log2
+            const bool qlive = den > 0.f;
+            const float inv_den = qlive ? 1.f / den : 0.f, cq = qlive ? mx + __builtin_amdgcn_logf(den) : INFINITY;   // log2
             const f32x16 dP = mfma3(vbh, vbl, dobh, dobl, zero16());
             float D = 0.f;
 #pragma unroll
@@ -1747,11 +1751,13 @@ MPG_DEV void mab_bwd2_body(const MpgMab& p) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) { s[i] = s[i] * sc2 + kneg[i]; mx = fmaxf(mx, s[i]); }
             mx = fmaxf(mx, other_half(mx));
+            const float msafe = mx == -INFINITY ? 0.f : mx;   // (a query whose keys are all ignored: zero weights, as in mab_bwdS_kernel)
             float den = 0.f;
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { s[i] = __builtin_amdgcn_exp2f(s[i] - mx); den += s[i]; }
+            for (int i = 0; i < 16; ++i) { s[i] = __builtin_amdgcn_exp2f(s[i] - msafe); den += s[i]; }
             den += other_half(den);
-            const float inv_den = 1.f / den, cq = mx + __builtin_amdgcn_logf(den);
+            const bool qlive = den > 0.f;
+            const float inv_den = qlive ? 1.f / den : 0.f, cq = qlive ? mx + __builtin_amdgcn_logf(den) : INFINITY;   // log2
             const f32x16 dP = mfma3(vbh, vbl, dobh, dobl, zero16());
             float D = 0.f;
 #pragma unroll

@@ -13,6 +13,7 @@ gradients and outputs are stored in full.
 
 Run:  python tests/gen_golden.py          (no-op with a message if /root/reference is absent)
       python tests/gen_golden.py fixtures (published weights, drop-in records: see ``fixtures``)
+      python tests/gen_golden.py mab_masks (the attention block on the key-mask catalogue alone: see ``mab_masks``)
 """
 import json
 import os
@@ -554,7 +555,7 @@ def main():
                     f"{loss}_G_loss": G_loss.item(), f"{loss}_dG_df": gg.numpy()})
         print("loss", loss, D_loss.item(), G_loss.item())
     np.savez_compressed(os.path.join(OUT, "losses.npz"), **rec)
-    return 0
+    return mab_masks()
 
 
 PART_BYTES = 900 * 1024   # a committed file stays below 1 MiB: larger fixtures are split into <stem>.npz, <stem>.part1.npz, ...
@@ -573,6 +574,69 @@ def save_parts(stem, arrays):
     parts.append(cur)
     for i, p in enumerate(parts):
         np.savez_compressed(os.path.join(OUT, stem + (".npz" if i == 0 else f".part{i}.npz")), **p)
+
+
+def mab_masks():
+    """The reference's own ``gapt.model.MAB`` in fp64 on the key-mask catalogue of tests/test_mab_masks_cpu.py -- whole key
+    tiles of 32 ignored, single real keys, the jet with no real key -- at (L, S) = (70, 70) and (1, 70), E = 64, with and without
+    ``layer_norm``, forward and backward: ``mab_masks_f64.npz`` (inputs, mask names, per-jet summaries of the outputs and
+    input gradients, summaries of the parameter gradients).  The jet whose keys are all ignored stays in only if the installed
+    torch gives it finite rows on the route the reference takes (``<case>__jets`` lists the jets a case ran)."""
+    if not os.path.isdir(REF):
+        print(f"reference not found at {REF}; nothing generated")
+        return 0
+    sys.path.insert(0, REF)
+    sys.path.insert(0, HERE)
+    import gapt as rga  # reference
+    from test_mab_masks_cpu import catalogue, DEAD
+    os.makedirs(OUT, exist_ok=True)
+    dt, E, H, S = torch.float64, 64, 4, 70
+    names, ign = catalogue(S)
+    P = len(names)
+    f32 = lambda t: t.float().to(dt)      # (inputs are float32 values, stored as such: half the bytes, exact in fp64)
+    y_all = f32(seeded((P, S, E), 471, 0.5))
+    rec = {"names": np.array(names), "ignore": ign.numpy(), "y": y_all.numpy().astype(np.float32)}
+    for L in (70, 1):
+        x_all = y_all if L == S else f32(seeded((P, L, E), 472, 0.5))
+        g_all = f32(seeded((P, L, E), 473))
+        if L != S:
+            rec[f"L{L}__x"] = x_all.numpy().astype(np.float32)
+        rec[f"L{L}__g"] = g_all.numpy().astype(np.float32)
+        for ln in (False, True):
+            args = dict(embed_dim=E, num_heads=H, ff_layers=[], final_linear=False, layer_norm=ln, dropout_p=0.0,
+                        linear_args={"leaky_relu_alpha": 0.2, "dropout_p": 0.0})
+
+            def run(keep):
+                blk = rga.model.MAB(**args).to(dt)
+                shapes = {"mab." + k: tuple(v.shape) for k, v in blk.state_dict().items()}   # (the names the block has inside a SAB)
+                blk.load_state_dict({k[len("mab."):]: v for k, v in init_state_dict(shapes, seed=70 + int(ln), dtype=dt).items()})
+                B = len(keep)
+                x = x_all[keep].clone().requires_grad_(True)
+                y = x if L == S else y_all[keep].clone().requires_grad_(True)
+                out = blk(x, y, ign[keep].reshape(B, 1, S).repeat(1, L, 1))     # (the [B, L, S] mask SAB / PMA hand a MAB)
+                (out * g_all[keep]).sum().backward()
+                # per jet: sum, l2 and 64 sampled entries of the output and of the input gradients
+                r = {"out": np.stack([summarize("out", out[b]) for b in range(B)]),
+                     "dx": np.stack([summarize("dx", x.grad[b]) for b in range(B)])}
+                if L != S:
+                    r["dy"] = np.stack([summarize("dy", y.grad[b]) for b in range(B)])
+                for k, q in blk.named_parameters():
+                    r["grad__" + k] = summarize(k, q.grad)
+                return r
+            keep = list(range(P))
+            r = run(keep)
+            dead_ok = all(np.isfinite(v).all() for v in r.values())
+            if not dead_ok:
+                keep = [i for i, n in enumerate(names) if n != DEAD]
+                r = run(keep)
+                assert all(np.isfinite(v).all() for v in r.values())
+            tag = f"L{L}_ln{int(ln)}"
+            rec[f"{tag}__jets"] = np.array(keep)
+            for k, v in r.items():
+                rec[f"{tag}__{k}"] = v
+            print("mab masks", tag, "dead jet finite on the reference's route:", dead_ok, float(np.abs(r["out"]).max()))
+    save_parts("mab_masks_f64", rec)
+    return 0
 
 
 def fixtures():
@@ -657,4 +721,4 @@ def fixtures():
 
 
 if __name__ == "__main__":
-    sys.exit(fixtures() if sys.argv[1:] == ["fixtures"] else main())
+    sys.exit(fixtures() if sys.argv[1:] == ["fixtures"] else mab_masks() if sys.argv[1:] == ["mab_masks"] else main())

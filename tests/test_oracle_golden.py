@@ -240,6 +240,40 @@ def test_loss_branches_vs_reference(loss):
     assert np.abs(gg.numpy() - g[f"{loss}_dG_df"]).max() < 1e-12 * max(1.0, np.abs(g[f"{loss}_dG_df"]).max())
 
 
+@pytest.mark.parametrize("L", [70, 1])
+@pytest.mark.parametrize("ln", [False, True], ids=["plain", "layer_norm"])
+def test_mab_on_the_mask_catalogue_f64(L, ln):
+    """``oracle.gapt_ref.mab_forward`` against the reference's own ``gapt.model.MAB`` (fp64) on the key-mask catalogue of
+    tests/test_mab_masks_cpu.py at 70 keys -- whole key tiles ignored, single real keys and, where the reference's route gives it
+    finite rows (torch >= 2.5: ``_safe_softmax``), the jet with no real key: per-jet summaries of the output and the input
+    gradients, summaries of the parameter gradients, <= 1e-10."""
+    from test_mab_masks_cpu import catalogue, DEAD
+    g = load_golden("mab_masks_f64.npz")
+    S, E = 70, 64
+    names, ign = catalogue(S)
+    assert names == [str(n) for n in g["names"]] and np.array_equal(ign.numpy(), g["ignore"])   # (the catalogue the golden was made on)
+    tag = f"L{L}_ln{int(ln)}"
+    keep = [int(i) for i in g[f"{tag}__jets"]]
+    assert names.index(DEAD) in keep      # (torch 2.10 goldens: the dead jet is pinned by the reference itself)
+    sd = {k: v.requires_grad_(True) for k, v in T.init_state_dict(ln_sab_shapes() if ln else _mab_shapes("mab"), 70 + int(ln), torch.float64).items()}
+    y_all = torch.from_numpy(g["y"]).double()
+    x = (y_all if L == S else torch.from_numpy(g[f"L{L}__x"]).double())[keep].clone().requires_grad_(True)
+    y = x if L == S else y_all[keep].clone().requires_grad_(True)
+    out = oracle.mab_forward(sd, "mab", x, y, ign[keep], num_heads=4, layer_norm=ln)
+    (out * torch.from_numpy(g[f"L{L}__g"]).double()[keep]).sum().backward()
+    assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(x.grad).all())
+    checks = [("out", out.detach()), ("dx", x.grad)] + ([] if L == S else [("dy", y.grad)])
+    for what, t in checks:
+        ref = g[f"{tag}__{what}"]
+        scale = np.abs(ref[:, 1:]).max()
+        for j, b in enumerate(keep):
+            got = summarize(what, t[j])
+            # (a jet is held to its own magnitude, with a floor of 1e-3 of the batch's for rows that are identically zero)
+            assert np.abs(got - ref[j]).max() <= 1e-10 * max(np.abs(ref[j][1:]).max(), 1e-3 * scale), (what, names[b])
+    for k, v in sd.items():
+        assert rel_err(summarize(k[len("mab."):], v.grad), g[f"{tag}__grad__{k[len('mab.'):]}"]) < 1e-10, k
+
+
 def ln_sab_shapes(E=64):
     sh = dict(T._mab_shapes("mab", E))
     for n in ("norm1", "norm2"):
