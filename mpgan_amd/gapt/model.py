@@ -125,14 +125,12 @@ class MAB(nn.Module):
 
     @staticmethod
     def _ignore_of(y_mask, B: int, S: int):
-        """The float key mask [B*S] (1 = ignore) the kernels take, from the bool / float mask the blocks pass around."""
+        """The float key mask [B*S] (1 = ignore) the kernels take, from the bool / float mask [B, S] or [B, L, S] the blocks pass
+        around: a view (no copy, no launch) of a float [B, S] mask that is contiguous or the slice ``[:, :, 0]`` of a [B, S, 1] one."""
         if y_mask is None:
             return None
-        ignore = getattr(y_mask, "_mpg_ignore", None)  # float key mask prepared once per network forward
-        if ignore is None or ignore.numel() != B * S:
-            km = y_mask if y_mask.dim() == 2 else y_mask[:, 0, :]
-            ignore = km.reshape(B * S).float().contiguous()
-        return ignore
+        km = y_mask if y_mask.dim() == 2 else y_mask[:, 0, :]
+        return km.reshape(B * S).float().contiguous()
 
     # -- the whole block as one launch (ops.mab_forward; csrc/mab.hip) ------------------------------------------
     def _fused_ok(self, x: Tensor, L: int, S: int) -> bool:
@@ -267,30 +265,17 @@ def _same_block_config(a: "MAB", b: "MAB") -> bool:
 
 
 def _attn_mask(mask: Tensor) -> Optional[Tensor]:
-    """JetNet mask (1 real, 0 padded) -> attention convention (True = ignore).  The float form the attention kernels
-    take ([B*N], 1 = ignore) rides along as an attribute, so that the blocks of a network do not each convert it."""
+    """JetNet mask [B, N, 1] (1 real, 0 padded) -> attention convention (True = ignore).  On the GPU it stays the float tensor
+    (1 = ignore) whose [B*N] view the attention kernels take (``MAB._ignore_of``): a bool copy would be one more launch per forward."""
     if mask is None:
         return None
-    return _ignore_mask(1 - mask)
-
-
-def _ignore_mask(inv: Tensor) -> Tensor:
-    """[B, N, 1] floats, 1 = ignore, as the attention mask the blocks pass around.  On the GPU the float tensor itself
-    travels (the kernels read it through ``_mpg_ignore``; a bool copy would be one more launch per forward)."""
-    am = inv if inv.is_cuda else inv.bool()
-    am._mpg_ignore = inv.reshape(-1).contiguous()
-    return am
+    inv = 1 - mask
+    return inv if inv.is_cuda else inv.bool()
 
 
 def _key_mask(mask: Optional[Tensor]) -> Optional[Tensor]:
-    """[B,N,1] attention mask -> the [B,N] key mask a MAB takes (keeping the prepared float form attached)."""
-    if mask is None:
-        return None
-    km = mask[:, :, 0]
-    ig = getattr(mask, "_mpg_ignore", None)
-    if ig is not None:
-        km._mpg_ignore = ig
-    return km
+    """[B,N,1] attention mask -> the [B,N] key mask a MAB takes."""
+    return None if mask is None else mask[:, :, 0]
 
 
 def _sab_args(embed_dim, sab_fc_layers, num_heads, layer_norm, dropout_p, linear_args):
@@ -318,7 +303,7 @@ class GAPT_G(nn.Module):
             return None, None
         if x.is_cuda:
             mask, ign = ops.rank_mask(x[:, :, 0], labels, self.num_particles, with_ignore=True)
-            return mask.unsqueeze(2), _ignore_mask(ign.unsqueeze(2))
+            return mask.unsqueeze(2), ign.unsqueeze(2)
         mask = _rank_mask(x[:, :, 0], labels, self.num_particles)
         return mask, _attn_mask(mask)
 
@@ -348,8 +333,7 @@ class GAPT_G(nn.Module):
             mask2d, ign = ops.rank_mask(x[:, :, 0], labels, self.num_particles, out=None if mask_out is None else mask_out.view(B, -1),
                                         with_ignore=True, ignore_out=None if ign_out is None else ign_out.view(B, -1))
         mask = mask2d.unsqueeze(2)
-        am = _ignore_mask(ign.unsqueeze(2))
-        x = _run_sabs(self.sabs, x, am)
+        x = _run_sabs(self.sabs, x, ign.unsqueeze(2))
         x = self.final_fc(x)
         if feat_out is not None:
             assert not torch.is_grad_enabled()
@@ -376,7 +360,7 @@ class GAPT_G(nn.Module):
         else:
             mask2d, ign = ops.rank_mask(x[:, :, 0], labels, self.num_particles, out=None if mask_out is None else mask_out.view(B, -1),
                                         with_ignore=True, ignore_out=None if ign_out is None else ign_out.view(B, -1))
-        return _run_sabs(self.sabs, x, _ignore_mask(ign.unsqueeze(2))), mask2d.unsqueeze(2), ign
+        return _run_sabs(self.sabs, x, ign.unsqueeze(2)), mask2d.unsqueeze(2), ign
 
     def generate_into(self, x: Tensor, labels: Tensor, out: Tensor) -> Tensor:
         """``forward`` into caller-owned output rows, no gradient (``train.TrainStep``'s D step)."""
@@ -419,9 +403,9 @@ class GAPT_D(nn.Module):
             if x.is_cuda and ops.double_backward_on(x.device):
                 # interpolated jets (gradient penalty) carry fractional mask values: the reference's own order of operations,
                 # so that "exactly 1" is decided on the same roundings
-                am = _ignore_mask(1 - (x.detach()[..., -1:] + 0.5))
+                am = 1 - (x.detach()[..., -1:] + 0.5)
             else:
-                am = _ignore_mask(0.5 - x.detach()[..., -1:])   # (no gradient flows through the mask column: :336-338, bool mask)
+                am = 0.5 - x.detach()[..., -1:]   # (no gradient flows through the mask column: :336-338, bool mask)
             x = x[..., :-1]
         x = self.input_embedding(x)   # (a column slice of the [.., 4] rows: the GEMM takes the row stride as it is)
         x = _run_sabs(self.sabs, x, am)
@@ -434,7 +418,7 @@ class GAPT_D(nn.Module):
         """``features`` for callers that hold the particle features [B, N, F], the mask and 1 - mask [B, N] apart."""
         B, N = x3.shape[:2]
         inv = (1 - mask) if ignore is None else ignore
-        am = _ignore_mask(inv.reshape(B, N, 1))
+        am = inv.reshape(B, N, 1)
         x = self.input_embedding(x3)
         x = _run_sabs(self.sabs, x, am)
         return self.pma(x, am), None
@@ -457,7 +441,7 @@ class GAPT_D(nn.Module):
         B = pre.shape[0] if feat_buf is None else feat_buf.shape[0]
         N = pre.shape[1]
         inv = (1 - mask) if ignore is None else ignore
-        am = _ignore_mask(inv.reshape(B, N, 1))
+        am = inv.reshape(B, N, 1)
         _, x = ops.GenDiscBridgeFn.apply(pre, W1, b1, feat_buf, W2, b2, act1, True, alpha, p, self.training)
         x = _run_sabs(self.sabs, x, am)
         return self.pma(x, am), None

@@ -275,7 +275,8 @@ class MPLayer(nn.Module):
         return self.fn(h.contiguous()).reshape(B, N, self.output_node_size)
 
     def forward(self, x: Tensor, use_mask: bool = False, mask: Tensor = None, labels: Tensor = None,
-                num_jet_particles: Tensor = None) -> Tensor:
+                num_jet_particles: Tensor = None, *, handoff: "ops.LayerHandoff" = None) -> Tensor:
+        """``handoff`` (not in the reference signature): this call's link to the layers around it, from ``MPNet._run_layers``."""
         assert not (use_mask and mask is None), "need ``mask`` tensor if using ``use_mask`` option"
         assert not (self.clabels and labels is None), "need ``labels`` tensor if using ``clabels`` option"
         assert not (self.mask_fne_np and num_jet_particles is None), "need ``num_jet_particles`` tensor if using ``mask_fne_np`` option"
@@ -296,26 +297,19 @@ class MPLayer(nn.Module):
         else:
             packed = self._packed()
         # consecutive fused layers of a network hand each other the layer-1 node terms a | c (ops.LayerHandoff): the launch
-        # that produces a layer's output rows also projects them for the next layer
-        handoff = None
-        nxt = self.__dict__.get("_next_layer")
-        ac_in = getattr(x, "_mpg_ac", None)
-        # (x straight out of another fused layer: this layer's backward may run that layer's input-gradient chain in its own launch)
-        prev_node = x.grad_fn if (x.grad_fn is not None and type(x.grad_fn).__name__ == "FusedMPLayerFnBackward") else None
-        if packed is not None and (ac_in is not None or nxt is not None or prev_node is not None):
-            nx = None
-            if nxt is not None and nxt.fused and not nxt._diff_cols and nxt.training == self.training and nxt.n_es == 0:
-                nx = (nxt._packed(), nxt.fe.net[0].bias)
-            handoff = ops.LayerHandoff(next=nx, ac_in=ac_in, prev_node=prev_node)
-        y = ops.FusedMPLayerFn.apply(
+        # that produces a layer's output rows also projects them for the layer above
+        if handoff is not None:
+            nxt = handoff.above
+            if packed is None:   # (images packed for this call: nothing from below fits them; the layer above may still take its chain)
+                handoff.below = None
+            elif nxt is not None and nxt.fused and not nxt._diff_cols and nxt.training == self.training and nxt.n_es == 0:
+                handoff.next = (nxt._packed(), nxt.fe.net[0].bias)
+        return ops.FusedMPLayerFn.apply(
             x, mask if use_mask else None,
             W1, fe[0].bias, fe[1].weight, fe[1].bias, fe[2].weight, fe[2].bias,
-            fn[0].weight, fn[0].bias, fn[1].weight, fn[1].bias, fn[2].weight, fn[2].bias,
-            self.sum, self.fe.leaky_relu_alpha, self.fe.dropout_p, self.training, packed, nbr, self.num_knn,
-            es, self.n_es, xfn, handoff, not torch.is_grad_enabled())
-        if handoff is not None and handoff.ac_out is not None:
-            y._mpg_ac = handoff.ac_out
-        return y
+            fn[0].weight, fn[0].bias, fn[1].weight, fn[1].bias, fn[2].weight, fn[2].bias, es, xfn,
+            ops.MPLayerSettings(self.sum, self.fe.leaky_relu_alpha, self.fe.dropout_p, self.training, packed, nbr, self.num_knn,
+                                self.n_es, handoff, not torch.is_grad_enabled()))
 
     def _folded_w1(self, W1: Tensor) -> Tensor:
         """fe.net.0.weight with the coordinate-difference columns folded into the node columns: the reference appends
@@ -412,12 +406,13 @@ class MPNet(nn.Module):
                                           **linear_args))
 
     def _run_layers(self, x, use_mask, mask, labels, njp):
-        """The loop over ``mp_layers`` (mpgan/model.py:511-512).  Each layer is told which layer takes its output (a transient
-        attribute, set per call: ``nn.DataParallel`` replicas then see their own device's layers)."""
-        n = len(self.mp_layers)
-        for k, layer in enumerate(self.mp_layers):
-            layer.__dict__["_next_layer"] = self.mp_layers[k + 1] if k + 1 < n else None
-            x = layer(x, use_mask, mask, labels, njp)
+        """The loop over ``mp_layers`` (mpgan/model.py:511-512).  It owns the coupling of consecutive layers: each call gets its
+        own ``ops.LayerHandoff``, which names the handoff of the layer below and the layer above (objects of this pass alone:
+        ``nn.DataParallel`` replicas, each on its own thread, never share one)."""
+        handoff = None
+        for layer, above in zip(self.mp_layers, [*self.mp_layers[1:], None]):
+            handoff = ops.LayerHandoff(handoff, above)
+            x = layer(x, use_mask, mask, labels, njp, handoff=handoff)
         return x
 
     def forward(self, x: Tensor, labels: Tensor = None) -> Tensor:

@@ -11,6 +11,7 @@ import itertools
 import os
 import sys
 import threading
+from collections import namedtuple
 from typing import Optional
 
 import torch
@@ -632,39 +633,50 @@ def dw_workgroups(nblk, N):
     return min(nruns, max(256, -(-nruns // (64 // R))))
 
 
+# What ``FusedMPLayerFn.forward`` saves for its backward, in ``save_for_backward`` order (entries a call has no use for are None) ...
+MPLayerSaved = namedtuple("MPLayerSaved", "x2 m1 ac agg h1 h2 W1 b2 b3 W2 W3 V1 V2 V3 sign3 nbr stE2 es wq xf2 order")
+# ... and the non-tensor state of the call that the backward needs (``ctx.cfg``)
+MPLayerCfg = namedtuple("MPLayerCfg", "B N F agg_scale alpha thr dscale tag SC f16 nq")
+# Everything ``FusedMPLayerFn.apply`` takes that is not a tensor with a gradient (see its ``forward``)
+MPLayerSettings = namedtuple("MPLayerSettings", "sum_agg alpha p_drop training packed nbr num_knn nq handoff no_grad",
+                             defaults=(None, None, 0, 0, None, False))
+
+
+def mplayer_saved(node):
+    """The saved tensors of a ``FusedMPLayerFn`` backward node (the ``grad_fn`` behind a fused MPLayer's output), by name."""
+    return MPLayerSaved(*node.saved_tensors)
+
+
 def _fn_grad_chain(ctx, gy2):
     """Buffers and the ``MpgChain`` block of the node network's input-gradient chain of the layer behind ``ctx`` (the backward
     of mpgan/model.py:279) for the upstream gradient rows ``gy2`` [B*N, out]: (dz3, dz2, dz1, dh0, chain)."""
-    x2, m1, ac, agg, h1, h2, W1, b2, b3, W2, W3, V1, V2, V3 = ctx.saved_tensors[:14]
-    pk = ctx.packed
-    B, N, F, agg_scale, alpha, thr, dscale, tag = ctx.cfg[:8]
-    V, dev = B * N, gy2.device
+    sv, cfg, pk = mplayer_saved(ctx), ctx.cfg, ctx.packed
+    V1, V2, V3, alpha, thr, dscale, tag = sv.V1, sv.V2, sv.V3, cfg.alpha, cfg.thr, cfg.dscale, cfg.tag
+    V, dev = cfg.B * cfg.N, gy2.device
     n1, n2, out_f = V1.shape[0], V2.shape[0], V3.shape[0]
     dz3 = torch.empty_like(gy2) if thr else gy2
     dz2 = torch.empty((V, n2), device=dev, dtype=torch.float32)
     dz1 = torch.empty((V, n1), device=dev, dtype=torch.float32)
     dh0 = torch.empty((V, V1.shape[1]), device=dev, dtype=torch.float32)  # [dagg | dx(node path) | (conditioning columns)]
-    c = chain_struct(V, [dict(img=pk.ptr("V3T"), K=out_f, N=n2, gate=(h2, True, tag + TAG_N1, thr, dscale), out=dz2),
-                         dict(img=pk.ptr("V2T"), K=n2, N=n1, gate=(h1, True, tag + TAG_N0, thr, dscale), out=dz1),
+    c = chain_struct(V, [dict(img=pk.ptr("V3T"), K=out_f, N=n2, gate=(sv.h2, True, tag + TAG_N1, thr, dscale), out=dz2),
+                         dict(img=pk.ptr("V2T"), K=n2, N=n1, gate=(sv.h1, True, tag + TAG_N0, thr, dscale), out=dz1),
                          dict(img=pk.ptr("V1T"), K=n1, N=V1.shape[1], out=dh0)],
                      A=gy2, lda=gy2.stride(0), K1=out_f, in_gate=(tag + TAG_N2, thr, dscale), in_out=dz3 if thr else None,
                      alpha=alpha, seed_t=seed_tensor(dev), f16=False)
     return dz3, dz2, dz1, dh0, c
 
 
-def _below_chain(prev, dx, x2, thr, alpha, V):
+def _below_chain(prev, dx, thr, alpha, V):
     """``_fn_grad_chain`` of the layer that produced this layer's input (``prev``: its backward context), fed with this layer's
     ``dx`` rows -- or None when that layer cannot take it: not a fused layer's direct output, another dropout mode or slope,
-    rows that are not this layer's x, no backward pending there."""
+    another number of rows, no backward pending there."""
     if prev is None or getattr(prev, "cfg", None) is None or getattr(prev, "packed", None) is None:
         return None
     try:
-        saved = prev.saved_tensors
+        sv, cfg = mplayer_saved(prev), prev.cfg
     except RuntimeError:   # (already released: its backward has run)
         return None
-    pB, pN, pF, _, palpha, pthr, _, _ = prev.cfg[:8]
-    h1, h2, V3 = saved[4], saved[5], saved[13]
-    if h1 is None or h2 is None or pB * pN != V or V3.shape[0] != dx.shape[1] or pthr != thr or palpha != alpha:
+    if sv.h1 is None or sv.h2 is None or cfg.B * cfg.N != V or sv.V3.shape[0] != dx.shape[1] or (cfg.thr, cfg.alpha) != (thr, alpha):
         return None
     if not any(prev.needs_input_grad):
         return None
@@ -672,16 +684,21 @@ def _below_chain(prev, dx, x2, thr, alpha, V):
 
 
 class LayerHandoff:
-    """What consecutive fused MPLayers of one network pass to each other around ``FusedMPLayerFn`` (``MPNet`` wires it):
-    ``next`` = (PackedMPLayer, fe.net.0.bias) of the layer that will take this layer's output; ``ac_in`` / ``ac_out`` =
-    (a | c [B*N, 192], the PackedMPLayer whose W1 image produced it, data pointer of the rows it was computed from, that
-    set's parameter key)."""
-    __slots__ = ("next", "ac_in", "ac_out", "prev_node")
+    """What one fused MPLayer of a network pass receives from the layer below and leaves for the layer above.  The loop over
+    the layers (``MPNet._run_layers``) makes one per layer and pass and hands it in as ``handoff=``; nothing is kept on modules
+    or tensors.  ``below``: the handoff of the layer below; ``above``: the layer that takes this layer's output; ``next``:
+    (PackedMPLayer, fe.net.0.bias) of ``above`` when this layer's launch may project its output rows for it (set by
+    ``MPLayer.forward``).  ``FusedMPLayerFn.forward`` leaves ``ac_out`` = (a | c [B*N, 192], the PackedMPLayer whose W1 image
+    produced it, data pointer of the rows it was computed from, that set's parameter key) where its edge launch ran that
+    projection, and ``node`` = its ``ctx`` (the ``grad_fn`` of its output) when a backward is pending.  Both are offers: the layer
+    above takes ``ac_out`` only for those very rows and images, and runs this layer's input-gradient chain in its own backward
+    launch (``_below_chain``) only when its ``x`` is that node's output itself -- a hook or a ``.to()`` between two layers costs
+    launches, never a value.  A bare ``MPLayer`` called outside such a loop, on another fused layer's output too, gets no handoff
+    and so takes one launch per piece, with the same bits."""
+    __slots__ = ("below", "above", "next", "ac_out", "node")
 
-    def __init__(self, next=None, ac_in=None, prev_node=None):
-        # prev_node: the autograd node (a FusedMPLayerFn backward context) that produced this layer's x, or None -- this
-        # layer's backward may then run that layer's node-network input-gradient chain in its own launch (mpg_edge_bwd_fn)
-        self.next, self.ac_in, self.ac_out, self.prev_node = next, ac_in, None, prev_node
+    def __init__(self, below=None, above=None):
+        self.below, self.above, self.next, self.ac_out, self.node = below, above, None, None, None
 
 
 class FusedMPLayerFn(torch.autograd.Function):
@@ -689,13 +706,12 @@ class FusedMPLayerFn(torch.autograd.Function):
     features, no conditioning labels; fe = 3 layers [96,160,192], fn = 2 hidden layers + linear."""
 
     @staticmethod
-    def forward(ctx, x, mask, W1, b1, W2, b2, W3, b3, V1, c1, V2, c2, V3, c3, sum_agg, alpha, p_drop, training,
-                packed=None, nbr=None, num_knn=0, es=None, nq=0, xfn=None, handoff=None, no_grad=False):
-        """``nbr`` (from ``knn_sets``) restricts receiver i's senders to its ``num_knn`` nearest neighbours
-        (``fully_connected=False``, mpgan/model.py:319-381); the mean then divides by ``num_knn`` (:267).
+    def forward(ctx, x, mask, W1, b1, W2, b2, W3, b3, V1, c1, V2, c2, V3, c3, es, xfn, settings):
+        """``settings``: an ``MPLayerSettings``.  Its ``nbr`` (from ``knn_sets``) restricts receiver i's senders to its ``num_knn``
+        nearest neighbours (``fully_connected=False``, mpgan/model.py:319-381); the mean then divides by ``num_knn`` (:267).
 
-        ``handoff`` (a ``LayerHandoff`` or None) couples consecutive layers of a network: ``handoff.ac_in`` are this layer's
-        layer-1 node terms a | c already computed by the launch that produced ``x`` (then no projection launch here), and
+        Its ``handoff`` (a ``LayerHandoff`` or None) couples consecutive layers of a network: ``handoff.below.ac_out`` are this
+        layer's layer-1 node terms a | c already computed by the launch that produced ``x`` (then no projection launch here), and
         ``handoff.next`` is the next layer's ``(PackedMPLayer, b1)``: where this call's edge launch runs the node network as
         its epilogue it appends that layer's projection and leaves the result in ``handoff.ac_out``.
 
@@ -703,6 +719,7 @@ class FusedMPLayerFn(torch.autograd.Function):
         columns of the reference (mpgan/model.py:247-253, :297-313), one scalar per edge each; they multiply the columns
         ``W1[:, 2F : 2F + nq]`` (``Z1 = a_i + c_j + sum_q es_q w_q``) and get a gradient.  ``xfn`` [B, N, F + E]: the node
         network's view of the nodes when conditioning columns are appended to it (:270-276); ``V1`` then has E more columns."""
+        sum_agg, alpha, p_drop, training, packed, nbr, num_knn, nq, handoff, no_grad = settings
         _chk(x, "x")
         B, N, F = x.shape
         V = B * N
@@ -725,8 +742,9 @@ class FusedMPLayerFn(torch.autograd.Function):
 
         # layer-1 node terms a | c = x [W1a ; W1c]^T (+ b1 on the a half): handed over by the launch that produced x, or one launch
         ac = None
-        if handoff is not None and handoff.ac_in is not None:
-            ac_pre, pk_pre, x_ptr, key_pre = handoff.ac_in   # (valid for these very rows and the weight images as they are now)
+        below = handoff.below if handoff is not None else None
+        if below is not None and below.ac_out is not None:
+            ac_pre, pk_pre, x_ptr, key_pre = below.ac_out   # (valid for these very rows and the weight images as they are now)
             if pk_pre is pk and key_pre == pk._key and x_ptr == x2.data_ptr() and tuple(ac_pre.shape) == (V, 2 * H1):
                 ac = ac_pre
         if ac is None:
@@ -822,19 +840,22 @@ class FusedMPLayerFn(torch.autograd.Function):
                 agg = agg + aggp[q]  #  then agree bit for bit; torch.sum over the chunk axis adds in another order)
             chain(V, fn_layers, A=agg, lda=H3, K1=H3, **fn_kw)
         ctx.packed = pk
-        ctx.prev_node = handoff.prev_node if (handoff is not None and need_grad) else None
+        # (x the very output of the layer below: this layer's backward may run that layer's input-gradient chain in its own launch)
+        ctx.prev_node = below.node if (below is not None and need_grad and x.grad_fn is below.node) else None
         ctx.pre = None   # filled by the backward of the layer ABOVE when it has run this layer's input-gradient chain already
+        if handoff is not None and need_grad:
+            handoff.node = ctx
 
         if need_grad and dev_state(dev).sign_tap is not None:
             dev_state(dev).sign_tap.append(dict(B=B, N=N, ac=ac, stE2=stE2, sign3=sign3, h1=h1, h2=h2))
-        ctx.save_for_backward(x2, m1, ac, agg, h1, h2, W1, b2, b3, W2, W3, V1, V2, V3, sign3, nbr, stE2, es, wq, xf2, order)
-        ctx.cfg = (B, N, F, agg_scale, alpha, thr, dscale, tag, SC, f16, nq)
+        ctx.save_for_backward(*MPLayerSaved(x2, m1, ac, agg, h1, h2, W1, b2, b3, W2, W3, V1, V2, V3, sign3, nbr, stE2, es, wq, xf2, order))
+        ctx.cfg = MPLayerCfg(B, N, F, agg_scale, alpha, thr, dscale, tag, SC, f16, nq)
         return y.reshape(B, N, V3.shape[0])
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        x2, m1, ac, agg, h1, h2, W1, b2, b3, W2, W3, V1, V2, V3, sign3, nbr, stE2, es, wq, xf2, order = ctx.saved_tensors
+        x2, m1, ac, agg, h1, h2, W1, b2, b3, W2, W3, V1, V2, V3, sign3, nbr, stE2, es, wq, xf2, order = mplayer_saved(ctx)
         pk = ctx.packed
         B, N, F, agg_scale, alpha, thr, dscale, tag, SC, f16, nq = ctx.cfg
         nbr_p = None if nbr is None else C.c_void_p(nbr.data_ptr())
@@ -846,8 +867,8 @@ class FusedMPLayerFn(torch.autograd.Function):
         def gt(H, site, act):
             return (H, H.stride(0), act, seed_t, tag + site, thr, dscale)
 
-        need_w = any(ctx.needs_input_grad[2:14])   # False in the G step: D's weights get no update there
-        need_x = ctx.needs_input_grad[0]
+        need_x, _, *need_p, _, need_xfn, _ = ctx.needs_input_grad   # (as forward's arguments: x, mask, the twelve parameters, es, xfn, settings)
+        need_w = any(need_p)   # False in the G step: D's weights get no update there
 
         # ---- node network fn (mpgan/model.py:279) backward: its input-gradient chain -- already run by the layer above as the
         #      epilogue of its data-gradient launch (ctx.pre, for exactly this upstream gradient), or launched below
@@ -918,7 +939,7 @@ class FusedMPLayerFn(torch.autograd.Function):
                 cdx = chain_struct(V, [dict(img=pk.ptr("W1ST"), K=2 * H1, N=F, resid=dh0[:, H3:H3 + F], out=dx)],
                                    A=dap, lda=H1, K1=H1, A2=dcp, lda2=H1, alpha=alpha, f16=False)
             if cdx is not None and OPTIONS["bwd_epilogue"] and es is None:
-                below = _below_chain(ctx.prev_node, dx, x2, thr, alpha, V)
+                below = _below_chain(ctx.prev_node, dx, thr, alpha, V)
                 rc = _lib.lib().mpg_edge_bwd_fn(C.byref(e), C.byref(cdx), None if below is None else C.byref(below[4]), _stream())
                 if rc == _lib.MPG_FN_NA and below is not None:   # (the pair is not covered: the layer alone may be)
                     below = None
@@ -1004,12 +1025,11 @@ class FusedMPLayerFn(torch.autograd.Function):
                           A=dap, lda=H1, K1=H1, A2=dc, lda2=dc.stride(0), alpha=alpha, f16=False)
             dx = dx.reshape(B, N, F)
         dxfn = None
-        if len(ctx.needs_input_grad) > 23 and ctx.needs_input_grad[23] and dh0.shape[1] > H3 + F:
+        if need_xfn and dh0.shape[1] > H3 + F:
             # the conditioning columns appended to the node network's input (mpgan/model.py:270-276): their gradient is the
             # tail of dh0; the x columns of xfn are the same nodes as x, whose node-path gradient is already in dx above
             dxfn = torch.cat((torch.zeros((V, F), device=dev, dtype=torch.float32), dh0[:, H3 + F:]), dim=1).reshape(B, N, -1)
-        return (dx, None, dW1, db1, dW2, db2, dW3, db3, dV1, dc1, dV2, dc2, dV3, dc3,
-                None, None, None, None, None, None, None, des, None, dxfn, None, None)[:len(ctx.needs_input_grad)]
+        return dx, None, dW1, db1, dW2, db2, dW3, db3, dV1, dc1, dV2, dc2, dV3, dc3, des, dxfn, None
 
 
 def _grad_target(t):
@@ -1583,7 +1603,7 @@ class FusedMABLayerNormFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gout):
         x2, y2, ignore, o, z, za, n1w, n1b, n2w, n2b = ctx.saved_tensors
-        B, L, S, E = ctx.cfg[:4]
+        B, L, S, E, *_ = ctx.cfg
         need = ctx.needs_input_grad
         need_ln = any(need[9:13])
         dx, dy, grads, rows = _mab_backward_block(x2, y2, ignore, o, z, ctx.params, ctx.pk, ctx.cfg, gout, need[0], need[1],

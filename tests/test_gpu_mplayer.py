@@ -100,8 +100,9 @@ def _fused_node(y):
 def _hip_signs(y, B, N):
     """Signs (True = negative) of the pre-activations the HIP forward behind ``y`` saw (``conftest.hip_signs_from``)."""
     from conftest import hip_signs_from
-    saved = _fused_node(y).saved_tensors   # (x2, m1, ac, agg, h1, h2, W1, b2, b3, W2, W3, V1, V2, V3, sign3, nbr, stE2, ...)
-    return hip_signs_from(saved[2], saved[16], saved[14], saved[4], saved[5], B, N)
+    from mpgan_amd import ops
+    saved = ops.mplayer_saved(_fused_node(y))
+    return hip_signs_from(saved.ac, saved.stE2, saved.sign3, saved.h1, saved.h2, B, N)
 
 
 def _sign_disagreements(neg, probe64, mask64):
@@ -722,12 +723,12 @@ def test_edge_scalars_separable_case_equals_node_features(p_drop, use_mask, N, a
             es = torch.stack((U.unsqueeze(1) + Vv.unsqueeze(2), torch.zeros(B, N, N, device=dev)), dim=2)   # [b, j, q, i] = u_i + v_j
             es.retain_grad()
             y = ops.FusedMPLayerFn.apply(X, mask, torch.cat((A, Cc, Ww), 1), B1, w2, bb2, w3, bb3, torch.cat((v1a, v1x), 1), cc1, v2, cc2,
-                                         v3, cc3, True, alpha, p_drop, True, None, None, 0, es, 1, None)
+                                         v3, cc3, es, None, ops.MPLayerSettings(True, alpha, p_drop, True, nq=1))
         else:
             X2 = torch.cat((X, U.unsqueeze(2), Vv.unsqueeze(2)), 2)
             W1 = torch.cat((A, Ww, z1, Cc, z1, Ww), 1)
             y = ops.FusedMPLayerFn.apply(X2, mask, W1, B1, w2, bb2, w3, bb3, torch.cat((v1a, v1x, z2), 1), cc1, v2, cc2, v3, cc3,
-                                         True, alpha, p_drop, True, None, None, 0)
+                                         None, None, ops.MPLayerSettings(True, alpha, p_drop, True))
         (y * up).sum().backward()
         return y.detach(), [q.grad for q in leaves]
 
@@ -841,8 +842,8 @@ def test_node_network_as_edge_epilogue_is_bit_identical(B, N, F, out, p_drop, us
             y = layer(x, use_mask, mask)
         res = {"y": y.detach().clone()}
         if train:
-            saved = _fused_node(y).saved_tensors
-            res.update(agg=saved[3].clone(), h1=saved[4].clone(), h2=saved[5].clone())
+            saved = ops.mplayer_saved(_fused_node(y))
+            res.update(agg=saved.agg.clone(), h1=saved.h1.clone(), h2=saved.h2.clone())
             (y * up).sum().backward()
             res["dx"] = x.grad.clone()
             res.update({k: q.grad.clone() for k, q in layer.named_parameters()})
@@ -984,6 +985,93 @@ def test_layers_hand_over_their_node_terms(which, train, two_term):
         assert torch.equal(a[k], b_[k]), (k, float((a[k] - b_[k]).abs().max()))
 
 
+_KEEP = ("mpg_chain", "mpg_edge_fwd", "mpg_edge_fwd_fn", "mpg_edge_bwd", "mpg_edge_bwd_fn")
+
+
+def _layer_pair_runs(N, shift=None):
+    """Two fused MPLayers 32 -> 32 -> 32 (default widths, dropout 0.5, training mode) on B = 2 jets, one sender chunk: the pair
+    run through ``MPNet._run_layers`` (each layer with its ``ops.LayerHandoff``) and called by hand (no handoff), same seed and
+    tags.  ``shift``: a forward pre-hook on the second layer replaces its x by x + shift in the coupled pass; the by-hand pass
+    is given that input.  Returns ((results, forward launches, backward launches) coupled, the same by hand)."""
+    import itertools
+    import os
+    from mpgan_amd import ops
+    from mpgan_amd.mpgan import MPNet
+    dev = _dev()
+    B, F = 2, 32
+    torch.manual_seed(11)
+    net = MPNet(N, F, mp_iters=2, hidden_node_size=F, linear_args={"dropout_p": 0.5}).to(dev).train()
+    lo, hi = net.mp_layers
+    assert lo.fused and hi.fused
+    rs = np.random.RandomState(40 + N)
+    x0 = torch.from_numpy(rs.normal(0, 0.5, size=(B, N, F))).float().to(dev)
+    m = np.zeros((B, N, 1))
+    for b in range(B):
+        m[b, rs.permutation(N)[: rs.randint(N // 2, N + 1)], 0] = 1
+    mask = torch.from_numpy(m).float().to(dev)
+    up = torch.from_numpy(rs.normal(size=(B, N, F))).float().to(dev)
+
+    def run(coupled):
+        ops.dev_state(dev).tags = itertools.count(123)
+        ops.set_seed(2024, dev)
+        net.zero_grad()
+        x = x0.clone().requires_grad_(True)
+        hook = hi.register_forward_pre_hook(lambda mod, args: (args[0] + shift,) + tuple(args[1:])) if (coupled and shift is not None) else None
+        calls = _count_calls(ops)
+        try:
+            if coupled:
+                y = net._run_layers(x, True, mask, None, None)
+            else:
+                y = lo(x, True, mask)
+                y = hi(y if shift is None else y + shift, True, mask)
+            fwd = [k for k in calls.names if k in _KEEP]
+            del calls.names[:]
+            (y * up).sum().backward()
+        finally:
+            calls.restore()
+            if hook is not None:
+                hook.remove()
+        res = {"y": y.detach().clone(), "dx": x.grad.clone()}
+        res.update({k: q.grad.clone() for k, q in net.named_parameters()})
+        assert len(res) == 2 + 24 and all(bool(torch.isfinite(v).all()) for v in res.values())
+        return res, fwd, [k for k in calls.names if k in _KEEP]
+
+    os.environ["MPG_FORCE_SC"] = "1"
+    try:
+        y = lo(x0, True, mask)
+        hi(y, True, mask)     # (weight images built)
+        return run(True), run(False)
+    finally:
+        os.environ.pop("MPG_FORCE_SC", None)
+
+
+@pytest.mark.parametrize("N", [30, 33])
+def test_coupled_and_uncoupled_layer_pairs_give_the_same_bits(N):
+    """Output, dx and the twelve parameter gradients of both layers: bit-identical with and without the hand-off.  N = 30 (one
+    receiver block, one sender chunk): the only form in which both epilogues and both halves of the hand-off run -- the launch
+    sequences say so.  N = 33 (two receiver blocks): the data-gradient launch takes no epilogue, so the lower layer's pending
+    chain that was handed over is quietly not used."""
+    (a, fa, ba), (b_, fb, bb) = _layer_pair_runs(N)
+    for k in a:
+        assert torch.equal(a[k], b_[k]), (k, float((a[k] - b_[k]).abs().max()))
+    if N == 30:
+        assert fa == ["mpg_chain", "mpg_edge_fwd_fn", "mpg_edge_fwd_fn"], fa
+        assert fb == ["mpg_chain", "mpg_edge_fwd_fn"] * 2, fb
+        assert ba == ["mpg_chain", "mpg_edge_bwd_fn", "mpg_edge_bwd_fn"], ba
+        assert bb == ["mpg_chain", "mpg_edge_bwd_fn"] * 2, bb
+
+
+def test_forward_pre_hook_between_layers_breaks_the_coupling_safely():
+    """A forward pre-hook on the second layer makes another tensor of x (x + 0.25): the a | c terms the lower layer's launch
+    projected (of the rows before the shift) and that layer's pending input-gradient chain are refused by the validity checks --
+    every piece takes its own launch, and all results equal the by-hand pass on the shifted input bit for bit."""
+    (a, fa, ba), (b_, fb, bb) = _layer_pair_runs(30, shift=0.25)
+    for k in a:
+        assert torch.equal(a[k], b_[k]), (k, float((a[k] - b_[k]).abs().max()))
+    assert fa == fb == ["mpg_chain", "mpg_edge_fwd_fn"] * 2, (fa, fb)
+    assert ba == bb == ["mpg_chain", "mpg_edge_bwd_fn"] * 2, (ba, bb)
+
+
 @pytest.mark.parametrize("alpha", [0.2, 1.0])
 @pytest.mark.parametrize("B,N,p_drop", [(6, 30, 0.0), (5, 30, 0.5), (4, 30, 0.3), (2, 150, 0.5), (3, 33, 0.0), (256, 30, 0.5)])
 def test_two_term_layer3_agrees_with_three_terms(B, N, p_drop, alpha):
@@ -1021,8 +1109,8 @@ def test_two_term_layer3_agrees_with_three_terms(B, N, p_drop, alpha):
         layer.zero_grad()
         x = x0.clone().requires_grad_(True)
         y = layer(x, True, mask)
-        saved = _fused_node(y).saved_tensors
-        res = {"sign3": saved[14].clone(), "stE2": saved[16].clone(), "y": y.detach().clone()}
+        saved = ops.mplayer_saved(_fused_node(y))
+        res = {"sign3": saved.sign3.clone(), "stE2": saved.stE2.clone(), "y": y.detach().clone()}
         (y * up).sum().backward()
         res["dx"] = x.grad.clone()
         res.update({k: q.grad.clone() for k, q in layer.named_parameters()})

@@ -131,6 +131,30 @@ def test_fused_backwards_decline_double_backward():
         assert "@once_differentiable\n    def backward" in src, fn
 
 
+def test_mab_key_mask_is_a_view_of_the_mask_it_is_given():
+    """``MAB._ignore_of``: the float [B*S] key mask the attention kernels take, derived from the mask alone (nothing rides on
+    the tensor).  A float contiguous [B, S] mask and the slice ``[:, :, 0]`` of a [B, S, 1] one -- what travels through a
+    network pass -- come back as views (same storage: no copy, no launch); a [B, L, S] mask gives its first query row's keys;
+    a bool mask its float form."""
+    from mpgan_amd.gapt import MAB
+    B, S, L = 3, 5, 2
+    gen = torch.Generator().manual_seed(0)
+    m2 = (torch.rand(B, S, generator=gen) < 0.5).float()
+    got = MAB._ignore_of(m2, B, S)
+    assert got.shape == (B * S,) and torch.equal(got, m2.reshape(B * S)) and got.data_ptr() == m2.data_ptr()
+    m3 = (torch.rand(B, S, 1, generator=gen) < 0.5).float()
+    km = m3[:, :, 0]
+    got = MAB._ignore_of(km, B, S)
+    assert got.shape == (B * S,) and torch.equal(got, m3.reshape(B * S)) and got.data_ptr() == km.data_ptr() == m3.data_ptr()
+    mq = (torch.rand(B, 1, S, generator=gen) < 0.5).float().expand(B, L, S).contiguous()
+    got = MAB._ignore_of(mq, B, S)
+    assert got.shape == (B * S,) and got.is_contiguous() and torch.equal(got, mq[:, 0, :].reshape(B * S))
+    mb = torch.rand(B, S, generator=gen) < 0.5
+    got = MAB._ignore_of(mb, B, S)
+    assert got.dtype == torch.float32 and torch.equal(got, mb.float().reshape(B * S))
+    assert MAB._ignore_of(None, B, S) is None
+
+
 def test_jetnet_file_reader(tmp_path):
     """JetNet's on-disk layout (particle_features [n, N, 4], jet_features [n, 4] = pt, eta, mass, num_particles) read
     from a file the test writes itself, normalised as train.py:41-67 configures JetNet: x / max + shift per particle
