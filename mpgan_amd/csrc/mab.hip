@@ -1899,12 +1899,57 @@ int mab_split_fwd_waves(int B) {
     return 0;
 }
 
-template <typename K>
-int mab_launch(K kernel, const MpgMab* p, int lds_bytes, hipStream_t st, bool one_jet_per_wave = false) {
+// ---- launches: every kernel of this file is named once, in the tables below ----
+// the dynamic-LDS grant of ONE kernel (once per device: the macro's counter is a static of this instantiation), then its launch
+template <typename P, void (*K)(const P)>
+int mab_go(const P* p, int grid, int block, int lds_bytes, hipStream_t st) {
+    MPG_ENSURE_LDS(K, lds_bytes);
+    hipLaunchKernelGGL(K, dim3(grid), dim3(block), lds_bytes, st, *p);
+    return (int)hipGetLastError();
+}
+using MabGo = int (*)(const MpgMab*, int, int, int, hipStream_t);
+using MabChainGo = int (*)(const MpgMabChain*, int, int, int, hipStream_t);
+#define MAB_GO(...) mab_go<MpgMab, __VA_ARGS__>
+#define MAB_CROSS_LN(K, NT) {{MAB_GO(K<NT, false, false>), MAB_GO(K<NT, false, true>)}, {MAB_GO(K<NT, true, false>), MAB_GO(K<NT, true, true>)}}
+const MabGo MAB_FWD[2][2][2] = {MAB_CROSS_LN(mab_fwd_kernel, 1), MAB_CROSS_LN(mab_fwd_kernel, 2)};      // [E / 32 - 1][cross][ln]
+const MabGo MAB_BWD[2][2][2] = {MAB_CROSS_LN(mab_bwd_kernel, 1), MAB_CROSS_LN(mab_bwd_kernel, 2)};
+const MabGo MAB_BWDS[2][2][2] = {MAB_CROSS_LN(mab_bwdS_kernel, 1), MAB_CROSS_LN(mab_bwdS_kernel, 2)};
+const MabGo MAB_FWDN[2][2] = {{MAB_GO(mab_fwdN_kernel<1, false>), MAB_GO(mab_fwdN_kernel<1, true>)},    // [E / 32 - 1][ln]
+                              {MAB_GO(mab_fwdN_kernel<2, false>), MAB_GO(mab_fwdN_kernel<2, true>)}};
+// the split kernels (two waves per jet) exist at E = 64 only, and never with LayerNorm
+const MabGo MAB_FWD2[2][2] = {{MAB_GO(mab_fwd2_kernel<false, 4>), MAB_GO(mab_fwd2_kernel<false, 8>)},   // [cross][waves == 8]
+                              {MAB_GO(mab_fwd2_kernel<true, 4>), MAB_GO(mab_fwd2_kernel<true, 8>)}};
+const MabGo MAB_BWD2[2] = {MAB_GO(mab_bwd2_kernel<false>), MAB_GO(mab_bwd2_kernel<true>)};              // [cross]
+const MabChainGo MAB_CHAIN[2] = {mab_go<MpgMabChain, mab_chain_fwd_kernel<1>>, mab_go<MpgMabChain, mab_chain_fwd_kernel<2>>};     // [E / 32 - 1]
+const MabChainGo MAB_CHAIN2[2] = {mab_go<MpgMabChain, mab_chain_fwd2_kernel<4>>, mab_go<MpgMabChain, mab_chain_fwd2_kernel<8>>};  // [waves == 8]
+#undef MAB_CROSS_LN
+#undef MAB_GO
+
+// small sets, a wave per jet: mab_waves() jets to a workgroup
+int mab_launch(MabGo go, const MpgMab* p, int lds_bytes, hipStream_t st, bool one_jet_per_wave = false) {
     const int nw = mab_waves(p->B);
     const int grid = ((p->B + nw - 1) / nw < 1024 || one_jet_per_wave) ? (p->B + nw - 1) / nw : 1024;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * nw), lds_bytes, st, *p);
-    return (int)hipGetLastError();
+    return go(p, grid, 64 * nw, lds_bytes, st);
+}
+
+// dynamic LDS bytes (NT = E / 32).  Forward: Win + Wo, Wf + biases
+int mab_fwd_lds(int NT) { return 2 * 1024 * (3 * NT * 2 * NT + 2 * NT * 2 * NT) + 4 * 160 * NT; }
+// backward: Win, WinT (3E x E) + Wf, WoT, WfT (E x E) + biases
+int mab_bwd_lds(int NT) { return 2 * 1024 * (2 * 3 * NT * 2 * NT + 3 * NT * 2 * NT) + 4 * 128 * NT; }
+// large sets.  Forward: Win's image holds 3 key tiles' fragments at E = 64, 1 at E = 32; the rest of up to 5 behind the biases.
+// Backward: Win + WoT + the 80 KiB exchange area + biases + statistics
+int mab_big_lds(int NT, bool backward) {
+    if (!backward) return mab_fwd_lds(NT) + (5 - 3 * NT / 2) * 8 * NT * 1024;
+    return 2 * 1024 * (3 * NT * 2 * NT + NT * 2 * NT) + 80 * 1024 + 4 * 128 * NT + 4 * 3 * (2 * NT) * 160;
+}
+
+// a block with layer_norm=True (ln1_w set) brings all of its norms' arguments: 0, or -6
+int mab_ln_check(const MpgMab* p, bool backward) {
+    if (p->ln1_w == nullptr) return 0;
+    if (p->ln2_w == nullptr || !(p->ln_eps > 0.f)) return -6;
+    if (!backward) return (p->ln1_b == nullptr || p->ln2_b == nullptr) ? -6 : 0;
+    const bool rows = p->dn1 != nullptr;     // the rows of the norms' parameter gradients: all four or none
+    return (p->save_za == nullptr || rows != (p->gn1 != nullptr) || rows != (p->dn2 != nullptr) || rows != (p->gn2 != nullptr)) ? -6 : 0;
 }
 
 }  // namespace
@@ -1914,103 +1959,31 @@ extern "C" int mpg_mab_bwd(const MpgMab* p, void* stream) {
     if (p->dout == nullptr || p->save_z == nullptr || (p->dk == nullptr) != (p->dv == nullptr)) return -5;
     if (p->lddout % 4 || (p->dq != nullptr && p->lddq % 4) || (p->dk != nullptr && p->lddkv % 4) ||
         (p->dx != nullptr && p->lddx % 4) || (p->dy != nullptr && p->lddy % 4)) return -3;
+    if (const int rc = mab_ln_check(p, true)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool cross = p->y != p->x;
+    const bool cross = p->y != p->x, ln = p->ln1_w != nullptr;
     const int NT = p->E / 32;
-    const int lds = 2 * 1024 * (2 * 3 * NT * 2 * NT + 3 * NT * 2 * NT) + 4 * 128 * NT;   // Win, WinT (3E x E) + Wf, WoT, WfT (E x E) + biases
-    if (p->L > 32 || p->S > 32 || getenv("MPG_MAB_BIG") != nullptr) {   // large sets: a workgroup per jet, a wave per tile of 32 tokens (mab_bwdS_kernel)
-        const bool ln = p->ln1_w != nullptr;
-        if (ln && (p->ln2_w == nullptr || p->save_za == nullptr || !(p->ln_eps > 0.f) || (p->dn1 == nullptr) != (p->gn1 == nullptr) ||
-                   (p->dn1 == nullptr) != (p->dn2 == nullptr) || (p->dn1 == nullptr) != (p->gn2 == nullptr))) return -6;
-        const int nw = (std::max(p->L, p->S) + 31) / 32;
-        // Win + WoT + the 80 KiB exchange area + biases + statistics
-        const int ldsS = 2 * 1024 * (3 * NT * 2 * NT + NT * 2 * NT) + 80 * 1024 + 4 * 128 * NT + 4 * 3 * (2 * NT) * 160;
-        const dim3 grid(p->B), block(64 * nw);
-#define MPG_BWDN(NTv, CR, LNv) do { MPG_ENSURE_LDS((mab_bwdS_kernel<NTv, CR, LNv>), ldsS); \
-        hipLaunchKernelGGL((mab_bwdS_kernel<NTv, CR, LNv>), grid, block, ldsS, st, *p); } while (0)
-        if (NT == 2) { if (cross) { if (ln) MPG_BWDN(2, true, true); else MPG_BWDN(2, true, false); }
-                       else { if (ln) MPG_BWDN(2, false, true); else MPG_BWDN(2, false, false); } }
-        else { if (cross) { if (ln) MPG_BWDN(1, true, true); else MPG_BWDN(1, true, false); }
-               else { if (ln) MPG_BWDN(1, false, true); else MPG_BWDN(1, false, false); } }
-#undef MPG_BWDN
-        return (int)hipGetLastError();
-    }
-    if (p->ln1_w != nullptr) {   // layer_norm=True: one wave per jet
-        if (p->ln2_w == nullptr || p->save_za == nullptr || !(p->ln_eps > 0.f) || (p->dn1 == nullptr) != (p->gn1 == nullptr) ||
-            (p->dn1 == nullptr) != (p->dn2 == nullptr) || (p->dn1 == nullptr) != (p->gn2 == nullptr)) return -6;
-        if (p->E == 64) {
-            if (cross) { MPG_ENSURE_LDS((mab_bwd_kernel<2, true, true>), lds); return mab_launch(mab_bwd_kernel<2, true, true>, p, lds, st, true); }
-            MPG_ENSURE_LDS((mab_bwd_kernel<2, false, true>), lds);
-            return mab_launch(mab_bwd_kernel<2, false, true>, p, lds, st, true);
-        }
-        if (cross) return mab_launch(mab_bwd_kernel<1, true, true>, p, lds, st, true);
-        return mab_launch(mab_bwd_kernel<1, false, true>, p, lds, st, true);
-    }
-    if (p->E == 64 && mab_split(p->B)) {
-        // two waves per jet, two jets per workgroup
-        if (cross) {
-            MPG_ENSURE_LDS((mab_bwd2_kernel<true>), lds);
-            hipLaunchKernelGGL((mab_bwd2_kernel<true>), dim3((p->B + 1) / 2), dim3(256), lds, st, *p);
-        } else {
-            MPG_ENSURE_LDS((mab_bwd2_kernel<false>), lds);
-            hipLaunchKernelGGL((mab_bwd2_kernel<false>), dim3((p->B + 1) / 2), dim3(256), lds, st, *p);
-        }
-        return (int)hipGetLastError();
-    }
-    if (p->E == 64) {
-        if (cross) { MPG_ENSURE_LDS((mab_bwd_kernel<2, true>), lds); return mab_launch(mab_bwd_kernel<2, true>, p, lds, st, true); }
-        MPG_ENSURE_LDS((mab_bwd_kernel<2, false>), lds);
-        return mab_launch(mab_bwd_kernel<2, false>, p, lds, st, true);
-    }
-    if (cross) return mab_launch(mab_bwd_kernel<1, true>, p, lds, st, true);
-    return mab_launch(mab_bwd_kernel<1, false>, p, lds, st, true);
+    if (p->L > 32 || p->S > 32 || getenv("MPG_MAB_BIG") != nullptr)   // large sets: a workgroup per jet, a wave per tile of 32 tokens
+        return MAB_BWDS[NT - 1][cross][ln](p, p->B, 64 * ((std::max(p->L, p->S) + 31) / 32), mab_big_lds(NT, true), st);
+    if (NT == 2 && !ln && mab_split(p->B))                            // two waves per jet, two jets per workgroup
+        return MAB_BWD2[cross](p, (p->B + 1) / 2, 256, mab_bwd_lds(NT), st);
+    return mab_launch(MAB_BWD[NT - 1][cross][ln], p, mab_bwd_lds(NT), st, true);   // (layer_norm=True: always one wave per jet)
 }
 
 extern "C" int mpg_mab_fwd(const MpgMab* p, void* stream) {
     if (const int rc = mab_check(p)) return rc;
+    if (const int rc = mab_ln_check(p, false)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool cross = p->y != p->x;
+    const bool cross = p->y != p->x, ln = p->ln1_w != nullptr;
     const int NT = p->E / 32;
-    const int lds = 2 * 1024 * (3 * NT * 2 * NT + 2 * NT * 2 * NT) + 4 * 160 * NT;   // Win + Wo, Wf + biases
-    const bool ln = p->ln1_w != nullptr;
-    if (p->L > 32 || p->S > 32 || getenv("MPG_MAB_BIG") != nullptr) {   // large sets: a workgroup per jet, a wave per tile of 32 queries (mab_fwdN_kernel)
-        if (ln && (p->ln1_b == nullptr || p->ln2_w == nullptr || p->ln2_b == nullptr || !(p->ln_eps > 0.f))) return -6;
-        const int nw = (std::max(p->L, p->S) + 31) / 32;
-        const dim3 grid(p->B), block(64 * nw);
-        // (Win's image holds 3 key tiles' fragments at E = 64, 1 at E = 32; the rest of up to 5 behind the biases)
-        const int ldsF = lds + (5 - 3 * NT / 2) * 8 * NT * 1024;
-#define MPG_FWDN(NTv, LNv) do { MPG_ENSURE_LDS((mab_fwdN_kernel<NTv, LNv>), ldsF); \
-        hipLaunchKernelGGL((mab_fwdN_kernel<NTv, LNv>), grid, block, ldsF, st, *p); } while (0)
-        if (NT == 2) { if (ln) MPG_FWDN(2, true); else MPG_FWDN(2, false); }
-        else { if (ln) MPG_FWDN(1, true); else MPG_FWDN(1, false); }
-#undef MPG_FWDN
-        return (int)hipGetLastError();
+    if (p->L > 32 || p->S > 32 || getenv("MPG_MAB_BIG") != nullptr)   // large sets: a workgroup per jet, a wave per tile of 32 queries
+        return MAB_FWDN[NT - 1][ln](p, p->B, 64 * ((std::max(p->L, p->S) + 31) / 32), mab_big_lds(NT, false), st);
+    // layer_norm=True: one wave per jet (a token's statistics run over both feature tiles)
+    if (const int nw2 = (NT == 2 && !ln) ? mab_split_fwd_waves(p->B) : 0) {
+        const int npair = nw2 / 2;
+        return MAB_FWD2[cross][nw2 == 8](p, (p->B + npair - 1) / npair, 64 * nw2, mab_fwd_lds(NT) + npair * 2 * MAB_XCH, st);
     }
-    if (ln) {   // layer_norm=True: one wave per jet (a token's statistics run over both feature tiles)
-        if (p->ln1_b == nullptr || p->ln2_w == nullptr || p->ln2_b == nullptr || !(p->ln_eps > 0.f)) return -6;
-        if (p->E == 64) {
-            if (cross) { MPG_ENSURE_LDS((mab_fwd_kernel<2, true, true>), lds); return mab_launch(mab_fwd_kernel<2, true, true>, p, lds, st); }
-            MPG_ENSURE_LDS((mab_fwd_kernel<2, false, true>), lds);
-            return mab_launch(mab_fwd_kernel<2, false, true>, p, lds, st);
-        }
-        if (cross) return mab_launch(mab_fwd_kernel<1, true, true>, p, lds, st);
-        return mab_launch(mab_fwd_kernel<1, false, true>, p, lds, st);
-    }
-    if (const int nw2 = p->E == 64 ? mab_split_fwd_waves(p->B) : 0) {
-        const int npair = nw2 / 2, lds2 = lds + npair * 2 * MAB_XCH, grid = (p->B + npair - 1) / npair;
-        if (cross && nw2 == 4) { MPG_ENSURE_LDS((mab_fwd2_kernel<true, 4>), lds2); hipLaunchKernelGGL((mab_fwd2_kernel<true, 4>), dim3(grid), dim3(256), lds2, st, *p); }
-        else if (cross) { MPG_ENSURE_LDS((mab_fwd2_kernel<true, 8>), lds2); hipLaunchKernelGGL((mab_fwd2_kernel<true, 8>), dim3(grid), dim3(512), lds2, st, *p); }
-        else if (nw2 == 4) { MPG_ENSURE_LDS((mab_fwd2_kernel<false, 4>), lds2); hipLaunchKernelGGL((mab_fwd2_kernel<false, 4>), dim3(grid), dim3(256), lds2, st, *p); }
-        else { MPG_ENSURE_LDS((mab_fwd2_kernel<false, 8>), lds2); hipLaunchKernelGGL((mab_fwd2_kernel<false, 8>), dim3(grid), dim3(512), lds2, st, *p); }
-        return (int)hipGetLastError();
-    }
-    if (p->E == 64) {
-        if (cross) { MPG_ENSURE_LDS((mab_fwd_kernel<2, true>), lds); return mab_launch(mab_fwd_kernel<2, true>, p, lds, st); }
-        MPG_ENSURE_LDS((mab_fwd_kernel<2, false>), lds);
-        return mab_launch(mab_fwd_kernel<2, false>, p, lds, st);
-    }
-    if (cross) return mab_launch(mab_fwd_kernel<1, true>, p, lds, st);
-    return mab_launch(mab_fwd_kernel<1, false>, p, lds, st);
+    return mab_launch(MAB_FWD[NT - 1][cross][ln], p, mab_fwd_lds(NT), st);
 }
 
 extern "C" int mpg_mab_chain_fwd(const MpgMabChain* c, void* stream) {
@@ -2026,21 +1999,12 @@ extern "C" int mpg_mab_chain_fwd(const MpgMabChain* c, void* stream) {
         if (b > 0 && (p.x != c->blk[b - 1].out || p.ldx != c->blk[b - 1].ldo)) return -2;
         if (!(p.alpha >= 0.f && p.alpha <= 1.f)) return -4;
     }
-    const int nw = mab_waves(p0.B);
-    const int grid = (p0.B + nw - 1) / nw;              // one jet per wave: its rows stay in registers across the blocks
     const int NT = p0.E / 32;
-    const int lds = 2 * 1024 * (3 * NT * 2 * NT + 2 * NT * 2 * NT) + 4 * 160 * NT;
     hipStream_t st = (hipStream_t)stream;
-    if (const int nw2 = p0.E == 64 ? mab_split_fwd_waves(p0.B) : 0) {
-        // two waves per jet, two or four jets per workgroup
-        const int npair = nw2 / 2, lds2 = lds + npair * 2 * MAB_XCH, grid2 = (p0.B + npair - 1) / npair;
-        if (nw2 == 4) { MPG_ENSURE_LDS(mab_chain_fwd2_kernel<4>, lds2); hipLaunchKernelGGL(mab_chain_fwd2_kernel<4>, dim3(grid2), dim3(256), lds2, st, *c); }
-        else { MPG_ENSURE_LDS(mab_chain_fwd2_kernel<8>, lds2); hipLaunchKernelGGL(mab_chain_fwd2_kernel<8>, dim3(grid2), dim3(512), lds2, st, *c); }
-    } else if (p0.E == 64) {
-        MPG_ENSURE_LDS((mab_chain_fwd_kernel<2>), lds);
-        hipLaunchKernelGGL((mab_chain_fwd_kernel<2>), dim3(grid), dim3(64 * nw), lds, st, *c);
-    } else {
-        hipLaunchKernelGGL((mab_chain_fwd_kernel<1>), dim3(grid), dim3(64 * nw), lds, st, *c);
+    if (const int nw2 = NT == 2 ? mab_split_fwd_waves(p0.B) : 0) {   // two waves per jet, two or four jets per workgroup
+        const int npair = nw2 / 2;
+        return MAB_CHAIN2[nw2 == 8](c, (p0.B + npair - 1) / npair, 64 * nw2, mab_fwd_lds(NT) + npair * 2 * MAB_XCH, st);
     }
-    return (int)hipGetLastError();
+    const int nw = mab_waves(p0.B);       // one jet per wave: its rows stay in registers across the blocks
+    return MAB_CHAIN[NT - 1](c, (p0.B + nw - 1) / nw, 64 * nw, mab_fwd_lds(NT), st);
 }

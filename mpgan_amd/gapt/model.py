@@ -68,7 +68,7 @@ class MAB(nn.Module):
         if x.is_cuda and ops.double_backward_on(x.device):
             return self._forward_dd(x, y, ignore)
         if self._fused_ok(x, L, S):
-            return self._fused(x, y, ignore, B, L, S)
+            return self._fused(x, y, ignore)
         if x is y:   # the packed projections go to the attention core as they are (no q/k/v slices in autograd)
             qkv = _lin(x2, att.in_proj_weight, att.in_proj_bias, 0, 3 * E)
             o = ops.FusedPackedAttnFn.apply(qkv, None, ignore, B, L, S, self.num_heads)
@@ -132,7 +132,7 @@ class MAB(nn.Module):
         km = y_mask if y_mask.dim() == 2 else y_mask[:, 0, :]
         return km.reshape(B * S).float().contiguous()
 
-    # -- the whole block as one launch (ops.mab_forward; csrc/mab.hip) ------------------------------------------
+    # -- the whole block as one launch (ops.mab_block; csrc/mab.hip) ------------------------------------------
     def _fused_ok(self, x: Tensor, L: int, S: int) -> bool:
         return (MAB.fused and x.is_cuda and len(self.ff.net) == 1 and self.ff.plain
                 and ops.mab_fusable(self.embed_dim, self.num_heads, L, S))
@@ -153,30 +153,18 @@ class MAB(nn.Module):
         for pk in self.packed_sets():
             pk.refresh()
 
-    def _fused(self, x, y, ignore, B, L, S):
+    def _params(self) -> "ops.MABParams":
         att, lin = self.attention, self.ff.net[0]
-        E = self.embed_dim
-        kw = dict(alpha=self.ff.leaky_relu_alpha, ff_act=not self.ff.final_linear, p_mab=self.dropout_p,
-                  p_ff=self.ff.dropout_p, training=self.training)
-        ln = (self.norm1.weight, self.norm1.bias, self.norm2.weight, self.norm2.bias, self.norm1.eps) if self.layer_norm else None
-        if not torch.is_grad_enabled():
-            # (one query row for all jets -- PMA's seed -- is read with row stride 0)
-            x2 = x.reshape(1, E).contiguous().expand(B, E) if (x.shape[0] == 1 and B > 1) else x.reshape(B * L, E).contiguous()
-            y2 = None if x is y else y.reshape(B * S, E).contiguous()
-            out = ops.mab_forward(x2, y2, ignore, self._packed(), att.in_proj_bias, att.out_proj.bias, lin.bias,
-                                  B, L, S, self.num_heads, ln=ln, **kw)[0]
-            return out.reshape(B, L, E)
-        if ln is not None:   # layer_norm=True: both norms inside the block's launches (ops.FusedMABLayerNormFn)
+        return ops.MABParams(att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias, lin.weight, lin.bias)
+
+    def _fused(self, x, y, ignore):
+        """``x`` may be the one [1, 1, E] row all jets of ``y`` share (PMA's seed)."""
+        ln = None
+        if self.layer_norm:   # both norms inside the block's launches
             assert self.norm1.eps == self.norm2.eps
-            if x.shape[0] == 1 and B > 1:
-                x = x.expand(B, L, E)     # (a shared query row: autograd sums its gradient over the jets)
-            return ops.FusedMABLayerNormFn.apply(x, None if x is y else y, ignore, att.in_proj_weight, att.in_proj_bias,
-                                                 att.out_proj.weight, att.out_proj.bias, lin.weight, lin.bias, ln[0], ln[1], ln[2], ln[3],
-                                                 ln[4], self.num_heads, kw["alpha"], kw["ff_act"], kw["p_mab"], kw["p_ff"],
-                                                 kw["training"], self._packed())
-        return ops.FusedMABFn.apply(x, None if x is y else y, ignore, att.in_proj_weight, att.in_proj_bias,
-                                    att.out_proj.weight, att.out_proj.bias, lin.weight, lin.bias, self.num_heads,
-                                    kw["alpha"], kw["ff_act"], kw["p_mab"], kw["p_ff"], kw["training"], self._packed())
+            ln = (self.norm1.weight, self.norm1.bias, self.norm2.weight, self.norm2.bias, self.norm1.eps)
+        return ops.mab_block(x, None if x is y else y, ignore, self._packed(), self._params(), ln, self.num_heads,
+                             self.ff.leaky_relu_alpha, not self.ff.final_linear, self.dropout_p, self.ff.dropout_p, self.training)
 
 
 class SAB(nn.Module):
@@ -198,7 +186,7 @@ class PMA(nn.Module):
     def forward(self, x: Tensor, mask: Tensor = None):
         if self.S.shape[1] == 1 and x.is_cuda and x.size(0) > 1 and self.mab._fused_ok(x, 1, x.shape[1]) and not ops.double_backward_on(x.device):
             # one seed: the one-launch block reads the single row for every jet (no B copies, no reduction launch for its gradient)
-            return self.mab._fused(self.S, x, self.mab._ignore_of(_key_mask(mask), x.size(0), x.shape[1]), x.size(0), 1, x.shape[1])
+            return self.mab._fused(self.S, x, self.mab._ignore_of(_key_mask(mask), x.size(0), x.shape[1]))
         seeds = self.S.expand(x.size(0), -1, -1).contiguous()
         return self.mab(seeds, x, _key_mask(mask))
 
@@ -240,17 +228,14 @@ def _run_sabs(sabs, x: Tensor, am) -> Tensor:
         if len(run) >= 2 and B <= 4096:      # (one jet per wave: the launch covers at most 1,024 workgroups of four)
             first = run[0]
             ignore = MAB._ignore_of(_key_mask(am), B, N)
-            params = []
-            for m in run:
-                att, lin = m.attention, m.ff.net[0]
-                params += [att.in_proj_weight, att.in_proj_bias, att.out_proj.weight, att.out_proj.bias, lin.weight, lin.bias]
+            blocks = [m._params() for m in run]
             pks = [m._packed() for m in run]
             args = (first.num_heads, first.ff.leaky_relu_alpha, not first.ff.final_linear, first.dropout_p, first.ff.dropout_p,
                     first.training)
-            if torch.is_grad_enabled() and (x.requires_grad or any(q.requires_grad for q in params)):
-                x = ops.FusedSABChainFn.apply(x, ignore, *args, pks, *params)
+            if torch.is_grad_enabled() and (x.requires_grad or any(q.requires_grad for prm in blocks for q in prm)):
+                x = ops.FusedSABChainFn.apply(x, ignore, *args, pks, *(q for prm in blocks for q in prm))
             else:
-                x = ops.sab_chain_forward(x, ignore, *args, pks, params)
+                x = ops.sab_chain_forward(x, ignore, *args, pks, blocks)[0]
             i += len(run)
         else:
             x = sabs[i](x, am)

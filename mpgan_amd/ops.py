@@ -490,34 +490,18 @@ def refresh_many(packs):
         pk._key = pk._current_key()
 
 
-class PackedMPLayer:
-    """All weight images one MPLayer call needs (edge network, node network, their transposes and the stacked
-    a|c view of fe.net.0), in persistent buffers, rebuilt by ONE ``mpg_pack_many`` launch.
+class _PackedSet:
+    """Weight images in persistent buffers, rebuilt by ONE ``mpg_pack_many`` launch.  ``spec``: per image name,
+    (W, packed rows, packed cols, transpose, scale, f16, row_split, split_cols); ``params``: the weights the images are made of.
 
     ``ensure()`` rebuilds when a parameter's storage or autograd version changed (``optimizer.step()``,
     ``load_state_dict``).  Updates made behind torch's back -- ``train.TrainStep`` runs RMSprop on a flat buffer
     through ``mpg_rmsprop`` -- must call ``refresh()`` themselves (TrainStep does, inside its graph segments).
     """
 
-    def __init__(self, params, F, out, dscale, f16, plist=None):
-        W1, W2, W3, V1, V2, V3 = params
-        self.plist = plist  # the twelve Parameters (W1, b1, ..., V3, c3) when built by MPLayer: .grad targets
-        self.params, self.F, self.out, self.dscale, self.f16 = params, F, out, float(dscale), bool(f16)
-        dev = W1.device
-        KN = V1.shape[1]   # H3 + F (+ the conditioning columns appended to the node network's input)
-        # name: (W, packed rows, packed cols, transpose, scale, f16, row_split, split_cols)
-        spec = {
-            "W2": (W2, H2, H1, 0, dscale * SC_W2, f16, 0, 0), "W3": (W3, H3, H2, 0, dscale * SC_W3, f16, 0, 0),
-            "W3T": (W3, H2, H3, 1, dscale * SC_W3, True, 0, 0), "W2T": (W2, H1, H2, 1, dscale * SC_W2, True, 0, 0),
-            "V1": (V1, V1.shape[0], KN, 0, SC_WN, f16, 0, 0), "V2": (V2, V2.shape[0], V2.shape[1], 0, SC_WN, f16, 0, 0),
-            "V3": (V3, out, V3.shape[1], 0, SC_WN, f16, 0, 0),
-            "V3T": (V3, V3.shape[1], out, 1, 1.0, False, 0, 0), "V2T": (V2, V2.shape[1], V2.shape[0], 1, 1.0, False, 0, 0),
-            "V1T": (V1, KN, V1.shape[0], 1, 1.0, False, 0, 0),
-            "W1S": (W1, 2 * H1, F, 0, SC_WN, f16, H1, F),        # [a-half ; c-half] of fe.net.0.weight
-            "W1ST": (W1, F, 2 * H1, 1, 1.0, False, H1, F),
-        }
-        self.img = {k: torch.empty((_img_elems(v[1], v[2]),), device=dev, dtype=torch.bfloat16) for k, v in spec.items()}
-        self._spec = spec
+    def __init__(self, params, spec):
+        self.params, self._spec = params, spec
+        self.img = {k: torch.empty((_img_elems(v[1], v[2]),), device=params[0].device, dtype=torch.bfloat16) for k, v in spec.items()}
         self._key = None
 
     def _current_key(self):
@@ -537,6 +521,27 @@ class PackedMPLayer:
 
     def ptr(self, name):
         return C.c_void_p(self.img[name].data_ptr())
+
+
+class PackedMPLayer(_PackedSet):
+    """All weight images one MPLayer call needs (edge network, node network, their transposes and the stacked
+    a|c view of fe.net.0)."""
+
+    def __init__(self, params, F, out, dscale, f16, plist=None):
+        W1, W2, W3, V1, V2, V3 = params
+        self.plist = plist  # the twelve Parameters (W1, b1, ..., V3, c3) when built by MPLayer: .grad targets
+        self.F, self.out, self.dscale, self.f16 = F, out, float(dscale), bool(f16)
+        KN = V1.shape[1]   # H3 + F (+ the conditioning columns appended to the node network's input)
+        super().__init__(params, {
+            "W2": (W2, H2, H1, 0, dscale * SC_W2, f16, 0, 0), "W3": (W3, H3, H2, 0, dscale * SC_W3, f16, 0, 0),
+            "W3T": (W3, H2, H3, 1, dscale * SC_W3, True, 0, 0), "W2T": (W2, H1, H2, 1, dscale * SC_W2, True, 0, 0),
+            "V1": (V1, V1.shape[0], KN, 0, SC_WN, f16, 0, 0), "V2": (V2, V2.shape[0], V2.shape[1], 0, SC_WN, f16, 0, 0),
+            "V3": (V3, out, V3.shape[1], 0, SC_WN, f16, 0, 0),
+            "V3T": (V3, V3.shape[1], out, 1, 1.0, False, 0, 0), "V2T": (V2, V2.shape[1], V2.shape[0], 1, 1.0, False, 0, 0),
+            "V1T": (V1, KN, V1.shape[0], 1, 1.0, False, 0, 0),
+            "W1S": (W1, 2 * H1, F, 0, SC_WN, f16, H1, F),        # [a-half ; c-half] of fe.net.0.weight
+            "W1ST": (W1, F, 2 * H1, 1, 1.0, False, H1, F),
+        })
 
 
 def chain(M, layers, **kw):
@@ -1046,6 +1051,16 @@ def _grad_target(t):
     return base.grad.as_strided(t.size(), t.stride(), t.storage_offset() - base.storage_offset() + base.grad.storage_offset())
 
 
+def _deferred_targets(st, params):
+    """May the gradients of ``params`` be queued for the grouped weight-gradient launches?  (their ``.grad`` targets in order, the
+    ``WgradBatch``) while a TrainStep backward is collecting on ``st`` (a ``DeviceState``) and EVERY parameter has a target; else
+    None -- the caller then computes the gradients itself and returns them to autograd."""
+    if not st.grad_into_param or st.deferred_wgrad is None:
+        return None
+    targets = [_grad_target(q) for q in params]
+    return None if any(t is None for t in targets) else (targets, st.deferred_wgrad)
+
+
 class FusedLinearFn(torch.autograd.Function):
     """Linear -> [LeakyReLU] -> [Dropout] (one LinearNet layer; mpgan/model.py:77-83), optionally ``+ resid`` in the
     same launch (MAB's residual connections, gapt/model.py:131-137; only for a layer without activation)."""
@@ -1082,13 +1097,13 @@ class FusedLinearFn(torch.autograd.Function):
                       thr=thr, scale=dscale)
         dW = db = None
         want_b = has_b and ctx.needs_input_grad[2]
-        gW = gb = None
-        st = dev_state(g2.device)
-        if ctx.needs_input_grad[1] and st.grad_into_param and st.deferred_wgrad is not None:
-            gW, gb = _grad_target(ctx.wparam), _grad_target(ctx.bias) if want_b else None
-        if gW is not None and (not want_b or gb is not None):
+        queue = None
+        if ctx.needs_input_grad[1]:
+            queue = _deferred_targets(dev_state(g2.device), [ctx.wparam, ctx.bias] if want_b else [ctx.wparam])
+        if queue is not None:
             # TrainStep: queue dW (+ db) for the grouped launch at the end of the backward; it adds into .grad
-            st.deferred_wgrad.add(g2, x2, out=gW, bias_out=gb, accumulate=True)
+            targets, batch = queue
+            batch.add(g2, x2, out=targets[0], bias_out=targets[1] if want_b else None, accumulate=True)
         elif ctx.needs_input_grad[1]:
             if want_b:
                 db = torch.empty(W.shape[0], device=g2.device, dtype=torch.float32)
@@ -1270,38 +1285,16 @@ class FusedAttnFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------- one launch per MAB
-class PackedMAB:
-    """Weight images of one MAB for ``mpg_mab_fwd`` / ``mpg_mab_bwd`` (fp16 images of the three weights for the forward
-    products, bf16 images of their transposes for the gradient products), rebuilt by ONE ``mpg_pack_many`` launch;
-    ``ensure`` / ``refresh`` as ``PackedMPLayer``."""
+class PackedMAB(_PackedSet):
+    """Weight images of one MAB for ``mpg_mab_fwd`` / ``mpg_mab_bwd``: fp16 images of the three weights for the forward
+    products, bf16 images of their transposes for the gradient products."""
 
     def __init__(self, Win, Wo, Wf):
         E = Wo.shape[0]
-        self.params = (Win, Wo, Wf)
-        self._spec = {
-            "Win": (Win, 3 * E, E, 0, SC_WN, True), "Wo": (Wo, E, E, 0, SC_WN, True), "Wf": (Wf, E, E, 0, SC_WN, True),
-            "WinT": (Win, E, 3 * E, 1, 1.0, False), "WoT": (Wo, E, E, 1, 1.0, False), "WfT": (Wf, E, E, 1, 1.0, False),
-        }
-        self.img = {k: torch.empty((_img_elems(v[1], v[2]),), device=Wo.device, dtype=torch.bfloat16)
-                    for k, v in self._spec.items()}
-        self._key = None
-
-    def _current_key(self):
-        return tuple((q.data_ptr(), q._version) for q in self.params)
-
-    def jobs(self):
-        return [v + (0, 0, self.img[k]) for k, v in self._spec.items()]
-
-    def refresh(self):
-        refresh_many([self])
-
-    def ensure(self):
-        if self._key != self._current_key():
-            self.refresh()
-        return self
-
-    def ptr(self, name):
-        return C.c_void_p(self.img[name].data_ptr())
+        super().__init__((Win, Wo, Wf), {
+            "Win": (Win, 3 * E, E, 0, SC_WN, True, 0, 0), "Wo": (Wo, E, E, 0, SC_WN, True, 0, 0), "Wf": (Wf, E, E, 0, SC_WN, True, 0, 0),
+            "WinT": (Win, E, 3 * E, 1, 1.0, False, 0, 0), "WoT": (Wo, E, E, 1, 1.0, False, 0, 0), "WfT": (Wf, E, E, 1, 1.0, False, 0, 0),
+        })
 
 
 def mab_fusable(E: int, H: int, L: int, S: int) -> bool:
@@ -1313,53 +1306,99 @@ def mab_fusable(E: int, H: int, L: int, S: int) -> bool:
 MAB_MAX_TOKENS = 160
 MAB_CHAIN_TOKENS = 32      # (``mpg_mab_chain_fwd`` keeps a jet's rows in one wave's registers)
 
+# The six parameters of a block, as they travel together: in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias, ff weight, ff bias
+MABParams = namedtuple("MABParams", "Win bin Wo bo Wf bf")
+# The non-tensor state of one block invocation (``ctx.cfg``); p_mab / p_ff are the rates in force (0 outside training)
+MABCfg = namedtuple("MABCfg", "B L S E H alpha ff_act tag p_mab p_ff")
+# What a block's forward keeps for its backward, in ``save_for_backward`` order: the query rows, the key/value rows (None: self-attention),
+# the key mask or None, o (attention output), z (input of the feed-forward layer) and -- None without LayerNorm -- za (input of norm1)
+# and the norms' parameters
+MABSaved = namedtuple("MABSaved", "x2 y2 ignore o z za n1w n1b n2w n2b", defaults=(None,) * 5)
 
-def _mab_struct(x2, y2, ignore, pk, bin_, bo, bf, B, L, S, E, H, alpha, ff_act, tag, thr_mab, sc_mab, thr_ff, sc_ff):
+
+def _groups(seq, n):
+    return [tuple(seq[i:i + n]) for i in range(0, len(seq), n)]
+
+
+def mab_saved(node):
+    """The saved tensors of a ``FusedMABFn`` backward node (the ``grad_fn`` behind a one-launch block's output), by name."""
+    return MABSaved(*node.saved_tensors)
+
+
+def _mab_cfg(dev, B, L, S, E, H, alpha, ff_act, p_mab, p_ff, training):
+    """The ``MABCfg`` of a fresh invocation: it draws the block's dropout tag."""
+    p_mab, p_ff = (p_mab, p_ff) if training else (0.0, 0.0)
+    tag = next_tag(dev, "mab", max(drop_params(p_mab)[0], drop_params(p_ff)[0]))
+    return MABCfg(B, L, S, E, H, alpha, ff_act, tag, p_mab, p_ff)
+
+
+def _mab_struct(cfg, x2, y2, ignore, pk, prm, ln=None):
+    """``MpgMab`` with everything the forward and the backward share.  ``ln``: (norm1.weight, norm1.bias, norm2.weight, norm2.bias,
+    eps) of a block with ``layer_norm=True``."""
     m = _lib.MpgMab()
     m.x, m.ldx = _p(x2), x2.stride(0)
     m.y, m.ldy = (_p(x2), x2.stride(0)) if y2 is None else (_p(y2), y2.stride(0))
     m.ignore = _p(ignore)
-    m.Win, m.bin, m.Wo, m.bo, m.Wf, m.bf = pk.ptr("Win"), _p(bin_), pk.ptr("Wo"), _p(bo), pk.ptr("Wf"), _p(bf)
+    m.Win, m.bin, m.Wo, m.bo, m.Wf, m.bf = pk.ptr("Win"), _p(prm.bin), pk.ptr("Wo"), _p(prm.bo), pk.ptr("Wf"), _p(prm.bf)
     m.WinT, m.WoT, m.WfT = pk.ptr("WinT"), pk.ptr("WoT"), pk.ptr("WfT")
-    m.B, m.L, m.S, m.E, m.H = B, L, S, E, H
-    m.alpha, m.ff_act = alpha, int(ff_act)
-    m.seed, m.tag = _p(seed_tensor(x2.device)), tag
-    m.thr_mab, m.sc_mab, m.thr_ff, m.sc_ff = thr_mab, sc_mab, thr_ff, sc_ff
+    m.B, m.L, m.S, m.E, m.H = cfg.B, cfg.L, cfg.S, cfg.E, cfg.H
+    m.alpha, m.ff_act = cfg.alpha, int(cfg.ff_act)
+    m.seed, m.tag = _p(seed_tensor(x2.device)), cfg.tag
+    (m.thr_mab, m.sc_mab), (m.thr_ff, m.sc_ff) = drop_params(cfg.p_mab), drop_params(cfg.p_ff)
     m.wscale, m.ascale = SC_WN, SC_ACT
-    return m
-
-
-def _mab_set_ln(m, ln):
     if ln is not None:
         w1, b1, w2, b2, eps = ln
         m.ln1_w, m.ln1_b, m.ln2_w, m.ln2_b, m.ln_eps = _p(w1), _p(b1), _p(w2), _p(b2), float(eps)
+    return m
 
 
-def mab_forward(x2, y2, ignore, pk, bin_, bo, bf, B, L, S, H, *, alpha=0.2, ff_act=True, p_mab=0.0, p_ff=0.0,
-                training=False, tag=None, save=False, ln=None):
+def mab_forward(cfg, x2, y2, ignore, pk, prm, *, save=False, ln=None):
     """``mpg_mab_fwd``: x2 [B*L, E] queries, y2 [B*S, E] keys/values or None (self-attention), ignore [B*S] floats or
-    None.  Returns (out [B*L, E], o, z, tag) -- o and z only with ``save`` (what the backward needs).  ``ln``: (norm1.weight,
-    norm1.bias, norm2.weight, norm2.bias, eps) of a block with ``layer_norm=True``; ``save`` then also keeps za (the input of
-    norm1) and the return value is (out, o, z, tag, za)."""
+    None.  Returns (out [B*L, E], MABSaved); o, z and -- with ``ln`` -- za exist only with ``save`` (what the backward needs)."""
     _chk(x2, "x")
-    E = x2.shape[1]
-    dev = x2.device
-    thr_mab, sc_mab = drop_params(p_mab) if training else (0, 1.0)
-    thr_ff, sc_ff = drop_params(p_ff) if training else (0, 1.0)
-    if tag is None:
-        tag = next_tag(dev, "mab", max(thr_mab, thr_ff))
-    out = torch.empty((B * L, E), device=dev, dtype=torch.float32)
+    out = torch.empty((cfg.B * cfg.L, cfg.E), device=x2.device, dtype=torch.float32)
     o = torch.empty_like(out) if save else None
     z = torch.empty_like(out) if save else None
-    m = _mab_struct(x2, y2, ignore, pk, bin_, bo, bf, B, L, S, E, H, alpha, ff_act, tag, thr_mab, sc_mab, thr_ff, sc_ff)
-    m.out, m.ldo, m.save_o, m.save_z = _p(out), out.stride(0), _p(o), _p(z)
-    za = None
-    if ln is not None:
-        _mab_set_ln(m, ln)
-        za = torch.empty_like(out) if save else None
-        m.save_za = _p(za)
+    za = torch.empty_like(out) if (save and ln is not None) else None
+    m = _mab_struct(cfg, x2, y2, ignore, pk, prm, ln)
+    m.out, m.ldo, m.save_o, m.save_z, m.save_za = _p(out), out.stride(0), _p(o), _p(z), _p(za)
     check(_lib.lib().mpg_mab_fwd(C.byref(m), _stream()), "mpg_mab_fwd")
-    return (out, o, z, tag) if ln is None else (out, o, z, tag, za)
+    return out, MABSaved(x2, y2, ignore, o, z, za, *(ln[:4] if ln is not None else ()))
+
+
+def _mab_rows(x, y):
+    """The rows the kernels take of x [B, L, E] and y [B, S, E] or None: (x2, y2, B, L, S, shared).  ``shared``: x is ONE query
+    row for all B > 1 jets of y (PMA's learned seed, gapt/model.py:170-174: ``S.repeat(B, 1, 1)``) -- read with row stride 0
+    instead of being copied B times."""
+    B, L, E = x.shape
+    shared = B == 1 and L == 1 and y is not None and y.shape[0] > 1
+    if shared:
+        B = y.shape[0]
+    S = L if y is None else y.shape[1]
+    x2 = x.reshape(1, E).contiguous().expand(B, E) if shared else x.reshape(B * L, E).contiguous()
+    y2 = None if y is None else y.reshape(B * S, E).contiguous()
+    return x2, y2, B, L, S, shared
+
+
+def _mab_run(x, y, ignore, pk, prm, ln, H, alpha, ff_act, p_mab, p_ff, training, save):
+    """One block on x [B, L, E] / y [B, S, E] or None: (out [B, L, E], MABSaved, MABCfg, shared)."""
+    x2, y2, B, L, S, shared = _mab_rows(x, y)
+    cfg = _mab_cfg(x.device, B, L, S, x.shape[2], H, alpha, ff_act, p_mab, p_ff, training)
+    out, saved = mab_forward(cfg, x2, y2, ignore, pk, prm, save=save, ln=ln)
+    return out.reshape(B, L, cfg.E), saved, cfg, shared
+
+
+def mab_block(x, y, ignore, pk, prm, ln, H, alpha, ff_act, p_mab, p_ff, training):
+    """MAB.forward (gapt/model.py:124-139) as one launch: x [B, L, E] queries -- or the [1, 1, E] row all jets share, see
+    ``_mab_rows`` --, y [B, S, E] keys/values or None for self-attention, ``prm`` the block's ``MABParams``, ``ln`` as in
+    ``_mab_struct``.  With grad enabled through ``FusedMABFn``; without, nothing is kept (no o, z or za)."""
+    if not torch.is_grad_enabled():
+        return _mab_run(x, y, ignore, pk, prm, ln, H, alpha, ff_act, p_mab, p_ff, training, False)[0]
+    if ln is not None and x.shape[0] == 1 and y is not None and y.shape[0] > 1:
+        # the shared row of a layer_norm=True block is copied per jet: autograd sums its gradient over the jets
+        # (without LayerNorm the backward of FusedMABFn does, from the stride-0 row)
+        x = x.expand(y.shape[0], -1, -1)
+    return FusedMABFn.apply(x, y, ignore, *prm, *(ln if ln is not None else (None,) * 5), H, alpha, ff_act, p_mab, p_ff, training, pk)
 
 
 def _ln_param_grads(dn, gn, w, b, need_w, need_b):
@@ -1372,29 +1411,27 @@ def _ln_param_grads(dn, gn, w, b, need_w, need_b):
     for k, (rows, prm, need) in enumerate(((gn, w, need_w), (dn, b, need_b))):
         if not need:
             continue
-        tgt = _grad_target(prm) if (st.grad_into_param and st.deferred_wgrad is not None) else None
-        if tgt is not None:
-            st.deferred_wgrad.add(rows, rows[:, :1], out=torch.empty((E, 1), device=dn.device, dtype=torch.float32),
-                                  bias_out=tgt.reshape(-1), accumulate=True)
+        queue = _deferred_targets(st, [prm])
+        if queue is not None:
+            queue[1].add(rows, rows[:, :1], out=torch.empty((E, 1), device=dn.device, dtype=torch.float32),
+                         bias_out=queue[0][0].reshape(-1), accumulate=True)
         else:
             out[k] = rows.sum(0)
     return out
 
 
-def _mab_backward_block(x2, y2, ignore, o, z, params, pk, cfg, gout, need_x, need_y, need_w, ln=None, za=None, need_ln=False):
+def _mab_backward_block(cfg, sv, prm, pk, gout, need_x, need_y, need_w, eps=None, need_ln=False):
     """The backward of one attention block (``mpg_mab_bwd`` + its weight gradients: queued for the grouped launches inside a
-    TrainStep backward, computed at once otherwise): (dx rows or None, dy rows or None, the six parameter gradients or Nones).
-    ``ln`` / ``za``: the block's norms and the input of norm1 kept by the forward; with ``need_ln`` the rows for the norms'
-    parameter gradients are produced and returned as a fourth value (dn1, gn1, dn2, gn2)."""
-    B, L, S, E, H, alpha, ff_act, tag, p_mab, p_ff = cfg
-    bin_, bo, bf = params[1], params[3], params[5]
+    TrainStep backward, computed at once otherwise) from its ``MABCfg``, ``MABSaved`` and ``MABParams``: (dx rows or None, dy rows
+    or None, the six parameter gradients or Nones, lnrows).  ``eps``: of the norms of a ``layer_norm=True`` block; with
+    ``need_ln`` the rows for the norms' parameter gradients are produced, lnrows = (dn1, gn1, dn2, gn2), else None."""
+    B, L, S, E = cfg.B, cfg.L, cfg.S, cfg.E
+    x2, y2, o, z = sv.x2, sv.y2, sv.o, sv.z
     dev = x2.device
     cross = y2 is not None
-    thr_mab, sc_mab = drop_params(p_mab)
-    thr_ff, sc_ff = drop_params(p_ff)
     dout = gout.reshape(B * L, E).contiguous()
-    m = _mab_struct(x2, y2, ignore, pk, bin_, bo, bf, B, L, S, E, H, alpha, ff_act, tag, thr_mab, sc_mab, thr_ff, sc_ff)
-    m.save_o, m.save_z = _p(o), _p(z)
+    m = _mab_struct(cfg, x2, y2, sv.ignore, pk, prm, None if sv.n1w is None else (sv.n1w, sv.n1b, sv.n2w, sv.n2b, eps))
+    m.save_o, m.save_z, m.save_za = _p(o), _p(z), _p(sv.za)
     m.dout, m.lddout = _p(dout), dout.stride(0)
     dx = torch.empty((B * L, E), device=dev, dtype=torch.float32) if need_x else None
     dy = torch.empty((B * S, E), device=dev, dtype=torch.float32) if (cross and need_y) else None
@@ -1414,31 +1451,22 @@ def _mab_backward_block(x2, y2, ignore, o, z, params, pk, cfg, gout, need_x, nee
         dza = torch.empty_like(dout)
         m.dza = _p(dza)
     lnrows = None
-    if ln is not None:
-        _mab_set_ln(m, ln)
-        m.save_za = _p(za)
-        if need_ln:
-            lnrows = tuple(torch.empty((B * L, E), device=dev, dtype=torch.float32) for _ in range(4))
-            m.dn1, m.gn1, m.dn2, m.gn2 = (_p(t) for t in lnrows)
+    if need_ln:
+        lnrows = tuple(torch.empty((B * L, E), device=dev, dtype=torch.float32) for _ in range(4))
+        m.dn1, m.gn1, m.dn2, m.gn2 = (_p(t) for t in lnrows)
     check(_lib.lib().mpg_mab_bwd(C.byref(m), _stream()), "mpg_mab_bwd")
     grads = [None] * 6
     if need_w:
-        st = dev_state(dev)
-        tg = None
-        if st.grad_into_param and st.deferred_wgrad is not None:
-            tg = [_grad_target(q) for q in params]
-            if any(t is None for t in tg):
-                tg = None
-        if tg is not None:      # TrainStep: queued for the grouped launches, added into the flat gradient buffers
-            gWin, gbin, gWo, gbo, gWf, gbf = tg
-            wb = st.deferred_wgrad
+        queue = _deferred_targets(dev_state(dev), prm)
+        if queue is not None:      # TrainStep: queued for the grouped launches, added into the flat gradient buffers
+            g, wb = MABParams(*queue[0]), queue[1]
             if cross:
-                wb.add(dq, x2, out=gWin[:E], bias_out=gbin[:E], accumulate=True)
-                wb.add(dkv, y2, out=gWin[E:], bias_out=gbin[E:], accumulate=True)
+                wb.add(dq, x2, out=g.Win[:E], bias_out=g.bin[:E], accumulate=True)
+                wb.add(dkv, y2, out=g.Win[E:], bias_out=g.bin[E:], accumulate=True)
             else:
-                wb.add(dqkv, x2, out=gWin, bias_out=gbin, accumulate=True)
-            wb.add(dza, o, out=gWo, bias_out=gbo, accumulate=True)
-            wb.add(du, z, out=gWf, bias_out=gbf, accumulate=True)
+                wb.add(dqkv, x2, out=g.Win, bias_out=g.bin, accumulate=True)
+            wb.add(dza, o, out=g.Wo, bias_out=g.bo, accumulate=True)
+            wb.add(du, z, out=g.Wf, bias_out=g.bf, accumulate=True)
         else:
             def wgrad(dyv, xv):
                 db = torch.empty(dyv.shape[1], device=dev, dtype=torch.float32)
@@ -1450,170 +1478,102 @@ def _mab_backward_block(x2, y2, ignore, o, z, params, pk, cfg, gout, need_x, nee
                 grads[0], grads[1] = wgrad(dqkv, x2)
             grads[2], grads[3] = wgrad(dza, o)
             grads[4], grads[5] = wgrad(du, z)
-    return (dx, dy, grads) if ln is None else (dx, dy, grads, lnrows)
+    return dx, dy, grads, lnrows
 
 
-def sab_chain_forward(x, ignore, H, alpha, ff_act, p_mab, p_ff, training, pks, params):
-    """``FusedSABChainFn`` without a backward to prepare for: one launch, nothing kept but the last block's output."""
+def sab_chain_forward(x, ignore, H, alpha, ff_act, p_mab, p_ff, training, pks, blocks, save=False):
+    """``mpg_mab_chain_fwd``: the self-attention blocks ``blocks`` (their ``MABParams``; ``pks``: their ``PackedMAB`` sets) applied
+    to x [B, L, E] one after the other in ONE launch.  Returns (the last block's output [B, L, E], a ``MABSaved`` and a ``MABCfg``
+    per block); without ``save`` nothing is kept of o and z."""
     B, L, E = x.shape
     dev = x.device
-    x2 = x.reshape(B * L, E).contiguous()
-    thr_mab, sc_mab = drop_params(p_mab) if training else (0, 1.0)
-    thr_ff, sc_ff = drop_params(p_ff) if training else (0, 1.0)
     c = _lib.MpgMabChain()
     c.n = len(pks)
-    inp, keep = x2, []
-    for b in range(len(pks)):
+    inp, saved, cfgs = x.reshape(B * L, E).contiguous(), [], []
+    for b, (pk, prm) in enumerate(zip(pks, blocks)):
+        cfg = _mab_cfg(dev, B, L, L, E, H, alpha, ff_act, p_mab, p_ff, training)
         out = torch.empty((B * L, E), device=dev, dtype=torch.float32)
-        m = _mab_struct(inp, None, ignore, pks[b], params[6 * b + 1], params[6 * b + 3], params[6 * b + 5], B, L, L, E, H, alpha, ff_act,
-                        next_tag(dev, "mab", max(thr_mab, thr_ff)), thr_mab, sc_mab, thr_ff, sc_ff)
-        m.out, m.ldo = _p(out), E
+        o, z = (torch.empty_like(out), torch.empty_like(out)) if save else (None, None)
+        m = _mab_struct(cfg, inp, None, ignore, pk, prm)
+        m.out, m.ldo, m.save_o, m.save_z = _p(out), E, _p(o), _p(z)
         c.blk[b] = m
-        keep.append(out)
+        saved.append(MABSaved(inp, None, ignore, o, z))
+        cfgs.append(cfg)
         inp = out
     check(_lib.lib().mpg_mab_chain_fwd(C.byref(c), _stream()), "mpg_mab_chain_fwd")
-    return keep[-1].reshape(B, L, E)
+    return inp.reshape(B, L, E), saved, cfgs
 
 
 class FusedSABChainFn(torch.autograd.Function):
     """Several self-attention blocks applied one after the other (the SABs of GAPT_G / GAPT_D, gapt/model.py:261-262, :341-342)
-    with ONE forward launch (``mpg_mab_chain_fwd``: a wave keeps its jet's rows in registers from block to block); the backward
-    runs block by block (``mpg_mab_bwd``).  ``params``: (in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias, ff weight,
-    ff bias) per block; ``pks``: the blocks' ``PackedMAB`` sets."""
+    with ONE forward launch (``sab_chain_forward``: a wave keeps its jet's rows in registers from block to block); the backward
+    runs block by block (``mpg_mab_bwd``).  ``params``: the blocks' ``MABParams``, one after the other; ``pks``: their
+    ``PackedMAB`` sets."""
 
     @staticmethod
     def forward(ctx, x, ignore, H, alpha, ff_act, p_mab, p_ff, training, pks, *params):
-        B, L, E = x.shape
-        n = len(pks)
-        dev = x.device
-        x2 = x.reshape(B * L, E).contiguous()
-        thr_mab, sc_mab = drop_params(p_mab) if training else (0, 1.0)
-        thr_ff, sc_ff = drop_params(p_ff) if training else (0, 1.0)
-        c = _lib.MpgMabChain()
-        c.n = n
-        inp, outs, os_, zs_, tags = x2, [], [], [], []
-        for b in range(n):
-            bin_, bo, bf = params[6 * b + 1], params[6 * b + 3], params[6 * b + 5]
-            tag = next_tag(dev, "mab", max(thr_mab, thr_ff))
-            out, o, z = (torch.empty((B * L, E), device=dev, dtype=torch.float32) for _ in range(3))
-            m = _mab_struct(inp, None, ignore, pks[b], bin_, bo, bf, B, L, L, E, H, alpha, ff_act, tag, thr_mab, sc_mab, thr_ff, sc_ff)
-            m.out, m.ldo, m.save_o, m.save_z = _p(out), E, _p(o), _p(z)
-            c.blk[b] = m
-            outs.append(out); os_.append(o); zs_.append(z); tags.append(tag)
-            inp = out
-        check(_lib.lib().mpg_mab_chain_fwd(C.byref(c), _stream()), "mpg_mab_chain_fwd")
-        ctx.save_for_backward(x2, ignore, *outs[:-1], *os_, *zs_)
-        ctx.pks, ctx.params, ctx.n = pks, params, n
-        ctx.cfgs = [(B, L, L, E, H, alpha, ff_act, tags[b], p_mab if training else 0.0, p_ff if training else 0.0) for b in range(n)]
-        return outs[-1].reshape(B, L, E)
+        ctx.blocks = [MABParams(*g) for g in _groups(params, len(MABParams._fields))]
+        out, saved, ctx.cfgs = sab_chain_forward(x, ignore, H, alpha, ff_act, p_mab, p_ff, training, pks, ctx.blocks, save=True)
+        # the key mask once, then per block what differs: its input rows (the output of the block before), o and z
+        ctx.save_for_backward(ignore, *(t for sv in saved for t in (sv.x2, sv.o, sv.z)))
+        ctx.pks = pks
+        return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
-        n = ctx.n
-        sv = ctx.saved_tensors
-        x2, ignore = sv[0], sv[1]
-        ins = [x2] + list(sv[2:2 + n - 1])            # the input rows of block b: x, then the outputs of the blocks before
-        os_, zs_ = sv[2 + n - 1:2 + 2 * n - 1], sv[2 + 2 * n - 1:2 + 3 * n - 1]
-        B, L, _, E = ctx.cfgs[0][:4]
-        g = gout
-        all_grads = [None] * (6 * n)
-        for b in reversed(range(n)):
-            prm = ctx.params[6 * b:6 * b + 6]
-            need_w = any(ctx.needs_input_grad[9 + 6 * b:9 + 6 * b + 6])
+        ignore, *rows = ctx.saved_tensors
+        saved = [MABSaved(x2=x2, y2=None, ignore=ignore, o=o, z=z) for x2, o, z in _groups(rows, 3)]
+        need_params = _groups(ctx.needs_input_grad[9:], len(MABParams._fields))
+        g, all_grads = gout, []
+        for b in reversed(range(len(saved))):
             need_x = b > 0 or ctx.needs_input_grad[0]
-            dx, _, grads = _mab_backward_block(ins[b], None, ignore, os_[b], zs_[b], prm, ctx.pks[b], ctx.cfgs[b], g, need_x, False, need_w)
-            all_grads[6 * b:6 * b + 6] = grads
-            g = dx
-        return (None if g is None else g.reshape(B, L, E), None, None, None, None, None, None, None, None, *all_grads)
+            g, _, grads, _ = _mab_backward_block(ctx.cfgs[b], saved[b], ctx.blocks[b], ctx.pks[b], g, need_x, False, any(need_params[b]))
+            all_grads[:0] = grads
+        return (None if g is None else g.reshape(gout.shape), None, None, None, None, None, None, None, None, *all_grads)
 
 
 class FusedMABFn(torch.autograd.Function):
-    """MAB.forward (gapt/model.py:124-139) as ONE launch each way (``mpg_mab_fwd`` / ``mpg_mab_bwd``).  x [B, L, E]
-    queries, y [B, S, E] keys/values or None for self-attention.  The forward keeps only o (attention output) and z
-    (input of the feed-forward layer); the backward recomputes the rest and hands the three pre-activation gradients to
-    the grouped weight-gradient launches (``TrainStep``) or computes the weight gradients itself."""
-
-    @staticmethod
-    def forward(ctx, x, y, ignore, Win, bin_, Wo, bo, Wf, bf, H, alpha, ff_act, p_mab, p_ff, training, pk):
-        """``x`` [1, 1, E] with ``y`` [B, S, E], B > 1: ONE query row shared by all jets (PMA's learned seed, gapt/model.py:170-174:
-        ``S.repeat(B, 1, 1)``) -- read with row stride 0 instead of being copied B times, and its gradient summed over the jets by
-        the grouped weight-gradient launch (as a bias sum) instead of a reduction launch of its own."""
-        B, L, E = x.shape
-        bcast = B == 1 and L == 1 and y is not None and y.shape[0] > 1
-        if bcast:
-            B = y.shape[0]
-        S = L if y is None else y.shape[1]
-        x2 = x.reshape(1, E).contiguous().expand(B, E) if bcast else x.reshape(B * L, E).contiguous()   # (row stride 0)
-        y2 = None if y is None else y.reshape(B * S, E).contiguous()
-        ctx.bcast = bcast
-        out, o, z, tag = mab_forward(x2, y2, ignore, pk, bin_, bo, bf, B, L, S, H, alpha=alpha, ff_act=ff_act,
-                                     p_mab=p_mab, p_ff=p_ff, training=training, save=True)
-        ctx.save_for_backward(x2, y2, ignore, o, z, bin_, bo, bf)
-        ctx.pk, ctx.params = pk, (Win, bin_, Wo, bo, Wf, bf)
-        ctx.seed = x if (bcast and x.is_leaf) else None     # (the parameter itself: its .grad takes the summed gradient directly)
-        ctx.cfg = (B, L, S, E, H, alpha, ff_act, tag, p_mab if training else 0.0, p_ff if training else 0.0)
-        return out.reshape(B, L, E)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gout):
-        x2, y2, ignore, o, z, bin_, bo, bf = ctx.saved_tensors
-        B, L, S, E, H, alpha, ff_act, tag, p_mab, p_ff = ctx.cfg
-        dev = x2.device
-        dx, dy, grads = _mab_backward_block(x2, y2, ignore, o, z, ctx.params, ctx.pk, ctx.cfg, gout,
-                                            ctx.needs_input_grad[0], ctx.needs_input_grad[1], any(ctx.needs_input_grad[3:9]))
-        if ctx.bcast and dx is not None:
-            # the shared query row's gradient: the sum over the jets -- a bias-sum job of the grouped launch when there is one
-            st = dev_state(dev)
-            gS = _grad_target(ctx.seed) if (st.grad_into_param and st.deferred_wgrad is not None and ctx.seed is not None) else None
-            if gS is not None:
-                st.deferred_wgrad.add(dx, dx[:, :1], out=torch.empty((E, 1), device=dev, dtype=torch.float32), bias_out=gS.reshape(-1),
-                                      accumulate=True)
-                dx = None
-            else:
-                dx = dx.sum(0).reshape(1, 1, E)
-            return (dx, None if dy is None else dy.reshape(B, S, E), None, *grads, None, None, None, None, None, None, None)
-        return (None if dx is None else dx.reshape(B, L, E), None if dy is None else dy.reshape(B, S, E), None,
-                *grads, None, None, None, None, None, None, None)
-
-
-class FusedMABLayerNormFn(torch.autograd.Function):
-    """``FusedMABFn`` for a block with ``layer_norm=True`` (gapt/model.py:118-120, :131-136): ``nn.LayerNorm`` behind each of
-    the two residuals, inside the same launch each way (``mpg_mab_fwd`` / ``mpg_mab_bwd`` with the norms' parameters set: one wave
-    per jet).  The forward also keeps za, the input of norm1; the backward leaves, per row, the gradients with respect to the
-    norms' outputs and those times the normalised inputs -- their column sums, the norms' parameter gradients, ride in the grouped
-    weight-gradient launch.  x [B, L, E], y [B, S, E] or None."""
+    """``mab_block`` with a backward: ONE launch each way (``mpg_mab_fwd`` / ``mpg_mab_bwd``).  The forward keeps a ``MABSaved``
+    (o, z and, with LayerNorm, za; the backward recomputes the rest); the backward hands the three pre-activation gradients to
+    the grouped weight-gradient launches (``TrainStep``) or computes the weight gradients itself.  ``n1w`` ... ``eps``: norm1 /
+    norm2 of a block with ``layer_norm=True`` (gapt/model.py:118-120, :131-136), which then run inside the same launches (one wave
+    per jet); None without.  The backward then leaves, per row, the gradients with respect to the norms' outputs and those times
+    the normalised inputs: their column sums are the norms' parameter gradients (``_ln_param_grads``)."""
 
     @staticmethod
     def forward(ctx, x, y, ignore, Win, bin_, Wo, bo, Wf, bf, n1w, n1b, n2w, n2b, eps, H, alpha, ff_act, p_mab, p_ff, training, pk):
-        B, L, E = x.shape
-        S = L if y is None else y.shape[1]
-        x2 = x.reshape(B * L, E).contiguous()
-        y2 = None if y is None else y.reshape(B * S, E).contiguous()
-        ln = (n1w, n1b, n2w, n2b, eps)
-        out, o, z, tag, za = mab_forward(x2, y2, ignore, pk, bin_, bo, bf, B, L, S, H, alpha=alpha, ff_act=ff_act,
-                                         p_mab=p_mab, p_ff=p_ff, training=training, save=True, ln=ln)
-        ctx.save_for_backward(x2, y2, ignore, o, z, za, n1w, n1b, n2w, n2b)
-        ctx.pk, ctx.params, ctx.eps = pk, (Win, bin_, Wo, bo, Wf, bf), eps
-        ctx.cfg = (B, L, S, E, H, alpha, ff_act, tag, p_mab if training else 0.0, p_ff if training else 0.0)
-        return out.reshape(B, L, E)
+        ctx.params = MABParams(Win, bin_, Wo, bo, Wf, bf)
+        ln = None if n1w is None else (n1w, n1b, n2w, n2b, eps)
+        out, saved, ctx.cfg, ctx.shared = _mab_run(x, y, ignore, pk, ctx.params, ln, H, alpha, ff_act, p_mab, p_ff, training, True)
+        ctx.save_for_backward(*saved)
+        ctx.pk, ctx.eps = pk, eps
+        # the shared row's gradient is the sum over the jets; the parameter itself: its .grad can take that sum directly
+        ctx.seed = x if (ctx.shared and x.is_leaf) else None
+        return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
-        x2, y2, ignore, o, z, za, n1w, n1b, n2w, n2b = ctx.saved_tensors
-        B, L, S, E, *_ = ctx.cfg
-        need = ctx.needs_input_grad
-        need_ln = any(need[9:13])
-        dx, dy, grads, rows = _mab_backward_block(x2, y2, ignore, o, z, ctx.params, ctx.pk, ctx.cfg, gout, need[0], need[1],
-                                                  any(need[3:9]), ln=(n1w, n1b, n2w, n2b, ctx.eps), za=za, need_ln=need_ln)
-        g1 = g2 = (None, None)
-        if need_ln:
-            g1 = _ln_param_grads(rows[0], rows[1], n1w, n1b, need[9], need[10])
-            g2 = _ln_param_grads(rows[2], rows[3], n2w, n2b, need[11], need[12])
-        return (None if dx is None else dx.reshape(B, L, E), None if dy is None else dy.reshape(B, S, E), None, *grads,
-                g1[0], g1[1], g2[0], g2[1], None, None, None, None, None, None, None, None)
+        sv, cfg, need = MABSaved(*ctx.saved_tensors), ctx.cfg, ctx.needs_input_grad
+        dx, dy, grads, rows = _mab_backward_block(cfg, sv, ctx.params, ctx.pk, gout, need[0], need[1], any(need[3:9]),
+                                                  eps=ctx.eps, need_ln=any(need[9:13]))
+        gln = [None] * 4
+        if rows is not None:
+            gln = (_ln_param_grads(rows[0], rows[1], sv.n1w, sv.n1b, need[9], need[10])
+                   + _ln_param_grads(rows[2], rows[3], sv.n2w, sv.n2b, need[11], need[12]))
+        if ctx.shared and dx is not None:
+            # a bias-sum job of the grouped weight-gradient launch when there is one, instead of a reduction launch of its own
+            queue = _deferred_targets(dev_state(dx.device), [ctx.seed]) if ctx.seed is not None else None
+            if queue is not None:
+                queue[1].add(dx, dx[:, :1], out=torch.empty((cfg.E, 1), device=dx.device, dtype=torch.float32),
+                             bias_out=queue[0][0].reshape(-1), accumulate=True)
+                dx = None
+            else:
+                dx = dx.sum(0).reshape(1, 1, cfg.E)
+        elif dx is not None:
+            dx = dx.reshape(cfg.B, cfg.L, cfg.E)
+        return (dx, None if dy is None else dy.reshape(cfg.B, cfg.S, cfg.E), None, *grads, *gln, None, None, None, None, None, None, None, None)
 
 
 # ------------------------------------------------------------------------------------- per-jet pieces around the layers
@@ -1780,11 +1740,10 @@ class GenDiscBridgeFn(torch.autograd.Function):
                                           ("2", g2, feat.reshape(M, F), W2, b2, need[4], b2 is not None and need[5])):
             dW = db = None
             if g is not None:
-                gW = gb = None
-                if nW and st.grad_into_param and st.deferred_wgrad is not None:
-                    gW, gb = _grad_target(W), _grad_target(b) if nb else None
-                if gW is not None and (not nb or gb is not None):
-                    st.deferred_wgrad.add(g, xin, out=gW, bias_out=gb, accumulate=True)
+                queue = _deferred_targets(st, [W, b] if nb else [W]) if nW else None
+                if queue is not None:
+                    targets, batch = queue
+                    batch.add(g, xin, out=targets[0], bias_out=targets[1] if nb else None, accumulate=True)
                 elif nW:
                     if nb:
                         db = torch.empty(W.shape[0], device=dev, dtype=torch.float32)

@@ -344,7 +344,7 @@ def test_bridge_changes_no_result_of_a_training_step():
 
 def test_layer_norm_networks_train_on_the_one_launch_blocks():
     """GAPT with ``layer_norm=True`` inside a ``TrainStep``: every block (SABs and the pooling block) runs as one launch each way with
-    its norms inside (``ops.FusedMABLayerNormFn``), the norms' parameter gradients ride in the grouped weight-gradient launch
+    its norms inside (``ops.FusedMABFn`` with its norm inputs set), the norms' parameter gradients ride in the grouped weight-gradient launch
     as column sums.  hipGraph replay == eager bit for bit; against the block-by-block route (``MAB.fused = False``:
     ``mpg_layernorm_*`` launches) losses and parameters agree -- which also pins that a frozen norm (the discriminator's inside
     train_G) leaves its gradient buffer alone on both routes; the norms' parameters move."""

@@ -195,7 +195,7 @@ def test_fused_equals_block_by_block():
 
 
 def test_layer_norm_block_exact_dropout_vs_oracle(launches):
-    """``layer_norm=True`` blocks on the one-launch kernels (``ops.FusedMABLayerNormFn``: norm1 / norm2 inside ``mpg_mab_fwd`` /
+    """``layer_norm=True`` blocks on the one-launch kernels (``ops.FusedMABFn`` with its norm inputs set: norm1 / norm2 inside ``mpg_mab_fwd`` /
     ``mpg_mab_bwd``): training mode with dropout at all three sites, E = 64 and 32, self- and cross-attention, padded keys,
     random norm weights -- against autograd on the fp64 oracle fed with the very masks the kernels drew: output, input
     gradients, the six block parameters and the four norm parameters.  One launch each way."""
@@ -317,3 +317,116 @@ def test_large_set_kernels_on_small_sets_agree_with_the_one_wave_kernels(monkeyp
         assert rel_err(dx1, dx0) < 1e-4, name
         for k in g1:
             assert rel_err(g1[k], g0[k]) < 1e-4, (name, k)
+
+
+def _restart_dropout(dev, seed, first_tag):
+    """The same dropout seed and site tags, hence masks, for the pass that follows."""
+    import itertools
+    from mpgan_amd import ops
+    ops.set_seed(seed, dev)
+    ops.dev_state(dev).tags = itertools.count(first_tag)
+
+
+def _route_case(kind, E, n, ln, p):
+    """(block, x [3, n, E], attention mask) for the route tests: a fully ignored tile edge in every jet -- the last key of the
+    first tile: key n - 1 at n = 30 and 32, key 31 at n = 33, where key 32 (the one live key of the second tile) stays --, jet 1
+    dead (every key ignored), the rest ignored at random."""
+    from mpgan_amd.gapt import SAB, PMA
+    torch.manual_seed(21)
+    args = dict(SAB_ARGS, embed_dim=E, num_heads=E // 16, layer_norm=ln, dropout_p=p, linear_args=dict(LA, dropout_p=p))
+    blk = (PMA(num_seeds=1, **args) if kind == "pma" else SAB(**args)).cuda()
+    with torch.no_grad():
+        for k, q in blk.named_parameters():
+            if ".norm" in k:
+                q.add_(0.2 * torch.randn_like(q))
+    gen = torch.Generator().manual_seed(9)
+    x = torch.randn(3, n, E, generator=gen).cuda()
+    ign = torch.rand(3, n, generator=gen) > 0.8
+    ign[:, 0] = False
+    ign[:, min(n, 32) - 1] = True
+    ign[:, 32:] = False
+    ign[1] = True
+    return blk, x, ign.float().reshape(3, n, 1).cuda()
+
+
+ROUTE_CASES = [("sab", 64, 30), ("sab", 64, 32), ("sab", 64, 33), ("pma", 64, 30), ("sab", 32, 30)]
+
+
+@pytest.mark.parametrize("ln", [False, True])
+@pytest.mark.parametrize("kind,E,n", ROUTE_CASES)
+def test_no_grad_and_grad_routes_give_the_same_bits(kind, E, n, ln, launches):
+    """A block under ``torch.no_grad()`` and with grad enabled goes through the same entry point (``ops.mab_block``) and the same
+    ``mpg_mab_fwd`` launch, one per pass; only what is kept differs.  Self-attention at 30, 32 (the last small-set size) and 33
+    tokens (the first large-set size), PMA's shared seed row over 30 keys, E = 32; with and without LayerNorm; an ignored tile
+    edge and a dead jet in the key mask; in eval mode, and in training mode with p = 1/2 on the same dropout masks."""
+    for train in (False, True):
+        blk, x, am = _route_case(kind, E, n, ln, 0.5 if train else 0.0)
+        blk.train(train)
+        outs = []
+        for grad in (False, True):
+            _restart_dropout(x.device, 99, 6000)
+            launches.clear()
+            with torch.set_grad_enabled(grad):
+                y = blk(x, am)
+            assert launches.get("mpg_mab_fwd") == 1 and "mpg_mab_chain_fwd" not in launches and "mpg_gemm" not in launches, (train, grad, launches)
+            assert (y.grad_fn is not None) == grad
+            outs.append(y.detach())
+        assert torch.isfinite(outs[0]).all()
+        assert torch.equal(outs[0], outs[1]), (train, float((outs[0] - outs[1]).abs().max()))
+
+
+@pytest.mark.parametrize("ln", [False, True])
+@pytest.mark.parametrize("kind,E,n", ROUTE_CASES)
+def test_saved_state_by_name_and_norm_gradients(kind, E, n, ln, launches):
+    """``ops.mab_saved`` of a grad-enabled pass: za exactly with LayerNorm, y2 exactly for cross attention, o and z of shape
+    [B * L, E]; and the backward of the one Function returns gradients for the four norm parameters exactly with LayerNorm."""
+    from mpgan_amd import ops
+    blk, x, am = _route_case(kind, E, n, ln, 0.0)
+    L = 1 if kind == "pma" else n
+    y = blk(x.requires_grad_(True), am)
+    assert type(y.grad_fn).__name__ == "FusedMABFnBackward"
+    sv = ops.mab_saved(y.grad_fn)
+    assert (sv.za is None) == (not ln) and (sv.n1w is None) == (not ln)
+    assert (sv.y2 is None) == (kind == "sab")
+    assert sv.o.shape == (3 * L, E) and sv.z.shape == (3 * L, E) and (not ln or sv.za.shape == (3 * L, E))
+    assert sv.ignore is not None and sv.ignore.shape == (3 * n,)
+    launches.clear()
+    grads = y.grad_fn.apply(torch.ones_like(y))       # FusedMABFn.backward itself: one gradient slot per input of FusedMABFn.apply
+    assert launches.get("mpg_mab_bwd") == 1, launches
+    assert len(grads) == 21
+    assert all((g is not None) == ln for g in grads[9:13]), [g is None for g in grads]
+    assert all(g is None for g in grads[13:]) and all(g is not None for g in grads[3:9])
+    if ln:
+        mab = blk.mab
+        y.backward(torch.ones_like(y))          # the same gradients through autograd: each slot is its own parameter's
+        for g, q in zip(grads[9:13], (mab.norm1.weight, mab.norm1.bias, mab.norm2.weight, mab.norm2.bias)):
+            assert g.shape == q.shape and torch.isfinite(g).all()
+            assert torch.allclose(g, q.grad, rtol=1e-6, atol=0.0), float((g - q.grad).abs().max())
+
+
+@pytest.mark.parametrize("nblk", [2, 3])
+@pytest.mark.parametrize("n", [30, 32])
+def test_sab_chain_no_grad_and_grad_routes_give_the_same_bits(nblk, n, launches):
+    """``_run_sabs`` on two and three plain SABs: the pass without and the pass with a backward to prepare for build the same
+    ``mpg_mab_chain_fwd`` launch (``ops.sab_chain_forward``, ``save`` off and on) -- one each, no ``mpg_mab_fwd``, equal bits --
+    and the backward runs one ``mpg_mab_bwd`` per block."""
+    from mpgan_amd.gapt import SAB
+    from mpgan_amd.gapt.model import _run_sabs
+    torch.manual_seed(17)
+    la = dict(LA, dropout_p=0.5)
+    sabs = [SAB(**dict(SAB_ARGS, dropout_p=0.5, linear_args=la)).cuda().train() for _ in range(nblk)]
+    _, x, am = _route_case("sab", 64, n, False, 0.0)
+    outs = []
+    for grad in (False, True):
+        _restart_dropout(x.device, 98, 6500)
+        launches.clear()
+        with torch.set_grad_enabled(grad):
+            y = _run_sabs(sabs, x, am)
+        assert launches.get("mpg_mab_chain_fwd") == 1 and "mpg_mab_fwd" not in launches, (grad, launches)
+        outs.append(y)
+    assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1].detach())
+    launches.clear()
+    outs[1].square().sum().backward()
+    assert launches.get("mpg_mab_bwd") == nblk and "mpg_mab_fwd" not in launches, launches
+    for sab in sabs:
+        assert all(q.grad is not None and torch.isfinite(q.grad).all() for q in sab.parameters())

@@ -265,3 +265,56 @@ def test_synthetic_jet_laws_and_learning_rates_per_jet_type():
         assert bool(((data[..., 3] > 0)[:, :-1] >= (data[..., 3] > 0)[:, 1:]).all())   # real particles first
         mean[law] = float(n.float().mean())
     assert mean["top"] > 27 > mean["gluon"] > mean["quark"] > mean["uniform"]
+
+
+def test_packed_sets_share_one_job_layout_and_see_parameter_changes():
+    """``PackedMPLayer`` / ``PackedMAB`` on CPU tensors (construction launches nothing): twelve and six pack jobs of one tuple
+    length -- what ``refresh_many`` unpacks --, and a key that moves with an in-place update and with a new storage."""
+    from mpgan_amd import ops
+    F, out, E = 6, 8, 32
+    W1, W2, W3 = torch.randn(ops.H1, 2 * F + 1), torch.randn(ops.H2, ops.H1), torch.randn(ops.H3, ops.H2)
+    V1, V2, V3 = torch.randn(16, ops.H3 + F), torch.randn(16, 16), torch.randn(out, 16)
+    Win, Wo, Wf = torch.randn(3 * E, E), torch.randn(E, E), torch.randn(E, E)
+    for pk, n in ((ops.PackedMPLayer((W1, W2, W3, V1, V2, V3), F, out, 2.0, True), 12), (ops.PackedMAB(Win, Wo, Wf), 6)):
+        jobs = pk.jobs()
+        assert len(jobs) == n and {len(j) for j in jobs} == {9}
+        assert set(pk.img) == set(pk._spec) and len(pk.img) == n
+        for W, rows, cols, tr, scale, f16, row_split, split_cols, img in jobs:
+            assert any(W is q for q in pk.params) and tr in (0, 1) and img.numel() == ops._img_elems(rows, cols)
+            assert (row_split, split_cols) == (0, 0) or (row_split, split_cols) == (ops.H1, F)
+        key = pk._current_key()
+        assert pk._key is None and key == pk._current_key()
+        last = pk.params[-1]
+        last.add_(1.0)
+        key2 = pk._current_key()
+        assert key2 != key and key2[:-1] == key[:-1]
+        pk.params[0].data = pk.params[0].data.clone()
+        key3 = pk._current_key()
+        assert key3 != key2 and key3[1:] == key2[1:]
+    assert sum(1 for j in ops.PackedMPLayer((W1, W2, W3, V1, V2, V3), F, out, 2.0, True).jobs() if j[6]) == 2   # W1S, W1ST
+
+
+def test_deferred_targets_only_inside_a_collecting_backward_with_every_target():
+    """``ops._deferred_targets``: the ``.grad`` targets in order plus the batch while ``grad_into_param`` is on, a batch is
+    collecting and EVERY parameter has a target; None otherwise."""
+    from mpgan_amd import ops
+    st = ops.DeviceState(-1)
+    W = torch.nn.Parameter(torch.randn(6, 4))
+    b = torch.nn.Parameter(torch.randn(6))
+    bare = torch.nn.Parameter(torch.randn(3))          # no .grad buffer
+    W.grad, b.grad = torch.zeros_like(W), torch.zeros_like(b)
+    batch = object()
+    assert ops._deferred_targets(st, [W, b]) is None                       # nothing switched on
+    st.deferred_wgrad = batch
+    assert ops._deferred_targets(st, [W, b]) is None                       # grad_into_param off
+    st.grad_into_param, st.deferred_wgrad = True, None
+    assert ops._deferred_targets(st, [W, b]) is None                       # no batch
+    st.deferred_wgrad = batch
+    assert ops._deferred_targets(st, [W, bare]) is None                    # one parameter without a target
+    assert ops._deferred_targets(st, [W, None]) is None
+    targets, got = ops._deferred_targets(st, [W, b])
+    assert got is batch and len(targets) == 2 and targets[0] is W.grad and targets[1] is b.grad
+    rows = W[2:5]                                                          # a row slice of a leaf: the matching view of its .grad
+    (t,), _ = ops._deferred_targets(st, [rows])
+    assert t.shape == (3, 4) and t.data_ptr() == W.grad[2:5].data_ptr()
+    assert ops._deferred_targets(st, [b, W])[0][0] is b.grad
