@@ -597,6 +597,33 @@ int mpg_normal(float* out, uint64_t n, const uint64_t* seed, uint32_t tag, float
 int mpg_normal_rank_mask(float* out, int B, int N, int L, const uint64_t* seed, uint32_t tag, float mean, float std,
                          const float* labels, int ld_lab, float* mask, float* ignore, void* stream);
 
+/* mpg_augment / mpg_augment_bwd: augment.augment (mpgan/augment.py; train_D / train_G, train.py:438-442, :508-511) on B jets
+ * of N particles, F features each at row stride ld floats and jet stride jet_stride floats (the same for x and y: the second
+ * half of a 2B-jet batch is a valid target).  All four stages are affine in (eta, phi) and act on a whole jet, so their
+ * mixed composition is one map per jet,  y[b, i, 0:2] = A_b x[b, i, 0:2] + t_b;  columns >= 2 pass through (copied when
+ * y != x; y may be x).  Padded particles are moved like the others, as the reference moves them.
+ * Draws: word(i) = the project's counter-based hash of (the 64-bit *seed, tag, jet b, draw index i) -- the stream of the
+ * dropout masks and of mpg_normal --, u(i) = (word(i) >> 8) * 2^-24 in [0, 1).  p is read from DEVICE memory (one float: a
+ * captured hipGraph follows a changed probability without recapture); a stage is TAKEN iff its flag bit is set, p != 1 and
+ * u(mix draw) < p -- p == 1 takes nothing, rand_mix's own quirk.  A stage whose bit is clear draws nothing.  Starting from
+ * A = I, t = 0, in the reference's order:
+ *   MPG_AUG_R90        mix u(0);  k = floor(4 u(1));  A <- R^k A, t <- R^k t,  R = [[0, -1], [1, 0]] (entries exactly 0 / +-1)
+ *   MPG_AUG_FLIP       mix u(2);  s_eta = u(3) >= 0.5 ? +1 : -1, s_phi likewise from u(4);  A <- diag(s) A, t <- diag(s) t
+ *   MPG_AUG_TRANSLATE  mix u(5);  t <- t + ((u(6), u(7)) - 0.5) * translate_ratio
+ *   MPG_AUG_SCALE      mix u(8);  z = sqrt(-2 ln v(9)) cos(2 pi v(10)), v(i) = ((word(i) >> 8) + 0.5) * 2^-24 (mpg_normal's
+ *                      form);  f = exp(scale_sd * z);  A <- f A, t <- f t
+ * params [B, 6] receives (a00, a01, a10, a11, t0, t1) per jet.  N == 0 (x, y may be NULL): the maps alone.
+ * mpg_augment_bwd: dx[b, i, 0:2] = A_b^T dy[b, i, 0:2] from the saved params, columns >= 2 copied; no random stream.
+ * B >= 1, 2 <= F <= ld, jet_stride >= N ld (else -1). */
+#define MPG_AUG_R90 1
+#define MPG_AUG_FLIP 2
+#define MPG_AUG_TRANSLATE 4
+#define MPG_AUG_SCALE 8
+int mpg_augment(const float* x, float* y, uint64_t jet_stride, int ld, int F, int B, int N, const uint64_t* seed, uint32_t tag,
+                const float* p, int flags, float translate_ratio, float scale_sd, float* params, void* stream);
+int mpg_augment_bwd(const float* dy, float* dx, uint64_t jet_stride, int ld, int F, int B, int N, const float* params,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

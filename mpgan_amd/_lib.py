@@ -253,6 +253,9 @@ SIGNATURES = {
     "mpg_jet_emd_host": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, C.c_int]),
     "mpg_jet_emd_host_iters": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp,
                                          C.c_int]),
+    "mpg_augment": (C.c_int, [_fp, _fp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_uint32, _fp, C.c_int, C.c_float,
+                              C.c_float, _fp, C.c_void_p]),
+    "mpg_augment_bwd": (C.c_int, [_fp, _fp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_void_p]),
 }
 
 

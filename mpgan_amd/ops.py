@@ -447,6 +447,87 @@ def normal_noise_masked(shape, std: float, labels: torch.Tensor, site: int = 0, 
     return out, mask.view(B, N), ign.view(B, N)
 
 
+# ------------------------------------------------------------------------------------- augmentation
+AUG_TAG = 0x41000000   # site tags of ``augment`` (clear of NOISE_TAG and of the dropout sites below 2^27)
+AUG_R90, AUG_FLIP, AUG_TRANSLATE, AUG_SCALE = 1, 2, 4, 8   # MPG_AUG_* of include/mpgan_amd.h
+
+
+def augment_flags(aug_r90=False, aug_f=False, aug_t=False, aug_s=False) -> int:
+    """The reference's four switches (``--aug-r90 / -f / -t / -s``) as ``mpg_augment``'s flag bits."""
+    return AUG_R90 * bool(aug_r90) + AUG_FLIP * bool(aug_f) + AUG_TRANSLATE * bool(aug_t) + AUG_SCALE * bool(aug_s)
+
+
+def _jet_layout(x: torch.Tensor, name: str):
+    _chk(x, name)
+    B, N, F = x.shape
+    if x.stride(2) != 1 or x.stride(1) < F or x.stride(0) < N * x.stride(1):
+        raise ValueError(f"{name}: rows of unit feature stride, jets of whole rows expected (strides {x.stride()})")
+    return B, N, F
+
+
+def augment_params(B: int, p_tensor: torch.Tensor, flags: int, translate_ratio: float, scale_sd: float, site: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The per-jet maps ``augment`` would apply to ``B`` jets at ``site`` under the current seed, [B, 6] =
+    (a00, a01, a10, a11, t0, t1), without applying them."""
+    _chk(p_tensor, "p_tensor")
+    params = out if out is not None else torch.empty((B, 6), device=p_tensor.device, dtype=torch.float32)
+    assert params.shape == (B, 6) and params.is_contiguous()
+    check(_lib.lib().mpg_augment(None, None, 0, 2, 2, B, 0, _p(seed_tensor(p_tensor.device)), AUG_TAG + int(site), _p(p_tensor),
+                                 int(flags), translate_ratio, scale_sd, _p(params), _stream()), "mpg_augment")
+    return params
+
+
+def augment(x: torch.Tensor, p_tensor: torch.Tensor, flags: int, translate_ratio: float, scale_sd: float, site: int,
+            out: Optional[torch.Tensor] = None, params: Optional[torch.Tensor] = None):
+    """``mpgan.augment.augment`` (train.py:438-442, :508-511) on jets [B, N, F >= 2] as ONE launch: per jet the mixed
+    composition of the enabled stages is one affine map of (eta, phi), drawn from the counter-based stream of the device seed
+    and ``site`` (0: train_D's generated jets, 1: train_G's, 2: train_D's real jets).  ``p_tensor``: the probability as a
+    one-float device tensor.  ``out``: None (a new tensor), ``x`` itself (in place) or a tensor of ``x``'s shape and strides.
+    Returns (y, params [B, 6]); no autograd (``AugmentFn``)."""
+    B, N, F = _jet_layout(x, "x")
+    _chk(p_tensor, "p_tensor")
+    if out is None:
+        x = x.contiguous()
+        out = torch.empty_like(x)
+    elif out is not x:
+        _jet_layout(out, "out")
+        if out.shape != x.shape or out.stride() != x.stride():
+            raise ValueError("augment: out must have x's shape and strides")
+    if params is None:
+        params = torch.empty((B, 6), device=x.device, dtype=torch.float32)
+    assert params.shape == (B, 6) and params.is_contiguous()
+    check(_lib.lib().mpg_augment(_p(x), _p(out), x.stride(0), x.stride(1), F, B, N, _p(seed_tensor(x.device)), AUG_TAG + int(site),
+                                 _p(p_tensor), int(flags), translate_ratio, scale_sd, _p(params), _stream()), "mpg_augment")
+    return out, params
+
+
+def augment_apply_reference(x: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
+    """The torch statement of what ``augment`` applies: y[b, i, :2] = A_b x[b, i, :2] + t_b with
+    params[b] = (a00, a01, a10, a11, t0, t1), columns >= 2 unchanged.  Any device and dtype (tests, the CPU path)."""
+    a00, a01, a10, a11, t0, t1 = (params[:, k].reshape(-1, 1) for k in range(6))
+    x0, x1 = x[..., 0], x[..., 1]
+    return torch.cat((torch.stack((a00 * x0 + a01 * x1 + t0, a10 * x0 + a11 * x1 + t1), dim=2), x[..., 2:]), dim=2)
+
+
+class AugmentFn(torch.autograd.Function):
+    """``augment`` with its backward dx = A^T dy (``mpg_augment_bwd``): between a generator's jets and the discriminator in
+    train_G.  ``params``: the caller's [B, 6] buffer, which receives the maps.  Returns y."""
+
+    @staticmethod
+    def forward(ctx, x, p_tensor, flags, translate_ratio, scale_sd, site, params):
+        y, ctx.params = augment(x, p_tensor, flags, translate_ratio, scale_sd, site, params=params)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        B, N, F = dy.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(dy)
+        check(_lib.lib().mpg_augment_bwd(_p(dy), _p(dx), N * F, F, F, B, N, _p(ctx.params), _stream()), "mpg_augment_bwd")
+        return dx, None, None, None, None, None, None
+
+
 def dropout_mask(rows: int, F: int, tag: int, thr: int, device="cuda"):
     """The {0,1} keep mask [rows, F] of dropout site ``tag`` under the current seed (tests)."""
     out = torch.empty((rows, F), device=device, dtype=torch.float32)

@@ -9,6 +9,8 @@ The gradient penalty (train.py:286-324, ``--gp``) needs a second derivative thro
 only (``once_differentiable``), so the penalty's own pass D(interpolated) takes the double-backward route
 (``ops.double_backward_route``: every product an ``ops.MatMulFn`` on the HIP GEMM, the rest ATen) while D(real) and
 D(generated) stay on the fused kernels; both discriminators (``MPDiscriminator``, ``GAPT_D``) have that route.
+Jet augmentation (``--aug-*``, train.py:438-442, :508-511; ``TrainStep(augment=...)``) is one affine map per jet drawn on the
+device inside the iteration (``ops.augment``), from the seed that keys the noise and the dropout masks.
 
 Two pieces of work the reference does and throws away are not done (results-neutral, SURVEY.md
 section 3.1): the D step does not back-propagate into G (its gradients are zeroed before use,
@@ -22,13 +24,15 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
 from torch import nn
 
 from . import _lib, ops, dist as mdist
-from .mpgan import MPGenerator, MPDiscriminator
+from .mpgan import MPGenerator, MPDiscriminator, augment as maugment
 
 LR = {  # setup_training.py:848-872 (lr_disc, lr_gen) per jet type for model = mpgan
     "g": (3e-5, 1e-5), "t": (6e-5, 2e-5), "q": (1.5e-5, 0.5e-5),
@@ -289,6 +293,23 @@ def _forward_writes_no_state(module: nn.Module) -> bool:
 LOSSES = ("ls", "og", "w", "hinge")
 
 
+@dataclass
+class Augment:
+    """The reference's augmentation switches (``--aug-r90 / --aug-f / --aug-t / --aug-s``, ``--translate-ratio``, ``--scale-sd``,
+    ``--aug-prob``; setup_training.py:385-402, its defaults) for ``TrainStep(augment=...)``; the reference's own argument
+    namespace has the same field names and is taken as it is."""
+    aug_r90: bool = False
+    aug_f: bool = False
+    aug_t: bool = False
+    aug_s: bool = False
+    translate_ratio: float = 0.125
+    scale_sd: float = 0.125
+    aug_prob: float = 1.0      # (rand_mix: p == 1 takes nothing)
+
+
+AUG_SITES = {"D_fake": 0, "G_fake": 1, "D_real": 2}   # ops.augment's sites within an iteration
+
+
 def d_loss(loss: str, out: torch.Tensor, B: int, real: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``calc_D_loss`` (train.py:331-395, without label smoothing / noise) on D's outputs for the CONCATENATED
     batch ``out[:B]`` = real, ``out[B:]`` = generated: D_real_loss + D_fake_loss, each a mean over its B jets.
@@ -328,7 +349,7 @@ class TrainStep:
                  lr_disc: float = 3e-5, lr_gen: float = 1e-5, noise_std: float = 0.2, use_graphs: bool = True,
                  process_group=None, world_size: int = 1, batch_real_fake: bool = True, loss: str = "ls",
                  optimizer: str = "rmsprop", betas=(0.9, 0.999), gp_lambda: float = 0.0,
-                 graph_collectives: Optional[bool] = None):
+                 graph_collectives: Optional[bool] = None, augment=None):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
         self.gp_lambda = float(gp_lambda)
@@ -426,6 +447,17 @@ class TrainStep:
         self.wgrad_side = dev.type == "cuda" and os.environ.get("MPG_WGRAD_SIDE", "1") != "0"
         self._wside = None
         self.bridge = dev.type == "cuda" and os.environ.get("MPG_BRIDGE", "1") != "0"
+        # Jet augmentation (train.py:438-442, :508-511): one affine map of (eta, phi) per jet, drawn on the device from the seed
+        # that keys the noise and the dropout masks (ops.augment) -- one launch on the generated half of the D step's batch, one
+        # each way between the generator's jets and the discriminator in the G step.  The probability lives in device memory:
+        # ``set_aug_prob`` reaches a captured graph.  ``aug_params[site]`` holds the last maps drawn at each site (AUG_SITES).
+        self.aug = self.aug_p = None
+        if augment is not None:
+            flags = ops.augment_flags(augment.aug_r90, augment.aug_f, augment.aug_t, augment.aug_s)
+            self.aug_p = torch.full((1,), float(augment.aug_prob), device=dev)
+            if flags:      # (all four switches off: the step without augmentation, launch for launch)
+                self.aug = SimpleNamespace(flags=flags, translate_ratio=float(augment.translate_ratio), scale_sd=float(augment.scale_sd))
+                self.aug_params = [torch.zeros(batch_size, 6, device=dev) for _ in AUG_SITES]
         # the generator's noise and its jets' masks drawn by one launch (MPG_NOISE_MASK=0: mpg_normal, then mpg_rank_mask)
         self.noise_mask = dev.type == "cuda" and os.environ.get("MPG_NOISE_MASK", "1") != "0"
         self.fixed_noise = None  # tests: (noise_D, noise_G) used instead of fresh samples
@@ -463,10 +495,31 @@ class TrainStep:
                 and getattr(self.D, "fused_head", lambda: None)() is not None and self.batch_real_fake
                 and not self.gp_lambda)
 
+    def set_aug_prob(self, p: float):
+        """The augmentation probability from the next iteration on (the reference's ``aug_prob`` / ``augment_p[-1]``); a
+        captured graph reads it from device memory: no recapture."""
+        if self.aug_p is None:
+            raise RuntimeError("TrainStep was built without augmentation")
+        self.aug_p.fill_(float(p))
+
+    def _augment(self, x: torch.Tensor, site: int, in_place: bool = False) -> torch.Tensor:
+        """``augment.augment(args, x, p)`` at ``site``; on the device with ``ops.AugmentFn``'s backward where ``x`` takes a
+        gradient.  CPU (host-logic tests with toy modules): the torch statement with torch's generator."""
+        a = self.aug
+        if self.dev.type != "cuda":
+            args = SimpleNamespace(device=self.dev, aug_r90=a.flags & ops.AUG_R90, aug_f=a.flags & ops.AUG_FLIP,
+                                   aug_t=a.flags & ops.AUG_TRANSLATE, aug_s=a.flags & ops.AUG_SCALE,
+                                   translate_ratio=a.translate_ratio, scale_sd=a.scale_sd)
+            return maugment.augment(args, x, float(self.aug_p))
+        if torch.is_grad_enabled() and x.requires_grad:
+            return ops.AugmentFn.apply(x, self.aug_p, a.flags, a.translate_ratio, a.scale_sd, site, self.aug_params[site])
+        return ops.augment(x, self.aug_p, a.flags, a.translate_ratio, a.scale_sd, site, out=x if in_place else None,
+                           params=self.aug_params[site])[0]
+
     def _bridge(self) -> bool:
         """GAPT: gen's ``final_fc`` + tanh and disc's ``input_embedding`` as one launch each way (``ops.GenDiscBridgeFn``;
-        MPG_BRIDGE=0: the three launches)."""
-        if not self.bridge or not hasattr(self.G, "bridge_head") or not hasattr(self.D, "bridge_tail"):
+        MPG_BRIDGE=0: the three launches).  Not while augmenting: the map sits between the tanh and the embedding."""
+        if self.aug is not None or not self.bridge or not hasattr(self.G, "bridge_head") or not hasattr(self.D, "bridge_tail"):
             return False
         h, t = self.G.bridge_head(), self.D.bridge_tail()
         # (final_fc's weight is a view into the flat parameter buffer: the launch reads its rows as float4 -- a generator composed
@@ -548,16 +601,22 @@ class TrainStep:
                 with torch.no_grad():
                     z, pm = self._noise_masked(0, self._mask2[B:], self._ign2[B:])
                     self.G.generate_parts(z, self.labels, feat_out=self._x3[B:], mask_out=self._mask2[B:], ign_out=self._ign2[B:], premask=pm)
+                    if self.aug is not None:
+                        self._augment(self._x3[B:], AUG_SITES["D_fake"], in_place=True)
                 y, mask = self.D.features_parts(self._x3, self._mask2, self._labels2, ignore=self._ign2)
             else:
                 with torch.no_grad():
                     self.G.generate_into(self._noise(0), self.labels, self._dcat[B:])
+                    if self.aug is not None:
+                        self._augment(self._dcat[B:], AUG_SITES["D_fake"], in_place=True)
                 y, mask = self.D.features(self._dcat, self._labels2)
             dy = self._head_loss(y, mask, False, 2 * self.B, self.D_loss, True)
             self._backward(y, dy)
             return
         with torch.no_grad():
             fake = self.G(self._noise(0), self.labels)
+            if self.aug is not None:       # (D(real) sees the batch as it is: train.py:425 runs before the augmentation)
+                fake = self._augment(fake, AUG_SITES["D_fake"], in_place=True)
         if self.batch_real_fake:
             out = self.D(torch.cat([self.data, fake], 0), torch.cat([self.labels, self.labels], 0))
         else:
@@ -565,7 +624,11 @@ class TrainStep:
         loss = d_loss(self.loss, out, self.B, self._real)
         self.D_loss.copy_(loss.detach())   # (D_real_loss + D_fake_loss: the reference's losses["D"] leaves the penalty out)
         if self.gp_lambda:
-            gp = self.gradient_penalty(self.data, fake)
+            real = self.data
+            if self.aug is not None:       # (calc_D_loss is handed the augmented real batch: train.py:441, :452)
+                with torch.no_grad():
+                    real = self._augment(self.data, AUG_SITES["D_real"])
+            gp = self.gradient_penalty(real, fake)
             self.GP.copy_(gp.detach())
             loss = loss + gp
         self._backward(loss)
@@ -649,6 +712,11 @@ class TrainStep:
                 fake = self.G.generate_parts(z, self.labels, premask=pm)
             else:
                 fake = self.G(self._noise(1), self.labels)
+        if self.aug is not None:     # (here, on the main stream, also for jets the generator-ahead branch made)
+            if isinstance(fake, tuple):
+                fake = (self._augment(fake[0], AUG_SITES["G_fake"]),) + tuple(fake[1:])
+            else:
+                fake = self._augment(fake, AUG_SITES["G_fake"])
         if bridge:
             y, mask = self.D.features_rows(fake[0], self.G.bridge_head(), None, fake[1], self.labels, ignore=fake[2])
             dy = self._head_loss(y, mask, True, self.B, self.G_loss, False)
