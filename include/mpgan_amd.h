@@ -624,6 +624,40 @@ int mpg_augment(const float* x, float* y, uint64_t jet_stride, int ld, int F, in
 int mpg_augment_bwd(const float* dy, float* dx, uint64_t jet_stride, int ld, int F, int B, int N, const float* params,
                     void* stream);
 
+/* The keyed shuffle of a device-resident data set (csrc/shuffle.h: one body for the device and the host).
+ * perm(key, epoch, i, n), 0 <= i < n <= 2^31 - 1, is a bijection of [0, n) computed from (key, epoch, i) alone -- a balanced
+ * Feistel network with cycle walking, its round function the project's counter-based hash (the stream of the dropout masks, of
+ * mpg_normal and of the augmentation draws):
+ *   word(tag, row, grp) with the 64-bit key in place of the seed, lo = (uint32) key, hi = (uint32) (key >> 32), all in uint32:
+ *       x = (row + lo) * 0x9E3779B1;  x ^= (grp + tag * 0x10001) * 0x85EBCA77 + hi;
+ *       x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *   n == 1: perm = 0.  Otherwise k = the bit length of n - 1, h = (k + 1) / 2 (integer division), m = 2^h - 1: the domain is
+ *   [0, 2^(2h)), 2^(2h) < 4 n.  Starting from x = i:
+ *       L = x >> h, R = x & m;
+ *       four rounds r = 0, 1, 2, 3:  (L, R) <- (R, L ^ (word(MPG_SHUFFLE_TAG + r, R, (uint32) epoch) & m));
+ *       x = (L << h) | R;
+ *   again from the new x while x >= n (the walk); perm = the first x < n.  Only the low 32 bits of the epoch enter.
+ * The stream is continuous: position g = 0, 1, 2, ... takes data-set row perm(key, g / n, g % n, n).  No batch is dropped or
+ * short, a batch may straddle two epochs, and every n consecutive positions from a multiple of n visit every row once.
+ * MPG_SHUFFLE_TAG stays clear of the dropout sites (below 2^27), of the noise tags and of the augmentation tags.
+ *
+ * mpg_shuffle_index_host: out[c] = the row of position pos0 + c, c < count; no HIP call.  1 <= n <= 2^31 - 1, count >= 0 (else -1). */
+#define MPG_SHUFFLE_TAG 0x53000000
+int mpg_shuffle_index_host(uint64_t key, uint64_t pos0, int64_t count, int64_t n, int32_t* out);
+
+/* mpg_batch_feed: one training batch gathered from the resident data set -- normalised particles [n, N, 4] fp32 (a particle row
+ * is one 16-byte-aligned float4) and labels_in [n] -- in ONE launch: jet j < B takes position *cursor + j of the stream above.
+ * With v = the jet's particle rows, m = v[:, 3] and l = its label, the launch writes what TrainStep.set_batch writes, bit for bit:
+ *   data [B, N, 4] = v;  labels [B] = l;  dcat[:B] = v ([*, N, 4]);  x3[:B] = v[:, 0:3] ([*, N, 3]);  mask2[:B] = m + 0.5f and
+ *   ign2[:B] = 0.5f - m ([*, N]);  labels2[j] = labels2[B + j] = l ([2B]).
+ * Any output may be NULL (labels_in too, when labels and labels2 are).  The same launch then moves *cursor on by `stride` (a
+ * rank of W strides by W B), behind every workgroup's read of it: the workgroup that arrives last on the agent-scope counter
+ * *ticket does it and leaves the counter at zero, as it found it (no second kernel).  *cursor and *ticket live in device memory.
+ * n < 1, n > 2^31 - 1, B < 1, N < 1, a NULL cursor, ticket or data set: -1; particles, data or dcat off a 16-byte boundary: -2. */
+int mpg_batch_feed(const float* particles, const float* labels_in, int64_t n, int N, uint64_t key, uint64_t* cursor,
+                   uint32_t* ticket, int B, uint64_t stride, float* data, float* labels, float* dcat, float* x3, float* mask2,
+                   float* ign2, float* labels2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -256,6 +256,9 @@ SIGNATURES = {
     "mpg_augment": (C.c_int, [_fp, _fp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_uint32, _fp, C.c_int, C.c_float,
                               C.c_float, _fp, C.c_void_p]),
     "mpg_augment_bwd": (C.c_int, [_fp, _fp, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_void_p]),
+    "mpg_shuffle_index_host": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, _fp]),
+    "mpg_batch_feed": (C.c_int, [_fp, _fp, C.c_int64, C.c_int, C.c_uint64, _fp, _fp, C.c_int, C.c_uint64, _fp, _fp, _fp, _fp, _fp,
+                                 _fp, _fp, C.c_void_p]),
 }
 
 

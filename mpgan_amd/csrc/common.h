@@ -25,6 +25,7 @@ template <> struct FragT<true> { typedef f16x8 type; typedef _Float16 elem; };
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define MPG_DEV __device__ __forceinline__
+#define MPG_HD __host__ __device__ __forceinline__   // (what a host twin restates bit for bit: csrc/shuffle.h)
 
 // compile-time loop: f(std::integral_constant<int, I>) for I = B .. E-1.  The fused kernels index register
 // arrays with these constants; `#pragma unroll` over run-time ints gives up on their deeply nested bodies
@@ -177,7 +178,7 @@ struct DropCfg {
     float scale;     // 256/(256-thr)
 };
 
-MPG_DEV uint32_t drop_word(uint32_t seed_lo, uint32_t seed_hi, uint32_t tag, uint32_t row, uint32_t grp) {
+MPG_HD uint32_t drop_word(uint32_t seed_lo, uint32_t seed_hi, uint32_t tag, uint32_t row, uint32_t grp) {
     uint32_t x = (row + seed_lo) * 0x9E3779B1u;
     x ^= (grp + tag * 0x10001u) * 0x85EBCA77u + seed_hi;
     x ^= x >> 16; x *= 0x7feb352du;

@@ -12,7 +12,9 @@ generated jets.  This module holds
 * ``read_jetnet_file`` / ``JetArrayDataset.from_jetnet_file`` -- the reader of JetNet's on-disk layout
   (``<data_dir>/<jet_type>[150].hdf5`` with the datasets ``particle_features [n, N, 4]`` = (etarel, phirel, ptrel, mask)
   and ``jet_features [n, 4]`` = (pt, eta, mass, num_particles), jetnet >= 0.2.1 as ``requirements.txt:2`` pins it; the
-  same two arrays in an ``.npz`` are read alike).
+  same two arrays in an ``.npz`` are read alike),
+* ``DeviceJetLoader`` -- the whole data set resident on the training device, shuffled by a keyed permutation and gathered into
+  ``TrainStep``'s buffers by one launch inside the captured iteration (``TrainStep(loader=...)``).
 """
 from __future__ import annotations
 
@@ -178,3 +180,120 @@ class JetArrayDataset(torch.utils.data.Dataset):
 
     def __getitem__(self, i):
         return self.particle_data[i], self.jet_features[i]
+
+
+LOADER_KEY_TERM = 0xA0761D6478BD642F   # what tells the shuffle's key from the noise / dropout seed derived from the same torch seed
+
+
+class DeviceJetLoader:
+    """A data set held on the training device and fed to ``train.TrainStep`` without the host: ``particle_data [n, N, 4]`` and
+    ``jet_features [n, 1]`` (a ``JetArrayDataset``, or the two arrays as a pair) stay on ``device``; the jets are visited in the
+    order of a keyed shuffle (``perm(key, epoch, i, n)`` of include/mpgan_amd.h: a function of the key and the position, no
+    permutation buffer) and one launch (``mpg_batch_feed``) gathers a batch into the step's buffers and moves the cursor on.
+
+    The stream of positions is continuous: position g takes row ``perm(key, g // n, g % n, n)``.  No batch is dropped or short
+    (``DataLoader(shuffle=True)`` ends an epoch on a short batch; a captured iteration has one batch size): a batch may
+    straddle two epochs, and every n consecutive positions from a multiple of n visit every jet once.
+
+    ``seed`` (default ``torch.initial_seed()``) gives the key -- NOT the rank: all ranks share one shuffle and take disjoint
+    slices of it, rank r of W starting at r * batch_size and striding by W * batch_size, so that together they consume the stream
+    contiguously (no ``DistributedSampler``).  ``state_dict()`` is the whole state of the data order: saved beside the
+    optimizers' state it makes a resumed run see the jets an uninterrupted one would.
+
+    CPU tensors (host-logic tests with toy modules): ``feed`` does the same through ``indices`` and ``index_select``."""
+
+    def __init__(self, dataset_or_arrays, batch_size: int, device, seed: Optional[int] = None, rank: int = 0, world_size: int = 1):
+        if hasattr(dataset_or_arrays, "particle_data"):
+            particles, labels = dataset_or_arrays.particle_data, dataset_or_arrays.jet_features
+        else:
+            particles, labels = dataset_or_arrays
+        particles = torch.as_tensor(particles, dtype=torch.float32)
+        labels = torch.as_tensor(labels, dtype=torch.float32)
+        if particles.dim() != 3 or particles.shape[-1] != 4 or particles.shape[0] < 1 or particles.shape[1] < 1:
+            raise ValueError(f"expected normalised particles [n >= 1, N >= 1, 4], got {tuple(particles.shape)}")
+        if labels.numel() != particles.shape[0]:
+            raise ValueError(f"expected one label per jet, got {tuple(labels.shape)} for {particles.shape[0]} jets")
+        if batch_size < 1 or world_size < 1 or not 0 <= rank < world_size:
+            raise ValueError(f"batch_size {batch_size}, rank {rank} of {world_size}: not a slice of the stream")
+        self.particle_data = particles.to(device).contiguous()
+        self.device = self.particle_data.device     # (with its index: "cuda" is the current device)
+        self.jet_features = labels.reshape(-1, 1).to(self.device).contiguous()
+        self.n, self.num_particles = int(particles.shape[0]), int(particles.shape[1])
+        self.batch_size, self.rank, self.world_size = int(batch_size), int(rank), int(world_size)
+        s = torch.initial_seed() if seed is None else int(seed)
+        self.key = (s * 0x9E3779B97F4A7C15 + LOADER_KEY_TERM) & 0xFFFFFFFFFFFFFFFF
+        # the next stream position of this rank, in device memory: the feed launch reads it and moves it on (a replayed
+        # hipGraph holds its address: it is written in place, never replaced)
+        self.cursor = torch.full((1,), self.rank * self.batch_size, dtype=torch.int64, device=self.device)
+        self._ticket = torch.zeros((1,), dtype=torch.int32, device=self.device)   # the launch's arrival counter: zero between launches
+        self._base = 0    # the global position iteration 0 starts at (non-zero only behind a resume under another layout)
+        self._captured = False   # (TrainStep: a captured feed launch holds the key as an argument)
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def stride(self) -> int:
+        return self.world_size * self.batch_size
+
+    @property
+    def steps_per_epoch(self) -> int:
+        return -(-self.n // self.stride)
+
+    @property
+    def position(self) -> int:
+        """This rank's next stream position (reads the cursor: synchronises)."""
+        return int(self.cursor.item())
+
+    @property
+    def epoch(self) -> int:
+        return self.position // self.n
+
+    def indices(self, step: int) -> torch.Tensor:
+        """The data-set rows of this rank's iteration ``step`` (0 = the first of the run) as a CPU int64 tensor, computed on
+        the host by the kernel's own function (``mpg_shuffle_index_host``)."""
+        from . import ops
+        return ops.shuffle_indices(self.key, self._base + self.rank * self.batch_size + int(step) * self.stride, self.batch_size, self.n)
+
+    def feed(self, step_buffers):
+        """Write the next batch into ``step_buffers`` -- a ``TrainStep``, or anything with (some of) its attributes ``data``,
+        ``labels``, ``_dcat``, ``_x3``, ``_mask2``, ``_ign2``, ``_labels2`` -- exactly as ``TrainStep.set_batch`` would, and move
+        the cursor on: one launch on the current stream, capturable."""
+        from . import ops
+        B = self.batch_size
+        buf = {k: getattr(step_buffers, a, None) for k, a in (("data", "data"), ("labels", "labels"), ("dcat", "_dcat"), ("x3", "_x3"),
+                                                             ("mask2", "_mask2"), ("ign2", "_ign2"), ("labels2", "_labels2"))}
+        if self.device.type == "cuda":
+            ops.batch_feed(self.particle_data, self.jet_features, self.key, self.cursor, self._ticket, B, self.stride, **buf)
+            return
+        idx = ops.shuffle_indices(self.key, int(self.cursor.item()), B, self.n)
+        x, l = self.particle_data.index_select(0, idx), self.jet_features.index_select(0, idx)
+        for name, val in (("data", x), ("dcat", x), ("x3", x[..., :3]), ("mask2", x[..., 3:] + 0.5), ("ign2", 0.5 - x[..., 3]),
+                          ("labels", l), ("labels2", torch.cat([l, l]))):
+            t = buf[name]
+            if t is not None:
+                t[:val.shape[0]].copy_(val.reshape((val.shape[0],) + tuple(t.shape[1:])))
+        self.cursor.add_(self.stride)
+
+    def state_dict(self) -> dict:
+        """The whole state of the data order (reads the cursor: synchronises)."""
+        return {"key": self.key, "cursor": self.position, "n": self.n, "batch_size": self.batch_size, "rank": self.rank,
+                "world_size": self.world_size}
+
+    def load_state_dict(self, sd: dict):
+        """Go on where the saved loader stopped.  The data set must be the one saved (same n).  Saved by another rank, or under
+        another world or batch size: the cursor is re-derived from the GLOBAL position (where the saved step of all ranks
+        began), so that the ranks of the resumed run consume the stream contiguously from there."""
+        if int(sd["n"]) != self.n:
+            raise ValueError(f"DeviceJetLoader: the saved state belongs to a data set of {int(sd['n'])} jets, this one has "
+                             f"{self.n}: the shuffle is a permutation of the data set it was made for")
+        key = int(sd["key"]) & 0xFFFFFFFFFFFFFFFF
+        if self._captured and key != self.key:
+            raise RuntimeError("DeviceJetLoader: the feed launch has been captured with this loader's key; load the saved state "
+                               "before the first step")
+        self.key = key
+        glob = int(sd["cursor"]) - int(sd["rank"]) * int(sd["batch_size"])
+        if glob < 0:
+            raise ValueError(f"DeviceJetLoader: cursor {sd['cursor']} lies before rank {sd['rank']}'s first batch")
+        self._base = glob % self.stride
+        self.cursor.fill_(glob + self.rank * self.batch_size)

@@ -447,8 +447,44 @@ def normal_noise_masked(shape, std: float, labels: torch.Tensor, site: int = 0, 
     return out, mask.view(B, N), ign.view(B, N)
 
 
+# ------------------------------------------------------------------------------------- data feed
+SHUFFLE_TAG = 0x53000000   # MPG_SHUFFLE_TAG of include/mpgan_amd.h (+ the Feistel round; clear of NOISE_TAG, AUG_TAG and the dropout sites)
+
+
+def shuffle_indices(key: int, pos0: int, count: int, n: int) -> torch.Tensor:
+    """Data-set rows of the stream positions ``pos0 .. pos0 + count - 1`` of the keyed shuffle (``mpg_shuffle_index_host``: the
+    kernel's own function compiled for the host, no device involved) as a CPU int64 tensor."""
+    out = torch.empty(int(count), dtype=torch.int32)
+    check(_lib.lib().mpg_shuffle_index_host(int(key) & 0xFFFFFFFFFFFFFFFF, int(pos0) & 0xFFFFFFFFFFFFFFFF, int(count), int(n),
+                                            C.c_void_p(out.data_ptr())), "mpg_shuffle_index_host")
+    return out.long()
+
+
+def batch_feed(particles: torch.Tensor, labels_in: torch.Tensor, key: int, cursor: torch.Tensor, ticket: torch.Tensor, B: int,
+               stride: int, data=None, labels=None, dcat=None, x3=None, mask2=None, ign2=None, labels2=None):
+    """``mpg_batch_feed``: one launch that gathers the ``B`` jets at the stream positions ``cursor .. cursor + B - 1`` of the keyed
+    shuffle from the resident ``particles [n, N, 4]`` / ``labels_in [n]`` into the given buffers (what ``TrainStep.set_batch``
+    writes; any may be None) and moves ``cursor`` (one int64 on the device) on by ``stride``."""
+    _chk(particles, "particles")
+    n, N, F = particles.shape
+    if F != 4 or not particles.is_contiguous():
+        raise ValueError(f"batch_feed: contiguous particles [n, N, 4] expected, got {tuple(particles.shape)}")
+    if cursor.dtype != torch.int64 or ticket.dtype != torch.int32 or cursor.device != particles.device or ticket.device != particles.device:
+        raise ValueError("batch_feed: cursor (int64) and ticket (int32) live on the data set's device")
+    need = {"data": (data, B * N * 4), "labels": (labels, B), "dcat": (dcat, B * N * 4), "x3": (x3, B * N * 3),
+            "mask2": (mask2, B * N), "ign2": (ign2, B * N), "labels2": (labels2, 2 * B), "labels_in": (labels_in, n)}
+    for name, (t, k) in need.items():
+        if t is not None:
+            _chk(t, name)
+            if not t.is_contiguous() or t.numel() < k:
+                raise ValueError(f"batch_feed: {name} must be contiguous with at least {k} elements, got {tuple(t.shape)}")
+    check(_lib.lib().mpg_batch_feed(_p(particles), _p(labels_in), n, N, int(key) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(cursor.data_ptr()),
+                                    C.c_void_p(ticket.data_ptr()), int(B), int(stride), _p(data), _p(labels), _p(dcat), _p(x3),
+                                    _p(mask2), _p(ign2), _p(labels2), _stream()), "mpg_batch_feed")
+
+
 # ------------------------------------------------------------------------------------- augmentation
-AUG_TAG = 0x41000000   # site tags of ``augment`` (clear of NOISE_TAG and of the dropout sites below 2^27)
+AUG_TAG = 0x41000000  # site tags of ``augment`` (clear of NOISE_TAG and of the dropout sites below 2^27)
 AUG_R90, AUG_FLIP, AUG_TRANSLATE, AUG_SCALE = 1, 2, 4, 8   # MPG_AUG_* of include/mpgan_amd.h
 
 

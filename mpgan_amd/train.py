@@ -11,6 +11,8 @@ only (``once_differentiable``), so the penalty's own pass D(interpolated) takes 
 D(generated) stay on the fused kernels; both discriminators (``MPDiscriminator``, ``GAPT_D``) have that route.
 Jet augmentation (``--aug-*``, train.py:438-442, :508-511; ``TrainStep(augment=...)``) is one affine map per jet drawn on the
 device inside the iteration (``ops.augment``), from the seed that keys the noise and the dropout masks.
+The training data can live on the device as well (``TrainStep(loader=data.DeviceJetLoader(...))``): the batch is then gathered by
+one launch at the top of the iteration, inside the capture, in the order of a keyed shuffle.
 
 Two pieces of work the reference does and throws away are not done (results-neutral, SURVEY.md
 section 3.1): the D step does not back-propagate into G (its gradients are zeroed before use,
@@ -349,7 +351,7 @@ class TrainStep:
                  lr_disc: float = 3e-5, lr_gen: float = 1e-5, noise_std: float = 0.2, use_graphs: bool = True,
                  process_group=None, world_size: int = 1, batch_real_fake: bool = True, loss: str = "ls",
                  optimizer: str = "rmsprop", betas=(0.9, 0.999), gp_lambda: float = 0.0,
-                 graph_collectives: Optional[bool] = None, augment=None):
+                 graph_collectives: Optional[bool] = None, augment=None, loader=None):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
         self.gp_lambda = float(gp_lambda)
@@ -466,6 +468,23 @@ class TrainStep:
         # (FlatParams.step(zero_grad=True)): no memset of its own at the top of train_D / train_G.  A caller that accumulates
         # into the networks' .grad between iterations calls ``mark_grads_dirty()``.
         self._clean = {"D": True, "G": True}
+        # a device-resident data set (data.DeviceJetLoader): its feed launch is the first thing of every iteration
+        self.loader = None
+        if loader is not None:
+            self.attach_loader(loader)
+
+    def attach_loader(self, loader):
+        """Take the batches from ``loader`` (``data.DeviceJetLoader``) instead of ``set_batch``: one launch at the top of the D
+        segment, inside the capture on every route.  Before the first captured ``step``."""
+        if self._graphs is not None:
+            raise RuntimeError("attach_loader: the iteration has been captured already (the feed launch is part of the graph); "
+                               "attach the loader before the first step")
+        if loader.batch_size != self.B or loader.num_particles != self.N:
+            raise ValueError(f"loader serves batches of {loader.batch_size} jets of {loader.num_particles} particles; the step "
+                             f"was built for {self.B} x {self.N}")
+        if loader.device != self.data.device:
+            raise ValueError(f"loader lives on {loader.device}, the step on {self.data.device}")
+        self.loader = loader
 
     # -- the three segments between collectives ------------------------------------------------
     def _noise(self, which: int = 0):
@@ -537,6 +556,8 @@ class TrainStep:
 
     def _seg_D(self):  # train_D up to and including backward (train.py:419-460)
         # parameter gradients are added straight into the flat buffers (no AccumulateGrad kernel per parameter)
+        if self.loader is not None:     # (first: the generator-ahead branch reads self.labels)
+            self.loader.feed(self)
         self.state.grad_into_param = True
         self.state.order_cache = None   # (ops.jet_order: the masks of this iteration live where last iteration's did)
         # (the dropout / noise seed of this iteration was set by the last launch of the iteration before: _seg_end)
@@ -773,6 +794,8 @@ class TrainStep:
         for f in (self.fD, self.fG):
             ts += [f.flat, f.sq, f.step_count] + ([f.aux] if f.aux is not None else [])
             ts += list(f.module.buffers()) + [p for p in f.module.parameters() if not p.requires_grad]
+        if self.loader is not None:      # (the data stream's cursor: the warm-up iterations of ``capture`` consume no jets)
+            ts.append(self.loader.cursor)
         return ts
 
     def capture(self, warmup: int = 3):
@@ -828,8 +851,14 @@ class TrainStep:
             pool = g.pool()
             graphs.append(g)
         self._graphs = graphs
+        if self.loader is not None:
+            self.loader._captured = True
 
     def set_batch(self, data: torch.Tensor, labels: torch.Tensor):
+        if self.loader is not None:
+            raise RuntimeError("set_batch: this step takes its batches from the attached DeviceJetLoader, whose feed launch "
+                               "overwrites these buffers at the top of every iteration; build the step without a loader to "
+                               "set batches by hand")
         self.data.copy_(data, non_blocking=True)
         self.labels.copy_(labels, non_blocking=True)
         self._dcat[:self.B].copy_(self.data)
