@@ -282,15 +282,19 @@ class GAPT_G(nn.Module):
         self.final_fc = LinearNet(final_fc_layers, input_size=embed_dim, output_size=output_feat_size,
                                   final_linear=True, **linear_args)
 
-    def _mask(self, x, labels):
-        """(mask [B, N, 1] or None, the attention mask built from it): on the GPU one launch writes both."""
+    def _mask(self, x, labels, mask_out: Tensor = None, ign_out: Tensor = None, premask=None):
+        """(mask [B, N, 1] or None, the attention mask built from it): on the GPU one launch writes both -- into the caller's
+        rows ``mask_out`` / ``ign_out`` when given -- unless the caller drew them with the noise (``premask``: mask [B, N], 1 - mask)."""
         if not self.use_mask:
             return None, None
-        if x.is_cuda:
-            mask, ign = ops.rank_mask(x[:, :, 0], labels, self.num_particles, with_ignore=True)
-            return mask.unsqueeze(2), ign.unsqueeze(2)
-        mask = _rank_mask(x[:, :, 0], labels, self.num_particles)
-        return mask, _attn_mask(mask)
+        if premask is None and not x.is_cuda:
+            mask = _rank_mask(x[:, :, 0], labels, self.num_particles)
+            return mask, _attn_mask(mask)
+        B = x.shape[0]
+        mask, ign = premask if premask is not None else ops.rank_mask(
+            x[:, :, 0], labels, self.num_particles, out=None if mask_out is None else mask_out.view(B, -1), with_ignore=True,
+            ignore_out=None if ign_out is None else ign_out.view(B, -1))
+        return mask.unsqueeze(2), ign.unsqueeze(2)
 
     def forward(self, x: Tensor, labels: Tensor = None):
         mask, am = self._mask(x, labels)
@@ -310,15 +314,7 @@ class GAPT_G(nn.Module):
                        premask=None):
         """``forward`` without gluing the mask column on: (particle features [B, N, F] after tanh, mask [B, N, 1], 1 - mask
         [B, N]); see ``MPGenerator.generate_parts``.  ``premask``: (mask [B, N], 1 - mask) already drawn with the noise."""
-        assert x.is_cuda and self.use_mask
-        B = x.shape[0]
-        if premask is not None:
-            mask2d, ign = premask
-        else:
-            mask2d, ign = ops.rank_mask(x[:, :, 0], labels, self.num_particles, out=None if mask_out is None else mask_out.view(B, -1),
-                                        with_ignore=True, ignore_out=None if ign_out is None else ign_out.view(B, -1))
-        mask = mask2d.unsqueeze(2)
-        x = _run_sabs(self.sabs, x, ign.unsqueeze(2))
+        x, mask, ign = self.generate_rows(x, labels, mask_out, ign_out, premask)
         x = self.final_fc(x)
         if feat_out is not None:
             assert not torch.is_grad_enabled()
@@ -339,13 +335,8 @@ class GAPT_G(nn.Module):
         1 - mask [B, N]) -- for a caller that runs ``final_fc``, the tanh and the discriminator's embedding as one launch
         (``GAPT_D.features_rows``)."""
         assert x.is_cuda and self.use_mask
-        B = x.shape[0]
-        if premask is not None:
-            mask2d, ign = premask
-        else:
-            mask2d, ign = ops.rank_mask(x[:, :, 0], labels, self.num_particles, out=None if mask_out is None else mask_out.view(B, -1),
-                                        with_ignore=True, ignore_out=None if ign_out is None else ign_out.view(B, -1))
-        return _run_sabs(self.sabs, x, ign.unsqueeze(2)), mask2d.unsqueeze(2), ign
+        mask, am = self._mask(x, labels, mask_out, ign_out, premask)
+        return _run_sabs(self.sabs, x, am), mask, am.squeeze(2)
 
     def generate_into(self, x: Tensor, labels: Tensor, out: Tensor) -> Tensor:
         """``forward`` into caller-owned output rows, no gradient (``train.TrainStep``'s D step)."""
@@ -393,6 +384,16 @@ class GAPT_D(nn.Module):
                 am = 0.5 - x.detach()[..., -1:]   # (no gradient flows through the mask column: :336-338, bool mask)
             x = x[..., :-1]
         x = self.input_embedding(x)   # (a column slice of the [.., 4] rows: the GEMM takes the row stride as it is)
+        return self._pooled(x, am)
+
+    @staticmethod
+    def _attn_mask_of(mask: Tensor, ignore: Tensor = None) -> Tensor:
+        """[B, N, 1] attention mask (1 = ignore) of a mask [B, N, 1] held apart: its ready-made complement ``ignore`` [B, N]
+        when the caller has one (a view), else 1 - mask (one launch, before the embedding's)."""
+        return ((1 - mask) if ignore is None else ignore).reshape(mask.shape[0], -1, 1)
+
+    def _pooled(self, x: Tensor, am: Tensor):
+        """The shared tail of the ``features*`` calls: embedded rows -> attention blocks -> pooled seed ([B, 1, E], None)."""
         x = _run_sabs(self.sabs, x, am)
         return self.pma(x, am), None
 
@@ -401,12 +402,8 @@ class GAPT_D(nn.Module):
 
     def features_parts(self, x3: Tensor, mask: Tensor, labels: Tensor = None, ignore: Tensor = None):
         """``features`` for callers that hold the particle features [B, N, F], the mask and 1 - mask [B, N] apart."""
-        B, N = x3.shape[:2]
-        inv = (1 - mask) if ignore is None else ignore
-        am = inv.reshape(B, N, 1)
-        x = self.input_embedding(x3)
-        x = _run_sabs(self.sabs, x, am)
-        return self.pma(x, am), None
+        am = self._attn_mask_of(mask, ignore)
+        return self._pooled(self.input_embedding(x3), am)
 
     def bridge_tail(self):
         """(weight [E, F], bias, LeakyReLU alpha, dropout p) of ``input_embedding`` when it can run inside
@@ -423,13 +420,9 @@ class GAPT_D(nn.Module):
         the [B, N, F] batch whose first B - Bg jets are real -- the generated features are written behind them."""
         W2, b2, alpha, p = self.bridge_tail()
         W1, b1, act1 = head
-        B = pre.shape[0] if feat_buf is None else feat_buf.shape[0]
-        N = pre.shape[1]
-        inv = (1 - mask) if ignore is None else ignore
-        am = inv.reshape(B, N, 1)
+        am = self._attn_mask_of(mask, ignore)
         _, x = ops.GenDiscBridgeFn.apply(pre, W1, b1, feat_buf, W2, b2, act1, True, alpha, p, self.training)
-        x = _run_sabs(self.sabs, x, am)
-        return self.pma(x, am), None
+        return self._pooled(x, am)
 
     def forward(self, x: Tensor, labels: Tensor = None):
         pooled, _ = self.features(x, labels)

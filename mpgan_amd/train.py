@@ -343,6 +343,42 @@ def g_loss(loss: str, out: torch.Tensor) -> torch.Tensor:
     raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
 
 
+class _GenAhead:
+    """The generator-ahead branch of ``TrainStep``: train_G's generator forward on a side stream beside the D step."""
+    # Where it joins: at the end of the D segment when that segment is a hipGraph of its own (a capture must end with every
+    # forked stream joined), otherwise only where the G step picks its jets up -- so that the D all-reduce (graph_collectives:
+    # inside the one graph; eagerly: between the segments) waits for D's backward and its weight-gradient stream alone, not for
+    # the generator's forward beside them
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.stream = None     # (made by the first fork)
+        self.jets = None       # what the forked call returned, until ``take``
+        self.open = False      # forked and not joined yet
+        self.joined = None     # "seg_D" | "seg_G": where the last iteration / capture joined the branch (tests read it)
+
+    def fork(self, generate):  # generate() on the side stream, behind everything the main stream holds so far
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.dev)
+        main = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(main)
+        self.open = True
+        with torch.cuda.stream(self.stream):
+            self.jets = generate()
+        for t in (self.jets if isinstance(self.jets, tuple) else (self.jets,)):
+            if t is not None:
+                t.record_stream(main)   # (its consumer, the G step, runs on this stream)
+
+    def join(self, place: str):  # an open branch is ordered before whatever follows on the main stream
+        if self.open:
+            torch.cuda.current_stream(self.dev).wait_stream(self.stream)
+            self.open, self.joined = False, place
+
+    def take(self):  # the forked call's jets (None without a fork), handed over once
+        jets, self.jets = self.jets, None
+        return jets
+
+
 class TrainStep:
     """G+D iteration (train.py:829-878 body) with static buffers, optional hipGraph replay and an
     optional process group for data-parallel gradient averaging (RCCL over xGMI)."""
@@ -354,8 +390,20 @@ class TrainStep:
                  graph_collectives: Optional[bool] = None, augment=None, loader=None):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+        self.dev = dev = next(G.parameters()).device
+        gpu = dev.type == "cuda"
+
+        # Every MPG_* switch of this file is read HERE, once, as the step is built: a change of the environment afterwards
+        # reaches neither a later iteration nor ``capture``.  What each one does is said where its attribute is set, below.
+        def _switch(name: str, default: str = "1") -> str:
+            return os.environ.get(name, default)
+        on = {k: _switch(k) != "0" for k in ("MPG_PARTS", "MPG_GEN_AHEAD", "MPG_GEN_AHEAD_LATE", "MPG_WGRAD_SIDE", "MPG_BRIDGE", "MPG_NOISE_MASK")}
+        if graph_collectives is None:
+            graph_collectives = _switch("MPG_GRAPH_COLLECTIVES", "") == "1"
+        # (tests, measurements: the three graphs of a multi-rank iteration without a process group)
+        self.split_graphs = bool(_switch("MPG_SPLIT_GRAPHS", ""))
         self.gp_lambda = float(gp_lambda)
-        self.GP = torch.zeros((), device=next(G.parameters()).device)   # last penalty value (the reference's losses["gp"])
+        self.GP = torch.zeros((), device=dev)   # last penalty value (the reference's losses["gp"])
         self.fixed_alpha = None   # tests: the interpolation weights [B, 1, 1] instead of fresh uniform samples
         self.G, self.D = G, D
         self.loss = loss
@@ -371,15 +419,11 @@ class TrainStep:
         # RCCL collectives can be captured into a hipGraph like kernels: the two gradient all-reduces then sit INSIDE
         # one graph and a multi-rank iteration is a single replay.  Opt-in (argument, or MPG_GRAPH_COLLECTIVES=1):
         # the default keeps the all-reduces as ordinary calls between three graph segments.
-        if graph_collectives is None:
-            graph_collectives = os.environ.get("MPG_GRAPH_COLLECTIVES") == "1"
         self.graph_collectives = bool(graph_collectives) and process_group is not None
-        dev = next(G.parameters()).device
-        self.dev = dev
         self.state = ops.dev_state(dev)
         self.fG = FlatParams(G, optimizer, betas)
         self.fD = FlatParams(D, optimizer, betas)
-        if dev.type == "cuda":
+        if gpu:
             # The generator's noise and every dropout mask come from counter-based streams keyed by the DEVICE seed, which
             # torch.manual_seed does not reach.  Unless the caller has set it (ops.set_seed), derive it here from torch's
             # seed -- the reference's contract: torch.manual_seed(seed), setup_training.py:184 -- and this process's rank,
@@ -412,12 +456,12 @@ class TrainStep:
         self._x3 = torch.zeros(2 * batch_size, num_particles, 3, device=dev)
         self._mask2 = torch.zeros(2 * batch_size, num_particles, 1, device=dev)
         self._ign2 = torch.zeros(2 * batch_size, num_particles, device=dev)
-        self.parts = (dev.type == "cuda" and hasattr(G, "generate_parts") and hasattr(D, "features_parts") and D.parts_ok()
+        self.parts = (gpu and hasattr(G, "generate_parts") and hasattr(D, "features_parts") and D.parts_ok()
                       and getattr(G, "use_mask", True) and not getattr(G, "lfc", False)
-                      and getattr(G, "mask_args", {}).get("mask_c", True) and os.environ.get("MPG_PARTS", "1") != "0")
+                      and getattr(G, "mask_args", {}).get("mask_c", True) and on["MPG_PARTS"])
         self.D_loss = torch.zeros((), device=dev)
         self.G_loss = torch.zeros((), device=dev)
-        self.use_graphs = use_graphs and dev.type == "cuda"
+        self.use_graphs = use_graphs and gpu
         self._graphs = None
         # The G step's generator forward depends on nothing the D step writes (G's weights, fresh noise, the labels): it is
         # launched at the top of the D step on a second stream and runs BESIDE it -- the edge launches of a batch of 256 jets
@@ -429,26 +473,21 @@ class TrainStep:
         # (power-iteration vectors) the forked train-mode forward would update what the D step's eval-mode call reads on
         # the main stream at the same time -- a race, and the reference's order the other way round (train.py:432-447 before
         # :500-511).
-        self.gen_ahead = (dev.type == "cuda" and isinstance(G, MPGenerator) and _forward_writes_no_state(G)
-                          and os.environ.get("MPG_GEN_AHEAD", "1") != "0")
-        self._side = None
-        self._fake_ahead = None
-        # where the generator-ahead branch joins: at the end of the D segment when that segment is a hipGraph of its own (a
-        # capture must end with every forked stream joined), otherwise only where the G step picks its jets up -- so that the D
-        # all-reduce (graph_collectives: inside the one graph; eagerly: between the segments) waits for D's backward and its
-        # weight-gradient stream alone, not for the generator's forward beside them
-        self._defer_join = False
-        self._join_pending = False
-        self._fork_late = False
-        self.gen_join = None       # ("seg_D" | "seg_G": where the last iteration / capture joined the branch; tests read it)
+        self.gen_ahead = gpu and isinstance(G, MPGenerator) and _forward_writes_no_state(G) and on["MPG_GEN_AHEAD"]
+        self._ahead = _GenAhead(dev)      # (never forked without gen_ahead)
         # The launches that only produce weight gradients (mpg_edge_dw + reduction, the grouped node-network weight
         # gradients: about a quarter of the step) feed nothing before the optimizer: they run on a second side stream, forked
         # per layer behind mpg_edge_bwd and joined at the end of the backward (before the all-reduce / optimizer step), so
         # that they start on CUs the one-round data-gradient launches leave idle and their launch boundaries stop
         # serialising with the data path.  MPG_WGRAD_SIDE=0 switches it off.
-        self.wgrad_side = dev.type == "cuda" and os.environ.get("MPG_WGRAD_SIDE", "1") != "0"
+        self.wgrad_side = gpu and on["MPG_WGRAD_SIDE"]
         self._wside = None
-        self.bridge = dev.type == "cuda" and os.environ.get("MPG_BRIDGE", "1") != "0"
+        # The generator-ahead branch is forked at the top of the D segment (MPG_GEN_AHEAD_LATE=0: beside the D step's own
+        # generator call), or -- default -- behind the D step's last data-gradient launch, beside the weight-gradient tail
+        # (_backward): the lower layer's mpg_edge_dw, its reduction, the grouped weight gradients, the optimizer and the packing
+        # are small or latency-bound launches that leave most CUs idle, and two full-chip forwards fill them
+        self.gen_ahead_late = self.gen_ahead and self.wgrad_side and on["MPG_GEN_AHEAD_LATE"]
+        self.bridge = gpu and on["MPG_BRIDGE"]      # (see ``_bridge``)
         # Jet augmentation (train.py:438-442, :508-511): one affine map of (eta, phi) per jet, drawn on the device from the seed
         # that keys the noise and the dropout masks (ops.augment) -- one launch on the generated half of the D step's batch, one
         # each way between the generator's jets and the discriminator in the G step.  The probability lives in device memory:
@@ -461,7 +500,7 @@ class TrainStep:
                 self.aug = SimpleNamespace(flags=flags, translate_ratio=float(augment.translate_ratio), scale_sd=float(augment.scale_sd))
                 self.aug_params = [torch.zeros(batch_size, 6, device=dev) for _ in AUG_SITES]
         # the generator's noise and its jets' masks drawn by one launch (MPG_NOISE_MASK=0: mpg_normal, then mpg_rank_mask)
-        self.noise_mask = dev.type == "cuda" and os.environ.get("MPG_NOISE_MASK", "1") != "0"
+        self.noise_mask = gpu and on["MPG_NOISE_MASK"]
         self.fixed_noise = None  # tests: (noise_D, noise_G) used instead of fresh samples
         self._seen_versions = (self.fD.versions(), self.fG.versions())
         # the flat gradient buffers start as zeros and every optimizer launch of an iteration leaves them cleared again
@@ -472,6 +511,10 @@ class TrainStep:
         self.loader = None
         if loader is not None:
             self.attach_loader(loader)
+
+    @property
+    def gen_join(self):      # ("seg_D" | "seg_G", None before the first join: tests read it)
+        return self._ahead.joined
 
     def attach_loader(self, loader):
         """Take the batches from ``loader`` (``data.DeviceJetLoader``) instead of ``set_batch``: one launch at the top of the D
@@ -546,15 +589,74 @@ class TrainStep:
         return h is not None and t is not None and ops.bridge_fusable(h[0].shape[1], h[0].shape[0], t[0].shape[0]) \
             and t[0].shape[1] == h[0].shape[0] and h[0].data_ptr() % 16 == 0
 
-    def _head_loss(self, y, mask, gen_step: bool, n_jets: int, loss_out, wgrad: bool):
-        w, b, mean, sigmoid, p = self.D.fused_head()
-        grads = (w.grad, None if b is None else b.grad) if wgrad else None
-        _, dy = ops.disc_head_loss(y, mask, w, b, mean=mean, sigmoid=sigmoid, p_drop=p, training=self.D.training,
-                                   loss=self.loss, n_real=self.B, gen_step=gen_step, count=self.B, loss_out=loss_out,
-                                   want_dy=True, wgrad=grads)
-        return dy
+    def _route(self, rows_ok: bool = True) -> str:
+        """How the generator's jets reach the discriminator in the segment that asks (``rows_ok=False``: not by "rows")."""
+        #   "rows"    the one-launch bridge (``generate_rows`` -> ``features_rows``)
+        #   "parts"   features and mask held apart (``generate_parts`` -> ``features_parts``)
+        #   "into"    the [B, N, 4] batch with the fused head (``generate_into`` / ``G(...)`` -> ``features``)
+        #   "module"  the plain modules with a torch loss: gradient penalty, batch norm in D, CPU toy networks
+        # Asked at the top of each segment and never kept: ``GAPT_G.bridge_head`` depends on ``G.training``, which differs
+        # between train_D and train_G, and weights may be swapped between steps.
+        if not self._fused_ends():
+            return "module"
+        if not self.parts:
+            return "into"
+        return "rows" if rows_ok and self._bridge() else "parts"
 
-    def _seg_D(self):  # train_D up to and including backward (train.py:419-460)
+    def _generate_for_D(self, route: str):
+        """train_D's generated half (train.py:432-442), without gradient: (the generated jets, augmented in place; the 2B jets of
+        the static batch as ``_features`` takes them, the generated ones written behind the real ones -- None on "module")."""
+        # ("rows": the generator's rows stand in for the features and there are no jets yet -- never augmented: ``_bridge``)
+        own = slice(self.B, None)
+        with torch.no_grad():
+            if route in ("rows", "parts"):
+                rows = {"mask_out": self._mask2[own], "ign_out": self._ign2[own]}
+                z, pm = self._noise_masked(0, **rows)
+                if route == "rows":
+                    fake, jets = None, (self.G.generate_rows(z, self.labels, premask=pm, **rows)[0], self._mask2, self._ign2)
+                else:
+                    fake, jets = self._x3[own], (self._x3, self._mask2, self._ign2)
+                    self.G.generate_parts(z, self.labels, feat_out=fake, premask=pm, **rows)
+            elif route == "into":
+                fake, jets = self._dcat[own], self._dcat
+                self.G.generate_into(self._noise(0), self.labels, fake)
+            else:
+                fake, jets = self.G(self._noise(0), self.labels), None
+            if self.aug is not None:       # (D(real) sees the batch as it is: train.py:425 runs before the augmentation)
+                fake = self._augment(fake, AUG_SITES["D_fake"], in_place=True)
+        return fake, jets
+
+    def _generate(self, route: str):
+        """train_G's ``gen_data = gen(...)`` (train.py:500-511): (rows or particle features, mask, 1 - mask) or [B, N, 4] jets."""
+        if route in ("rows", "parts"):
+            z, pm = self._noise_masked(1)
+            return (self.G.generate_rows if route == "rows" else self.G.generate_parts)(z, self.labels, premask=pm)
+        return self.G(self._noise(1), self.labels)
+
+    def _features(self, route: str, jets, labels, gen_step: bool):
+        """D up to its fused head on a fused route: (y, mask) for ``_head_loss_backward``."""
+        if route == "into":
+            return self.D.features(jets, labels)
+        x, mask, ign = jets
+        if route == "parts":
+            return self.D.features_parts(x, mask, labels, ignore=ign)
+        head, real = self.G.bridge_head(), None
+        if not gen_step:
+            # (the generator takes no gradient in train_D: its final_fc enters the launch as plain data; the generated
+            # features are written behind the real ones)
+            head, real = (head[0].detach(), None if head[1] is None else head[1].detach(), head[2]), self._x3
+        return self.D.features_rows(x, head, real, mask, labels, ignore=ign)
+
+    def _head_loss_backward(self, y, mask, gen_step: bool, then=None):
+        """The fused head with its loss (train_D: with the head's own weight gradients), then the backward from (y, dy)."""
+        w, b, mean, sigmoid, p = self.D.fused_head()
+        _, dy = ops.disc_head_loss(y, mask, w, b, mean=mean, sigmoid=sigmoid, p_drop=p, training=self.D.training, loss=self.loss,
+                                   n_real=self.B, gen_step=gen_step, count=self.B, loss_out=self.G_loss if gen_step else self.D_loss,
+                                   want_dy=True, wgrad=None if gen_step else (w.grad, None if b is None else b.grad))
+        self._backward(y, dy, then)
+
+    def _seg_D(self, join: bool = True):  # train_D up to and including backward (train.py:419-460)
+        # (join=False: the generator-ahead branch stays open for a _seg_G that follows in the same graph / eager run)
         # parameter gradients are added straight into the flat buffers (no AccumulateGrad kernel per parameter)
         if self.loader is not None:     # (first: the generator-ahead branch reads self.labels)
             self.loader.feed(self)
@@ -562,12 +664,7 @@ class TrainStep:
         self.state.order_cache = None   # (ops.jet_order: the masks of this iteration live where last iteration's did)
         # (the dropout / noise seed of this iteration was set by the last launch of the iteration before: _seg_end)
         self.D.train()
-        # the generator-ahead branch: forked at the top of the segment (MPG_GEN_AHEAD_LATE=0: beside the D step's own generator
-        # call), or -- default -- behind the D step's last data-gradient launch, beside the weight-gradient tail (_backward): the
-        # lower layer's mpg_edge_dw, its reduction, the grouped weight gradients, the optimizer and the packing are small or
-        # latency-bound launches that leave most CUs idle, and two full-chip forwards fill them
-        self._fork_late = self.gen_ahead and self.wgrad_side and os.environ.get("MPG_GEN_AHEAD_LATE", "1") != "0"
-        if self.gen_ahead and not self._fork_late:
+        if self.gen_ahead and not self.gen_ahead_late:
             self._fork_generator()
         self.G.eval()
         if not self._clean["D"]:     # (cleared by the optimizer launch of the iteration before: see _seg_G)
@@ -575,19 +672,14 @@ class TrainStep:
         self._clean["D"] = False
         _set_requires_grad(self.fD, True)
         try:
-            self._seg_D_body()
+            self._seg_D_body(self._fork_generator if self.gen_ahead_late else None)
         finally:
-            if self.gen_ahead:
-                if self._defer_join:
-                    self._join_pending = True
-                elif self._side is not None:   # join: everything of this segment is ordered before whatever follows it
-                    torch.cuda.current_stream(self.dev).wait_stream(self._side)
-                    self.gen_join = "seg_D"
+            if join:     # everything of this segment is ordered before whatever follows it
+                self._ahead.join("seg_D")
 
     def _fork_generator(self):
         """train_G's ``gen_data = gen(...)`` (train.py:500-511) on the side stream, in training mode."""
-        if self._side is None:
-            self._side = torch.cuda.Stream(device=self.dev)
+        # (never by the "rows" route: the branch exists for ``MPGenerator`` only -- ``gen_ahead`` -- which has no bridge)
         # G's weight images are shared by this forward and the D step's own generator call: built (on first use, or behind an
         # outside write) on THIS stream, before the fork -- built inside the forward they would be written on the side stream
         # while the other call reads them
@@ -595,49 +687,14 @@ class TrainStep:
         for m in self.G.modules():
             if hasattr(m, "_packed") and getattr(m, "fused", False):
                 m._packed().ensure()
-        self._side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(self._side):
-            if self.parts and self._fused_ends():
-                z, pm = self._noise_masked(1)
-                self._fake_ahead = self.G.generate_parts(z, self.labels, premask=pm)
-            else:
-                self._fake_ahead = self.G(self._noise(1), self.labels)
-        for t in (self._fake_ahead if isinstance(self._fake_ahead, tuple) else (self._fake_ahead,)):
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(self.dev))   # (its consumer, the G step, runs on this stream)
+        self._ahead.fork(lambda: self._generate(self._route(rows_ok=False)))
 
-    def _seg_D_body(self):
-        if self._fused_ends():
-            # real jets sit in the first half of the static batch; the generator writes the second half itself
-            B = self.B
-            if self.parts and self._bridge():
-                with torch.no_grad():
-                    z, pm = self._noise_masked(0, self._mask2[B:], self._ign2[B:])
-                    pre, _, _ = self.G.generate_rows(z, self.labels, mask_out=self._mask2[B:], ign_out=self._ign2[B:], premask=pm)
-                    W1, b1, act1 = self.G.bridge_head()
-                # (the generator takes no gradient in train_D: its final_fc enters the launch as plain data)
-                head = (W1.detach(), None if b1 is None else b1.detach(), act1)
-                y, mask = self.D.features_rows(pre, head, self._x3, self._mask2, self._labels2, ignore=self._ign2)
-            elif self.parts:
-                with torch.no_grad():
-                    z, pm = self._noise_masked(0, self._mask2[B:], self._ign2[B:])
-                    self.G.generate_parts(z, self.labels, feat_out=self._x3[B:], mask_out=self._mask2[B:], ign_out=self._ign2[B:], premask=pm)
-                    if self.aug is not None:
-                        self._augment(self._x3[B:], AUG_SITES["D_fake"], in_place=True)
-                y, mask = self.D.features_parts(self._x3, self._mask2, self._labels2, ignore=self._ign2)
-            else:
-                with torch.no_grad():
-                    self.G.generate_into(self._noise(0), self.labels, self._dcat[B:])
-                    if self.aug is not None:
-                        self._augment(self._dcat[B:], AUG_SITES["D_fake"], in_place=True)
-                y, mask = self.D.features(self._dcat, self._labels2)
-            dy = self._head_loss(y, mask, False, 2 * self.B, self.D_loss, True)
-            self._backward(y, dy)
-            return
-        with torch.no_grad():
-            fake = self.G(self._noise(0), self.labels)
-            if self.aug is not None:       # (D(real) sees the batch as it is: train.py:425 runs before the augmentation)
-                fake = self._augment(fake, AUG_SITES["D_fake"], in_place=True)
+    def _seg_D_body(self, late_fork=None):
+        route = self._route()
+        fake, jets = self._generate_for_D(route)
+        if route != "module":
+            # real jets sit in the first half of the static batch; the generator has written the second half itself
+            return self._head_loss_backward(*self._features(route, jets, self._labels2, False), False, late_fork)
         if self.batch_real_fake:
             out = self.D(torch.cat([self.data, fake], 0), torch.cat([self.labels, self.labels], 0))
         else:
@@ -652,7 +709,7 @@ class TrainStep:
             gp = self.gradient_penalty(real, fake)
             self.GP.copy_(gp.detach())
             loss = loss + gp
-        self._backward(loss)
+        self._backward(loss, then=late_fork)
 
     def gradient_penalty(self, real: torch.Tensor, fake: torch.Tensor) -> torch.Tensor:
         """``gradient_penalty`` of train.py:286-324:  gp_lambda * mean_b (|| dD(x_b)/dx_b ||_2 - 1)^2  at
@@ -669,9 +726,11 @@ class TrainStep:
         norm = torch.sqrt((grads.reshape(B, -1) ** 2).sum(1) + 1e-12)
         return self.gp_lambda * ((norm - 1) ** 2).mean()
 
-    def _backward(self, root, grad=None):
+    def _backward(self, root, grad=None, then=None):
         """root.backward(grad) with the stand-alone Linear layers' weight gradients collected and issued as grouped
         launches that add straight into the flat gradient buffers."""
+        # (then: called behind the last of them and before the weight-gradient stream joins, never behind a failed backward --
+        # train_D's late fork of the generator-ahead branch)
         self.state.deferred_wgrad = ops.WgradBatch()
         if self.wgrad_side:
             if self._wside is None:
@@ -680,12 +739,10 @@ class TrainStep:
         try:
             torch.autograd.backward([root], None if grad is None else [grad])
             self.state.deferred_wgrad.flush()
-            if self._fork_late:   # (D step only: _seg_G clears the flag before its own backward; never behind a failed backward)
-                self._fork_late = False
-                self._fork_generator()
+            if then is not None:
+                then()
         finally:
             self.state.deferred_wgrad = None
-            self._fork_late = False
             if self.wgrad_side:
                 # join: the weight gradients are complete before whatever follows the backward (all-reduce, optimizer step)
                 self.state.wgrad_stream = None
@@ -706,7 +763,6 @@ class TrainStep:
             ops.refresh_many(packs)
 
     def _seg_G(self):  # D_optimizer.step() (train.py:461) + train_G up to backward (:494-520)
-        self._fork_late = False
         # optimizer.zero_grad() of the next train_D (train.py:419) rides in this launch: the buffer is cleared behind its last use
         self.fD.step(self.lr_disc, gscale=1.0 / self.world, zero_grad=True)
         self._clean["D"] = True
@@ -716,43 +772,19 @@ class TrainStep:
             self.fG.zero_grad()
         self._clean["G"] = False
         _set_requires_grad(self.fD, False)
-        if self._join_pending:       # (the deferred join of the generator-ahead branch: its jets are used from here on)
-            self._join_pending = False
-            if self._side is not None:
-                torch.cuda.current_stream(self.dev).wait_stream(self._side)
-                self.gen_join = "seg_G"
-        fake, self._fake_ahead = self._fake_ahead, None
-        parts = self.parts and self._fused_ends()
-        bridge = parts and fake is None and self._bridge()
-        if bridge:
-            z, pm = self._noise_masked(1)
-            fake = self.G.generate_rows(z, self.labels, premask=pm)
-        elif fake is None:
-            if parts:
-                z, pm = self._noise_masked(1)
-                fake = self.G.generate_parts(z, self.labels, premask=pm)
-            else:
-                fake = self.G(self._noise(1), self.labels)
+        self._ahead.join("seg_G")    # (a branch the D segment left open: its jets are used from here on)
+        ahead = self._ahead.take()
+        route = self._route(rows_ok=ahead is None)     # (the branch's jets came by ``_route(rows_ok=False)`` as well)
+        fake = self._generate(route) if ahead is None else ahead
         if self.aug is not None:     # (here, on the main stream, also for jets the generator-ahead branch made)
             if isinstance(fake, tuple):
                 fake = (self._augment(fake[0], AUG_SITES["G_fake"]),) + tuple(fake[1:])
             else:
                 fake = self._augment(fake, AUG_SITES["G_fake"])
-        if bridge:
-            y, mask = self.D.features_rows(fake[0], self.G.bridge_head(), None, fake[1], self.labels, ignore=fake[2])
-            dy = self._head_loss(y, mask, True, self.B, self.G_loss, False)
-            self._backward(y, dy)
-        elif parts:
-            y, mask = self.D.features_parts(fake[0], fake[1], self.labels, ignore=fake[2])
-            dy = self._head_loss(y, mask, True, self.B, self.G_loss, False)
-            self._backward(y, dy)
-        elif self._fused_ends():
-            y, mask = self.D.features(fake, self.labels)
-            dy = self._head_loss(y, mask, True, self.B, self.G_loss, False)
-            self._backward(y, dy)
+        if route != "module":
+            self._head_loss_backward(*self._features(route, fake, self.labels, True), True)
         else:
-            out = self.D(fake, self.labels)
-            loss = g_loss(self.loss, out)
+            loss = g_loss(self.loss, self.D(fake, self.labels))
             self._backward(loss)
             self.G_loss.copy_(loss.detach())
         _set_requires_grad(self.fD, True)
@@ -778,13 +810,9 @@ class TrainStep:
         mdist.allreduce_sum_(flat.grad, self.pg, self.world)  # sum; 1/world is folded into the optimiser step
 
     def _eager(self):
-        self._defer_join = True
-        try:
-            self._seg_D(); self._allreduce(self.fD)
-            self._seg_G(); self._allreduce(self.fG)
-            self._seg_end()
-        finally:
-            self._defer_join = False
+        self._seg_D(join=False); self._allreduce(self.fD)
+        self._seg_G(); self._allreduce(self.fG)
+        self._seg_end()
 
     def _training_state(self):
         """Everything an iteration changes: parameters, optimiser moments and step counters, the dropout seed, the losses --
@@ -829,25 +857,22 @@ class TrainStep:
         graphs = []
         pool = None
         # one graph per segment between collectives; without a process group the whole iteration is one graph
-        split = (self.world > 1 or self.pg is not None or os.environ.get("MPG_SPLIT_GRAPHS")) and not self.graph_collectives
+        split = (self.world > 1 or self.pg is not None or self.split_graphs) and not self.graph_collectives
+        seg_D_open = lambda: self._seg_D(join=False)    # (D and G segments in ONE graph: the branch may stay open across them)
         if self.graph_collectives:
             if torch.distributed.get_backend(self.pg) != "nccl":
                 raise RuntimeError("graph_collectives needs an nccl (RCCL) process group: only its collectives are stream operations")
             rD, rG = (lambda: self._allreduce(self.fD)), (lambda: self._allreduce(self.fG))
-            groups = [(self._seg_D, rD, self._seg_G, rG, self._seg_end)]
+            groups = [(seg_D_open, rD, self._seg_G, rG, self._seg_end)]
         elif split:
             groups = [(self._seg_D,), (self._seg_G,), (self._seg_end,)]
         else:
-            groups = [(self._seg_D, self._seg_G, self._seg_end)]
+            groups = [(seg_D_open, self._seg_G, self._seg_end)]
         for segs in groups:
             g = torch.cuda.CUDAGraph()
-            self._defer_join = len(segs) > 1     # (D and G segments in ONE graph: the branch may stay open across them)
-            try:
-                with torch.cuda.graph(g, pool=pool):
-                    for seg in segs:
-                        seg()
-            finally:
-                self._defer_join = False
+            with torch.cuda.graph(g, pool=pool):
+                for seg in segs:
+                    seg()
             pool = g.pool()
             graphs.append(g)
         self._graphs = graphs

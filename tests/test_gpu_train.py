@@ -1151,3 +1151,82 @@ def test_device_seed_follows_torch_seed_and_travels_with_the_checkpoint():
     finally:
         st.seed_is_default, st.auto_seed_key = True, None
         torch.manual_seed(before)
+
+
+def test_generator_ahead_branch_joins_where_each_arrangement_says(monkeypatch):
+    """Where the generator-ahead branch joins the main stream, without a process group (``TrainStep.gen_join``): at the end of a D
+    segment that stands alone -- called directly, or a hipGraph of its own -- and only where the G step takes the jets when both
+    segments share an eager iteration or one graph.  The default MPGAN at B = 8, N = 30 without dropout: the smallest shape with
+    the branch, its late fork and the weight-gradient stream all live.  Every arrangement, and the step without the branch, ends
+    at the same bits after two iterations."""
+    from mpgan_amd import train
+    from oracle.train_ref import synthetic_batch
+    B, N = 8, 30
+    data, labels = synthetic_batch(B, N, seed=3)
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    noise = tuple(torch.randn(B, N, 32, device="cuda", generator=gen) * 0.2 for _ in range(2))
+
+    def run(how, n_graphs=None, env=()):
+        with monkeypatch.context() as m:
+            for name, value in env:
+                m.setenv(name, value)
+            G, D = _setup(B, N, disc_dropout=0.0)
+            ts = train.TrainStep(G, D, B, N, lr_disc=train.LR["g"][0], lr_gen=train.LR["g"][1], use_graphs=n_graphs is not None)
+        ts.set_batch(data.cuda(), labels.cuda())
+        ts.fixed_noise = noise
+        if n_graphs is not None:
+            ts.capture(warmup=0)
+            assert len(ts._graphs) == n_graphs
+        for _ in range(2):
+            if how == "segments":
+                ts._seg_D(); ts._seg_G(); ts._seg_end()
+            elif how == "eager":
+                ts._eager()
+            else:
+                ts.step()
+        torch.cuda.synchronize()
+        return ts, (ts.fD.flat.clone(), ts.fG.flat.clone(), ts.D_loss.clone(), ts.G_loss.clone())
+
+    results = []
+    for how, n_graphs, env, joined in (("segments", None, (), "seg_D"), ("eager", None, (), "seg_G"), ("graphs", 1, (), "seg_G"),
+                                       ("graphs", 3, (("MPG_SPLIT_GRAPHS", "1"),), "seg_D")):
+        ts, res = run(how, n_graphs, env)
+        assert ts.gen_ahead and ts.gen_ahead_late and ts.wgrad_side, how
+        assert ts.gen_join == joined, (how, n_graphs, ts.gen_join)
+        results.append(res)
+    ts, res = run("eager", env=(("MPG_GEN_AHEAD", "0"),))
+    assert ts.gen_ahead is False and ts.gen_join is None
+    results.append(res)
+    for res in results[1:]:
+        assert all(torch.equal(a, b) for a, b in zip(results[0], res))
+    assert all(bool(torch.isfinite(t).all()) for t in results[0])
+
+
+def test_a_backward_that_raises_leaves_no_branch_and_no_weight_gradient_state_open(monkeypatch):
+    """A Python exception out of the D step's backward: the late fork of the generator-ahead branch sits behind that backward and
+    must not have run -- no side stream, no jets pending, nothing to join -- and the weight-gradient collection is taken down
+    (``deferred_wgrad``, ``wgrad_stream``, ``wgrad_keep``).  The step then runs a whole iteration as if nothing had happened."""
+    from mpgan_amd import train, ops
+    from oracle.train_ref import synthetic_batch
+    B, N = 8, 30
+    G, D = _setup(B, N, disc_dropout=0.0)
+    ts = train.TrainStep(G, D, B, N, use_graphs=False)
+    assert ts.gen_ahead and ts.gen_ahead_late and ts.wgrad_side
+    data, labels = synthetic_batch(B, N, seed=3)
+    ts.set_batch(data.cuda(), labels.cuda())
+
+    def refuse(*args, **kwargs):
+        raise RuntimeError("backward refused")
+    with monkeypatch.context() as m:
+        m.setattr(torch.autograd, "backward", refuse)
+        with pytest.raises(RuntimeError, match="backward refused"):
+            ts._seg_D()
+    assert ts._ahead.jets is None and not ts._ahead.open
+    assert ts._ahead.stream is None and ts.gen_join is None        # (the first fork makes the stream: there was none)
+    st = ops.dev_state(ts.dev)
+    assert st.deferred_wgrad is None and st.wgrad_stream is None and len(st.wgrad_keep) == 0
+    ts.mark_grads_dirty()
+    ts._eager()
+    torch.cuda.synchronize()
+    assert ts.gen_join == "seg_G" and ts._ahead.jets is None and not ts._ahead.open
+    assert np.isfinite(float(ts.D_loss)) and np.isfinite(float(ts.G_loss))

@@ -318,3 +318,28 @@ def test_deferred_targets_only_inside_a_collecting_backward_with_every_target():
     (t,), _ = ops._deferred_targets(st, [rows])
     assert t.shape == (3, 4) and t.data_ptr() == W.grad[2:5].data_ptr()
     assert ops._deferred_targets(st, [b, W])[0][0] is b.grad
+
+
+@pytest.mark.parametrize("switches", ["1", "0"])
+def test_cpu_and_gradient_penalty_steps_take_the_module_route(monkeypatch, switches):
+    """``TrainStep._route()`` names how the generator's jets reach the discriminator.  A step on the CPU (toy modules) and a
+    step with a gradient penalty -- whose D(interpolated) needs the modules' own graph -- go by the plain modules with a torch
+    loss, whatever the route switches say; the switches are read when the step is built, never after."""
+    from mpgan_amd import train
+    from test_dist_cpu import ToyG, ToyD, ToyD2, N as TN, LAT
+    for name in ("MPG_PARTS", "MPG_BRIDGE", "MPG_GEN_AHEAD", "MPG_GEN_AHEAD_LATE", "MPG_WGRAD_SIDE", "MPG_NOISE_MASK"):
+        monkeypatch.setenv(name, switches)
+    monkeypatch.delenv("MPG_SPLIT_GRAPHS", raising=False)
+    torch.manual_seed(3)
+    plain = train.TrainStep(ToyG(), ToyD(), 4, TN, latent=LAT, use_graphs=False)
+    gp = train.TrainStep(ToyG(), ToyD2(), 4, TN, latent=LAT, use_graphs=False, loss="w", gp_lambda=10.0)
+    for ts in (plain, gp):
+        assert ts._route() == "module" and ts._route(rows_ok=False) == "module"
+        assert not ts._bridge() and not ts._fused_ends()
+        # nothing of the device-only arrangements is on for a CPU step, and there is no branch to join
+        assert not (ts.parts or ts.gen_ahead or ts.gen_ahead_late or ts.wgrad_side or ts.bridge or ts.noise_mask)
+        assert ts.gen_join is None and ts.split_graphs is False
+    # sampled at construction: the environment changing afterwards reaches nothing
+    monkeypatch.setenv("MPG_SPLIT_GRAPHS", "1")
+    assert plain.split_graphs is False
+    assert train.TrainStep(ToyG(), ToyD(), 4, TN, latent=LAT, use_graphs=False).split_graphs is True
