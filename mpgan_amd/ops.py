@@ -6,6 +6,7 @@ no CPU path: tensors must live on a gfx950 device.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import itertools
 import os
@@ -367,7 +368,7 @@ def linear_bwd_weight(dy, x, *, out=None, out_col0=0, out_scale=1.0, bias_out=No
 # there instead of launching one small split-K GEMM + reduction per layer; TrainStep flushes the queue -- grouped
 # launches -- before the optimizer.)
 # workgroups a single weight-gradient GEMM of a group aims for when choosing its split-K factor
-WGRAD_TARGET_WGS = int(__import__("os").environ.get("MPG_WGRAD_TARGET", "512"))
+WGRAD_TARGET_WGS = int(os.environ.get("MPG_WGRAD_TARGET", "512"))
 
 
 GROUP_MAX = 16   # MPG_GROUP_MAX of include/mpgan_amd.h
@@ -664,7 +665,10 @@ class PackedMPLayer(_PackedSet):
 def chain(M, layers, **kw):
     """mpg_chain front-end.  ``layers``: dicts with img, K, N and optionally bias, nbias, act, drop=(tag,thr,scale),
     gate=(H, act, tag, thr, scale), out (tensor [M, >=N]), wscale (the image holds wscale * W)."""
-    c = chain_struct(M, layers, **kw)
+    run_chain(chain_struct(M, layers, **kw))
+
+
+def run_chain(c):   # (c: an ``MpgChain`` block, see ``chain_struct``)
     check(_lib.lib().mpg_chain(C.byref(c), _stream()), "mpg_chain")
 
 
@@ -701,9 +705,9 @@ def chain_struct(M, layers, *, A, lda, K1, A2=None, lda2=0, a_slabs=1, a_slab_st
 
 
 EDGE_SCALARS = 2          # MPG_EDGE_SCALARS of include/mpgan_amd.h
-MAX_CHUNK_SENDERS_ES = 116   # ... with edge scalars (their columns take part of the list's LDS)
 PARK_BYTES_PER_BLOCK = 10240   # E2 / dZ2 of one (jet, receiver block, sender) block as fp16 fragments: 160 x 32 x 2 bytes
 MAX_CHUNK_SENDERS = 160   # mpg_edge_bwd keeps the list of a chunk's unmasked senders in LDS (csrc/edge_bwd2.hip)
+MAX_CHUNK_SENDERS_ES = 116   # ... with edge scalars (their columns take part of the list's LDS)
 
 
 def jet_order(mask2d: torch.Tensor) -> torch.Tensor:
@@ -769,9 +773,17 @@ def mplayer_saved(node):
     return MPLayerSaved(*node.saved_tensors)
 
 
+# The node network's input gradients of one layer -- dz3, dz2, dz1 (at its three pre-activations) and dh0 = [dagg | dx(node path)
+# | (conditioning columns)] -- with the ``MpgChain`` block that computes them (None once it has run) ...
+FnGrads = namedtuple("FnGrads", "dz3 dz2 dz1 dh0 chain")
+# ... and what the backward of the layer ABOVE leaves in ``ctx.pre`` when its data-gradient launch has run that chain already: valid for
+# exactly the gradient rows at ``gy_ptr``, which ``keep`` holds alive
+FnGradsDone = namedtuple("FnGradsDone", "grads gy_ptr keep")
+
+
 def _fn_grad_chain(ctx, gy2):
     """Buffers and the ``MpgChain`` block of the node network's input-gradient chain of the layer behind ``ctx`` (the backward
-    of mpgan/model.py:279) for the upstream gradient rows ``gy2`` [B*N, out]: (dz3, dz2, dz1, dh0, chain)."""
+    of mpgan/model.py:279) for the upstream gradient rows ``gy2`` [B*N, out]: an ``FnGrads``."""
     sv, cfg, pk = mplayer_saved(ctx), ctx.cfg, ctx.packed
     V1, V2, V3, alpha, thr, dscale, tag = sv.V1, sv.V2, sv.V3, cfg.alpha, cfg.thr, cfg.dscale, cfg.tag
     V, dev = cfg.B * cfg.N, gy2.device
@@ -785,7 +797,7 @@ def _fn_grad_chain(ctx, gy2):
                          dict(img=pk.ptr("V1T"), K=n1, N=V1.shape[1], out=dh0)],
                      A=gy2, lda=gy2.stride(0), K1=out_f, in_gate=(tag + TAG_N2, thr, dscale), in_out=dz3 if thr else None,
                      alpha=alpha, seed_t=seed_tensor(dev), f16=False)
-    return dz3, dz2, dz1, dh0, c
+    return FnGrads(dz3, dz2, dz1, dh0, c)
 
 
 def _below_chain(prev, dx, thr, alpha, V):
@@ -823,6 +835,336 @@ class LayerHandoff:
         self.below, self.above, self.next, self.ac_out, self.node = below, above, None, None, None
 
 
+# One fused MPLayer call as its helpers see it: the saved tensors by name (an ``MPLayerSaved``; during the forward the one that will be
+# saved), the ``MPLayerCfg``, the ``PackedMPLayer`` and the device's seed tensor
+MPCall = namedtuple("MPCall", "sv cfg pk seed_t")
+# What ``edge_plan`` decides from sizes and switches alone
+EdgePlan = namedtuple("EdgePlan", "SC RB need_grad epilogue tickets write_agg lpt")
+
+
+def edge_plan(B, N, *, es=False, mask=False, need_grad=False, options=None):
+    """What one fused MPLayer forward decides from sizes and switches alone (no tensor, no launch), as an ``EdgePlan``: ``SC`` sender
+    chunks and ``RB`` receiver blocks per jet; ``epilogue``: the node network is tried as the edge launch's epilogue; ``tickets`` /
+    ``write_agg``: that launch needs arrival counters / stores ``agg``; ``lpt``: more workgroups than CUs, handed out heaviest jet
+    first (``jet_order``).  ``es`` / ``mask`` / ``need_grad``: the call has edge scalars / a mask / a backward pending; ``options``:
+    ``OPTIONS`` as they are now.  Raises when the call would park more than the kernels can address."""
+    opt = OPTIONS if options is None else options
+    SC = _sender_chunks(B, N, MAX_CHUNK_SENDERS_ES if es else None)
+    RB = (N + 31) // 32
+    if need_grad and B * RB * N * PARK_BYTES_PER_BLOCK > 0x7fffffff:
+        # (mpg_edge_fwd / mpg_edge_bwd return -7: the parked fragments are addressed with 32-bit offsets)
+        raise RuntimeError(f"FusedMPLayerFn: {B} jets x {N} particles park {B * RB * N * PARK_BYTES_PER_BLOCK / 2**30:.1f} GiB of "
+                           f"edge activations for the backward, beyond the kernels' 2 GiB per launch; split the batch "
+                           f"(at most {0x7fffffff // (RB * N * PARK_BYTES_PER_BLOCK)} jets per call at this size)")
+    epilogue = bool(opt["fn_epilogue"] and not es and (SC == 1 or opt["fn_chunks"]))
+    lpt = bool(mask and opt["lpt_order"] and B * RB * SC > NUM_CUS and B + N + 2 + (B + 63) // 64 * (N + 1) <= 16384)
+    # (agg: nobody reads it without a backward, unless the chunks' partial sums travel through its slabs; tickets: the last workgroup
+    #  to arrive per (jet, receiver block) adds them up)
+    return EdgePlan(SC, RB, bool(need_grad), epilogue, tickets=SC > 1, write_agg=bool(need_grad or SC > 1), lpt=lpt)
+
+
+def _fill_edge(e, sv, cfg, seed_t):
+    # The sixteen fields ``MpgEdgeFwd``, ``MpgEdgeBwd`` and ``MpgEdgeDw`` share, from the call's saved tensors (``sv.ac m1 nbr es wq``),
+    # its ``MPLayerCfg`` and the seed tensor.  Returns ``e``.
+    e.a, e.c, e.ld_ac, e.mask = _p(sv.ac), _p(sv.ac, H1), 2 * H1, _p(sv.m1)
+    e.B, e.N, e.alpha, e.agg_scale = cfg.B, cfg.N, cfg.alpha, cfg.agg_scale
+    e.nbr, e.es, e.wq = _p(sv.nbr), _p(sv.es), _p(sv.wq)
+    e.seed, e.tag_base, e.thr, e.dscale, e.f16 = _p(seed_t), cfg.tag, cfg.thr, cfg.dscale, int(cfg.f16)
+    return e
+
+
+def _fill_edge_grad(e, sv, dh0, park):
+    # The six further fields ``MpgEdgeBwd`` and ``MpgEdgeDw`` share: the upstream gradient of ``agg`` (the head of the ``dh0`` rows), the
+    # forward's by-products and the parked dZ2 with its exponents (``park``: an ``EdgeGradBufs``).  Returns ``e``.
+    e.dagg, e.ld_dagg = _p(dh0), dh0.stride(0)
+    e.sign3, e.stageE2, e.stageZ2, e.gexp = _p(sv.sign3), _p(sv.stE2), _p(park.stZ2), _p(park.gexp)
+    return e
+
+
+# ---- forward
+def _unit_cols(t):
+    return t if t.stride(1) == 1 else t.contiguous()   # (every consumer takes the row stride, only unit column stride matters)
+
+
+def _row_views(x, mask, xfn):
+    # (x2 [V, F], m1 [V] or None, xf2 [V, F + E]): the nodes, their mask and the node network's view of the nodes as rows.
+    V = x.shape[0] * x.shape[1]
+    x2 = _unit_cols(x.reshape(V, -1))   # a view when x is a feature slice of a contiguous tensor (D's x[..., :-1])
+    m1 = None if mask is None else mask.reshape(V).contiguous()
+    return x2, m1, x2 if xfn is None else _unit_cols(xfn.detach().reshape(V, -1))
+
+
+def _edge_scalar_terms(es, W1, cfg):
+    # (es [B, N, EDGE_SCALARS, N] contiguous, wq [EDGE_SCALARS, H1] = their columns of fe.net.0.weight), or (None, None).
+    if es is None:
+        return None, None
+    B, N, F, nq = cfg.B, cfg.N, cfg.F, cfg.nq
+    assert 0 < nq <= EDGE_SCALARS and tuple(es.shape) == (B, N, EDGE_SCALARS, N) and W1.shape[1] == 2 * F + nq
+    wq = torch.zeros((EDGE_SCALARS, H1), device=W1.device, dtype=torch.float32)
+    wq[:nq] = W1.detach()[:, 2 * F:2 * F + nq].t()
+    return es.detach().float().contiguous(), wq
+
+
+def _ac_chain(pk, b1, rows, ac, cfg):
+    # The ``MpgChain`` of a layer's node terms ``ac`` = a | c = rows [W1a ; W1c]^T (+ b1 on the a half); ``pk``: that layer's images.
+    F = rows.shape[1]
+    return chain_struct(rows.shape[0], [dict(img=pk.ptr("W1S"), K=F, N=2 * H1, bias=b1, nbias=H1, out=ac, wscale=SC_WN)],
+                        A=rows, lda=rows.stride(0), K1=F, alpha=cfg.alpha, f16=cfg.f16, ascale=SC_ACT)
+
+
+def _node_terms(below, pk, x2, b1, cfg):
+    # Layer-1 node terms a | c [V, 2 * H1] of the rows ``x2``: handed over by the launch that produced x (``below.ac_out``, valid for
+    # these very rows and the weight images as they are now), or one launch.
+    shape = (x2.shape[0], 2 * H1)
+    if below is not None and below.ac_out is not None:
+        ac, pk_pre, x_ptr, key_pre = below.ac_out
+        if pk_pre is pk and key_pre == pk._key and x_ptr == x2.data_ptr() and tuple(ac.shape) == shape:
+            return ac
+    ac = torch.empty(shape, device=x2.device, dtype=torch.float32)
+    run_chain(_ac_chain(pk, b1, x2, ac, cfg))
+    return ac
+
+
+def _edge_fwd_desc(call, aggp):
+    # ``MpgEdgeFwd`` of ``call`` with ``agg`` = ``aggp`` [SC, V, H3], or None for a launch that stores none.
+    sv, cfg, pk, seed_t = call
+    e = _fill_edge(MpgEdgeFwd(), sv, cfg, seed_t)
+    e.W2img, e.W3img, e.b2, e.b3 = pk.ptr("W2"), pk.ptr("W3"), _p(sv.b2), _p(sv.b3)
+    e.agg, e.SC, e.skip_masked = _p(aggp), cfg.SC, int(OPTIONS["skip_masked"])
+    # E2 (the second edge layer's output) parked as fp16 fragments for the backward, which takes LeakyReLU' from its signs
+    # instead of recomputing the layer, and for the weight-gradient kernel
+    e.sign3, e.stageE2, e.order = _p(sv.sign3), _p(sv.stE2), _p(sv.order)
+    # product form of the edge layers (MpgEdgeFwd.two_term; edge scalars ride on the three-term kernels only)
+    e.two_term = int(OPTIONS["fwd_two_term"]) if sv.es is None else 0
+    return e
+
+
+def _fn_fwd_layers(call, biases, y):
+    # The node network fn (mpgan/model.py:279) as three chained layers that end in ``y``; h1 / h2 are stored only for a backward.
+    sv, cfg, pk, _ = call
+    (n1, k1), n2, n3, tag, drop = sv.V1.shape, sv.V2.shape[0], sv.V3.shape[0], cfg.tag, (cfg.thr, cfg.dscale)
+    return [dict(img=pk.ptr("V1"), K=k1, N=n1, bias=biases[0], act=True, drop=(tag + TAG_N0, *drop), out=sv.h1, wscale=SC_WN),
+            dict(img=pk.ptr("V2"), K=n1, N=n2, bias=biases[1], act=True, drop=(tag + TAG_N1, *drop), out=sv.h2, wscale=SC_WN),
+            dict(img=pk.ptr("V3"), K=n2, N=n3, bias=biases[2], act=False, drop=(tag + TAG_N2, *drop), out=y, wscale=SC_WN)]
+
+
+def _fn_fwd_chain(call, fn_layers, agg):
+    # ``MpgChain`` of the node network on [agg | xf2] rows.
+    sv, cfg, _, seed_t = call
+    return chain_struct(cfg.B * cfg.N, fn_layers, A=agg, lda=H3, K1=H3, A2=sv.xf2, lda2=sv.xf2.stride(0), alpha=cfg.alpha,
+                        seed_t=seed_t, f16=cfg.f16, ascale=SC_ACT)
+
+
+def _next_node_terms(handoff, y, cfg):
+    # (ac_next, the next layer's PackedMPLayer, the ``MpgChain`` of its a | c projection of the rows ``y``) where the epilogue form may
+    # append that projection, else None.
+    out_f = y.shape[1]
+    pk_n, b1_n = handoff.next if handoff is not None and handoff.next is not None else (None, None)
+    if pk_n is None or out_f % 4 or out_f > 32 or pk_n.F != out_f or pk_n.f16 != cfg.f16:
+        return None
+    pk_n.ensure()
+    ac_next = torch.empty((y.shape[0], 2 * H1), device=y.device, dtype=torch.float32)
+    return ac_next, pk_n, _ac_chain(pk_n, b1_n, y, ac_next, cfg)
+
+
+_NOT_COVERED = object()   # what a route returns when its kernel answers MPG_FN_NA: not one of its shapes
+
+
+def _fwd_epilogue(call, plan, aggp, fn_layers, handoff):
+    # The edge network with the node network -- and the next layer's a | c projection -- as the epilogue of ONE launch
+    # (``mpg_edge_fwd_fn``: a whole jet per workgroup or ticketed sender chunks, the default widths).  Returns ``agg`` (None when no
+    # backward will read it), or ``_NOT_COVERED``.
+    e = _edge_fwd_desc(call, aggp if plan.write_agg else None)
+    if plan.tickets:
+        e.tickets = _p(_tickets(aggp.device, call.cfg.B * plan.RB))   # arrival counters of the (jet, receiver block)s: zero, and left zero
+    cs = _fn_fwd_chain(call, fn_layers, aggp)
+    y = fn_layers[-1]["out"]
+    nxt = _next_node_terms(handoff, y, call.cfg)
+    rc = _lib.lib().mpg_edge_fwd_fn(C.byref(e), C.byref(cs), None if nxt is None else C.byref(nxt[2]), _stream())
+    if rc == _lib.MPG_FN_NA:
+        return _NOT_COVERED
+    check(rc, "mpg_edge_fwd_fn")
+    if nxt is not None:
+        handoff.ac_out = (nxt[0], nxt[1], y.data_ptr(), nxt[1]._key)
+    return aggp[0] if plan.need_grad else None   # (SC > 1: the last workgroup to arrive left the chunks' total in slab 0)
+
+
+def _fwd_two_launches(call, aggp, fn_layers):
+    # ``mpg_edge_fwd``, the chunks' sum, ``mpg_chain`` (fn): every shape.  Returns ``agg``.
+    check(_lib.lib().mpg_edge_fwd(C.byref(_edge_fwd_desc(call, aggp)), _stream()), "mpg_edge_fwd")
+    agg = aggp[0]
+    for q in range(1, call.cfg.SC):   # (in chunk order, slab by slab: the order the epilogue form's last arriver takes -- the two routes
+        agg = agg + aggp[q]           #  then agree bit for bit; torch.sum over the chunk axis adds in another order)
+    run_chain(_fn_fwd_chain(call, fn_layers, agg))
+    return agg
+
+
+def _leave_offers(ctx, handoff, x, need_grad):
+    # What the backwards of this layer and of its neighbours find: ``ctx.prev_node`` (x is the very output of the layer below: this
+    # layer's backward may run that layer's input-gradient chain in its own launch), ``ctx.pre`` (filled by the backward of the
+    # layer ABOVE when it has run this layer's input-gradient chain already) and ``handoff.node``.
+    below = handoff.below if handoff is not None else None
+    ctx.prev_node = below.node if (below is not None and need_grad and x.grad_fn is below.node) else None
+    ctx.pre = None
+    if handoff is not None and need_grad:
+        handoff.node = ctx
+
+
+# ---- backward
+# The twelve parameter-gradient targets of one backward: the parameters' .grad buffers (``direct``: added into, and autograd gets
+# None) or fresh tensors; all None when no parameter wants a gradient
+MPGradTargets = namedtuple("MPGradTargets", "W1 b1 W2 b2 W3 b3 V1 c1 V2 c2 V3 c3 direct")
+# Buffers of the edge network's backward: the chunks' partial da [SC, V, H1] and the receiver blocks' partial dc [RB, V, H1]; dZ2 parked
+# as fp16 fragments (as the lanes hold them) with the gradient-unit exponent per (jet, receiver block), for a weight-gradient pass
+# only; the edge scalars' gradient and their columns' partials
+EdgeGradBufs = namedtuple("EdgeGradBufs", "dap dcp stZ2 gexp des daq")
+SlabSums = namedtuple("SlabSums", "da dc dadc")   # da, dc [V, H1]; dadc [V, 2 * H1] where they were summed into one buffer, else None
+
+
+def _taken_fn_grads(ctx, gy2):
+    # The ``FnGrads`` the layer above has left in ``ctx.pre`` -- if it ran the chain for exactly this upstream gradient -- else None.
+    pre, ctx.pre = ctx.pre, None
+    ok = pre is not None and pre.gy_ptr == gy2.data_ptr() and gy2.shape == pre.grads.dz3.shape   # (dz3 [V, out]: rows as its upstream's)
+    return pre.grads._replace(chain=None) if ok else None
+
+
+def _grad_targets(call, need_w):
+    # DeviceState.grad_into_param: add into the parameters' .grad buffers directly and return None for them.
+    sv, pk = call.sv, call.pk
+    if not need_w:
+        return MPGradTargets(*(None,) * 12, direct=False)
+    if (dev_state(sv.x2.device).grad_into_param and pk.plist is not None
+            and all(q.grad is not None and q.grad.is_contiguous() for q in pk.plist)):
+        return MPGradTargets(*(q.grad for q in pk.plist), direct=True)
+    W1, W2, W3, V1, V2, V3 = sv.W1, sv.W2, sv.W3, sv.V1, sv.V2, sv.V3
+    return MPGradTargets(*(t for W in (W1, W2, W3, V1, V2, V3) for t in (torch.empty_like(W), W.new_empty(W.shape[0]))), direct=False)
+
+
+def _edge_grad_bufs(call, need_w):
+    sv, cfg = call.sv, call.cfg
+    V, RB, dev = cfg.B * cfg.N, (cfg.N + 31) // 32, sv.x2.device
+    stZ2 = torch.empty((cfg.B * RB * cfg.N, H2, 32), device=dev, dtype=torch.float16) if need_w else None
+    gexp = torch.empty((cfg.B * RB,), device=dev, dtype=torch.int32) if need_w else None
+    des = None if sv.es is None else torch.zeros_like(sv.es)   # (zero-masked senders' rows are not written)
+    daq = None if sv.es is None else torch.empty((cfg.SC, V, EDGE_SCALARS, H1), device=dev, dtype=torch.float32)
+    return EdgeGradBufs(torch.empty((cfg.SC, V, H1), device=dev, dtype=torch.float32),
+                        torch.empty((RB, V, H1), device=dev, dtype=torch.float32), stZ2, gexp, des, daq)
+
+
+def _edge_bwd_desc(call, dh0, bufs):
+    sv, cfg, pk, seed_t = call
+    e = _fill_edge_grad(_fill_edge(MpgEdgeBwd(), sv, cfg, seed_t), sv, dh0, bufs)
+    e.W2img, e.W3Timg, e.W2Timg, e.b2 = pk.ptr("W2"), pk.ptr("W3T"), pk.ptr("W2T"), _p(sv.b2)
+    e.SC, e.order, e.des, e.daq = cfg.SC, _p(sv.order), _p(bufs.des), _p(bufs.daq)
+    e.da, e.dc = _p(bufs.dap), _p(bufs.dcp)
+    return e
+
+
+def _edge_dw_desc(call, dh0, bufs, tg, part):
+    # ``MpgEdgeDw``: the gradients of fe.net.1 / fe.net.2 into ``tg``, through the per-workgroup partials ``part`` [nwg, ...].
+    sv, cfg, _, seed_t = call
+    d = _fill_edge_grad(_fill_edge(MpgEdgeDw(), sv, cfg, seed_t), sv, dh0, bufs)
+    d.part, d.nwg = _p(part), part.shape[0]
+    d.dW3, d.dW2, d.db3, d.db2, d.accumulate = _p(tg.W3), _p(tg.W2), _p(tg.b3), _p(tg.b2), int(tg.direct)
+    d.defer_reduce = int(OPTIONS["dw_reduce_grouped"])   # (its reduction rides in the grouped reduction launch)
+    return d
+
+
+def _dx_chain(call, dh0, dx, A, A2=None):
+    # ``MpgChain`` of dx = dx(node path) + [da | dc] [W1a ; W1c]: one chained layer over the stacked transposed view of fe.net.0.weight.
+    # Its three feeds are (A, A2) = (dap, dcp): slab 0 of the partial da and dc [slabs, V, H1] (one chunk, one receiver block: the
+    # epilogue of the data-gradient launch); (dadc,): [da | dc] rows as ``mpg_slab_sums`` left them; (da, dc): da rows beside dc rows.
+    cfg, pk = call.cfg, call.pk
+    return chain_struct(cfg.B * cfg.N, [dict(img=pk.ptr("W1ST"), K=2 * H1, N=cfg.F, resid=dh0[:, H3:H3 + cfg.F], out=dx)],
+                        A=A, lda=A.stride(-2), K1=A.shape[-1], A2=A2, lda2=0 if A2 is None else A2.stride(-2), alpha=cfg.alpha, f16=False)
+
+
+def _data_grad(ctx, call, dh0, bufs, dx):
+    # The data-gradient launch of the edge network.  Where the epilogue form covers the call (a whole jet per workgroup) it runs the
+    # layer's dx chain behind it, and behind that the node network's input-gradient chain of the layer BELOW, which produced x (its
+    # backward then finds its work done: ``ctx.pre``).  Returns which of the routes ran: "with_below", "epilogue" or "plain".
+    cfg, lib = call.cfg, _lib.lib()
+    e = C.byref(_edge_bwd_desc(call, dh0, bufs))
+    tries = []   # (route, the layer's dx chain, the lower layer's FnGrads or None), in the order they are tried
+    if dx is not None and cfg.SC == 1 and cfg.N <= 32 and OPTIONS["bwd_epilogue"] and call.sv.es is None:
+        cdx = _dx_chain(call, dh0, dx, bufs.dap, bufs.dcp)
+        below = _below_chain(ctx.prev_node, dx, cfg.thr, cfg.alpha, cfg.B * cfg.N)
+        if below is not None:
+            tries.append(("with_below", cdx, below))
+        tries.append(("epilogue", cdx, None))   # (the pair is not covered: the layer alone may be)
+    for route, cdx, below in tries:
+        rc = lib.mpg_edge_bwd_fn(e, C.byref(cdx), None if below is None else C.byref(below.chain), _stream())
+        if rc != _lib.MPG_FN_NA:
+            check(rc, "mpg_edge_bwd_fn")
+            if below is not None:
+                ctx.prev_node.pre = FnGradsDone(below, gy_ptr=dx.data_ptr(), keep=dx)
+            return route
+    check(lib.mpg_edge_bwd(e, _stream()), "mpg_edge_bwd")
+    return "plain"
+
+
+def _slab_sums(dap, dcp):
+    # The chunks' partial da and the receiver blocks' partial dc, added slab by slab into [da | dc] rows: one launch (none for one
+    # slab each).
+    (SC, V, _), RB = dap.shape, dcp.shape[0]
+    if SC == 1 and RB == 1:
+        return SlabSums(dap[0], dcp[0], None)
+    dadc = torch.empty((V, 2 * H1), device=dap.device, dtype=torch.float32)
+    check(_lib.lib().mpg_slab_sums(_p(dap), SC, V * H1, _p(dcp), RB, V * H1, _p(dadc), V, H1, _stream()), "mpg_slab_sums")
+    return SlabSums(dadc[:, :H1], dadc[:, H1:], dadc)
+
+
+def _weight_grads(call, gy2, fng, bufs, sums, tg):
+    # ``mpg_edge_dw`` (fe.net.1, fe.net.2), then the six dense weight gradients -- fn's three layers and the two halves of fe.net.0
+    # (a = W1[:, :F] x + b1, c = W1[:, F:] x) -- as ONE grouped launch.
+    # These launches feed nothing before the optimizer: with a side stream set (TrainStep) they are forked off here, behind the
+    # data-gradient kernel that produced their inputs, and this stream goes straight on to dx and the layers below.  Same launches,
+    # same order per parameter: results are bit-identical.
+    sv, cfg, dev, acc, wb = call.sv, call.cfg, call.sv.x2.device, tg.direct, WgradBatch()
+    wb.add(fng.dz3, sv.h2, out=tg.V3, bias_out=tg.c3, accumulate=acc)
+    wb.add(fng.dz2, sv.h1, out=tg.V2, bias_out=tg.c2, accumulate=acc)
+    wb.add(fng.dz1, sv.agg, out=tg.V1, out_col0=0, bias_out=tg.c1, accumulate=acc)
+    wb.add(fng.dz1, sv.xf2, out=tg.V1, out_col0=H3, accumulate=acc)
+    wb.add(sums.da, sv.x2, out=tg.W1, out_col0=0, bias_out=tg.b1, accumulate=acc)
+    wb.add(sums.dc, sv.x2, out=tg.W1, out_col0=cfg.F, accumulate=acc)
+    nwg = dw_workgroups(cfg.B * ((cfg.N + 31) // 32) * cfg.N, cfg.N)
+    part = torch.empty((nwg, H3 * H2 + H2 * H1 + H3 + H2), device=dev, dtype=torch.float32)   # per-workgroup partials of mpg_edge_dw
+    d = _edge_dw_desc(call, fng.dh0, bufs, tg, part)
+    st = dev_state(dev)
+    side = st.wgrad_stream if (acc and sv.es is None) else None
+    if side is not None:
+        # wgrad_keep: EVERYTHING a launch on the side stream reads or writes stays referenced until TrainStep joins the stream -- taken
+        # from the records that hold those tensors (the saved state, the node network's gradients and their upstream rows, the data
+        # gradients and their sums, the partials here and every queued job) rather than listed by hand
+        st.wgrad_keep.append((sv, gy2, fng[:4], bufs, sums, part, list(wb.jobs)))
+        side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+        check(_lib.lib().mpg_edge_dw(C.byref(d), _stream()), "mpg_edge_dw")
+        wb.flush(dw=d if d.defer_reduce else None)
+
+
+def _edge_backward(ctx, call, gy2, fng, tg, dx):
+    # The layer's backward launches: fn's input-gradient chain (unless done), the edge network's data path, then (``tg`` has targets)
+    # the weight-gradient pass.  The parked dZ2 lives as long as this call.  Returns (the data-gradient route that ran, the SlabSums, des).
+    sv, cfg = call.sv, call.cfg
+    need_w = tg.W1 is not None
+    bufs = _edge_grad_bufs(call, need_w)
+    if fng.chain is not None:
+        run_chain(fng.chain)
+    route = _data_grad(ctx, call, fng.dh0, bufs, dx)
+    sums = _slab_sums(bufs.dap, bufs.dcp)
+    if need_w:
+        _weight_grads(call, gy2, fng, bufs, sums, tg)
+        if sv.es is not None:   # the columns of the edge scalars: sum over receivers of daq
+            F, nq = cfg.F, cfg.nq
+            dWq = bufs.daq.sum((0, 1))[:nq].t()
+            if tg.direct:
+                tg.W1[:, 2 * F:2 * F + nq] += dWq
+            else:
+                tg.W1[:, 2 * F:2 * F + nq] = dWq
+    return route, sums, bufs.des
+
+
 class FusedMPLayerFn(torch.autograd.Function):
     """MPLayer.forward (mpgan/model.py:206-282), default configuration: fully connected, no edge
     features, no conditioning labels; fe = 3 layers [96,160,192], fn = 2 hidden layers + linear."""
@@ -844,314 +1186,69 @@ class FusedMPLayerFn(torch.autograd.Function):
         sum_agg, alpha, p_drop, training, packed, nbr, num_knn, nq, handoff, no_grad = settings
         _chk(x, "x")
         B, N, F = x.shape
-        V = B * N
-        dev = x.device
-        thr, dscale = drop_params(p_drop) if training else (0, 1.0)
-        seed_t = seed_tensor(dev)
-        tag = next_tag(dev, "mplayer", thr)
-        x2 = x.reshape(V, F)          # a view when x is a feature slice of a contiguous tensor (D's x[..., :-1]) ...
-        if x2.stride(1) != 1:
-            x2 = x2.contiguous()      # ... every consumer below takes the row stride, only unit column stride matters
-        m1 = None if mask is None else mask.reshape(V).contiguous()
-        f16 = FWD_F16
-        out_f = V3.shape[0]
-        if packed is None or packed.dscale != dscale or packed.f16 != f16:  # direct callers: pack for this call
-            packed = PackedMPLayer((W1, W2, W3, V1, V2, V3), F, out_f, dscale, f16)
-        pk = packed.ensure()
-
-        def dr(site):
-            return (tag + site, thr, dscale)
-
-        # layer-1 node terms a | c = x [W1a ; W1c]^T (+ b1 on the a half): handed over by the launch that produced x, or one launch
-        ac = None
-        below = handoff.below if handoff is not None else None
-        if below is not None and below.ac_out is not None:
-            ac_pre, pk_pre, x_ptr, key_pre = below.ac_out   # (valid for these very rows and the weight images as they are now)
-            if pk_pre is pk and key_pre == pk._key and x_ptr == x2.data_ptr() and tuple(ac_pre.shape) == (V, 2 * H1):
-                ac = ac_pre
-        if ac is None:
-            ac = torch.empty((V, 2 * H1), device=dev, dtype=torch.float32)
-            chain(V, [dict(img=pk.ptr("W1S"), K=F, N=2 * H1, bias=b1, nbias=H1, out=ac, wscale=SC_WN)], A=x2, lda=x2.stride(0), K1=F,
-                  alpha=alpha, f16=f16, ascale=SC_ACT)
-        SC = _sender_chunks(B, N, MAX_CHUNK_SENDERS_ES if es is not None else None)
-        aggp = torch.empty((SC, V, H3), device=dev, dtype=torch.float32)
-        e = MpgEdgeFwd()
-        e.a, e.c, e.ld_ac, e.mask = _p(ac), _p(ac, H1), 2 * H1, _p(m1)
-        e.W2img, e.W3img = pk.ptr("W2"), pk.ptr("W3")
-        e.b2, e.b3, e.agg = _p(b2), _p(b3), _p(aggp)
-        e.B, e.N, e.SC = B, N, SC
-        agg_scale = 1.0 if sum_agg else 1.0 / (num_knn if nbr is not None else N)
-        e.alpha, e.agg_scale = alpha, agg_scale
-        e.nbr = None if nbr is None else C.c_void_p(nbr.data_ptr())
-        e.seed, e.tag_base, e.thr, e.dscale = _p(seed_t), tag, thr, dscale
-        e.skip_masked = int(OPTIONS["skip_masked"])
-        e.f16 = int(f16)
-        # product form of the edge layers (MpgEdgeFwd.two_term; edge scalars ride on the three-term kernels only)
-        e.two_term = int(OPTIONS["fwd_two_term"]) if es is None else 0
-        wq = None
-        if es is not None:
-            assert 0 < nq <= EDGE_SCALARS and tuple(es.shape) == (B, N, EDGE_SCALARS, N) and W1.shape[1] == 2 * F + nq
-            es = es.detach().float().contiguous()
-            wq = torch.zeros((EDGE_SCALARS, H1), device=dev, dtype=torch.float32)
-            wq[:nq] = W1.detach()[:, 2 * F:2 * F + nq].t()
-            e.es, e.wq = _p(es), _p(wq)
-        RB = (N + 31) // 32
-        order = None
-        if m1 is not None and OPTIONS["lpt_order"] and B * RB * SC > NUM_CUS and B + N + 2 + (B + 63) // 64 * (N + 1) <= 16384:
-            order = jet_order(m1.view(B, N))
-            e.order = C.c_void_p(order.data_ptr())
+        V, dev, out_f = B * N, x.device, V3.shape[0]
         # ``no_grad``: the caller's torch.is_grad_enabled() was off (train_D's generator call): inside forward() grad mode is
         # always off and needs_input_grad still says what the PARAMETERS want, so without the flag such a call would write
         # everything a backward reads -- sign words, 10 KB of parked fragments per block, agg, h1, h2 -- for nothing
         need_grad = any(ctx.needs_input_grad) and not no_grad
-        if need_grad and B * RB * N * PARK_BYTES_PER_BLOCK > 0x7fffffff:
-            # (mpg_edge_fwd / mpg_edge_bwd return -7: the parked fragments are addressed with 32-bit offsets)
-            raise RuntimeError(f"FusedMPLayerFn: {B} jets x {N} particles park {B * RB * N * PARK_BYTES_PER_BLOCK / 2**30:.1f} GiB of "
-                               f"edge activations for the backward, beyond the kernels' 2 GiB per launch; split the batch "
-                               f"(at most {0x7fffffff // (RB * N * PARK_BYTES_PER_BLOCK)} jets per call at this size)")
-        sign3 = torch.empty((B * RB * N * 192,), device=dev, dtype=torch.int32) if need_grad else None
-        e.sign3 = None if sign3 is None else C.c_void_p(sign3.data_ptr())
-        # E2 (the second edge layer's output) parked as fp16 fragments for the backward, which takes LeakyReLU' from its
-        # signs instead of recomputing the layer, and for the weight-gradient kernel
-        stE2 = torch.empty((B * RB * N, H2, 32), device=dev, dtype=torch.float16) if need_grad else None
-        e.stageE2 = None if stE2 is None else C.c_void_p(stE2.data_ptr())
-        # node network fn: three chained layers -- as the epilogue of the edge launch where that form covers the call
-        # (mpg_edge_fwd_fn: a whole jet per workgroup, the default widths), else one more launch
-        xf2 = x2
-        if xfn is not None:
-            xf2 = xfn.detach().reshape(V, -1)
-            if xf2.stride(1) != 1:
-                xf2 = xf2.contiguous()
+        plan = edge_plan(B, N, es=es is not None, mask=mask is not None, need_grad=need_grad)   # (raises before any allocation or launch)
+        thr, dscale = drop_params(p_drop) if training else (0, 1.0)
+        seed_t = seed_tensor(dev)
+        agg_scale = 1.0 if sum_agg else 1.0 / (num_knn if nbr is not None else N)
+        cfg = MPLayerCfg(B, N, F, agg_scale, alpha, thr, dscale, next_tag(dev, "mplayer", thr), plan.SC, FWD_F16, nq)
+        if packed is None or packed.dscale != dscale or packed.f16 != cfg.f16:  # direct callers: pack for this call
+            packed = PackedMPLayer((W1, W2, W3, V1, V2, V3), F, out_f, dscale, cfg.f16)
+        pk = packed.ensure()
+        x2, m1, xf2 = _row_views(x, mask, xfn)
         assert V1.shape[1] == H3 + xf2.shape[1]
-        n1, n2 = V1.shape[0], V2.shape[0]
-        # (what only a backward reads -- agg for fn.net.0's weight gradient, the hidden activations -- is not written without one)
-        h1 = torch.empty((V, n1), device=dev, dtype=torch.float32) if need_grad else None
-        h2 = torch.empty((V, n2), device=dev, dtype=torch.float32) if need_grad else None
-        y = torch.empty((V, out_f), device=dev, dtype=torch.float32)
-        fn_layers = [dict(img=pk.ptr("V1"), K=V1.shape[1], N=n1, bias=c1, act=True, drop=dr(TAG_N0), out=h1, wscale=SC_WN),
-                     dict(img=pk.ptr("V2"), K=n1, N=n2, bias=c2, act=True, drop=dr(TAG_N1), out=h2, wscale=SC_WN),
-                     dict(img=pk.ptr("V3"), K=n2, N=out_f, bias=c3, act=False, drop=dr(TAG_N2), out=y, wscale=SC_WN)]
-        fn_kw = dict(A2=xf2, lda2=xf2.stride(0), alpha=alpha, seed_t=seed_t, f16=f16, ascale=SC_ACT)
-        rc = _lib.MPG_FN_NA
-        if OPTIONS["fn_epilogue"] and es is None and (SC == 1 or OPTIONS["fn_chunks"]):
-            if SC > 1:
-                e.tickets = _p(_tickets(dev, B * RB))   # arrival counters of the (jet, receiver block)s: zero, and left zero
-            if not need_grad and SC == 1:   # (with sender chunks the partial sums travel through the slabs of agg)
-                e.agg = None
-            cs = chain_struct(V, fn_layers, A=aggp, lda=H3, K1=H3, **fn_kw)
-            cs2 = ac_next = None
-            if handoff is not None and handoff.next is not None and out_f % 4 == 0 and out_f <= 32:
-                # the next layer's a | c projection of the rows this launch produces, appended to the epilogue
-                pk_n, b1_n = handoff.next
-                if pk_n.F == out_f and pk_n.f16 == f16:
-                    pk_n.ensure()
-                    ac_next = torch.empty((V, 2 * H1), device=dev, dtype=torch.float32)
-                    cs2 = chain_struct(V, [dict(img=pk_n.ptr("W1S"), K=out_f, N=2 * H1, bias=b1_n, nbias=H1, out=ac_next, wscale=SC_WN)],
-                                       A=y, lda=out_f, K1=out_f, alpha=alpha, f16=f16, ascale=SC_ACT)
-            rc = _lib.lib().mpg_edge_fwd_fn(C.byref(e), C.byref(cs), None if cs2 is None else C.byref(cs2), _stream())
-            if rc != _lib.MPG_FN_NA:
-                check(rc, "mpg_edge_fwd_fn")
-                agg = aggp[0] if need_grad else None   # (SC > 1: the last workgroup to arrive left the chunks' total in slab 0)
-                if cs2 is not None:
-                    handoff.ac_out = (ac_next, pk_n, y.data_ptr(), pk_n._key)
-        if rc == _lib.MPG_FN_NA:
-            e.agg = _p(aggp)
-            check(_lib.lib().mpg_edge_fwd(C.byref(e), _stream()), "mpg_edge_fwd")
-            agg = aggp[0]
-            for q in range(1, SC):   # (in chunk order, slab by slab: the order the epilogue form's last arriver takes -- the two routes
-                agg = agg + aggp[q]  #  then agree bit for bit; torch.sum over the chunk axis adds in another order)
-            chain(V, fn_layers, A=agg, lda=H3, K1=H3, **fn_kw)
-        ctx.packed = pk
-        # (x the very output of the layer below: this layer's backward may run that layer's input-gradient chain in its own launch)
-        ctx.prev_node = below.node if (below is not None and need_grad and x.grad_fn is below.node) else None
-        ctx.pre = None   # filled by the backward of the layer ABOVE when it has run this layer's input-gradient chain already
-        if handoff is not None and need_grad:
-            handoff.node = ctx
-
+        ac = _node_terms(handoff.below if handoff is not None else None, pk, x2, b1, cfg)
+        es, wq = _edge_scalar_terms(es, W1, cfg)
+        order = jet_order(m1.view(B, N)) if plan.lpt else None
+        # (what only a backward reads -- the sign words of the third edge layer, the parked E2, the hidden activations, and agg for
+        # fn.net.0's weight gradient -- is not written without one)
+        sign3 = torch.empty((B * plan.RB * N * 192,), device=dev, dtype=torch.int32) if need_grad else None
+        stE2 = torch.empty((B * plan.RB * N, H2, 32), device=dev, dtype=torch.float16) if need_grad else None
+        h1 = torch.empty((V, V1.shape[0]), device=dev, dtype=torch.float32) if need_grad else None
+        h2 = torch.empty((V, V2.shape[0]), device=dev, dtype=torch.float32) if need_grad else None
+        sv = MPLayerSaved(x2, m1, ac, None, h1, h2, W1, b2, b3, W2, W3, V1, V2, V3, sign3, nbr, stE2, es, wq, xf2, order)   # (agg: below)
+        call, y = MPCall(sv, cfg, pk, seed_t), torch.empty((V, out_f), device=dev, dtype=torch.float32)
+        aggp = torch.empty((plan.SC, V, H3), device=dev, dtype=torch.float32)
+        fn_layers = _fn_fwd_layers(call, (c1, c2, c3), y)
+        agg = _fwd_epilogue(call, plan, aggp, fn_layers, handoff) if plan.epilogue else _NOT_COVERED
+        if agg is _NOT_COVERED:
+            agg = _fwd_two_launches(call, aggp, fn_layers)
+        _leave_offers(ctx, handoff, x, need_grad)
         if need_grad and dev_state(dev).sign_tap is not None:
             dev_state(dev).sign_tap.append(dict(B=B, N=N, ac=ac, stE2=stE2, sign3=sign3, h1=h1, h2=h2))
-        ctx.save_for_backward(*MPLayerSaved(x2, m1, ac, agg, h1, h2, W1, b2, b3, W2, W3, V1, V2, V3, sign3, nbr, stE2, es, wq, xf2, order))
-        ctx.cfg = MPLayerCfg(B, N, F, agg_scale, alpha, thr, dscale, tag, SC, f16, nq)
-        return y.reshape(B, N, V3.shape[0])
+        ctx.packed, ctx.cfg = pk, cfg
+        ctx.save_for_backward(*sv._replace(agg=agg))
+        return y.reshape(B, N, out_f)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        x2, m1, ac, agg, h1, h2, W1, b2, b3, W2, W3, V1, V2, V3, sign3, nbr, stE2, es, wq, xf2, order = mplayer_saved(ctx)
-        pk = ctx.packed
-        B, N, F, agg_scale, alpha, thr, dscale, tag, SC, f16, nq = ctx.cfg
-        nbr_p = None if nbr is None else C.c_void_p(nbr.data_ptr())
-        V = B * N
-        dev = x2.device
-        seed_t = seed_tensor(dev)
+        sv, cfg = mplayer_saved(ctx), ctx.cfg
+        (B, N, F), V, dev = cfg[:3], cfg.B * cfg.N, sv.x2.device
+        call = MPCall(sv, cfg, ctx.packed, seed_tensor(dev))
         gy2 = gy.reshape(V, -1).contiguous()
-
-        def gt(H, site, act):
-            return (H, H.stride(0), act, seed_t, tag + site, thr, dscale)
-
         need_x, _, *need_p, _, need_xfn, _ = ctx.needs_input_grad   # (as forward's arguments: x, mask, the twelve parameters, es, xfn, settings)
-        need_w = any(need_p)   # False in the G step: D's weights get no update there
-
-        # ---- node network fn (mpgan/model.py:279) backward: its input-gradient chain -- already run by the layer above as the
-        #      epilogue of its data-gradient launch (ctx.pre, for exactly this upstream gradient), or launched below
-        n1, n2, out_f = V1.shape[0], V2.shape[0], V3.shape[0]
-        pre, fnb = ctx.pre, None
-        ctx.pre = None
-        if pre is not None and pre["gy_ptr"] == gy2.data_ptr() and tuple(gy2.shape) == (V, out_f):
-            dz3, dz2, dz1, dh0 = pre["dz3"], pre["dz2"], pre["dz1"], pre["dh0"]
-        else:
-            dz3, dz2, dz1, dh0, fnb = _fn_grad_chain(ctx, gy2)
-        dV1 = dV2 = dV3 = dc1 = dc2 = dc3 = None
-        wb = WgradBatch()  # all six weight gradients of the layer go out as one grouped launch (below)
-        # DeviceState.grad_into_param: add into the parameters' .grad buffers directly and return None for them
-        direct = (need_w and dev_state(dev).grad_into_param and pk.plist is not None
-                  and all(q.grad is not None and q.grad.is_contiguous() for q in pk.plist))
-        if need_w:
-            if direct:
-                gW1, gb1, gW2, gb2, gW3, gb3, dV1, dc1, dV2, dc2, dV3, dc3 = (q.grad for q in pk.plist)
-            else:
-                dc3, dc2, dc1 = (torch.empty(t.shape[1], device=dev, dtype=torch.float32) for t in (dz3, dz2, dz1))
-                dV3, dV2, dV1 = torch.empty_like(V3), torch.empty_like(V2), torch.empty_like(V1)
-            wb.add(dz3, h2, out=dV3, bias_out=dc3, accumulate=direct)
-            wb.add(dz2, h1, out=dV2, bias_out=dc2, accumulate=direct)
-            wb.add(dz1, agg, out=dV1, out_col0=0, bias_out=dc1, accumulate=direct)
-            wb.add(dz1, xf2, out=dV1, out_col0=H3, accumulate=direct)
-
-        # ---- edge network backward: data path, then (if wanted) the weight-gradient pass
-        RB = (N + 31) // 32
-        nblk = B * RB * N
-        dap = torch.empty((SC, V, H1), device=dev, dtype=torch.float32)
-        dcp = torch.empty((RB, V, H1), device=dev, dtype=torch.float32)
-        stZ2 = None
-        if need_w:
-            stZ2 = torch.empty((nblk, H2, 32), device=dev, dtype=torch.float16)   # fp16 fragments as the lanes hold them
-            gexp = torch.empty((B * RB,), device=dev, dtype=torch.int32)           # gradient-unit exponent per (jet, receiver block)
-        e = MpgEdgeBwd()
-        e.a, e.c, e.ld_ac, e.mask = _p(ac), _p(ac, H1), 2 * H1, _p(m1)
-        e.dagg, e.ld_dagg = _p(dh0), dh0.stride(0)
-        e.sign3 = C.c_void_p(sign3.data_ptr())
-        e.W2img = pk.ptr("W2")
-        e.W3Timg, e.W2Timg = pk.ptr("W3T"), pk.ptr("W2T")
-        e.b2 = _p(b2)
-        e.da, e.dc = _p(dap), _p(dcp)
-        e.stageE2 = C.c_void_p(stE2.data_ptr())
-        e.stageZ2 = None if stZ2 is None else C.c_void_p(stZ2.data_ptr())
-        e.gexp = None if stZ2 is None else C.c_void_p(gexp.data_ptr())
-        e.B, e.N, e.SC = B, N, SC
-        e.alpha, e.agg_scale, e.nbr = alpha, agg_scale, nbr_p
-        e.seed, e.tag_base, e.thr, e.dscale = _p(seed_t), tag, thr, dscale
-        e.f16 = int(f16)
-        if order is not None:
-            e.order = C.c_void_p(order.data_ptr())
-        des = daq = None
-        if es is not None:
-            des = torch.zeros_like(es)   # (zero-masked senders' rows are not written)
-            daq = torch.empty((SC, V, EDGE_SCALARS, H1), device=dev, dtype=torch.float32)
-            e.es, e.wq, e.des, e.daq = _p(es), _p(wq), _p(des), _p(daq)
-        if fnb is not None:
-            check(_lib.lib().mpg_chain(C.byref(fnb), _stream()), "mpg_chain")
-        # dx = dx(node path) + [da | dc] [W1a ; W1c]: one chained layer over the stacked transposed view -- as the epilogue of
-        # the data-gradient launch where that form covers the call (a whole jet per workgroup), and behind it the node
-        # network's input-gradient chain of the layer BELOW, which produced x (its backward then finds its work done)
-        dx = cdx = None
-        rc = _lib.MPG_FN_NA
+        # node network fn (mpgan/model.py:279): its input-gradient chain -- already run by the layer above as the epilogue of its
+        # data-gradient launch, or launched by _edge_backward
+        fng = _taken_fn_grads(ctx, gy2) or _fn_grad_chain(ctx, gy2)
+        tg = _grad_targets(call, any(need_p))   # (no parameter wants one in the G step: D's weights get no update there)
+        dx = torch.empty((V, F), device=dev, dtype=torch.float32) if need_x else None
+        route, sums, des = _edge_backward(ctx, call, gy2, fng, tg, dx)
         if need_x:
-            dx = torch.empty((V, F), device=dev, dtype=torch.float32)
-            if SC == 1 and RB == 1:
-                cdx = chain_struct(V, [dict(img=pk.ptr("W1ST"), K=2 * H1, N=F, resid=dh0[:, H3:H3 + F], out=dx)],
-                                   A=dap, lda=H1, K1=H1, A2=dcp, lda2=H1, alpha=alpha, f16=False)
-            if cdx is not None and OPTIONS["bwd_epilogue"] and es is None:
-                below = _below_chain(ctx.prev_node, dx, thr, alpha, V)
-                rc = _lib.lib().mpg_edge_bwd_fn(C.byref(e), C.byref(cdx), None if below is None else C.byref(below[4]), _stream())
-                if rc == _lib.MPG_FN_NA and below is not None:   # (the pair is not covered: the layer alone may be)
-                    below = None
-                    rc = _lib.lib().mpg_edge_bwd_fn(C.byref(e), C.byref(cdx), None, _stream())
-                if rc != _lib.MPG_FN_NA:
-                    check(rc, "mpg_edge_bwd_fn")
-                    if below is not None:
-                        ctx.prev_node.pre = dict(gy_ptr=dx.data_ptr(), keep=dx, dz3=below[0], dz2=below[1], dz1=below[2], dh0=below[3])
-        if rc == _lib.MPG_FN_NA:
-            check(_lib.lib().mpg_edge_bwd(C.byref(e), _stream()), "mpg_edge_bwd")
-        if SC == 1 and RB == 1:
-            da, dc, dadc = dap[0], dcp[0], None
-        else:
-            # the chunks' partial da and the receiver blocks' partial dc, added slab by slab into [da | dc] rows: one launch
-            dadc = torch.empty((V, 2 * H1), device=dev, dtype=torch.float32)
-            check(_lib.lib().mpg_slab_sums(_p(dap), SC, V * H1, _p(dcp), RB, V * H1, _p(dadc), V, H1, _stream()), "mpg_slab_sums")
-            da, dc = dadc[:, :H1], dadc[:, H1:]
-        dW1 = db1 = dW2 = db2 = dW3 = db3 = None
-        # The weight-gradient launches below feed nothing before the optimizer: with a side stream set (TrainStep) they are
-        # forked off here, behind the data-gradient kernel that produced their inputs, and this stream goes straight on
-        # to dx and the layers below.  Same launches, same order per parameter: results are bit-identical.
-        st_dev = dev_state(dev)
-        side = st_dev.wgrad_stream if (need_w and direct and es is None) else None
-        main = torch.cuda.current_stream(dev) if side is not None else None
-        if need_w:
-            nwg = dw_workgroups(nblk, N)
-            part = torch.empty((nwg, H3 * H2 + H2 * H1 + H3 + H2), device=dev, dtype=torch.float32)
-            if direct:
-                dW3, dW2, db3, db2 = gW3, gW2, gb3, gb2
-            else:
-                dW3, dW2 = torch.empty_like(W3), torch.empty_like(W2)
-                db3, db2 = torch.empty_like(b3), torch.empty_like(b2)
-            d = MpgEdgeDw()
-            d.a, d.c, d.ld_ac, d.mask = _p(ac), _p(ac, H1), 2 * H1, _p(m1)
-            d.dagg, d.ld_dagg = _p(dh0), dh0.stride(0)
-            d.sign3 = C.c_void_p(sign3.data_ptr())
-            d.stageE2, d.stageZ2 = C.c_void_p(stE2.data_ptr()), C.c_void_p(stZ2.data_ptr())
-            d.gexp = C.c_void_p(gexp.data_ptr())
-            d.part, d.nwg = _p(part), nwg
-            d.dW3, d.dW2, d.db3, d.db2, d.accumulate = _p(dW3), _p(dW2), _p(db3), _p(db2), int(direct)
-            d.B, d.N = B, N
-            d.alpha, d.agg_scale, d.nbr = alpha, agg_scale, nbr_p
-            d.seed, d.tag_base, d.thr, d.dscale = _p(seed_t), tag, thr, dscale
-            d.f16 = int(f16)
-            d.defer_reduce = int(OPTIONS["dw_reduce_grouped"])   # (its reduction rides in the grouped reduction launch below)
-            if es is not None:
-                d.es, d.wq = _p(es), _p(wq)
-            # layer 1 (fe.net.0): a = W1[:, :F] x + b1, c = W1[:, F:] x
-            if direct:
-                dW1, db1 = gW1, gb1
-            else:
-                dW1 = torch.empty_like(W1)
-                db1 = torch.empty(H1, device=dev, dtype=torch.float32)
-            wb.add(da, x2, out=dW1, out_col0=0, bias_out=db1, accumulate=direct)
-            wb.add(dc, x2, out=dW1, out_col0=F, accumulate=direct)
-            if side is not None:
-                # everything these launches read or write stays referenced until TrainStep joins the stream
-                st_dev.wgrad_keep.append((ac, m1, dh0, sign3, stE2, stZ2, gexp, part, da, dc, dap, dcp, dadc, x2, xf2, agg, h1, h2,
-                                          dz1, dz2, dz3, gy2, nbr, [j[7] for j in wb.jobs]))
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    check(_lib.lib().mpg_edge_dw(C.byref(d), _stream()), "mpg_edge_dw")
-                    wb.flush(dw=d if d.defer_reduce else None)
-            else:
-                check(_lib.lib().mpg_edge_dw(C.byref(d), _stream()), "mpg_edge_dw")
-                wb.flush(dw=d if d.defer_reduce else None)
-            del stZ2
-            if es is not None:   # the columns of the edge scalars: sum over receivers of daq
-                dWq = daq.sum((0, 1))[:nq].t()
-                if direct:
-                    dW1[:, 2 * F:2 * F + nq] += dWq
-                else:
-                    dW1[:, 2 * F:2 * F + nq] = dWq
-            if direct:  # already in .grad: autograd gets nothing to accumulate
-                dW1 = db1 = dW2 = db2 = dW3 = db3 = dV1 = dc1 = dV2 = dc2 = dV3 = dc3 = None
-        if need_x:
-            if rc == _lib.MPG_FN_NA:   # (not done by the data-gradient launch: its own launch)
-                if dadc is not None:
-                    chain(V, [dict(img=pk.ptr("W1ST"), K=2 * H1, N=F, resid=dh0[:, H3:H3 + F], out=dx)],
-                          A=dadc, lda=2 * H1, K1=2 * H1, alpha=alpha, f16=False)
-                else:
-                    chain(V, [dict(img=pk.ptr("W1ST"), K=2 * H1, N=F, resid=dh0[:, H3:H3 + F], out=dx)],
-                          A=dap, lda=H1, K1=H1, A2=dc, lda2=dc.stride(0), alpha=alpha, f16=False)
+            if route == "plain":   # (not done by the data-gradient launch: its own launch)
+                run_chain(_dx_chain(call, fng.dh0, dx, *((sums.dadc,) if sums.dadc is not None else (sums.da, sums.dc))))
             dx = dx.reshape(B, N, F)
         dxfn = None
-        if need_xfn and dh0.shape[1] > H3 + F:
+        if need_xfn and fng.dh0.shape[1] > H3 + F:
             # the conditioning columns appended to the node network's input (mpgan/model.py:270-276): their gradient is the
             # tail of dh0; the x columns of xfn are the same nodes as x, whose node-path gradient is already in dx above
-            dxfn = torch.cat((torch.zeros((V, F), device=dev, dtype=torch.float32), dh0[:, H3 + F:]), dim=1).reshape(B, N, -1)
-        return dx, None, dW1, db1, dW2, db2, dW3, db3, dV1, dc1, dV2, dc2, dV3, dc3, des, dxfn, None
+            dxfn = torch.cat((torch.zeros((V, F), device=dev, dtype=torch.float32), fng.dh0[:, H3 + F:]), dim=1).reshape(B, N, -1)
+        # (parameter gradients already in .grad: autograd gets nothing to accumulate)
+        return (dx, None, *((None,) * 12 if tg.direct else tg[:12]), des, dxfn, None)
 
 
 def _grad_target(t):

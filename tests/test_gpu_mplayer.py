@@ -880,7 +880,7 @@ class _count_calls:
 
     def __init__(self, ops):
         from mpgan_amd import _lib
-        self._lib, self.names = _lib, []
+        self._lib, self.names, self.args = _lib, [], []   # (args: each call's arguments, beside its name)
         real = _lib.lib()
         outer = self
 
@@ -892,6 +892,7 @@ class _count_calls:
 
                 def f(*a):
                     outer.names.append(k)
+                    outer.args.append(a)
                     return fn(*a)
                 return f
         self.saved = _lib._lib
@@ -1137,3 +1138,104 @@ def test_two_term_layer3_agrees_with_three_terms(B, N, p_drop, alpha):
     if alpha == 1.0:
         assert max(v for k, v in errs.items() if k != "y") < 5e-4, errs
     assert flips <= 1e-3 * n_pre, (flips, n_pre)
+
+
+def _one_layer_run(N, kw=None, force_sc=None, mode="train", direct=False):
+    """One ``MPLayer(32, [96, 160, 192], [256, 256], 32, dropout_p=0.5)`` in training mode on B = 2 jets with some particles masked
+    out: a first call builds the weight images, then ONE forward (+ backward) under a fixed seed and tag counter with every ``mpg_*``
+    entry point recorded (``_count_calls``).  ``mode``: "train", "frozen" (no parameter wants a gradient, x does) or "nograd"; ``direct``: the backward
+    adds into zero-filled ``.grad`` buffers (``DeviceState.grad_into_param``; asserted: ``MpgEdgeDw.accumulate`` says which route ran).
+    Returns (results by name, launches)."""
+    import itertools
+    import os
+    from mpgan_amd import ops
+    from mpgan_amd.mpgan import MPLayer
+    dev = _dev()
+    B, F = 2, 32
+    torch.manual_seed(7)
+    layer = MPLayer(F, [96, 160, 192], [256, 256], 32, dropout_p=0.5, **(kw or {})).to(dev).train()
+    rs = np.random.RandomState(100 + N)
+    x0 = torch.from_numpy(rs.normal(0, 0.5, size=(B, N, F))).float().to(dev)
+    m = np.zeros((B, N, 1))
+    for b in range(B):
+        m[b, rs.permutation(N)[: rs.randint(N // 2, N)], 0] = 1
+    mask = torch.from_numpy(m).float().to(dev)
+    up = torch.from_numpy(rs.normal(size=(B, N, 32))).float().to(dev)
+    if mode == "frozen":
+        for q in layer.parameters():
+            q.requires_grad_(False)
+    st = ops.dev_state(dev)
+    env_sc = os.environ.get("MPG_FORCE_SC")
+    if force_sc:
+        os.environ["MPG_FORCE_SC"] = force_sc
+    try:
+        with torch.no_grad():
+            layer(x0, True, mask)   # (weight images built)
+        st.tags = itertools.count(51)
+        ops.set_seed(4242, dev)
+        for q in layer.parameters():
+            q.grad = torch.zeros_like(q) if direct else None
+        x = x0.clone().requires_grad_(mode != "nograd")
+        st.grad_into_param = direct
+        calls = _count_calls(ops)
+        try:
+            with torch.set_grad_enabled(mode != "nograd"):
+                y = layer(x, True, mask)
+            res = {"y": y.detach().clone()}
+            if mode != "nograd":
+                (y * up).sum().backward()
+                res["dx"] = x.grad.clone()
+                res.update({k: q.grad.clone() for k, q in layer.named_parameters() if q.grad is not None})
+        finally:
+            calls.restore()
+            st.grad_into_param = False
+    finally:
+        if env_sc is None:
+            os.environ.pop("MPG_FORCE_SC", None)
+        else:
+            os.environ["MPG_FORCE_SC"] = env_sc
+    if mode == "train":   # which route the gradients took: added into .grad by the launches themselves, or handed to autograd
+        acc = [a[0]._obj.accumulate for k, a in zip(calls.names, calls.args) if k == "mpg_edge_dw"]
+        assert acc == [int(direct)], acc
+    return res, calls.names
+
+
+@pytest.mark.parametrize("N", [30, 33])
+def test_direct_accumulation_equals_returned_gradients(N):
+    """``grad_into_param``: adding the twelve parameter gradients into zero-filled ``.grad`` buffers gives the bits autograd is
+    handed otherwise (adding into zeros is exact), and the same dx.  N = 30: both epilogues; N = 33: two receiver blocks, slab sums."""
+    (a, _), (b_, _) = _one_layer_run(N, force_sc="1"), _one_layer_run(N, force_sc="1", direct=True)
+    assert len(a) == len(b_) == 2 + 12
+    for k in a:
+        assert torch.equal(a[k], b_[k]), (k, float((a[k] - b_[k]).abs().max()))
+    assert all(bool(torch.isfinite(v).all()) and bool((v != 0).any()) for v in a.values())
+
+
+# Every ``mpg_*`` call of ONE forward + backward of ``_one_layer_run``, in order, as the host path made them before it was split into named
+# steps (recorded on that commit: profiles/mplayer_host_bit_identity.txt)
+_LAYER_CASES = {"N30_sc1": (30, None, "1", "train"), "N33_sc1": (33, None, "1", "train"), "N150": (150, None, None, "train"),
+                "N30_es": (30, dict(pos_diffs=True, delta_r=True), None, "train"),
+                "N30_knn": (30, dict(fully_connected=False, num_knn=10), None, "train"),
+                "N30_frozen": (30, None, None, "frozen"), "N30_nograd": (30, None, None, "nograd")}
+_LAUNCHES = {
+    "N30_sc1": ["mpg_chain", "mpg_edge_fwd_fn", "mpg_chain", "mpg_edge_bwd_fn", "mpg_edge_dw", "mpg_gemm_wgrad_group",
+               "mpg_splitk_reduce_group_dw"],
+    "N33_sc1": ["mpg_chain", "mpg_edge_fwd_fn", "mpg_chain", "mpg_edge_bwd", "mpg_slab_sums", "mpg_edge_dw", "mpg_gemm_wgrad_group",
+               "mpg_splitk_reduce_group_dw", "mpg_chain"],
+    "N150": ["mpg_chain", "mpg_edge_fwd_fn", "mpg_chain", "mpg_edge_bwd", "mpg_slab_sums", "mpg_edge_dw", "mpg_gemm_wgrad_group",
+            "mpg_splitk_reduce_group_dw", "mpg_chain"],
+    "N30_es": ["mpg_chain", "mpg_edge_fwd", "mpg_chain", "mpg_chain", "mpg_edge_bwd", "mpg_slab_sums", "mpg_edge_dw",
+              "mpg_gemm_wgrad_group", "mpg_splitk_reduce_group_dw", "mpg_chain"],
+    "N30_knn": ["mpg_knn_sets", "mpg_chain", "mpg_edge_fwd_fn", "mpg_chain", "mpg_edge_bwd", "mpg_slab_sums", "mpg_edge_dw",
+               "mpg_gemm_wgrad_group", "mpg_splitk_reduce_group_dw", "mpg_chain"],
+    "N30_frozen": ["mpg_chain", "mpg_edge_fwd_fn", "mpg_chain", "mpg_edge_bwd", "mpg_slab_sums", "mpg_chain"],
+    "N30_nograd": ["mpg_chain", "mpg_edge_fwd_fn"],
+}
+
+
+@pytest.mark.parametrize("case", sorted(_LAYER_CASES))
+def test_complete_launch_sequences(case):
+    """No launch added, dropped or reordered on any route: whole-jet forms (N = 30, 33 with one sender chunk), sender chunks with
+    tickets (N = 150), edge scalars, k-NN sets, the G-step form (frozen parameters: no weight-gradient launches) and no_grad."""
+    _, names = _one_layer_run(*_LAYER_CASES[case])
+    assert names == _LAUNCHES[case], names

@@ -343,3 +343,114 @@ def test_cpu_and_gradient_penalty_steps_take_the_module_route(monkeypatch, switc
     monkeypatch.setenv("MPG_SPLIT_GRAPHS", "1")
     assert plain.split_graphs is False
     assert train.TrainStep(ToyG(), ToyD(), 4, TN, latent=LAT, use_graphs=False).split_graphs is True
+
+
+# ---- the fused MPLayer's host path (ops.FusedMPLayerFn): descriptors, plan and dx layer from CPU tensors, nothing launched
+def _mp_call(B, N, F, extras, thr):
+    """An ``ops.MPCall`` over CPU tensors as ``FusedMPLayerFn.forward`` would save them, with its gradient buffers: (call, dh0, bufs)."""
+    import ctypes as C
+    from mpgan_amd import ops
+    H1, H2, H3 = ops.H1, ops.H2, ops.H3
+    V, RB, nq = B * N, (N + 31) // 32, 2 if extras else 0
+    f = lambda *s: torch.zeros(s)
+    W1, W2, W3, V1, V2, V3 = f(H1, 2 * F + nq), f(H2, H1), f(H3, H2), f(64, H3 + F), f(48, 64), f(F, 48)
+    pk = ops.PackedMPLayer((W1, W2, W3, V1, V2, V3), F, F, 2.0 if thr else 1.0, True)
+    sv = ops.MPLayerSaved(
+        x2=f(V, F), m1=f(V), ac=f(V, 2 * H1), agg=f(V, H3), h1=f(V, 64), h2=f(V, 48), W1=W1, b2=f(H2), b3=f(H3), W2=W2, W3=W3,
+        V1=V1, V2=V2, V3=V3, sign3=torch.zeros(B * RB * N * 192, dtype=torch.int32), nbr=torch.zeros(V, 8, dtype=torch.int32) if extras else None,
+        stE2=torch.zeros(B * RB * N, H2, 32, dtype=torch.float16), es=f(B, N, ops.EDGE_SCALARS, N) if extras else None,
+        wq=f(ops.EDGE_SCALARS, H1) if extras else None, xf2=f(V, F), order=torch.zeros(B, dtype=torch.int32) if extras else None)
+    cfg = ops.MPLayerCfg(B, N, F, 0.125, 0.25, thr, 2.0 if thr else 1.0, 7 if thr else 0, 2 if extras else 1, True, nq)
+    call = ops.MPCall(sv, cfg, pk, torch.zeros(1, dtype=torch.int64))
+    return call, f(V, H3 + F), ops._edge_grad_bufs(call, True)
+
+
+@pytest.mark.parametrize("extras,thr", [(True, 128), (False, 0)])
+def test_mplayer_edge_descriptors_agree(extras, thr):
+    """Every field that two or three of MpgEdgeFwd / MpgEdgeBwd / MpgEdgeDw have carries the same value in each, and the shared
+    fields are what the call holds: with k-NN sets, edge scalars and dropout, and with none of them."""
+    from mpgan_amd import ops, _lib
+    B, N, F = 3, 40, 8
+    call, dh0, bufs = _mp_call(B, N, F, extras, thr)
+    sv, cfg, pk, seed_t = call
+    tg = ops.MPGradTargets(*(torch.zeros(3) for _ in range(12)), direct=True)
+    descs = {"fwd": ops._edge_fwd_desc(call, torch.zeros(cfg.SC, B * N, ops.H3)), "bwd": ops._edge_bwd_desc(call, dh0, bufs),
+             "dw": ops._edge_dw_desc(call, dh0, bufs, tg, torch.zeros(5, 7))}
+    fields = {k: [f[0] for f in type(d)._fields_] for k, d in descs.items()}
+    shared = {n for a in fields for b in fields if a < b for n in set(fields[a]) & set(fields[b])}
+    ptr = lambda t, off=0: None if t is None else t.data_ptr() + 4 * off
+    want = dict(a=ptr(sv.ac), c=ptr(sv.ac, ops.H1), ld_ac=2 * ops.H1, mask=ptr(sv.m1), B=B, N=N, alpha=0.25, agg_scale=0.125,
+                nbr=ptr(sv.nbr), seed=ptr(seed_t), tag_base=cfg.tag, thr=thr, dscale=cfg.dscale, f16=1, es=ptr(sv.es), wq=ptr(sv.wq),
+                dagg=ptr(dh0), ld_dagg=dh0.stride(0), sign3=ptr(sv.sign3), stageE2=ptr(sv.stE2), stageZ2=ptr(bufs.stZ2), gexp=ptr(bufs.gexp))
+    assert set(want) <= shared, sorted(set(want) - shared)
+    assert (want["nbr"] is not None) == extras and (want["es"] is not None) == extras
+    for name in sorted(shared):
+        vals = {k: getattr(d, name) for k, d in descs.items() if name in fields[k]}
+        assert len(vals) >= 2 and len(set(vals.values())) == 1, (name, vals)
+        if name in want:
+            assert next(iter(vals.values())) == want[name], (name, vals, want[name])
+
+
+def test_mplayer_edge_plan(monkeypatch):
+    from mpgan_amd import ops
+    monkeypatch.delenv("MPG_FORCE_SC", raising=False)
+    on = dict(ops.OPTIONS, fn_epilogue=True, fn_chunks=True, lpt_order=True)
+    p = ops.edge_plan(256, 30, need_grad=True, options=on)
+    assert (p.SC, p.RB, p.epilogue, p.tickets, p.lpt, p.write_agg) == (1, 1, True, False, False, True)
+    assert not ops.edge_plan(256, 30, mask=True, options=on).lpt      # (every CU has one workgroup: nothing to order)
+    assert ops.edge_plan(512, 30, mask=True, options=on).lpt and not ops.edge_plan(512, 30, mask=False, options=on).lpt
+    p = ops.edge_plan(16, 150, need_grad=True, options=on)
+    assert (p.SC, p.RB, p.epilogue, p.tickets, p.write_agg) == (3, 5, True, True, True)
+    assert ops.edge_plan(16, 150, need_grad=False, options=on).write_agg   # (the chunks' partial sums travel through agg)
+    p = ops.edge_plan(2, 30, es=True, options=on)
+    assert not p.epilogue and -(-30 // p.SC) <= ops.MAX_CHUNK_SENDERS_ES
+    assert -(-150 // ops.edge_plan(1, 150, es=True, options=on).SC) <= ops.MAX_CHUNK_SENDERS_ES
+    p = ops.edge_plan(256, 30, need_grad=False, options=on)
+    assert p.SC == 1 and p.epilogue and not p.write_agg
+    assert not ops.edge_plan(256, 30, options=dict(on, fn_epilogue=False)).epilogue
+    assert not ops.edge_plan(16, 150, options=dict(on, fn_chunks=False)).epilogue
+    assert ops.edge_plan(256, 30, options=dict(on, fn_chunks=False)).epilogue
+    saved = ops.OPTIONS["fn_epilogue"]
+    try:   # (without ``options``: the module's switches as they are at the call)
+        ops.OPTIONS["fn_epilogue"] = False
+        assert not ops.edge_plan(256, 30).epilogue
+        ops.OPTIONS["fn_epilogue"] = True
+        assert ops.edge_plan(256, 30).epilogue
+    finally:
+        ops.OPTIONS["fn_epilogue"] = saved
+    monkeypatch.setenv("MPG_FORCE_SC", "1")
+    p = ops.edge_plan(16, 150, options=on)
+    assert p.SC == 1 and not p.tickets
+    monkeypatch.setenv("MPG_FORCE_SC", "2")
+    assert ops.edge_plan(256, 30, options=on).SC == 2
+
+
+def test_mplayer_park_limit_raises_before_anything_runs():
+    """32-bit offsets into the parked fragments: with a backward pending N = 30 takes 0x7fffffff // (1 * 30 * 10240) = 6990 jets."""
+    from mpgan_amd import ops
+    assert 0x7fffffff // (1 * 30 * ops.PARK_BYTES_PER_BLOCK) == 6990
+    ops.edge_plan(6990, 30, need_grad=True)
+    with pytest.raises(RuntimeError, match="at most 6990 jets"):
+        ops.edge_plan(6991, 30, need_grad=True)
+    ops.edge_plan(6991, 30, need_grad=False)
+
+
+def test_mplayer_dx_layer_is_one_definition():
+    """The dx chain's three feeds describe the same layer; only where its [da | dc] rows come from differs."""
+    from mpgan_amd import ops
+    H1, H3 = ops.H1, ops.H3
+    B, N, F = 3, 40, 8
+    call, dh0, bufs = _mp_call(B, N, F, False, 0)
+    V = B * N
+    dx, dadc = torch.zeros(V, F), torch.zeros(V, 2 * H1)
+    da, dc = bufs.dap[0], bufs.dcp[0]
+    chains = [ops._dx_chain(call, dh0, dx, bufs.dap, bufs.dcp), ops._dx_chain(call, dh0, dx, dadc), ops._dx_chain(call, dh0, dx, da, dc)]
+    feeds = [(bufs.dap.data_ptr(), H1, H1, bufs.dcp.data_ptr(), H1), (dadc.data_ptr(), 2 * H1, 2 * H1, None, 0),
+             (bufs.dap.data_ptr(), H1, H1, dc.data_ptr(), dc.stride(0))]
+    for c, feed in zip(chains, feeds):
+        assert (c.A, c.lda, c.K1, c.A2, c.lda2) == feed
+        L = c.L[0]
+        assert (c.M, c.nlayers, c.f16, c.alpha, c.seed) == (V, 1, 0, 0.25, None)
+        assert (L.Wimg, L.K, L.N) == (call.pk.img["W1ST"].data_ptr(), 2 * H1, F)
+        assert (L.resid, L.ldr, L.out, L.ldo) == (dh0.data_ptr() + 4 * H3, dh0.stride(0), dx.data_ptr(), F)
+        assert (L.bias, L.act, L.gateH, L.drop_thr) == (None, 0, None, 0)

@@ -16,7 +16,7 @@ orig_sc = ops._sender_chunks
 for name, skipbits, sc in (("base", 1, None), ("noskip", 0, None), ("nofill", 3, None), ("w2lo_from_lds", 5, None),
                            ("nofill+w2lolds", 7, None), ("SC=1", 1, 1), ("SC=4", 1, 4), ("SC=1 noskip", 0, 1)):
     ops.OPTIONS["skip_masked"] = skipbits
-    ops._sender_chunks = (lambda B, N, sc=sc: sc) if sc else orig_sc
+    ops._sender_chunks = (lambda B, N, max_chunk=None, sc=sc: sc) if sc else orig_sc
     with torch.no_grad():
         for _ in range(3):
             layer(x, True, mask)
