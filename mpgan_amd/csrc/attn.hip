@@ -338,9 +338,7 @@ extern "C" int mpg_attn_fwd(const MpgAttn* p, void* stream) {
     }
     const size_t lds = (size_t)2 * p->S * p->d * 4;
     if (lds > 160 * 1024) return -2;
-    MPG_ENSURE_LDS(attn_fwd_kernel, lds);
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(p->B * p->H), dim3(64), lds, (hipStream_t)stream, *p);
-    return (int)hipGetLastError();
+    return mpg_go<attn_fwd_kernel>(dim3(p->B * p->H), dim3(64), (int)lds, (hipStream_t)stream, *p);
 }
 
 extern "C" int mpg_attn_bwd(const MpgAttn* p, void* stream) {
@@ -355,23 +353,13 @@ extern "C" int mpg_attn_bwd(const MpgAttn* p, void* stream) {
         const int ppw = two ? 8 : 4;
         const dim3 grid((p->B * p->H + ppw - 1) / ppw), block(256);
         const size_t lds = need(two);
-        hipStream_t st = (hipStream_t)stream;
-#define MPG_ATTN_BWD(DV, TW)                                                                                              \
-    do {                                                                                                                  \
-        MPG_ENSURE_LDS((attn_bwd_fast<DV, TW>), lds);                                                                     \
-        hipLaunchKernelGGL((attn_bwd_fast<DV, TW>), grid, block, lds, st, *p);                                            \
-    } while (0)
-#define MPG_ATTN_BWD2(DV) do { if (two) MPG_ATTN_BWD(DV, true); else MPG_ATTN_BWD(DV, false); } while (0)
-        if (p->d == 8) MPG_ATTN_BWD2(8);
-        else if (p->d == 16) MPG_ATTN_BWD2(16);
-        else MPG_ATTN_BWD2(32);
-#undef MPG_ATTN_BWD2
-#undef MPG_ATTN_BWD
-        return (int)hipGetLastError();
+        using Go = int (*)(dim3, dim3, int, hipStream_t, const MpgAttn&);
+        static constexpr Go GO[3][2] = {{mpg_go<attn_bwd_fast<8, false>, MpgAttn>, mpg_go<attn_bwd_fast<8, true>, MpgAttn>},   // [d: 8, 16, 32][two]
+                                        {mpg_go<attn_bwd_fast<16, false>, MpgAttn>, mpg_go<attn_bwd_fast<16, true>, MpgAttn>},
+                                        {mpg_go<attn_bwd_fast<32, false>, MpgAttn>, mpg_go<attn_bwd_fast<32, true>, MpgAttn>}};
+        return GO[p->d == 8 ? 0 : (p->d == 16 ? 1 : 2)][two](grid, block, (int)lds, (hipStream_t)stream, *p);
     }
     const size_t lds = ((size_t)2 * p->S * p->d + 2 * p->L * p->d + (size_t)p->L * p->S) * 4;
     if (lds > 160 * 1024) return -2;
-    MPG_ENSURE_LDS(attn_bwd_kernel, lds);
-    hipLaunchKernelGGL(attn_bwd_kernel, dim3(p->B * p->H), dim3(64), lds, (hipStream_t)stream, *p);
-    return (int)hipGetLastError();
+    return mpg_go<attn_bwd_kernel>(dim3(p->B * p->H), dim3(64), (int)lds, (hipStream_t)stream, *p);
 }

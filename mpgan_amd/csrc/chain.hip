@@ -407,21 +407,17 @@ extern "C" int mpg_chain(const MpgChain* p, void* stream) {
     // k-steps per layer; the shapes MPLayer uses have straight-line instantiations, anything else the run-time loops
     int ks[3] = {0, 0, 0};
     for (int l = 0; l < p->nlayers; ++l) ks[l] = 2 * ((p->L[l].K + 31) / 32);
-#define MPG_CHAIN_LAUNCH(F16V, A, B, C)                                                               \
-    do {                                                                                              \
-        MPG_ENSURE_LDS((chain_kernel<F16V, A, B, C>), CH_LDS_BYTES);                                  \
-        hipLaunchKernelGGL((chain_kernel<F16V, A, B, C>), grid, block, CH_LDS_BYTES, st, *p);         \
-        return (int)hipGetLastError();                                                                \
-    } while (0)
-    if (p->f16) {
-        if (ks[0] == 14 && ks[1] == 16 && ks[2] == 16) MPG_CHAIN_LAUNCH(true, 14, 16, 16);   // fn forward
-        if (ks[0] == 2 && p->nlayers == 1) MPG_CHAIN_LAUNCH(true, 2, 0, 0);                   // a | c projection
-        MPG_CHAIN_LAUNCH(true, 0, 0, 0);
-    }
-    if (ks[0] == 2 && ks[1] == 16 && ks[2] == 16) MPG_CHAIN_LAUNCH(false, 2, 16, 16);         // fn input-gradient chain
-    if (ks[0] == 12 && p->nlayers == 1) MPG_CHAIN_LAUNCH(false, 12, 0, 0);                     // dx from da | dc
-    MPG_CHAIN_LAUNCH(false, 0, 0, 0);
-#undef MPG_CHAIN_LAUNCH
+    using Go = int (*)(dim3, dim3, int, hipStream_t, const MpgChain&);
+    static constexpr Go GO[2][3] = {   // [f16][shape]
+        {mpg_go<chain_kernel<false, 2, 16, 16>, MpgChain>,   // fn input-gradient chain
+         mpg_go<chain_kernel<false, 12, 0, 0>, MpgChain>,    // dx from da | dc
+         mpg_go<chain_kernel<false, 0, 0, 0>, MpgChain>},
+        {mpg_go<chain_kernel<true, 14, 16, 16>, MpgChain>,   // fn forward
+         mpg_go<chain_kernel<true, 2, 0, 0>, MpgChain>,      // a | c projection
+         mpg_go<chain_kernel<true, 0, 0, 0>, MpgChain>}};
+    const bool f16 = p->f16 != 0;
+    const int shape = (ks[0] == (f16 ? 14 : 2) && ks[1] == 16 && ks[2] == 16) ? 0 : ((ks[0] == (f16 ? 2 : 12) && p->nlayers == 1) ? 1 : 2);
+    return GO[f16][shape](grid, block, CH_LDS_BYTES, st, *p);
 }
 
 extern "C" int mpg_pack_many(const MpgPackJob* jobs, int njobs, void* stream) {

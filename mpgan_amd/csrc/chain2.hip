@@ -17,6 +17,7 @@
 // and the entry point's shape table; edge_fwd1_impl.h / edge_bwd1_impl.h run the same body as the epilogues of the fused edge kernels.
 #include "chain2_impl.h"
 #include "chain_int.h"
+#include "edge_units.h"   // rows_vec
 #include <stdlib.h>
 #include <stdio.h>
 
@@ -55,9 +56,7 @@ __global__ __launch_bounds__(256, 1) void chain2_kernel(const MpgChain p) {
 
 template <bool F16, int A, int B, int C, int DROP, int GATES, int RESID, bool SL>
 int c2_launch(const MpgChain* p, hipStream_t st) {
-    MPG_ENSURE_LDS((chain2_kernel<F16, A, B, C, DROP, GATES, RESID, SL>), C2_LDS);
-    hipLaunchKernelGGL((chain2_kernel<F16, A, B, C, DROP, GATES, RESID, SL>), dim3((p->M + 31) / 32), dim3(256), C2_LDS, st, *p);
-    return (int)hipGetLastError();
+    return mpg_go<chain2_kernel<F16, A, B, C, DROP, GATES, RESID, SL>>(dim3((p->M + 31) / 32), dim3(256), C2_LDS, st, *p);
 }
 template <bool F16, int A, int B, int C, int DROP, int GATES, int RESID>
 int c2_launch_sl(const MpgChain* p, bool sl, hipStream_t st) {
@@ -99,8 +98,7 @@ int mpg_chain2_try(const MpgChain* p, hipStream_t st) {
         const MpgChainLayer& L = p->L[l];
         ks[l] = 2 * ((L.K + 31) / 32);
         if (L.N > 256) C2_NA("N");
-        const bool vec = L.N % 4 == 0 && (L.out == nullptr || (L.ldo % 4 == 0 && ((uintptr_t)L.out & 15) == 0)) &&
-                         (L.resid == nullptr || (L.ldr % 4 == 0 && ((uintptr_t)L.resid & 15) == 0));
+        const bool vec = rows_vec(L) && (L.resid == nullptr || (L.ldr % 4 == 0 && ((uintptr_t)L.resid & 15) == 0));
         if (!vec) {
             if (l + 1 != p->nlayers) C2_NA("row groups of an inner layer");
             sl = true;

@@ -261,3 +261,13 @@ enum { TAG_E0 = 1, TAG_E1 = 2, TAG_E2 = 3, TAG_N0 = 4, TAG_N1 = 5, TAG_N2 = 6, T
         hipError_t _e = (expr);                                    \
         if (_e != hipSuccess) return (int)_e;                      \
     } while (0)
+
+// THE launch of a kernel that takes more dynamic LDS than the 64 KiB default: the grant (once per device -- the macro's
+// counters are statics of this instantiation, one set per kernel K), the launch, the launch's status.  Every such kernel goes
+// through here, named once in its unit's table of mpg_go instantiations; MPG_ENSURE_LDS has no other user.
+template <auto K, typename... A>
+int mpg_go(dim3 grid, dim3 block, int lds_bytes, hipStream_t st, const A&... args) {
+    MPG_ENSURE_LDS(K, lds_bytes);
+    hipLaunchKernelGGL(K, grid, block, lds_bytes, st, args...);
+    return (int)hipGetLastError();
+}

@@ -4,12 +4,6 @@
 // (edge_fwd2_impl.h): edge_fwd_q{0,1,2}.hip.  And mpg_pack_weights (the weight images every fused kernel takes).
 #include "edge_fwd1_impl.h"
 
-int mpg_edge_fwd_d1(const MpgEdgeFwd* p, hipStream_t st);   // edge_fwd_d1.hip: byte-threshold dropout
-int mpg_edge_fwd_q0(const MpgEdgeFwd* p, hipStream_t st);   // edge_fwd_q{0,1,2}.hip: with edge scalars, by dropout mode
-int mpg_edge_fwd_q1(const MpgEdgeFwd* p, hipStream_t st);
-int mpg_edge_fwd_q2(const MpgEdgeFwd* p, hipStream_t st);
-int mpg_edge_fwd_d2(const MpgEdgeFwd* p, hipStream_t st);   // edge_fwd_d2.hip: one-bit dropout (p = 1/2)
-
 namespace {
 
 // ------------------------------------------------------------------------------------------
@@ -54,14 +48,17 @@ extern "C" int mpg_pack_weights(const float* W, int ldw, int rows, int cols, int
     return (int)hipGetLastError();
 }
 
+#ifndef MPG_SINGLE_VARIANT
+int mpg_edge_fwd_d0(const MpgEdgeFwd* p, hipStream_t st) { return f1_launch<0>(p, st); }   // (this unit's share of the eight-wave kernel)
+#endif
+
 extern "C" int mpg_edge_fwd(const MpgEdgeFwd* p, void* stream) {
     if (p->B <= 0 || p->N <= 0 || p->SC <= 0) return -1;
     if (!(p->alpha >= 0.f && p->alpha <= 1.f)) return -4;  // lrelu() is max(v, alpha v)
     if (!p->f16 || !f1_terms_ok(p)) return -8;             // fp16 hi/lo images and activations; a product form that is built
     if ((p->N + p->SC - 1) / p->SC > F2_LIST_MAX) return -6;  // senders per chunk (their list lives in LDS)
-    // the parked E2 fragments (10,240 bytes per block) and the sign words are addressed with 32-bit offsets behind a buffer
-    // descriptor whose record count is an int: the same limit as mpg_edge_bwd's, refused here, before anything is written
-    if (p->stageE2 != nullptr && (long long)p->B * ((p->N + 31) / 32) * p->N * 10240LL > 0x7fffffffLL) return -7;
+    // the parked E2 fragments' 32-bit limit (edge_units.h): the same as mpg_edge_bwd's, refused here, before anything is written
+    if (p->stageE2 != nullptr && edge_park_over32(p->B, (p->N + 31) / 32, p->N)) return -7;
     hipStream_t st = (hipStream_t)stream;
 #ifdef MPG_SINGLE_VARIANT  // tools/ubench/fwd_bench.hip: one dropout mode, seconds to compile
 #ifdef MPG_FWD1   // (-DMPG_FWD1: the eight-wave form, edge_fwd1_impl.h; without it the four-wave one, no edge scalars)
@@ -70,11 +67,9 @@ extern "C" int mpg_edge_fwd(const MpgEdgeFwd* p, void* stream) {
     return f2_launch<MPG_SINGLE_VARIANT>(p, st);
 #endif
 #else
-    const int dm = p->thr == 0 ? 0 : (p->thr == 128 ? 2 : 1);
-    if (p->es != nullptr) {
-        if (p->wq == nullptr) return -3;
-        return dm == 0 ? mpg_edge_fwd_q0(p, st) : (dm == 1 ? mpg_edge_fwd_q1(p, st) : mpg_edge_fwd_q2(p, st));
-    }
-    return dm == 0 ? f1_launch<0>(p, st) : (dm == 1 ? mpg_edge_fwd_d1(p, st) : mpg_edge_fwd_d2(p, st));
+    static constexpr EdgeFwdUnit* UNIT[2][3] = {{mpg_edge_fwd_d0, mpg_edge_fwd_d1, mpg_edge_fwd_d2},    // [edge scalars][dropout mode]
+                                                {mpg_edge_fwd_q0, mpg_edge_fwd_q1, mpg_edge_fwd_q2}};
+    if (p->es != nullptr && p->wq == nullptr) return -3;
+    return UNIT[p->es != nullptr][edge_drop_mode(p->thr)](p, st);
 #endif
 }

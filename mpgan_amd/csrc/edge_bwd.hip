@@ -1,14 +1,12 @@
 // mpg_edge_bwd, the data-gradient kernel of the fused edge network: the entry point.  Launches without edge scalars take the
-// eight-wave kernel (edge_bwd1_impl.h): this unit holds its no-dropout variants, edge_bwd2_d1.hip / edge_bwd2_d2.hip those with
+// eight-wave kernel (edge_bwd1_impl.h): this unit holds its no-dropout variants, edge_bwd_d1.hip / edge_bwd_d2.hip those with
 // dropout, so that the three parts of the slow-to-compile template build side by side.  Launches with edge scalars take the
-// four-wave kernel (edge_bwd2_impl.h): edge_bwd2_q{0,1,2}.hip.
+// four-wave kernel (edge_bwd2_impl.h): edge_bwd_q{0,1,2}.hip.
 #include "edge_bwd1_impl.h"
 
-int mpg_edge_bwd_d1(const MpgEdgeBwd* p, hipStream_t st);   // edge_bwd2_d1.hip: byte-threshold dropout
-int mpg_edge_bwd_d2(const MpgEdgeBwd* p, hipStream_t st);   // edge_bwd2_d2.hip: one-bit dropout (p = 1/2)
-int mpg_edge_bwd_q0(const MpgEdgeBwd* p, hipStream_t st);   // edge_bwd2_q{0,1,2}.hip: with edge scalars, by dropout mode
-int mpg_edge_bwd_q1(const MpgEdgeBwd* p, hipStream_t st);
-int mpg_edge_bwd_q2(const MpgEdgeBwd* p, hipStream_t st);
+#ifndef MPG_SINGLE_VARIANT
+int mpg_edge_bwd_d0(const MpgEdgeBwd* p, hipStream_t st) { return b1_launch<0>(p, st); }   // (this unit's share of the eight-wave kernel)
+#endif
 
 extern "C" int mpg_edge_bwd(const MpgEdgeBwd* p, void* stream) {
     if (p->B <= 0 || p->N <= 0 || p->SC <= 0) return -1;
@@ -16,8 +14,7 @@ extern "C" int mpg_edge_bwd(const MpgEdgeBwd* p, void* stream) {
     if (!(p->alpha >= 0.f && p->alpha <= 1.f)) return -4;
     if (!p->f16) return -8;   // both gradient products take fp16 images
     if ((p->N + p->SC - 1) / p->SC > B2_LIST_MAX) return -6;  // senders per chunk (the list of unmasked ones lives in LDS)
-    const int RB = (p->N + 31) / 32;
-    if ((long long)p->B * RB * p->N * (NFR2 * 1024) > 0x7fffffffLL) return -7;  // staging offsets are 32-bit
+    if (edge_park_over32(p->B, (p->N + 31) / 32, p->N)) return -7;  // staging offsets are 32-bit
     if (p->stageZ2 != nullptr && p->gexp == nullptr) return -9;
     hipStream_t st = (hipStream_t)stream;
 #ifdef MPG_SINGLE_VARIANT
@@ -27,12 +24,12 @@ extern "C" int mpg_edge_bwd(const MpgEdgeBwd* p, void* stream) {
     return b2_launch<MPG_SINGLE_VARIANT>(p, st);
 #endif
 #else
-    const int dm = p->thr == 0 ? 0 : (p->thr == 128 ? 2 : 1);
+    static constexpr EdgeBwdUnit* UNIT[2][3] = {{mpg_edge_bwd_d0, mpg_edge_bwd_d1, mpg_edge_bwd_d2},    // [edge scalars][dropout mode]
+                                                {mpg_edge_bwd_q0, mpg_edge_bwd_q1, mpg_edge_bwd_q2}};
     if (p->es != nullptr) {
         if (p->wq == nullptr || p->des == nullptr || p->daq == nullptr) return -3;
         if ((p->N + p->SC - 1) / p->SC > B2_LIST_MAX_Q) return -6;
-        return dm == 0 ? mpg_edge_bwd_q0(p, st) : (dm == 1 ? mpg_edge_bwd_q1(p, st) : mpg_edge_bwd_q2(p, st));
     }
-    return dm == 0 ? b1_launch<0>(p, st) : (dm == 1 ? mpg_edge_bwd_d1(p, st) : mpg_edge_bwd_d2(p, st));
+    return UNIT[p->es != nullptr][edge_drop_mode(p->thr)](p, st);
 #endif
 }

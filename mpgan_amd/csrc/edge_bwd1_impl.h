@@ -496,34 +496,18 @@ __global__ __launch_bounds__(512) void edge_bwd1_fn_kernel(const MpgEdgeBwd p, c
 // the epilogue forms of one dropout mode / NEEDW (edge_bwd_fn_*.hip: one translation unit each); epi = 1, 2, 3 as above
 template <int D, bool NEEDW>
 int b1_launch_fn(const MpgEdgeBwd* p, const MpgChain* cdx, const MpgChain* cnx, int epi, hipStream_t st) {
-    const int RB = (p->N + 31) / 32;
-    dim3 grid(p->B * RB), block(512);
-    MpgChain none = {};   // nlayers = 0: no second chain
-    if (cnx == nullptr) cnx = &none;
-#define MPG_B1FN(E)                                                                                         \
-    do {                                                                                                    \
-        MPG_ENSURE_LDS((edge_bwd1_fn_kernel<D, NEEDW, E>), B2_LDS_BYTES);                                   \
-        hipLaunchKernelGGL((edge_bwd1_fn_kernel<D, NEEDW, E>), grid, block, B2_LDS_BYTES, st, *p, *cdx, *cnx); \
-    } while (0)
-    if (epi == 1) MPG_B1FN(1);
-    else if (epi == 2) MPG_B1FN(2);
-    else MPG_B1FN(3);
-#undef MPG_B1FN
-    return (int)hipGetLastError();
+    using Go = int (*)(dim3, dim3, int, hipStream_t, const MpgEdgeBwd&, const MpgChain&, const MpgChain&);
+    static constexpr Go GO[3] = {mpg_go<edge_bwd1_fn_kernel<D, NEEDW, 1>, MpgEdgeBwd, MpgChain, MpgChain>,   // [epi - 1]
+                                 mpg_go<edge_bwd1_fn_kernel<D, NEEDW, 2>, MpgEdgeBwd, MpgChain, MpgChain>,
+                                 mpg_go<edge_bwd1_fn_kernel<D, NEEDW, 3>, MpgEdgeBwd, MpgChain, MpgChain>};
+    return GO[epi - 1](dim3(p->B * ((p->N + 31) / 32)), dim3(512), B2_LDS_BYTES, st, *p, *cdx, chain_or_none(cnx));
 }
 
 template <int D>
 int b1_launch(const MpgEdgeBwd* p, hipStream_t st) {
-    const int RB = (p->N + 31) / 32;
-    dim3 grid(p->B * RB * p->SC), block(512);
-    if (p->stageZ2 != nullptr) {
-        MPG_ENSURE_LDS((edge_bwd1_kernel<D, true>), B2_LDS_BYTES);
-        hipLaunchKernelGGL((edge_bwd1_kernel<D, true>), grid, block, B2_LDS_BYTES, st, *p);
-    } else {
-        MPG_ENSURE_LDS((edge_bwd1_kernel<D, false>), B2_LDS_BYTES);
-        hipLaunchKernelGGL((edge_bwd1_kernel<D, false>), grid, block, B2_LDS_BYTES, st, *p);
-    }
-    return (int)hipGetLastError();
+    using Go = int (*)(dim3, dim3, int, hipStream_t, const MpgEdgeBwd&);
+    static constexpr Go GO[2] = {mpg_go<edge_bwd1_kernel<D, false>, MpgEdgeBwd>, mpg_go<edge_bwd1_kernel<D, true>, MpgEdgeBwd>};   // [stageZ2 != nullptr]
+    return GO[p->stageZ2 != nullptr](dim3(p->B * ((p->N + 31) / 32) * p->SC), dim3(512), B2_LDS_BYTES, st, *p);
 }
 
 }  // namespace

@@ -1,7 +1,7 @@
 // Backward of the fused edge network, data-gradient path (see edge_fwd2_impl.h for the forward and the chain layout).
 //
 // This header holds the FOUR-WAVE kernel, edge_bwd_kernel -- what mpg_edge_bwd launches when the edges carry scalars
-// (NQ = MPG_EDGE_SCALARS: edge_bwd2_q{0,1,2}.hip); it has no epilogue -- and the LDS plan and helpers it shares with the
+// (NQ = MPG_EDGE_SCALARS: edge_bwd_q{0,1,2}.hip); it has no epilogue -- and the LDS plan and helpers it shares with the
 // eight-wave kernels of edge_bwd1_impl.h, which take every other launch (mpg_edge_bwd without edge scalars, mpg_edge_bwd_fn).
 //
 //   dZ3 = m_j * dagg_i * keep3 * phi'(Z3)      phi'(Z3) from the forward's saved sign words
@@ -632,21 +632,13 @@ MPG_DEV void edge_bwd_body(const MpgEdgeBwd& p) {
 template <int DROP, bool NEEDW, int NQ>
 __global__ __launch_bounds__(256, 1) void edge_bwd_kernel(const MpgEdgeBwd p) { edge_bwd_body<DROP, NEEDW, NQ>(p); }
 
-// the NEEDW pair of one dropout mode and edge-scalar count (the library's are edge_bwd2_q{0,1,2}.hip, one translation unit per
+// the NEEDW pair of one dropout mode and edge-scalar count (the library's are edge_bwd_q{0,1,2}.hip, one translation unit per
 // dropout mode: this template is slow to compile; NQ = 0 is built by tools/ubench/bwd2_bench.hip only)
 template <int D, int NQ = 0>
 int b2_launch(const MpgEdgeBwd* p, hipStream_t st) {
-    const int RB = (p->N + 31) / 32;
-    dim3 grid(p->B * RB * p->SC), block(256);
-    const bool needw = p->stageZ2 != nullptr;
-    if (needw) {
-        MPG_ENSURE_LDS((edge_bwd_kernel<D, true, NQ>), B2_LDS_BYTES);
-        hipLaunchKernelGGL((edge_bwd_kernel<D, true, NQ>), grid, block, B2_LDS_BYTES, st, *p);
-    } else {
-        MPG_ENSURE_LDS((edge_bwd_kernel<D, false, NQ>), B2_LDS_BYTES);
-        hipLaunchKernelGGL((edge_bwd_kernel<D, false, NQ>), grid, block, B2_LDS_BYTES, st, *p);
-    }
-    return (int)hipGetLastError();
+    using Go = int (*)(dim3, dim3, int, hipStream_t, const MpgEdgeBwd&);
+    static constexpr Go GO[2] = {mpg_go<edge_bwd_kernel<D, false, NQ>, MpgEdgeBwd>, mpg_go<edge_bwd_kernel<D, true, NQ>, MpgEdgeBwd>};   // [stageZ2 != nullptr]
+    return GO[p->stageZ2 != nullptr](dim3(p->B * ((p->N + 31) / 32) * p->SC), dim3(256), B2_LDS_BYTES, st, *p);
 }
 
 }  // namespace

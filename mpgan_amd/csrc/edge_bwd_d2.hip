@@ -1,0 +1,4 @@
+// The one-bit-dropout (p = 1/2) variants of the eight-wave data-gradient kernel (edge_bwd1_impl.h; see edge_bwd.hip).
+#include "edge_bwd1_impl.h"
+
+int mpg_edge_bwd_d2(const MpgEdgeBwd* p, hipStream_t st) { return b1_launch<2>(p, st); }

@@ -4,25 +4,14 @@
 // the layer below, in one launch.  The kernel is edge_bwd1_impl.h's edge_bwd1_fn_kernel (eight waves; EPI variants,
 // chain2_impl.h's schedule for the chains); its instantiations compile side by side in edge_bwd_fn_d{0,1,2}w{0,1}.hip.  This unit holds the entry point: argument
 // checks and the variant table.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/mpgan_amd.h"
-
-#define MPG_FN_DECL(D, W) int mpg_edge_bwd_fn_d##D##w##W(const MpgEdgeBwd* p, const MpgChain* cdx, const MpgChain* cnx, int epi, hipStream_t st)
-MPG_FN_DECL(0, 0); MPG_FN_DECL(0, 1); MPG_FN_DECL(1, 0); MPG_FN_DECL(1, 1); MPG_FN_DECL(2, 0); MPG_FN_DECL(2, 1);
-#undef MPG_FN_DECL
-
-namespace {
-// rows of whole 16-byte groups (the chains' vector stores)?
-bool vec_rows(const MpgChainLayer& L) { return L.N % 4 == 0 && (L.out == nullptr || (L.ldo % 4 == 0 && ((uintptr_t)L.out & 15) == 0)); }
-}  // namespace
+#include "edge_units.h"
 
 extern "C" int mpg_edge_bwd_fn(const MpgEdgeBwd* p, const MpgChain* cdx, const MpgChain* cnx, void* stream) {
     if (p->B <= 0 || p->N <= 0 || cdx == nullptr) return -1;
     if (p->sign3 == nullptr || p->stageE2 == nullptr) return -3;
     if (!(p->alpha >= 0.f && p->alpha <= 1.f)) return -4;
     if (!p->f16) return -8;
-    if ((long long)p->B * p->N * 10240LL > 0x7fffffffLL && p->N <= 32) return -7;
+    if (edge_park_over32(p->B, 1, p->N) && p->N <= 32) return -7;   // (one receiver block; N > 32 is MPG_FN_NA below, and mpg_edge_bwd applies its own limit)
     if (p->stageZ2 != nullptr && p->gexp == nullptr) return -9;
     // what the epilogue form covers -- anything else: MPG_FN_NA, and the caller runs mpg_edge_bwd + mpg_chain (+ mpg_chain)
     if (p->SC != 1 || p->N > 32 || p->es != nullptr) return MPG_FN_NA;       // a whole jet per workgroup: its dc rows are complete
@@ -34,7 +23,7 @@ extern "C" int mpg_edge_bwd_fn(const MpgEdgeBwd* p, const MpgChain* cdx, const M
         if (L.N < 1 || L.N > 32 || L.out == nullptr || L.resid == nullptr || L.gateH != nullptr || L.bias != nullptr || L.act || L.drop_thr != 0) return MPG_FN_NA;
         if ((size_t)M * L.ldo * 4 >= 0x7fffffffull || (size_t)M * L.ldr * 4 >= 0x7fffffffull) return MPG_FN_NA;
     }
-    const bool dx_vec = vec_rows(cdx->L[0]) && cdx->L[0].ldr % 4 == 0 && ((uintptr_t)cdx->L[0].resid & 15) == 0;
+    const bool dx_vec = rows_vec(cdx->L[0]) && cdx->L[0].ldr % 4 == 0 && ((uintptr_t)cdx->L[0].resid & 15) == 0;
     int epi = dx_vec ? 1 : 3;
     if (cnx != nullptr) {   // the layer below: its node network's input-gradient chain on the dx rows
         if (!dx_vec) return MPG_FN_NA;
@@ -52,21 +41,14 @@ extern "C" int mpg_edge_bwd_fn(const MpgEdgeBwd* p, const MpgChain* cdx, const M
             if (L.gateH != nullptr && (L.ldh % 4 || ((uintptr_t)L.gateH & 15) || (size_t)M * L.ldh * 4 >= 0x7fffffffull)) return MPG_FN_NA;
             if (L.gateH != nullptr && L.gate_thr != 0 && L.gate_thr != p->thr) return MPG_FN_NA;
             if (L.out != nullptr && (size_t)M * L.ldo * 4 >= 0x7fffffffull) return MPG_FN_NA;
-            if (!vec_rows(L)) {
+            if (!rows_vec(L)) {
                 if (l != 2) return MPG_FN_NA;
                 epi = 2;
             }
         }
     }
-    hipStream_t st = (hipStream_t)stream;
-    const int dm = p->thr == 0 ? 0 : (p->thr == 128 ? 2 : 1);
-    const bool needw = p->stageZ2 != nullptr;
-    switch (dm * 2 + (needw ? 1 : 0)) {
-    case 0: return mpg_edge_bwd_fn_d0w0(p, cdx, cnx, epi, st);
-    case 1: return mpg_edge_bwd_fn_d0w1(p, cdx, cnx, epi, st);
-    case 2: return mpg_edge_bwd_fn_d1w0(p, cdx, cnx, epi, st);
-    case 3: return mpg_edge_bwd_fn_d1w1(p, cdx, cnx, epi, st);
-    case 4: return mpg_edge_bwd_fn_d2w0(p, cdx, cnx, epi, st);
-    default: return mpg_edge_bwd_fn_d2w1(p, cdx, cnx, epi, st);
-    }
+    static constexpr EdgeBwdFnUnit* UNIT[3][2] = {{mpg_edge_bwd_fn_d0w0, mpg_edge_bwd_fn_d0w1},    // [dropout mode][stageZ2 != nullptr]
+                                                  {mpg_edge_bwd_fn_d1w0, mpg_edge_bwd_fn_d1w1},
+                                                  {mpg_edge_bwd_fn_d2w0, mpg_edge_bwd_fn_d2w1}};
+    return UNIT[edge_drop_mode(p->thr)][p->stageZ2 != nullptr](p, cdx, cnx, epi, (hipStream_t)stream);
 }

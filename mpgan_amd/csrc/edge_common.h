@@ -1,7 +1,7 @@
 // Shared pieces of the fused edge-network kernels (forward: edge.hip, backward: edge_bwd.hip).
 #pragma once
 #include "common.h"
-#include "../../include/mpgan_amd.h"
+#include "edge_units.h"
 
 #ifndef MPG_CHAIN_PF
 #define MPG_CHAIN_PF 1
@@ -138,6 +138,7 @@ MPG_DEV float dither_of(uint32_t blk) {
 constexpr int NF3T = T2 * T3 * 2;  // W3^T image: 5 row tiles x 6 k-tiles x 2 = 60 fragments
 constexpr int NF2T = T1 * T2 * 2;  // W2^T image: 3 x 5 x 2 = 30
 constexpr int NFR2 = T2 * 2;       // B-operand fragments of a 160-feature tensor
+static_assert(NFR2 * 1024 == EDGE_PARK_BYTES, "a parked block is NFR2 fragments: the entry points' 32-bit limit (edge_units.h)");
 
 // LDS plan of the forward kernel: W3 hi | W3 lo | W2 hi  (W2 lo streams from L2)
 constexpr int NF2 = T2 * T1 * 2;  // 30 fragments of 1 KiB

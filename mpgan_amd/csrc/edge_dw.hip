@@ -755,25 +755,16 @@ __global__ __launch_bounds__(256) void edge_dw_reduce_group(const float* __restr
 
 }  // namespace
 
+using DwGo = int (*)(dim3, dim3, int, hipStream_t, const MpgEdgeDw&, const int&);
+
 #ifdef MPG_DW_Q_UNIT   // edge_dw_q.hip: the variants with edge scalars, compiled beside this unit
 int mpg_edge_dw_q(const MpgEdgeDw* p, int R, hipStream_t st) {
-    dim3 grid(p->nwg), block(512);
-    const int dm = p->thr == 0 ? 0 : (p->thr == 128 ? 2 : 1);
-    constexpr int LDSQ = DW_LDS_BYTES + MPG_EDGE_SCALARS * H1 * 4;
-#define MPG_DW_Q(D)                                                                                               \
-    do {                                                                                                          \
-        MPG_ENSURE_LDS((edge_dw_kernel<D, MPG_EDGE_SCALARS>), LDSQ);                                              \
-        hipLaunchKernelGGL((edge_dw_kernel<D, MPG_EDGE_SCALARS>), grid, block, LDSQ, st, *p, R);                  \
-    } while (0)
-    if (dm == 0) MPG_DW_Q(0);
-    else if (dm == 1) MPG_DW_Q(1);
-    else MPG_DW_Q(2);
-#undef MPG_DW_Q
-    return (int)hipGetLastError();
+    static constexpr DwGo GO[3] = {mpg_go<edge_dw_kernel<0, MPG_EDGE_SCALARS>, MpgEdgeDw, int>,   // [dropout mode]
+                                   mpg_go<edge_dw_kernel<1, MPG_EDGE_SCALARS>, MpgEdgeDw, int>,
+                                   mpg_go<edge_dw_kernel<2, MPG_EDGE_SCALARS>, MpgEdgeDw, int>};
+    return GO[edge_drop_mode(p->thr)](dim3(p->nwg), dim3(512), DW_LDS_BYTES + MPG_EDGE_SCALARS * H1 * 4, st, *p, R);
 }
 #else
-int mpg_edge_dw_q(const MpgEdgeDw* p, int R, hipStream_t st);
-
 extern "C" int mpg_edge_dw(const MpgEdgeDw* p, void* stream) {
     if (p->B <= 0 || p->N <= 0 || p->nwg <= 0) return -1;
     if (!p->f16) return -8;
@@ -786,27 +777,18 @@ extern "C" int mpg_edge_dw(const MpgEdgeDw* p, void* stream) {
         if (R * ((nruns + p->nwg - 1) / p->nwg) > 64) return -5;  // a workgroup walks at most 64 blocks (one ballot of valid bits)
     }
     hipStream_t st = (hipStream_t)stream;
-    dim3 grid(p->nwg);
-    const int dm = p->thr == 0 ? 0 : (p->thr == 128 ? 2 : 1);
     // six consumers + six builders, three waves per SIMD.  (The four + four form -- edge_dw_kernel, what the edge-scalar variant
     // still is -- lost its A/B without edge scalars by 1.5-3 % per launch.)
-#define MPG_DW_ONE(D)                                                                                             \
-    do {                                                                                                          \
-        MPG_ENSURE_LDS((edge_dw12_kernel<D>), DW_LDS_BYTES);                                                      \
-        hipLaunchKernelGGL((edge_dw12_kernel<D>), grid, dim3(768), DW_LDS_BYTES, st, *p, R);                      \
-    } while (0)
 #ifdef MPG_SINGLE_VARIANT  // tools/ubench/dw_bench.hip: one instantiation
-    MPG_DW_ONE(MPG_SINGLE_VARIANT);
+    const int rc = mpg_go<edge_dw12_kernel<MPG_SINGLE_VARIANT>>(dim3(p->nwg), dim3(768), DW_LDS_BYTES, st, *p, R);
 #else
-    if (p->es != nullptr) {
-        if (p->wq == nullptr) return -3;
-        if (int e = mpg_edge_dw_q(p, R, st)) return e;
-    } else if (dm == 0) MPG_DW_ONE(0);
-    else if (dm == 1) MPG_DW_ONE(1);
-    else MPG_DW_ONE(2);
+    static constexpr DwGo DW12[3] = {mpg_go<edge_dw12_kernel<0>, MpgEdgeDw, int>, mpg_go<edge_dw12_kernel<1>, MpgEdgeDw, int>,
+                                     mpg_go<edge_dw12_kernel<2>, MpgEdgeDw, int>};   // [dropout mode]
+    if (p->es != nullptr && p->wq == nullptr) return -3;
+    const int rc = p->es != nullptr ? mpg_edge_dw_q(p, R, st)
+                                    : DW12[edge_drop_mode(p->thr)](dim3(p->nwg), dim3(768), DW_LDS_BYTES, st, *p, R);
 #endif
-#undef MPG_DW_ONE
-    if (p->defer_reduce) return (int)hipGetLastError();   // (mpg_splitk_reduce_group_dw adds the partials up)
+    if (rc != 0 || p->defer_reduce) return rc;   // (deferred: mpg_splitk_reduce_group_dw adds the partials up)
     constexpr int PER = H3 * H2 + H2 * H1 + H3 + H2;
     // (the parked E2 carries the forward's operand scale SC_E2; db3 / db2 only the gradient unit)
     hipLaunchKernelGGL(edge_dw_reduce, dim3((PER + 31) / 32), dim3(256), 0, st, p->part, p->nwg, p->dscale / SC_E2, p->dscale, p->accumulate,

@@ -626,47 +626,37 @@ __global__ __launch_bounds__(512) void edge_fwd1_fn_kernel(const MpgEdgeFwd p, c
 // (LT = 1 above).  Anything else is not built into the library: the entry points answer -8.
 inline bool f1_terms_ok(const MpgEdgeFwd* p) { return p->two_term == 0 || p->two_term == 1; }
 
+using F1Go = int (*)(dim3, dim3, int, hipStream_t, const MpgEdgeFwd&);
+using F1FnGo = int (*)(dim3, dim3, int, hipStream_t, const MpgEdgeFwd&, const MpgChain&, const MpgChain&);
+inline dim3 f1_grid(const MpgEdgeFwd* p) { return dim3(p->B * ((p->N + 31) / 32) * p->SC); }
+
 template <int D, int NQ, int LT>
 int f1_launch_lt(const MpgEdgeFwd* p, hipStream_t st) {
-    const int RB = (p->N + 31) / 32;
-    dim3 grid(p->B * RB * p->SC), block(512);
-    if (p->sign3 != nullptr) {
-        MPG_ENSURE_LDS((edge_fwd1_kernel<D, true, NQ, LT>), F1_LDS_BYTES);
-        hipLaunchKernelGGL((edge_fwd1_kernel<D, true, NQ, LT>), grid, block, F1_LDS_BYTES, st, *p);
-    } else {
-        MPG_ENSURE_LDS((edge_fwd1_kernel<D, false, NQ, LT>), F1_LDS_BYTES);
-        hipLaunchKernelGGL((edge_fwd1_kernel<D, false, NQ, LT>), grid, block, F1_LDS_BYTES, st, *p);
-    }
-    return (int)hipGetLastError();
+    static constexpr F1Go GO[2] = {mpg_go<edge_fwd1_kernel<D, false, NQ, LT>, MpgEdgeFwd>,   // [sign3 != nullptr]
+                                   mpg_go<edge_fwd1_kernel<D, true, NQ, LT>, MpgEdgeFwd>};
+    return GO[p->sign3 != nullptr](f1_grid(p), dim3(512), F1_LDS_BYTES, st, *p);
 }
 template <int D, int NQ = 0>
 int f1_launch(const MpgEdgeFwd* p, hipStream_t st) {
 #ifdef MPG_SINGLE_VARIANT   // (tools/ubench/fwd_bench.hip: one form, -DMPG_F1_LT=n)
     return f1_launch_lt<D, NQ, MPG_F1_LT>(p, st);
 #else
-    return p->two_term == 1 ? f1_launch_lt<D, NQ, 1>(p, st) : f1_launch_lt<D, NQ, 0>(p, st);
+    static constexpr EdgeFwdUnit* LT[2] = {f1_launch_lt<D, NQ, 0>, f1_launch_lt<D, NQ, 1>};   // [two_term]
+    return LT[p->two_term == 1](p, st);
 #endif
 }
 
 // the fused forward + node network of one dropout mode / SIGN (edge_fwd_fn_*.hip: one translation unit each)
 template <int D, bool SIGN, int LT>
 int f1_launch_fn_lt(const MpgEdgeFwd* p, const MpgChain* c, const MpgChain* c2, bool sl, hipStream_t st) {
-    const int RB = (p->N + 31) / 32;
-    dim3 grid(p->B * RB * p->SC), block(512);
-    MpgChain none = {};   // nlayers = 0: no second chain
-    if (c2 == nullptr) c2 = &none;
-    if (sl) {
-        MPG_ENSURE_LDS((edge_fwd1_fn_kernel<D, SIGN, true, LT>), F1_LDS_BYTES);
-        hipLaunchKernelGGL((edge_fwd1_fn_kernel<D, SIGN, true, LT>), grid, block, F1_LDS_BYTES, st, *p, *c, *c2);
-    } else {
-        MPG_ENSURE_LDS((edge_fwd1_fn_kernel<D, SIGN, false, LT>), F1_LDS_BYTES);
-        hipLaunchKernelGGL((edge_fwd1_fn_kernel<D, SIGN, false, LT>), grid, block, F1_LDS_BYTES, st, *p, *c, *c2);
-    }
-    return (int)hipGetLastError();
+    static constexpr F1FnGo GO[2] = {mpg_go<edge_fwd1_fn_kernel<D, SIGN, false, LT>, MpgEdgeFwd, MpgChain, MpgChain>,   // [sl]
+                                     mpg_go<edge_fwd1_fn_kernel<D, SIGN, true, LT>, MpgEdgeFwd, MpgChain, MpgChain>};
+    return GO[sl](f1_grid(p), dim3(512), F1_LDS_BYTES, st, *p, *c, chain_or_none(c2));
 }
 template <int D, bool SIGN>
 int f1_launch_fn(const MpgEdgeFwd* p, const MpgChain* c, const MpgChain* c2, bool sl, hipStream_t st) {
-    return p->two_term == 1 ? f1_launch_fn_lt<D, SIGN, 1>(p, c, c2, sl, st) : f1_launch_fn_lt<D, SIGN, 0>(p, c, c2, sl, st);
+    static constexpr EdgeFwdFnUnit* LT[2] = {f1_launch_fn_lt<D, SIGN, 0>, f1_launch_fn_lt<D, SIGN, 1>};   // [two_term]
+    return LT[p->two_term == 1](p, c, c2, sl, st);
 }
 
 }  // namespace

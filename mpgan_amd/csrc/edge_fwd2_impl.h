@@ -455,16 +455,9 @@ __global__ __launch_bounds__(256, 1) void edge_fwd_kernel(const MpgEdgeFwd p) { 
 // dropout mode: this template is slow to compile; NQ = 0 is built by tools/ubench/fwd_bench.hip only)
 template <int D, int NQ = 0>
 int f2_launch(const MpgEdgeFwd* p, hipStream_t st) {
-    const int RB = (p->N + 31) / 32;
-    dim3 grid(p->B * RB * p->SC), block(256);
-    if (p->sign3 != nullptr) {
-        MPG_ENSURE_LDS((edge_fwd_kernel<D, true, NQ>), F2_LDS_BYTES);
-        hipLaunchKernelGGL((edge_fwd_kernel<D, true, NQ>), grid, block, F2_LDS_BYTES, st, *p);
-    } else {
-        MPG_ENSURE_LDS((edge_fwd_kernel<D, false, NQ>), F2_LDS_BYTES);
-        hipLaunchKernelGGL((edge_fwd_kernel<D, false, NQ>), grid, block, F2_LDS_BYTES, st, *p);
-    }
-    return (int)hipGetLastError();
+    using Go = int (*)(dim3, dim3, int, hipStream_t, const MpgEdgeFwd&);
+    static constexpr Go GO[2] = {mpg_go<edge_fwd_kernel<D, false, NQ>, MpgEdgeFwd>, mpg_go<edge_fwd_kernel<D, true, NQ>, MpgEdgeFwd>};   // [sign3 != nullptr]
+    return GO[p->sign3 != nullptr](dim3(p->B * ((p->N + 31) / 32) * p->SC), dim3(256), F2_LDS_BYTES, st, *p);
 }
 
 }  // namespace

@@ -360,9 +360,7 @@ extern "C" int mpg_knn_sets(const float* x, int ldx, const float* mask, int B, i
                             unsigned int* nbr, void* stream) {
     if (B <= 0 || N <= 0 || F <= 0 || k <= 0 || N > 192) return -1;
     const int lds = N * N * (int)sizeof(float);
-    MPG_ENSURE_LDS(knn_sets_kernel, lds);
-    hipLaunchKernelGGL(knn_sets_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, x, ldx, mask, N, F, k, self_loops ? 0 : 1, nbr);
-    return (int)hipGetLastError();
+    return mpg_go<knn_sets_kernel>(dim3(B), dim3(256), lds, (hipStream_t)stream, x, ldx, mask, N, F, k, self_loops ? 0 : 1, nbr);
 }
 
 extern "C" int mpg_layernorm_fwd(const float* x, int ldx, const float* w, const float* b, float* y, int ldy, float* stats,

@@ -429,8 +429,7 @@ extern "C" int mpg_jet_emd(const float* a, int ld_jet_a, const float* b, int ld_
         hipLaunchKernelGGL(jet_emd_kernel<2>, grid, block, lds, st, a, ld_jet_a, b, ld_jet_b, ld_part, na, nb, N, inv_r, cap, stride, out, status);
     } else {
         static_assert(6 * 64 >= kEmdMaxNodes, "six slots per lane hold every node");
-        MPG_ENSURE_LDS(jet_emd_kernel<6>, lds);
-        hipLaunchKernelGGL(jet_emd_kernel<6>, grid, block, lds, st, a, ld_jet_a, b, ld_jet_b, ld_part, na, nb, N, inv_r, cap, stride, out, status);
+        return mpg_go<jet_emd_kernel<6>>(grid, block, lds, st, a, ld_jet_a, b, ld_jet_b, ld_part, na, nb, N, inv_r, cap, stride, out, status);
     }
     return (int)hipGetLastError();
 }

@@ -1900,16 +1900,10 @@ int mab_split_fwd_waves(int B) {
 }
 
 // ---- launches: every kernel of this file is named once, in the tables below ----
-// the dynamic-LDS grant of ONE kernel (once per device: the macro's counter is a static of this instantiation), then its launch
-template <typename P, void (*K)(const P)>
-int mab_go(const P* p, int grid, int block, int lds_bytes, hipStream_t st) {
-    MPG_ENSURE_LDS(K, lds_bytes);
-    hipLaunchKernelGGL(K, dim3(grid), dim3(block), lds_bytes, st, *p);
-    return (int)hipGetLastError();
-}
-using MabGo = int (*)(const MpgMab*, int, int, int, hipStream_t);
-using MabChainGo = int (*)(const MpgMabChain*, int, int, int, hipStream_t);
-#define MAB_GO(...) mab_go<MpgMab, __VA_ARGS__>
+// (common.h's mpg_go: the dynamic-LDS grant of ONE kernel, once per device, then its launch)
+using MabGo = int (*)(dim3, dim3, int, hipStream_t, const MpgMab&);
+using MabChainGo = int (*)(dim3, dim3, int, hipStream_t, const MpgMabChain&);
+#define MAB_GO(...) mpg_go<__VA_ARGS__, MpgMab>
 #define MAB_CROSS_LN(K, NT) {{MAB_GO(K<NT, false, false>), MAB_GO(K<NT, false, true>)}, {MAB_GO(K<NT, true, false>), MAB_GO(K<NT, true, true>)}}
 const MabGo MAB_FWD[2][2][2] = {MAB_CROSS_LN(mab_fwd_kernel, 1), MAB_CROSS_LN(mab_fwd_kernel, 2)};      // [E / 32 - 1][cross][ln]
 const MabGo MAB_BWD[2][2][2] = {MAB_CROSS_LN(mab_bwd_kernel, 1), MAB_CROSS_LN(mab_bwd_kernel, 2)};
@@ -1920,8 +1914,8 @@ const MabGo MAB_FWDN[2][2] = {{MAB_GO(mab_fwdN_kernel<1, false>), MAB_GO(mab_fwd
 const MabGo MAB_FWD2[2][2] = {{MAB_GO(mab_fwd2_kernel<false, 4>), MAB_GO(mab_fwd2_kernel<false, 8>)},   // [cross][waves == 8]
                               {MAB_GO(mab_fwd2_kernel<true, 4>), MAB_GO(mab_fwd2_kernel<true, 8>)}};
 const MabGo MAB_BWD2[2] = {MAB_GO(mab_bwd2_kernel<false>), MAB_GO(mab_bwd2_kernel<true>)};              // [cross]
-const MabChainGo MAB_CHAIN[2] = {mab_go<MpgMabChain, mab_chain_fwd_kernel<1>>, mab_go<MpgMabChain, mab_chain_fwd_kernel<2>>};     // [E / 32 - 1]
-const MabChainGo MAB_CHAIN2[2] = {mab_go<MpgMabChain, mab_chain_fwd2_kernel<4>>, mab_go<MpgMabChain, mab_chain_fwd2_kernel<8>>};  // [waves == 8]
+const MabChainGo MAB_CHAIN[2] = {mpg_go<mab_chain_fwd_kernel<1>, MpgMabChain>, mpg_go<mab_chain_fwd_kernel<2>, MpgMabChain>};     // [E / 32 - 1]
+const MabChainGo MAB_CHAIN2[2] = {mpg_go<mab_chain_fwd2_kernel<4>, MpgMabChain>, mpg_go<mab_chain_fwd2_kernel<8>, MpgMabChain>};  // [waves == 8]
 #undef MAB_CROSS_LN
 #undef MAB_GO
 
@@ -1929,7 +1923,7 @@ const MabChainGo MAB_CHAIN2[2] = {mab_go<MpgMabChain, mab_chain_fwd2_kernel<4>>,
 int mab_launch(MabGo go, const MpgMab* p, int lds_bytes, hipStream_t st, bool one_jet_per_wave = false) {
     const int nw = mab_waves(p->B);
     const int grid = ((p->B + nw - 1) / nw < 1024 || one_jet_per_wave) ? (p->B + nw - 1) / nw : 1024;
-    return go(p, grid, 64 * nw, lds_bytes, st);
+    return go(dim3(grid), dim3(64 * nw), lds_bytes, st, *p);
 }
 
 // dynamic LDS bytes (NT = E / 32).  Forward: Win + Wo, Wf + biases
@@ -1964,9 +1958,9 @@ extern "C" int mpg_mab_bwd(const MpgMab* p, void* stream) {
     const bool cross = p->y != p->x, ln = p->ln1_w != nullptr;
     const int NT = p->E / 32;
     if (p->L > 32 || p->S > 32 || getenv("MPG_MAB_BIG") != nullptr)   // large sets: a workgroup per jet, a wave per tile of 32 tokens
-        return MAB_BWDS[NT - 1][cross][ln](p, p->B, 64 * ((std::max(p->L, p->S) + 31) / 32), mab_big_lds(NT, true), st);
+        return MAB_BWDS[NT - 1][cross][ln](dim3(p->B), dim3(64 * ((std::max(p->L, p->S) + 31) / 32)), mab_big_lds(NT, true), st, *p);
     if (NT == 2 && !ln && mab_split(p->B))                            // two waves per jet, two jets per workgroup
-        return MAB_BWD2[cross](p, (p->B + 1) / 2, 256, mab_bwd_lds(NT), st);
+        return MAB_BWD2[cross](dim3((p->B + 1) / 2), dim3(256), mab_bwd_lds(NT), st, *p);
     return mab_launch(MAB_BWD[NT - 1][cross][ln], p, mab_bwd_lds(NT), st, true);   // (layer_norm=True: always one wave per jet)
 }
 
@@ -1977,11 +1971,11 @@ extern "C" int mpg_mab_fwd(const MpgMab* p, void* stream) {
     const bool cross = p->y != p->x, ln = p->ln1_w != nullptr;
     const int NT = p->E / 32;
     if (p->L > 32 || p->S > 32 || getenv("MPG_MAB_BIG") != nullptr)   // large sets: a workgroup per jet, a wave per tile of 32 queries
-        return MAB_FWDN[NT - 1][ln](p, p->B, 64 * ((std::max(p->L, p->S) + 31) / 32), mab_big_lds(NT, false), st);
+        return MAB_FWDN[NT - 1][ln](dim3(p->B), dim3(64 * ((std::max(p->L, p->S) + 31) / 32)), mab_big_lds(NT, false), st, *p);
     // layer_norm=True: one wave per jet (a token's statistics run over both feature tiles)
     if (const int nw2 = (NT == 2 && !ln) ? mab_split_fwd_waves(p->B) : 0) {
         const int npair = nw2 / 2;
-        return MAB_FWD2[cross][nw2 == 8](p, (p->B + npair - 1) / npair, 64 * nw2, mab_fwd_lds(NT) + npair * 2 * MAB_XCH, st);
+        return MAB_FWD2[cross][nw2 == 8](dim3((p->B + npair - 1) / npair), dim3(64 * nw2), mab_fwd_lds(NT) + npair * 2 * MAB_XCH, st, *p);
     }
     return mab_launch(MAB_FWD[NT - 1][cross][ln], p, mab_fwd_lds(NT), st);
 }
@@ -2003,8 +1997,8 @@ extern "C" int mpg_mab_chain_fwd(const MpgMabChain* c, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (const int nw2 = NT == 2 ? mab_split_fwd_waves(p0.B) : 0) {   // two waves per jet, two or four jets per workgroup
         const int npair = nw2 / 2;
-        return MAB_CHAIN2[nw2 == 8](c, (p0.B + npair - 1) / npair, 64 * nw2, mab_fwd_lds(NT) + npair * 2 * MAB_XCH, st);
+        return MAB_CHAIN2[nw2 == 8](dim3((p0.B + npair - 1) / npair), dim3(64 * nw2), mab_fwd_lds(NT) + npair * 2 * MAB_XCH, st, *c);
     }
     const int nw = mab_waves(p0.B);       // one jet per wave: its rows stay in registers across the blocks
-    return MAB_CHAIN[NT - 1](c, (p0.B + nw - 1) / nw, 64 * nw, mab_fwd_lds(NT), st);
+    return MAB_CHAIN[NT - 1](dim3((p0.B + nw - 1) / nw), dim3(64 * nw), mab_fwd_lds(NT), st, *c);
 }

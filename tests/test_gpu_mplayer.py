@@ -801,6 +801,9 @@ def test_jet_order_and_heaviest_first_launches_change_no_result():
                                           # block) adds the chunks up and runs the epilogue (eight-wave form); backward: separate launches
     (3, 150, 32, 32, 0.5, True, True),
     (2, 100, 3, 32, 0.0, True, False),
+    (2, 5, 32, 3, 0.5, True, True),       # rows of 3 floats WITH dropout, one bit and byte thresholds: the element-store forms of
+    (2, 5, 32, 3, 0.3, True, True),       # the forward's epilogue in the dropout modes (one receiver block of 5)
+    (2, 5, 3, 32, 0.3, True, True),       # byte-threshold dropout with a 3-column dx (element stores in the backward's epilogue)
 ])
 @pytest.mark.parametrize("two_term", [0, 1])
 def test_node_network_as_edge_epilogue_is_bit_identical(B, N, F, out, p_drop, use_mask, train, two_term):
@@ -1216,7 +1219,9 @@ def test_direct_accumulation_equals_returned_gradients(N):
 _LAYER_CASES = {"N30_sc1": (30, None, "1", "train"), "N33_sc1": (33, None, "1", "train"), "N150": (150, None, None, "train"),
                 "N30_es": (30, dict(pos_diffs=True, delta_r=True), None, "train"),
                 "N30_knn": (30, dict(fully_connected=False, num_knn=10), None, "train"),
-                "N30_frozen": (30, None, None, "frozen"), "N30_nograd": (30, None, None, "nograd")}
+                "N30_frozen": (30, None, None, "frozen"), "N30_nograd": (30, None, None, "nograd"),
+                # frozen parameters on the whole-jet form (the data-gradient kernel parks nothing, dx is its epilogue) and with edge scalars
+                "N5_frozen_sc1": (5, None, "1", "frozen"), "N30_es_frozen": (30, dict(pos_diffs=True, delta_r=True), None, "frozen")}
 _LAUNCHES = {
     "N30_sc1": ["mpg_chain", "mpg_edge_fwd_fn", "mpg_chain", "mpg_edge_bwd_fn", "mpg_edge_dw", "mpg_gemm_wgrad_group",
                "mpg_splitk_reduce_group_dw"],
@@ -1230,6 +1235,9 @@ _LAUNCHES = {
                "mpg_gemm_wgrad_group", "mpg_splitk_reduce_group_dw", "mpg_chain"],
     "N30_frozen": ["mpg_chain", "mpg_edge_fwd_fn", "mpg_chain", "mpg_edge_bwd", "mpg_slab_sums", "mpg_chain"],
     "N30_nograd": ["mpg_chain", "mpg_edge_fwd_fn"],
+    # (N30_sc1 and N30_es without their three weight-gradient launches, as N30_frozen is N33_sc1 without them)
+    "N5_frozen_sc1": ["mpg_chain", "mpg_edge_fwd_fn", "mpg_chain", "mpg_edge_bwd_fn"],
+    "N30_es_frozen": ["mpg_chain", "mpg_edge_fwd", "mpg_chain", "mpg_chain", "mpg_edge_bwd", "mpg_slab_sums", "mpg_chain"],
 }
 
 

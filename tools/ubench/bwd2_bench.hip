@@ -3,7 +3,7 @@
 //         tools/ubench/bwd2_bench.hip mpgan_amd/csrc/edge.hip -o bwd2_bench
 //   bwd2_bench [B=256] [needw=1] [ragged=0|1|2 (2: scattered masks)] [N=30] [SC=1]
 // Prints the launch time and a checksum of da / dc / the parked fragments (to see that an experiment changed nothing).
-#include "../../mpgan_amd/csrc/edge_bwd2.hip"
+#include "../../mpgan_amd/csrc/edge_bwd.hip"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

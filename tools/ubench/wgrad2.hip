@@ -270,7 +270,5 @@ __global__ __launch_bounds__(256, 1) void wgrad2_kernel(const W2Group G) {
 }  // namespace
 
 int mpg_wgrad2_launch(const W2Group* G, hipStream_t st) {
-    MPG_ENSURE_LDS(wgrad2_kernel, W2_LDS);
-    hipLaunchKernelGGL(wgrad2_kernel, dim3(G->wg0[G->n]), dim3(256), W2_LDS, st, *G);
-    return (int)hipGetLastError();
+    return mpg_go<wgrad2_kernel>(dim3(G->wg0[G->n]), dim3(256), W2_LDS, st, *G);
 }
