@@ -3,8 +3,11 @@
 Mirrors the reference's ``train_D`` / ``train_G`` (train.py:398-523): losses ``ls`` (default, train.py:368-370,
 :471-472), ``og``, ``w``, ``hinge`` (``calc_D_loss`` :331-395, ``calc_G_loss`` :465-476), optimizers RMSprop
 (default), Adam, Adadelta as ``setup_training.optimizers`` builds them (setup_training.py:1511-1523),
-``num_critic = num_gen = 1``, generator noise ~ N(0, sd=0.2) sampled on the device every step
+generator noise ~ N(0, sd=0.2) sampled on the device every step
 (train.py:100-141), D in train mode (dropout on) in both sub-steps, G in eval mode in the D step.
+``--num-critic`` / ``--num-gen`` (setup_training.py:239-250) decide which of the two runs on a batch (train.py:841, :864;
+``TrainStep(num_critic=..., num_gen=...)``): a ``step()`` is one batch of the reference's epoch loop and runs train_D and
+train_G, train_D alone or train_G alone, each kind captured into graphs of its own.
 The gradient penalty (train.py:286-324, ``--gp``) needs a second derivative through D.  The fused ops are first-order
 only (``once_differentiable``), so the penalty's own pass D(interpolated) takes the double-backward route
 (``ops.double_backward_route``: every product an ``ops.MatMulFn`` on the HIP GEMM, the rest ATen) while D(real) and
@@ -145,6 +148,10 @@ class FlatParams:
         # parameter group: torch.optim's own load_state_dict carries unknown group keys along untouched)
         self.seed_device = None
         self.seed_rank = 0     # this process's rank in the data-parallel group (TrainStep sets it): saved beside the seed
+        # TrainStep: its ``batch_ndx`` (num_critic / num_gen schedule) is kept HERE, in G's FlatParams, and saved beside the seed; None
+        # outside a TrainStep.  (Not a reference back to the step: a cycle would leave the step's hipGraphs to the garbage
+        # collector, which may run in the middle of another step's capture.)
+        self.batch_ndx = None
 
     def zero_grad(self):
         self.grad.zero_()
@@ -189,6 +196,7 @@ class FlatParams:
     _STATE_KEYS = {"rmsprop": ("square_avg", None), "adam": ("exp_avg_sq", "exp_avg"), "adadelta": ("square_avg", "acc_delta")}
     SEED_KEY = "mpgan_amd_seed"
     SEED_RANK_KEY = "mpgan_amd_seed_rank"
+    BATCH_KEY = "mpgan_amd_batch_ndx"
 
     def _torch_optimizer(self, lr):
         """A torch.optim instance over detached CPU stand-ins of the parameters: the source of truth for the
@@ -221,6 +229,8 @@ class FlatParams:
         if self.seed_device is not None:
             sd["param_groups"][0][self.SEED_KEY] = ops.get_seed(self.seed_device)
             sd["param_groups"][0][self.SEED_RANK_KEY] = int(self.seed_rank)
+        if self.batch_ndx is not None:
+            sd["param_groups"][0][self.BATCH_KEY] = int(self.batch_ndx)
         return sd
 
     def load_state_dict(self, sd: dict):
@@ -269,6 +279,8 @@ class FlatParams:
             # share noise or masks behind a resume either.
             ops.set_seed(ops.rerank_seed(int(groups[0][self.SEED_KEY]), int(groups[0].get(self.SEED_RANK_KEY, 0)), self.seed_rank),
                          self.seed_device)
+        if self.batch_ndx is not None:     # (a file without the field -- the reference's, an older one -- resumes at the top of an epoch)
+            self.batch_ndx = int(groups[0].get(self.BATCH_KEY, 0))
         return self.lr
 
     def versions(self) -> int:
@@ -381,15 +393,30 @@ class _GenAhead:
 
 class TrainStep:
     """G+D iteration (train.py:829-878 body) with static buffers, optional hipGraph replay and an
-    optional process group for data-parallel gradient averaging (RCCL over xGMI)."""
+    optional process group for data-parallel gradient averaging (RCCL over xGMI).  ``num_critic`` / ``num_gen``: the reference's
+    ``--num-critic`` / ``--num-gen`` -- ``step()`` is one batch of the epoch loop and trains D, G or both as train.py:841 / :864
+    say for ``batch_ndx`` (``start_epoch()`` where the reference's ``for batch_ndx, ...`` begins); ``last_ran`` names what ran.
+    ``track_epoch_losses``: the epoch's loss sums on the device, read by ``epoch_losses()``."""
 
     def __init__(self, G: nn.Module, D: nn.Module, batch_size: int, num_particles: int, latent: int = 32,
                  lr_disc: float = 3e-5, lr_gen: float = 1e-5, noise_std: float = 0.2, use_graphs: bool = True,
                  process_group=None, world_size: int = 1, batch_real_fake: bool = True, loss: str = "ls",
                  optimizer: str = "rmsprop", betas=(0.9, 0.999), gp_lambda: float = 0.0,
-                 graph_collectives: Optional[bool] = None, augment=None, loader=None):
+                 graph_collectives: Optional[bool] = None, augment=None, loader=None, num_critic: int = 1, num_gen: int = 1,
+                 track_epoch_losses: bool = False):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+        for name, v in (("num_critic", num_critic), ("num_gen", num_gen)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+        if num_critic > 1 and num_gen > 1:
+            raise ValueError(f"num_critic = {num_critic} with num_gen = {num_gen}: the reference's --num-gen says \"num-critic must be "
+                             "1 for this to apply\" (setup_training.py:249; train.py:841 ignores num_gen when num_critic > 1)")
+        # The update schedule (``--num-critic`` / ``--num-gen``): ``step()`` is one batch of the reference's epoch loop
+        # (train.py:829-878) and ``batch_ndx`` its ``enumerate`` index, kept on the host (``start_epoch`` restarts it);
+        # ``last_ran`` names what the last ``step()`` ran.
+        self.num_critic, self.num_gen = num_critic, num_gen
+        self.last_ran = ()
         self.dev = dev = next(G.parameters()).device
         gpu = dev.type == "cuda"
 
@@ -423,6 +450,7 @@ class TrainStep:
         self.state = ops.dev_state(dev)
         self.fG = FlatParams(G, optimizer, betas)
         self.fD = FlatParams(D, optimizer, betas)
+        self.fG.batch_ndx = 0      # (the schedule's batch index: saved with G's optimizer state, see ``batch_ndx``)
         if gpu:
             # The generator's noise and every dropout mask come from counter-based streams keyed by the DEVICE seed, which
             # torch.manual_seed does not reach.  Unless the caller has set it (ops.set_seed), derive it here from torch's
@@ -462,7 +490,13 @@ class TrainStep:
         self.D_loss = torch.zeros((), device=dev)
         self.G_loss = torch.zeros((), device=dev)
         self.use_graphs = use_graphs and gpu
-        self._graphs = None
+        self._graphs = None          # the D+G iteration's graphs
+        self._alone_graphs = {}      # "D" / "G": the graphs of a batch on which only one of the two trains, captured on first use
+        self._pool = None            # (the memory pool all of them share)
+        # Epoch losses (train.py:862, :865, :960-962): sums of D_loss, GP and G_loss in device memory, added to behind the launch
+        # that writes each loss -- one small launch per loss, only when asked for; ``epoch_losses`` reads them
+        self.epoch_sums = {k: torch.zeros((), device=dev) for k in ("D", "gp", "G")} if track_epoch_losses else None
+        self._epoch_steps = 0
         # The G step's generator forward depends on nothing the D step writes (G's weights, fresh noise, the labels): it is
         # launched at the top of the D step on a second stream and runs BESIDE it -- the edge launches of a batch of 256 jets
         # are one workgroup per CU and as long as their fullest jet, so a fifth of the chip idles at the end of each; work
@@ -519,7 +553,7 @@ class TrainStep:
     def attach_loader(self, loader):
         """Take the batches from ``loader`` (``data.DeviceJetLoader``) instead of ``set_batch``: one launch at the top of the D
         segment, inside the capture on every route.  Before the first captured ``step``."""
-        if self._graphs is not None:
+        if self._graphs is not None or self._alone_graphs:
             raise RuntimeError("attach_loader: the iteration has been captured already (the feed launch is part of the graph); "
                                "attach the loader before the first step")
         if loader.batch_size != self.B or loader.num_particles != self.N:
@@ -653,10 +687,16 @@ class TrainStep:
         _, dy = ops.disc_head_loss(y, mask, w, b, mean=mean, sigmoid=sigmoid, p_drop=p, training=self.D.training, loss=self.loss,
                                    n_real=self.B, gen_step=gen_step, count=self.B, loss_out=self.G_loss if gen_step else self.D_loss,
                                    want_dy=True, wgrad=None if gen_step else (w.grad, None if b is None else b.grad))
+        self._sum_epoch("G" if gen_step else "D")
         self._backward(y, dy, then)
 
-    def _seg_D(self, join: bool = True):  # train_D up to and including backward (train.py:419-460)
-        # (join=False: the generator-ahead branch stays open for a _seg_G that follows in the same graph / eager run)
+    def _sum_epoch(self, key: str):   # epoch_loss[key] += ... (train.py:862, :865) in device memory, behind the launch that wrote the loss
+        if self.epoch_sums is not None:
+            self.epoch_sums[key].add_({"D": self.D_loss, "gp": self.GP, "G": self.G_loss}[key])
+
+    def _seg_D(self, join: bool = True, fork: bool = True):  # train_D up to and including backward (train.py:419-460)
+        # (join=False: the generator-ahead branch stays open for a _seg_G that follows in the same graph / eager run;
+        # fork=False: a batch on which the generator does not train -- no _seg_G follows, so the branch is never opened)
         # parameter gradients are added straight into the flat buffers (no AccumulateGrad kernel per parameter)
         if self.loader is not None:     # (first: the generator-ahead branch reads self.labels)
             self.loader.feed(self)
@@ -664,7 +704,7 @@ class TrainStep:
         self.state.order_cache = None   # (ops.jet_order: the masks of this iteration live where last iteration's did)
         # (the dropout / noise seed of this iteration was set by the last launch of the iteration before: _seg_end)
         self.D.train()
-        if self.gen_ahead and not self.gen_ahead_late:
+        if fork and self.gen_ahead and not self.gen_ahead_late:
             self._fork_generator()
         self.G.eval()
         if not self._clean["D"]:     # (cleared by the optimizer launch of the iteration before: see _seg_G)
@@ -672,7 +712,7 @@ class TrainStep:
         self._clean["D"] = False
         _set_requires_grad(self.fD, True)
         try:
-            self._seg_D_body(self._fork_generator if self.gen_ahead_late else None)
+            self._seg_D_body(self._fork_generator if fork and self.gen_ahead_late else None)
         finally:
             if join:     # everything of this segment is ordered before whatever follows it
                 self._ahead.join("seg_D")
@@ -701,6 +741,7 @@ class TrainStep:
             out = torch.cat([self.D(self.data.clone(), self.labels).reshape(-1), self.D(fake, self.labels).reshape(-1)])
         loss = d_loss(self.loss, out, self.B, self._real)
         self.D_loss.copy_(loss.detach())   # (D_real_loss + D_fake_loss: the reference's losses["D"] leaves the penalty out)
+        self._sum_epoch("D")
         if self.gp_lambda:
             real = self.data
             if self.aug is not None:       # (calc_D_loss is handed the augmented real batch: train.py:441, :452)
@@ -708,6 +749,7 @@ class TrainStep:
                     real = self._augment(self.data, AUG_SITES["D_real"])
             gp = self.gradient_penalty(real, fake)
             self.GP.copy_(gp.detach())
+            self._sum_epoch("gp")
             loss = loss + gp
         self._backward(loss, then=late_fork)
 
@@ -762,11 +804,28 @@ class TrainStep:
         if packs:
             ops.refresh_many(packs)
 
-    def _seg_G(self):  # D_optimizer.step() (train.py:461) + train_G up to backward (:494-520)
-        # optimizer.zero_grad() of the next train_D (train.py:419) rides in this launch: the buffer is cleared behind its last use
-        self.fD.step(self.lr_disc, gscale=1.0 / self.world, zero_grad=True)
+    def _seg_D_end(self):  # D_optimizer.step() (train.py:461) of a batch on which the generator does not train
+        # the seed moves on HERE, as it does in G's optimizer launch otherwise (_seg_end): the next critic step would redraw this
+        # one's generator noise, dropout masks and augmentation maps without it
+        self.fD.step(self.lr_disc, gscale=1.0 / self.world, zero_grad=True, advance_seed=ops.seed_tensor(self.dev))
         self._clean["D"] = True
         self._refresh_packed(self.D)
+        self.state.grad_into_param = False
+
+    def _seg_G(self, alone: bool = False):  # D_optimizer.step() (train.py:461) + train_G up to backward (:494-520)
+        if alone:
+            # a batch on which the discriminator does not train (num_gen > 1): what the top of _seg_D sets up, and train_G --
+            # the data loader yields the batch all the same, and train_G takes its labels (train.py:832-835, :872)
+            if self.loader is not None:
+                self.loader.feed(self)
+            self.state.grad_into_param = True
+            self.state.order_cache = None
+            self.D.train()
+        else:
+            # optimizer.zero_grad() of the next train_D (train.py:419) rides in this launch: the buffer is cleared behind its last use
+            self.fD.step(self.lr_disc, gscale=1.0 / self.world, zero_grad=True)
+            self._clean["D"] = True
+            self._refresh_packed(self.D)
         self.G.train()
         if not self._clean["G"]:
             self.fG.zero_grad()
@@ -787,6 +846,7 @@ class TrainStep:
             loss = g_loss(self.loss, self.D(fake, self.labels))
             self._backward(loss)
             self.G_loss.copy_(loss.detach())
+            self._sum_epoch("G")
         _set_requires_grad(self.fD, True)
 
     def _seg_end(self):  # G_optimizer.step() (train.py:521)
@@ -809,16 +869,40 @@ class TrainStep:
     def _allreduce(self, flat: FlatParams):
         mdist.allreduce_sum_(flat.grad, self.pg, self.world)  # sum; 1/world is folded into the optimiser step
 
-    def _eager(self):
-        self._seg_D(join=False); self._allreduce(self.fD)
-        self._seg_G(); self._allreduce(self.fG)
-        self._seg_end()
+    # -- which of train_D / train_G a batch runs, and the segments of each kind of batch --------------
+    KINDS = {"DG": ("D", "G"), "D": ("D",), "G": ("G",)}
+
+    def _kind(self, batch_ndx: int) -> str:
+        """"DG", "D" or "G": what the reference's loop runs on batch ``batch_ndx`` of an epoch."""
+        b = batch_ndx
+        run_D = self.num_critic > 1 or (b == 0 or (b - 1) % self.num_gen == 0)      # train.py:841
+        run_G = self.num_critic == 1 or (b - 1) % self.num_critic == 0             # train.py:864
+        return "DG" if run_D and run_G else ("D" if run_D else "G")                # (never neither: one of the two counts is 1)
+
+    def _segments(self, kind: str, joined: bool = False):
+        """The segments of one batch of ``kind``, in order: (segment, the network whose gradient all-reduce follows it or None)."""
+        # (joined: the D segment ends with the generator-ahead branch joined -- a hipGraph of its own; otherwise the branch stays
+        # open for the _seg_G that follows in the same graph / eager run)
+        if kind == "DG":
+            seg_D = self._seg_D if joined else (lambda: self._seg_D(join=False))
+            return [(seg_D, self.fD), (self._seg_G, self.fG), (self._seg_end, None)]
+        if kind == "D":
+            return [(lambda: self._seg_D(fork=False), self.fD), (self._seg_D_end, None)]
+        return [(lambda: self._seg_G(alone=True), self.fG), (self._seg_end, None)]
+
+    def _eager(self, kind: str = "DG"):
+        for seg, flat in self._segments(kind):
+            seg()
+            if flat is not None:
+                self._allreduce(flat)
 
     def _training_state(self):
         """Everything an iteration changes: parameters, optimiser moments and step counters, the dropout seed, the losses --
         and what a FORWARD changes: the modules' buffers (batch norm's running statistics and batch counter) and frozen
         parameters (spectral norm's power-iteration vectors, written in place by ``SpectralNorm.weight``)."""
         ts = [self.D_loss, self.G_loss, self.GP, ops.seed_tensor(self.dev)]
+        if self.epoch_sums is not None:
+            ts += list(self.epoch_sums.values())
         for f in (self.fD, self.fG):
             ts += [f.flat, f.sq, f.step_count] + ([f.aux] if f.aux is not None else [])
             ts += list(f.module.buffers()) + [p for p in f.module.parameters() if not p.requires_grad]
@@ -826,12 +910,16 @@ class TrainStep:
             ts.append(self.loader.cursor)
         return ts
 
-    def capture(self, warmup: int = 3):
+    def capture(self, warmup: int = 3, kind: str = "DG"):
         """Warm up eagerly on a side stream, then capture the three segments into hipGraphs.  The warm-up iterations are
         real ones (kernels get loaded, their LDS limits set, the allocator's pools filled -- none of which may happen
         during a capture): the training state is saved before and put back after them, so capturing -- which ``step``
         does on its first call -- leaves parameters, optimiser state, step counters and the dropout seed where they
-        were.  (A run resumed from a checkpoint continues from exactly the state it loaded.)"""
+        were.  (A run resumed from a checkpoint continues from exactly the state it loaded.)
+        ``kind``: the batch captured -- "DG" (train_D and train_G), or "D" / "G" where the num_critic / num_gen schedule runs
+        one of them alone; ``step`` captures each on its first use, in the middle of a run as well, all from one memory pool."""
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be one of {tuple(self.KINDS)}, got {kind!r}")
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(s):
@@ -842,7 +930,7 @@ class TrainStep:
                 # of the double-backward route draw from it): the warm-up's draws are taken back as well
                 rng = torch.cuda.get_rng_state(self.dev) if self.dev.type == "cuda" else None
             for _ in range(warmup):
-                self._eager()
+                self._eager(kind)
             if warmup:
                 for t, v in zip(self._training_state(), saved):
                     t.copy_(v)
@@ -855,29 +943,32 @@ class TrainStep:
         torch.cuda.current_stream(self.dev).wait_stream(s)
         torch.cuda.synchronize(self.dev)
         graphs = []
-        pool = None
         # one graph per segment between collectives; without a process group the whole iteration is one graph
-        split = (self.world > 1 or self.pg is not None or self.split_graphs) and not self.graph_collectives
-        seg_D_open = lambda: self._seg_D(join=False)    # (D and G segments in ONE graph: the branch may stay open across them)
         if self.graph_collectives:
             if torch.distributed.get_backend(self.pg) != "nccl":
                 raise RuntimeError("graph_collectives needs an nccl (RCCL) process group: only its collectives are stream operations")
-            rD, rG = (lambda: self._allreduce(self.fD)), (lambda: self._allreduce(self.fG))
-            groups = [(seg_D_open, rD, self._seg_G, rG, self._seg_end)]
-        elif split:
-            groups = [(self._seg_D,), (self._seg_G,), (self._seg_end,)]
-        else:
-            groups = [(seg_D_open, self._seg_G, self._seg_end)]
+            reduce = lambda flat: (lambda: self._allreduce(flat))
+            groups = [[f for seg, flat in self._segments(kind) for f in ((seg,) if flat is None else (seg, reduce(flat)))]]
+        elif self._split():
+            groups = [(seg,) for seg, _ in self._segments(kind, joined=True)]
+        else:   # (D and G segments in ONE graph: the branch may stay open across them)
+            groups = [[seg for seg, _ in self._segments(kind)]]
         for segs in groups:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
+            with torch.cuda.graph(g, pool=self._pool):
                 for seg in segs:
                     seg()
-            pool = g.pool()
+            self._pool = g.pool()
             graphs.append(g)
-        self._graphs = graphs
+        if kind == "DG":
+            self._graphs = graphs
+        else:
+            self._alone_graphs[kind] = graphs
         if self.loader is not None:
             self.loader._captured = True
+
+    def _split(self) -> bool:   # the gradient all-reduces are ordinary calls between the graphs of a batch
+        return (self.world > 1 or self.pg is not None or self.split_graphs) and not self.graph_collectives
 
     def set_batch(self, data: torch.Tensor, labels: torch.Tensor):
         if self.loader is not None:
@@ -917,21 +1008,71 @@ class TrainStep:
                 f"mpgan_amd: outside the fused path's numeric range (guard word {st}: 1 = |weight x operand scale| > 65504 in an "
                 f"fp16 image, 2 = non-finite weight; losses D {losses[0]}, G {losses[1]})")
 
+    @property
+    def batch_ndx(self) -> int:
+        """The reference's ``batch_ndx`` (train.py:829) of the batch the next ``step()`` is: steps since ``start_epoch``."""
+        return self.fG.batch_ndx
+
+    @property
+    def _batch_ndx(self) -> int:
+        return self.fG.batch_ndx
+
+    @_batch_ndx.setter
+    def _batch_ndx(self, b: int):
+        self.fG.batch_ndx = int(b)
+
+    def start_epoch(self):
+        """Where the reference's ``for batch_ndx, data in enumerate(...)`` begins (train.py:829): the schedule restarts -- batch
+        0 trains D whatever ``num_gen`` is, and G only with ``num_critic`` = 1 -- and so do the epoch's loss sums (train.py:940-941).
+        With ``num_critic = num_gen = 1`` every batch runs both and nothing depends on the index."""
+        self._batch_ndx = 0
+        self._epoch_steps = 0
+        if self.epoch_sums is not None:
+            for t in self.epoch_sums.values():
+                t.zero_()
+
+    def epoch_losses(self, reset: bool = True) -> dict:
+        """{"D", "gp", "G"}: the sums of the losses of the ``step()`` calls since ``start_epoch`` (or the last reset), divided as
+        the reference's epoch log divides them (train.py:960-962): the D side by steps / num_gen, G by steps / num_critic --
+        not by how often each ran (batch 0 and the schedule's phase make those differ).  Reads the sums: the one
+        synchronisation of ``track_epoch_losses``."""
+        if self.epoch_sums is None:
+            raise RuntimeError("TrainStep was built without track_epoch_losses")
+        n = self._epoch_steps
+        if n == 0:
+            raise RuntimeError("epoch_losses: no step() since the sums were last reset")
+        sums = dict(zip(self.epoch_sums, torch.stack(list(self.epoch_sums.values())).tolist()))
+        out = {"D": sums["D"] / (n / self.num_gen), "gp": sums["gp"] / (n / self.num_gen), "G": sums["G"] / (n / self.num_critic)}
+        if reset:
+            self._epoch_steps = 0
+            for t in self.epoch_sums.values():
+                t.zero_()
+        return out
+
     def step(self):
+        """One batch of the reference's epoch loop (train.py:829-878): train_D and / or train_G as ``num_critic`` / ``num_gen``
+        say for ``batch_ndx``, which it moves on."""
         self.sync_external_writes()
-        if self.use_graphs and self._graphs is None:
-            self.capture()
+        kind = self._kind(self._batch_ndx)
         if not self.use_graphs:
-            self._eager()
-            return
-        if len(self._graphs) == 1:
-            self._graphs[0].replay()
+            self._eager(kind)
         else:
-            gD, gG, gE = self._graphs
-            gD.replay(); self._allreduce(self.fD)
-            gG.replay(); self._allreduce(self.fG)
-            gE.replay()
-        self.fD.note_step(); self.fG.note_step()
+            graphs = self._graphs if kind == "DG" else self._alone_graphs.get(kind)
+            if graphs is None:
+                self.capture(kind=kind)
+                graphs = self._graphs if kind == "DG" else self._alone_graphs[kind]
+            if len(graphs) == 1:
+                graphs[0].replay()
+            else:   # (the gradient all-reduces between the segments' graphs)
+                for g, (_, flat) in zip(graphs, self._segments(kind)):
+                    g.replay()
+                    if flat is not None:
+                        self._allreduce(flat)
+            for net in self.KINDS[kind]:     # (only the networks this replay stepped)
+                (self.fD if net == "D" else self.fG).note_step()
+        self.last_ran = self.KINDS[kind]
+        self._batch_ndx += 1
+        self._epoch_steps += 1
 
     # -- optimiser state in the reference's checkpoint format (train.py:534-535, setup_training.py:1525-1535) -----
     def optimizer_state_dicts(self):
