@@ -352,7 +352,10 @@ int mpg_gen_tail_bwd(const float* dout, int ldd, const float* out, int ldo, floa
  *         loss < 0 : gout[b] = dL/dout[b] handed in by autograd
  *         loss >= 0: the loss named (0 ls, 1 og, 2 w, 3 hinge: calc_D_loss / calc_G_loss, train.py:331-395, :465-476),
  *                    jets [0, n_real) scored as real and the rest as generated (gen_step: all as real, generator
- *                    form), each term times inv_count; loss_out receives the sum of the terms.
+ *                    form), each term times inv_count; loss_out receives the sum of the terms.  With targets != NULL jet b
+ *                    is scored against targets[b] (any value: the ls / og terms and gradients with t = targets[b]; w / hinge
+ *                    take t > 0.5 as "real"), and *loss_extra, when given, is added to loss_out: the two outputs of
+ *                    mpg_label_targets.  Both NULL: the results of the 1 / 0 form, bit for bit.
  * aux [2B] and pooled [B,F] are scratch written by fwd and read by bwd. */
 typedef struct MpgDiscHead {
     const float* y; int ldy;              /* [B, N, F], row (particle) stride ldy                  */
@@ -369,6 +372,8 @@ typedef struct MpgDiscHead {
     float* terms; float* loss_out;        /* [B] scratch; scalar                                   */
     float* dy; int ld_dy;                 /* [B, N, F] or NULL                                     */
     float* dw; float* db; int accumulate;
+    const float* targets;                 /* [B] or NULL: jet b is scored against targets[b] instead of 1 / 0 (loss >= 0) */
+    const float* loss_extra;              /* scalar or NULL: added to the sum of the terms in loss_out                    */
 } MpgDiscHead;
 int mpg_disc_head_fwd(const MpgDiscHead* p, void* stream);
 int mpg_disc_head_bwd(const MpgDiscHead* p, void* stream);
@@ -623,6 +628,25 @@ int mpg_augment(const float* x, float* y, uint64_t jet_stride, int ld, int F, in
                 const float* p, int flags, float translate_ratio, float scale_sd, float* params, void* stream);
 int mpg_augment_bwd(const float* dy, float* dx, uint64_t jet_stride, int ld, int F, int B, int N, const float* params,
                     void* stream);
+
+/* mpg_label_targets: calc_D_loss's label smoothing and label noise (train.py:341-363; --label-smoothing / --label-noise,
+ * setup_training.py:271-274) for the 2B jets of a D step, rows [0, B) the real half, as the per-jet targets and the scalar that
+ * mpg_disc_head_loss / _bwd take (MpgDiscHead.targets, .loss_extra).  One workgroup; any B >= 1.
+ * Draws: word(g) = the project's counter-based hash of (the 64-bit *seed, tag, jet b, group g) -- the stream of the dropout
+ * masks, of mpg_normal and of the augmentation --, u_s = (word(0) >> 8) * 2^-24 and u_n = (word(1) >> 8) * 2^-24 in [0, 1).
+ * tag = MPG_LABEL_TAG + site, clear of the dropout sites (below 2^27) and of the noise, augmentation and shuffle tags.
+ *   Y_b = smoothing ? (real: 0.7f + 0.5f * u_s ~ U[0.7, 1.2);  generated: 0.3f * u_s ~ U[0, 0.3))  :  (real: 1;  generated: 0)
+ *         -- one fp32 rounding each --, then, where u_n < noise, real: Y_b = 0, generated: Y_b = 1 (noise in [0, 1], else -1).
+ * drawn [2B] (or NULL) receives Y.  What the loss makes of Y depends on its shape in the reference: without smoothing Y is
+ * [B, 1] like D's outputs and the losses are per jet -- targets = Y, *extra = 0.  With smoothing Y is [B] and
+ * MSELoss(out [B, 1], Y [B]) broadcasts to [B, B]:  mean_ij (out_i - Y_j)^2 = mean_i (out_i - mean(Y))^2 + popvar(Y)  per
+ * half, so  targets[b] = the mean of Y over b's half  and  *extra = popvar(Y_real) + popvar(Y_generated)  (BCELoss refuses
+ * those shapes: smoothing has a meaning for ls only).  Per half the mean first, then sum (Y - mean)^2 / B, both summed in one
+ * fixed order (a thread's strided partial, a tree over the 256 partials); no atomics.  *seed is read from device memory: a
+ * replayed hipGraph draws fresh labels. */
+#define MPG_LABEL_TAG 0x4C000000
+int mpg_label_targets(int B, int smoothing, float noise, const uint64_t* seed, uint32_t tag, float* targets, float* extra,
+                      float* drawn, void* stream);
 
 /* The keyed shuffle of a device-resident data set (csrc/shuffle.h: one body for the device and the host).
  * perm(key, epoch, i, n), 0 <= i < n <= 2^31 - 1, is a bijection of [0, n) computed from (key, epoch, i) alone -- a balanced

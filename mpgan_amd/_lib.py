@@ -146,6 +146,7 @@ class MpgDiscHead(C.Structure):
         ("loss", C.c_int), ("gen_step", C.c_int), ("n_real", C.c_int), ("inv_count", C.c_float),
         ("gout", _fp), ("terms", _fp), ("loss_out", _fp),
         ("dy", _fp), ("ld_dy", C.c_int), ("dw", _fp), ("db", _fp), ("accumulate", C.c_int),
+        ("targets", _fp), ("loss_extra", _fp),
     ]
 
 
@@ -259,6 +260,7 @@ SIGNATURES = {
     "mpg_shuffle_index_host": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, _fp]),
     "mpg_batch_feed": (C.c_int, [_fp, _fp, C.c_int64, C.c_int, C.c_uint64, _fp, _fp, C.c_int, C.c_uint64, _fp, _fp, _fp, _fp, _fp,
                                  _fp, _fp, C.c_void_p]),
+    "mpg_label_targets": (C.c_int, [C.c_int, C.c_int, C.c_float, _fp, C.c_uint32, _fp, _fp, _fp, C.c_void_p]),
 }
 
 

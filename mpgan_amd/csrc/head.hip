@@ -178,8 +178,9 @@ MPG_DEV void disc_head_bwd_jet(const MpgDiscHead& p, const int b, const int lane
     float g;  // dL/dout
     if (p.loss >= 0) {
         // D step: jets [0, n_real) are scored against 1, the rest against 0 (hinge: margins); G step (n_real = B with
-        // loss_g): every jet against 1, hinge in its generator form (= w)
-        const float t = b < p.n_real ? 1.f : 0.f;
+        // loss_g): every jet against 1, hinge in its generator form (= w).  p.targets: the jet's own target instead (label
+        // smoothing / noise, mpg_label_targets)
+        const float t = p.targets != nullptr ? p.targets[b] : (b < p.n_real ? 1.f : 0.f);
         float term;
         g = loss_grad((p.gen_step && p.loss == 3) ? 2 : p.loss, out, t, term) * p.inv_count;
         if (lane == 0) p.terms[b] = term * p.inv_count;
@@ -218,7 +219,11 @@ __global__ __launch_bounds__(256) void disc_head_reduce_kernel(const MpgDiscHead
             red[tid] = s;
             __syncthreads();
             for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-            if (tid == 0) *p.loss_out = red[0];
+            if (tid == 0) {
+                float v = red[0];
+                if (p.loss_extra != nullptr) v += *p.loss_extra;   // (the part of the loss no jet's output enters)
+                *p.loss_out = v;
+            }
         }
         return;
     }

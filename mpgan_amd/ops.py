@@ -393,13 +393,28 @@ class WgradBatch:
         part = torch.empty((splitk, N, K + hb), device=dy.device, dtype=torch.float32)
         self.jobs.append((dy, x, out, out_col0, out_scale, bias_out, splitk, part, accumulate))
 
+    def _groups(self):
+        """The queue cut into launches: at most GROUP_MAX jobs each, in order, and no two jobs of a launch writing the same buffer
+        -- the grouped reduction adds into ``out`` / ``bias_out`` with a plain read and write per element, so two jobs of ONE
+        launch on the same target (a module applied twice in one backward: D's two passes of ``batch_real_fake=False``) would
+        lose one of the two sums; in launches of their own they are ordered by the stream."""
+        groups, cur, seen = [], [], set()
+        for job in self.jobs:
+            out, col0, bias_out = job[2], job[3], job[5]
+            targets = {(out.data_ptr(), col0)} | (set() if bias_out is None else {(bias_out.data_ptr(), 0)})
+            if len(cur) == GROUP_MAX or targets & seen:
+                groups.append(cur)
+                cur, seen = [], set()
+            cur.append(job)
+            seen |= targets
+        return groups + ([cur] if cur else [])
+
     def flush(self, dw=None):
         """``dw``: an ``MpgEdgeDw`` whose launch ran with ``defer_reduce`` -- its per-workgroup reduction rides in the first group's
         reduction launch (``mpg_splitk_reduce_group_dw``; with no job at all it is that launch alone)."""
         if dw is not None and not self.jobs:
             check(_lib.lib().mpg_splitk_reduce_group_dw(None, 0, C.byref(dw), _stream()), "mpg_splitk_reduce_group_dw")
-        for i0 in range(0, len(self.jobs), GROUP_MAX):
-            jobs = self.jobs[i0:i0 + GROUP_MAX]
+        for i0, jobs in enumerate(self._groups()):
             n = len(jobs)
             gs, sk, rj = (MpgGemm * n)(), (C.c_int * n)(), (MpgReduceJob * n)()
             for i, (dy, x, out, col0, scale, bias_out, splitk, part, acc) in enumerate(jobs):
@@ -536,6 +551,33 @@ def augment(x: torch.Tensor, p_tensor: torch.Tensor, flags: int, translate_ratio
     check(_lib.lib().mpg_augment(_p(x), _p(out), x.stride(0), x.stride(1), F, B, N, _p(seed_tensor(x.device)), AUG_TAG + int(site),
                                  _p(p_tensor), int(flags), translate_ratio, scale_sd, _p(params), _stream()), "mpg_augment")
     return out, params
+
+
+# ------------------------------------------------------------------------------------- label smoothing / noise
+LABEL_TAG = 0x4C000000  # MPG_LABEL_TAG of include/mpgan_amd.h (+ site; clear of NOISE_TAG, AUG_TAG, SHUFFLE_TAG and the dropout sites below 2^27)
+
+
+def label_targets(B: int, smoothing: bool, noise: float, device="cuda", site: int = 0, out=None):
+    """``mpg_label_targets``: calc_D_loss's label smoothing / label noise (train.py:341-363) for the 2B jets of a D step under the
+    device's current seed, ONE launch.  Returns (targets [2B], extra [1], drawn [2B]): what ``disc_head_loss(targets=,
+    loss_extra=)`` and ``train.d_loss(real=, extra=)`` take, and the labels Y as drawn, before the reference's [B, B] broadcast
+    (``train.effective_targets`` states the rule).  ``out``: the three tensors to write into."""
+    B = int(B)
+    if B < 1:
+        raise ValueError(f"label_targets: B must be >= 1, got {B}")
+    if not 0.0 <= float(noise) <= 1.0:
+        raise ValueError(f"label_targets: noise must lie in [0, 1], got {noise!r}")
+    if out is None:
+        out = (torch.empty(2 * B, device=device, dtype=torch.float32), torch.empty(1, device=device, dtype=torch.float32),
+               torch.empty(2 * B, device=device, dtype=torch.float32))
+    targets, extra, drawn = out
+    for t, k, name in ((targets, 2 * B, "targets"), (extra, 1, "extra"), (drawn, 2 * B, "drawn")):
+        _chk(t, name)
+        if not t.is_contiguous() or t.numel() != k:
+            raise ValueError(f"label_targets: {name} must be contiguous with {k} elements, got {tuple(t.shape)}")
+    check(_lib.lib().mpg_label_targets(B, int(bool(smoothing)), float(noise), _p(seed_tensor(targets.device)), LABEL_TAG + int(site),
+                                       _p(targets), _p(extra), _p(drawn), _stream()), "mpg_label_targets")
+    return targets, extra, drawn
 
 
 def augment_apply_reference(x: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
@@ -2044,10 +2086,11 @@ class DiscHeadFn(torch.autograd.Function):
 
 
 def disc_head_loss(y, mask, w, b, *, mean, sigmoid, p_drop, training, loss, n_real, gen_step, count, loss_out,
-                   want_dy=True, wgrad=None):
+                   want_dy=True, wgrad=None, targets=None, loss_extra=None):
     """Head forward, the named loss and its gradient in two launches (+ one small reduction), no autograd node:
     returns (out [B], dy [B, N, F] or None).  ``loss_out`` (0-dim tensor) receives the loss value; ``wgrad`` =
-    (dw, db) buffers the head's own parameter gradients are ADDED to (the flat .grad views), or None."""
+    (dw, db) buffers the head's own parameter gradients are ADDED to (the flat .grad views), or None.  ``targets`` [B]: jet b
+    is scored against ``targets[b]`` instead of 1 / 0; ``loss_extra`` (one float): added to the loss value (``label_targets``)."""
     y, m = _head_inputs(y, mask)
     B, N, F = y.shape
     dev = y.device
@@ -2063,6 +2106,12 @@ def disc_head_loss(y, mask, w, b, *, mean, sigmoid, p_drop, training, loss, n_re
     h.dy, h.ld_dy = _p(dy), F
     if wgrad is not None:
         h.dw, h.db, h.accumulate = _p(wgrad[0]), _p(wgrad[1]), 1
+    for t, k, name in ((targets, B, "targets"), (loss_extra, 1, "loss_extra")):
+        if t is not None:
+            _chk(t, name)
+            if not t.is_contiguous() or t.numel() != k or t.device != dev:
+                raise ValueError(f"disc_head_loss: {name} must be contiguous with {k} elements on {dev}, got {tuple(t.shape)} on {t.device}")
+    h.targets, h.loss_extra = _p(targets), _p(loss_extra)
     check(_lib.lib().mpg_disc_head_loss(C.byref(h), _stream()), "mpg_disc_head_loss")
     return out, dy
 

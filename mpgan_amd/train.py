@@ -14,6 +14,8 @@ only (``once_differentiable``), so the penalty's own pass D(interpolated) takes 
 D(generated) stay on the fused kernels; both discriminators (``MPDiscriminator``, ``GAPT_D``) have that route.
 Jet augmentation (``--aug-*``, train.py:438-442, :508-511; ``TrainStep(augment=...)``) is one affine map per jet drawn on the
 device inside the iteration (``ops.augment``), from the seed that keys the noise and the dropout masks.
+Label smoothing / label noise (``--label-smoothing`` / ``--label-noise``, train.py:341-363; ``TrainStep(label_smoothing=...,
+label_noise=...)``) are per-jet targets drawn on the device by one launch in front of D's head (``ops.label_targets``).
 The training data can live on the device as well (``TrainStep(loader=data.DeviceJetLoader(...))``): the batch is then gathered by
 one launch at the top of the iteration, inside the capture, in the order of a keyed shuffle.
 
@@ -324,13 +326,31 @@ class Augment:
 AUG_SITES = {"D_fake": 0, "G_fake": 1, "D_real": 2}   # ops.augment's sites within an iteration
 
 
-def d_loss(loss: str, out: torch.Tensor, B: int, real: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``calc_D_loss`` (train.py:331-395, without label smoothing / noise) on D's outputs for the CONCATENATED
+def effective_targets(y_real: torch.Tensor, y_fake: torch.Tensor, smoothing: bool):
+    """(t [2B], extra): calc_D_loss's labels ``Y_real`` / ``Y_fake`` (train.py:353-363, after the noise) as ``d_loss`` and the fused
+    head take them -- loss = sum_b term(out_b, t_b) / B + extra.  Without smoothing the labels are [B, 1] like D's outputs: t = Y,
+    extra = 0.  With smoothing they are [B] and ``MSELoss(out [B, 1], Y [B])`` broadcasts to [B, B] (train.py:369-370):
+    mean_ij (out_i - Y_j)^2 = mean_i (out_i - mean(Y))^2 + popvar(Y) per half, so t is each half's mean and extra the two
+    population variances.  Any device and dtype."""
+    y_real, y_fake = y_real.reshape(-1), y_fake.reshape(-1)
+    if not smoothing:
+        return torch.cat([y_real, y_fake]), torch.zeros((), device=y_real.device, dtype=y_real.dtype)
+    t = torch.cat([y_real.mean().expand(y_real.numel()), y_fake.mean().expand(y_fake.numel())])
+    return t, y_real.var(unbiased=False) + y_fake.var(unbiased=False)
+
+
+def d_loss(loss: str, out: torch.Tensor, B: int, real: Optional[torch.Tensor] = None,
+           extra: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``calc_D_loss`` (train.py:331-395) on D's outputs for the CONCATENATED
     batch ``out[:B]`` = real, ``out[B:]`` = generated: D_real_loss + D_fake_loss, each a mean over its B jets.
-    Written on the whole vector with a 0/1 target (no slicing: a slice costs a zero-fill and a copy in autograd)."""
+    Written on the whole vector with a 0/1 target (no slicing: a slice costs a zero-fill and a copy in autograd).
+    Label smoothing / noise (train.py:353-363; ``og`` / ``ls`` only): ``real`` = the per-jet targets and ``extra`` the scalar of
+    ``effective_targets``, added to the value."""
     out = out.reshape(-1)
     if real is None:
         real = (torch.arange(2 * B, device=out.device) < B).to(out.dtype)   # 1 for the real half
+    if extra is not None:
+        return d_loss(loss, out, B, real) + extra.reshape(())
     if loss == "ls":
         return ((out - real) ** 2).sum() / B
     if loss == "og":  # nn.BCELoss (clamps its logarithms at -100)
@@ -396,16 +416,24 @@ class TrainStep:
     optional process group for data-parallel gradient averaging (RCCL over xGMI).  ``num_critic`` / ``num_gen``: the reference's
     ``--num-critic`` / ``--num-gen`` -- ``step()`` is one batch of the epoch loop and trains D, G or both as train.py:841 / :864
     say for ``batch_ndx`` (``start_epoch()`` where the reference's ``for batch_ndx, ...`` begins); ``last_ran`` names what ran.
-    ``track_epoch_losses``: the epoch's loss sums on the device, read by ``epoch_losses()``."""
+    ``track_epoch_losses``: the epoch's loss sums on the device, read by ``epoch_losses()``.  ``label_smoothing`` / ``label_noise``:
+    calc_D_loss's two options (train.py:341-363) for ``og`` / ``ls`` -- ``ls`` + smoothing in the reference's [B, B] broadcast
+    form, ``og`` + smoothing refused as the reference's BCELoss refuses it, ``w`` / ``hinge`` untouched by either."""
 
     def __init__(self, G: nn.Module, D: nn.Module, batch_size: int, num_particles: int, latent: int = 32,
                  lr_disc: float = 3e-5, lr_gen: float = 1e-5, noise_std: float = 0.2, use_graphs: bool = True,
                  process_group=None, world_size: int = 1, batch_real_fake: bool = True, loss: str = "ls",
                  optimizer: str = "rmsprop", betas=(0.9, 0.999), gp_lambda: float = 0.0,
                  graph_collectives: Optional[bool] = None, augment=None, loader=None, num_critic: int = 1, num_gen: int = 1,
-                 track_epoch_losses: bool = False):
+                 track_epoch_losses: bool = False, label_smoothing: bool = False, label_noise: float = 0.0):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+        if isinstance(label_noise, bool) or not 0.0 <= float(label_noise) <= 1.0:
+            raise ValueError(f"label_noise is a probability in [0, 1], got {label_noise!r}")
+        if label_smoothing and loss == "og":
+            raise ValueError("label_smoothing with loss = 'og': the reference draws the smoothed labels with shape [B] "
+                             "(train.py:354-355) and its nn.BCELoss refuses them against outputs [B, 1] (\"Using a target size ... "
+                             "that is different to the input size\", train.py:366); smoothing runs with loss = 'ls' only")
         for name, v in (("num_critic", num_critic), ("num_gen", num_gen)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
@@ -541,6 +569,17 @@ class TrainStep:
         # (FlatParams.step(zero_grad=True)): no memset of its own at the top of train_D / train_G.  A caller that accumulates
         # into the networks' .grad between iterations calls ``mark_grads_dirty()``.
         self._clean = {"D": True, "G": True}
+        # Label smoothing / label noise of calc_D_loss (train.py:353-363, ``--label-smoothing`` / ``--label-noise``): the D
+        # step's per-jet targets, drawn by one small launch in front of the head (ops.label_targets) from the seed that keys the
+        # noise and the dropout masks.  ``og`` / ``ls`` only, as in the reference (w / hinge never look at the two options);
+        # with neither on: no launch, no buffers, the step as it was.  ``label_drawn``: the labels Y of the last D step as
+        # drawn; ``label_targets`` / ``label_extra``: what the loss made of them (``effective_targets``).
+        self.label_smoothing, self.label_noise = bool(label_smoothing), float(label_noise)
+        self.labels_on = loss in ("og", "ls") and (self.label_smoothing or self.label_noise > 0.0)
+        if self.labels_on:
+            self.label_targets = torch.zeros(2 * batch_size, device=dev)
+            self.label_extra = torch.zeros(1, device=dev)
+            self.label_drawn = torch.zeros(2 * batch_size, device=dev)
         # a device-resident data set (data.DeviceJetLoader): its feed launch is the first thing of every iteration
         self.loader = None
         if loader is not None:
@@ -611,6 +650,27 @@ class TrainStep:
             return ops.AugmentFn.apply(x, self.aug_p, a.flags, a.translate_ratio, a.scale_sd, site, self.aug_params[site])
         return ops.augment(x, self.aug_p, a.flags, a.translate_ratio, a.scale_sd, site, out=x if in_place else None,
                            params=self.aug_params[site])[0]
+
+    def _draw_labels(self):
+        """calc_D_loss's ``Y_real`` / ``Y_fake`` (train.py:353-363) of this D step into the static label buffers.  CPU (host-logic
+        tests with toy modules): the reference's own four calls in its order, from torch's generator."""
+        B = self.B
+        if self.dev.type == "cuda":
+            ops.label_targets(B, self.label_smoothing, self.label_noise, self.dev,
+                              out=(self.label_targets, self.label_extra, self.label_drawn))
+            return
+        if self.label_smoothing:
+            y_real = torch.empty(B).uniform_(0.7, 1.2)
+            y_fake = torch.empty(B).uniform_(0.0, 0.3)
+        else:
+            y_real, y_fake = torch.ones(B), torch.zeros(B)
+        if self.label_noise:
+            y_real[torch.rand(B) < self.label_noise] = 0
+            y_fake[torch.rand(B) < self.label_noise] = 1
+        t, extra = effective_targets(y_real, y_fake, self.label_smoothing)
+        self.label_targets.copy_(t)
+        self.label_extra.copy_(extra.reshape(1))
+        self.label_drawn.copy_(torch.cat([y_real, y_fake]))
 
     def _bridge(self) -> bool:
         """GAPT: gen's ``final_fc`` + tanh and disc's ``input_embedding`` as one launch each way (``ops.GenDiscBridgeFn``;
@@ -684,9 +744,11 @@ class TrainStep:
     def _head_loss_backward(self, y, mask, gen_step: bool, then=None):
         """The fused head with its loss (train_D: with the head's own weight gradients), then the backward from (y, dy)."""
         w, b, mean, sigmoid, p = self.D.fused_head()
+        # (train_D under label smoothing / noise: the targets ``_draw_labels`` left; calc_G_loss has neither)
+        lab = {"targets": self.label_targets, "loss_extra": self.label_extra} if self.labels_on and not gen_step else {}
         _, dy = ops.disc_head_loss(y, mask, w, b, mean=mean, sigmoid=sigmoid, p_drop=p, training=self.D.training, loss=self.loss,
                                    n_real=self.B, gen_step=gen_step, count=self.B, loss_out=self.G_loss if gen_step else self.D_loss,
-                                   want_dy=True, wgrad=None if gen_step else (w.grad, None if b is None else b.grad))
+                                   want_dy=True, wgrad=None if gen_step else (w.grad, None if b is None else b.grad), **lab)
         self._sum_epoch("G" if gen_step else "D")
         self._backward(y, dy, then)
 
@@ -733,13 +795,19 @@ class TrainStep:
         route = self._route()
         fake, jets = self._generate_for_D(route)
         if route != "module":
+            if self.labels_on:
+                self._draw_labels()
             # real jets sit in the first half of the static batch; the generator has written the second half itself
             return self._head_loss_backward(*self._features(route, jets, self._labels2, False), False, late_fork)
         if self.batch_real_fake:
             out = self.D(torch.cat([self.data, fake], 0), torch.cat([self.labels, self.labels], 0))
         else:
             out = torch.cat([self.D(self.data.clone(), self.labels).reshape(-1), self.D(fake, self.labels).reshape(-1)])
-        loss = d_loss(self.loss, out, self.B, self._real)
+        if self.labels_on:     # (drawn where calc_D_loss draws them: behind both passes of D, in front of the penalty)
+            self._draw_labels()
+            loss = d_loss(self.loss, out, self.B, self.label_targets, self.label_extra)
+        else:
+            loss = d_loss(self.loss, out, self.B, self._real)
         self.D_loss.copy_(loss.detach())   # (D_real_loss + D_fake_loss: the reference's losses["D"] leaves the penalty out)
         self._sum_epoch("D")
         if self.gp_lambda:
