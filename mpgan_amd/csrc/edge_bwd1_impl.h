@@ -188,7 +188,9 @@ MPG_DEV void edge_bwd1_body(const MpgEdgeBwd& p, const MpgChain* const cdxp = nu
         pc0 = cj[lane];
         pc1 = cj[64 + (lane & 31)];
     };
-    prefetch(w);
+    // (an empty share has no list entry to take an index from -- lst[0] lies behind the list's end --: nothing is requested.
+    // Wave-uniform; inside the loop nvalid >= 1 and the clamp lands on a written entry.)
+    if (nvalid > 0) prefetch(w);
 #ifdef MPG_B1_STAMP
     unsigned long long b1_acc[6] = {}, b1_t = __builtin_amdgcn_s_memtime();
     const unsigned long long b1_l0 = b1_t;

@@ -283,7 +283,10 @@ MPG_DEV void edge_bwd_body(const MpgEdgeBwd& p) {
 #pragma unroll
                 for (int k = 0; k < 16; ++k) dqacc[q][m][k] = 0.f;
     }
-    prefetch(w);
+    // (an empty share has no list entry to take an index from -- lst[0] lies behind the list's end --: nothing is requested,
+    // neither sign words nor rows of c and es, all through raw pointers here.  Wave-uniform; inside the loop nvalid >= 1 and
+    // the clamp lands on a written entry.)
+    if (nvalid > 0) prefetch(w);
     for (int pq = w; 2 * pq < nvalid; pq += 4) {
         const bool has2 = 2 * pq + 1 < nvalid;
         B2_STAMP(0);
@@ -306,7 +309,7 @@ MPG_DEV void edge_bwd_body(const MpgEdgeBwd& p) {
 #pragma unroll
         for (int sd = 0; sd < 2; ++sd) {
             float mj;
-            if constexpr (NQ == 0) mj = lmk[min(2 * pq + sd, nvalid - 1)];
+            if constexpr (NQ == 0) mj = lmk[min(2 * pq + sd, nvalid - 1)];   // (inside the loop nvalid >= 1; an LDS read of a written entry)
             else mj = p.mask ? p.mask[b * p.N + jj[sd]] : 1.f;
             const float mjs = (sd == 0 || has2) ? mj * p.dscale * gunit : 0.f;
             float in_set = 1.f;

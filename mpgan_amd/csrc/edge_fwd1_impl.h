@@ -186,7 +186,10 @@ MPG_DEV void edge_fwd1_body(const MpgEdgeFwd& p, const MpgChain* const cp = null
             for (int q = 0; q < NQ; ++q) pes[q] = p.es[((size_t)(b * p.N + jn) * NQ + q) * p.N + (vi ? i : 0)];
         }
     };
-    prefetch(w);
+    // (an empty share -- a jet without unmasked senders, or fewer of them than sender chunks -- has no list entry to take an
+    // index from: lst[0] then lies behind the list's end, and a row of c "of" that stale word is up to 65535 rows away.  The
+    // condition is wave-uniform; inside the loop nvalid >= 1 and the clamp lands on a written entry.)
+    if (nvalid > 0) prefetch(w);
 #ifdef MPG_F1_STAMP
     unsigned long long f1_acc[8] = {}, f1_t = __builtin_amdgcn_s_memtime();
     const unsigned long long f1_t0 = f1_t;

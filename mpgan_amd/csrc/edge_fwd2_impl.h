@@ -198,7 +198,10 @@ MPG_DEV void edge_fwd_body(const MpgEdgeFwd& p) {
             }
         }
     };
-    prefetch(w);
+    // (an empty share -- a jet without unmasked senders, or fewer of them than sender chunks -- has no list entry to take an
+    // index from: lst[0] then lies behind the list's end, and the rows of c and es "of" that stale word are up to 65535 rows
+    // away.  The condition is wave-uniform; inside the loop nvalid >= 1 and the clamp lands on a written entry.)
+    if (nvalid > 0) prefetch(w);
     for (int pq = w; 2 * pq < nvalid; pq += 4) {
         const bool has2 = 2 * pq + 1 < nvalid;
         int jj[2];
@@ -208,7 +211,7 @@ MPG_DEV void edge_fwd_body(const MpgEdgeFwd& p) {
         uint32_t erow[2];
 #pragma unroll
         for (int sd = 0; sd < 2; ++sd) {
-            const float mj = lmk[min(2 * pq + sd, nvalid - 1)];
+            const float mj = lmk[min(2 * pq + sd, nvalid - 1)];   // (inside the loop nvalid >= 1; an LDS read of a written entry)
             mjs[sd] = (sd == 0 || has2) ? mj * p.dscale * (1.f / SC_E3) : 0.f;   // (the layer-3 output carries SC_E3)
             if (p.nbr != nullptr) {  // k-nearest-neighbour graph: sender j counts for this lane's receiver only if its bit is set
                 const unsigned int wb = p.nbr[(size_t)(b * p.N + (vi ? i : 0)) * ((p.N + 31) >> 5) + (jj[sd] >> 5)];

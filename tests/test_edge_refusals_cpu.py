@@ -59,6 +59,12 @@ CASES = [
     (_fwd, dict(f16=0), -8),
     (_fwd, dict(two_term=2), -8),
     (_fwd, dict(N=1000), -6),
+    # the border of the list: 161 senders in one chunk are refused, in two chunks they get past the list check (index mode) --
+    # and, with a fault the entry checks later, still return before any launch
+    (_fwd, dict(N=161, SC=1), -6),
+    (_fwd, dict(N=161, SC=1, es=PTR), -6),
+    (_fwd, dict(N=161, SC=2, es=PTR), -3),              # wq null
+    (_fwd, dict(N=160, SC=1, es=PTR), -3),
     (_fwd, dict(es=PTR), -3),                           # wq null
     (_fwd, dict(B=100000, N=150, stageE2=PTR), -7),
     (_fwd, dict(B=0, alpha=2.0), -1),                   # two faults at once: the order of the checks
@@ -74,6 +80,10 @@ CASES = [
     (_bwd, dict(alpha=-1.0), -4),
     (_bwd, dict(f16=0), -8),
     (_bwd, dict(N=1000), -6),
+    (_bwd, dict(N=161, SC=1), -6),
+    (_bwd, dict(N=161, SC=1, stageZ2=PTR), -6),
+    (_bwd, dict(N=161, SC=2, stageZ2=PTR), -9),         # past the list check: gexp null
+    (_bwd, dict(N=160, SC=1, stageZ2=PTR), -9),
     (_bwd, dict(B=100000, N=150), -7),
     (_bwd, dict(stageZ2=PTR), -9),                      # gexp null
     (_bwd, dict(es=PTR), -3),                           # wq null

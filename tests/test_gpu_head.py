@@ -249,3 +249,83 @@ def test_slab_sums_equal_sequential_adds():
     assert _lib.lib().mpg_slab_sums(ops._p(A), 2, 24, ops._p(A), 2, 24, ops._p(out), 4, 6, ops._stream()) == -2      # cols % 4
     A = torch.zeros(2 * 4 * 8 + 1, device="cuda")
     assert _lib.lib().mpg_slab_sums(ops._p(A, 1), 2, 32, ops._p(A, 1), 2, 32, ops._p(out), 4, 8, ops._stream()) == -5  # 16-byte alignment
+
+
+def test_label_zero_gives_an_empty_jet():
+    """A label of 0 (``int(label * N) == 0``) is how the generator comes by a jet without particles: ``ops.rank_mask`` and
+    ``ops.normal_noise_masked`` give it an all-zero mask and an all-one ``ignore``; the jets beside it keep theirs."""
+    from mpgan_amd import ops
+    dev = torch.device("cuda:0")
+    B, N, L = 3, 30, 32
+    labels = torch.tensor([[0.0], [7 * np.float32(1.0 / N)], [0.0]], device=dev)
+    ops.set_seed(5, dev)
+    z, m1, i1 = ops.normal_noise_masked((B, N, L), 0.2, labels, site=0, device=dev)
+    m0, i0 = ops.rank_mask(z[:, :, 0], labels, N, with_ignore=True)
+    for m, i in ((m0, i0), (m1, i1)):
+        assert float(m[0].abs().max()) == 0.0 and float(m[2].abs().max()) == 0.0
+        assert bool((i[0] == 1).all()) and bool((i[2] == 1).all())
+        assert float(m[1].sum()) == 7.0 and torch.equal(i[1], 1 - m[1])
+    assert torch.equal(m0, m1) and torch.equal(i0, i1)
+
+
+@pytest.mark.parametrize("N", [30, 150])
+def test_rank_mask_at_every_multiplicity(N):
+    """label = k * float32(1 / N) for every k in 0 .. N: the particle count is ``(labels * N).int() - 1 + 1`` as torch evaluates
+    it in fp32 -- where the product rounds decides whether a jet loses a particle, and k = 0 is the only empty one."""
+    from mpgan_amd import ops
+    g = torch.Generator(device="cuda").manual_seed(N)
+    x0 = torch.randn(N + 1, N, device="cuda", generator=g)
+    labels = (torch.arange(N + 1, device="cuda").float() * np.float32(1.0 / N)).reshape(N + 1, 1)
+    m, ign = ops.rank_mask(x0, labels, N, with_ignore=True)
+    n = ((labels[:, -1] * N).int() - 1 + 1).clamp(0, N)
+    n_cpu = ((labels[:, -1].cpu() * N).int() - 1 + 1).clamp(0, N)
+    assert torch.equal(n.cpu(), n_cpu)
+    assert torch.equal(m.sum(1).int(), n) and torch.equal(ign, 1 - m)
+    assert torch.equal(m, _ref_rank_mask(x0, labels, N))
+    assert [k for k in range(N + 1) if int(n_cpu[k]) == 0] == [0] and n_cpu.tolist() == list(range(N + 1))
+
+
+@pytest.mark.parametrize("sigmoid", [True, False])
+def test_disc_head_mean_with_an_empty_jet(sigmoid):
+    """``mean=True`` and a jet without particles: the pooled sum 0 is divided by 0 + 1e-12, so ``out`` is act(bias), the jet's dy
+    rows are exactly zero, and dw / db agree with the fp64 restatement -- through autograd and through the fused loss."""
+    from mpgan_amd import ops
+    from oracle import train_ref as T
+    g = torch.Generator(device="cuda").manual_seed(21)
+    B, N, F = 6, 30, 32
+    y = torch.randn(B, N, F, device="cuda", generator=g).mul_(0.3).requires_grad_(True)
+    mask = (torch.rand(B, N, 1, device="cuda", generator=g) < 0.7).float()
+    mask[2] = 0
+    w = torch.randn(1, F, device="cuda", generator=g).mul_(0.2).requires_grad_(True)
+    b = torch.randn(1, device="cuda", generator=g).requires_grad_(True)
+    up = torch.randn(B, device="cuda", generator=g)
+    out = ops.DiscHeadFn.apply(y, mask, w, b, True, sigmoid, 0.0, False)
+    (out * up).sum().backward()
+    yr, wr, br = (t.detach().double().requires_grad_(True) for t in (y, w, b))
+    ref = _ref_head(yr, mask.double(), wr, br, True, sigmoid).reshape(-1)
+    (ref * up.double()).sum().backward()
+    act = torch.sigmoid(b.detach().double()) if sigmoid else b.detach().double()
+    assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(y.grad).all())
+    assert abs(float(out[2]) - float(act)) < 1e-5 * max(1.0, abs(float(act)))
+    assert float(y.grad[2].abs().max()) == 0.0 and float(yr.grad[2].abs().max()) == 0.0
+    assert rel_err(out.detach().cpu().numpy(), ref.detach().cpu().numpy()) < 1e-5
+    for a, r in ((y.grad, yr.grad), (w.grad, wr.grad), (b.grad, br.grad)):
+        assert bool(torch.isfinite(a).all())
+        assert rel_err(a.cpu().numpy(), r.cpu().numpy()) < 1e-5
+    # the fused loss on the same head: D step, three real and three generated jets, the empty one among the real
+    loss = "ls" if sigmoid else "hinge"
+    loss_out = torch.zeros((), device="cuda")
+    dw, db = torch.zeros(1, F, device="cuda"), torch.zeros(1, device="cuda")
+    out2, dy = ops.disc_head_loss(y.detach(), mask, w.detach(), b.detach(), mean=True, sigmoid=sigmoid, p_drop=0.0, training=True,
+                                  loss=loss, n_real=B // 2, gen_step=False, count=B // 2, loss_out=loss_out, wgrad=(dw, db))
+    yr, wr, br = (t.detach().double().requires_grad_(True) for t in (y, w, b))
+    o = _ref_head(yr, mask.double(), wr, br, True, sigmoid)
+    Lr = T.d_loss_ref(loss, o[:B // 2], o[B // 2:])
+    Lr.backward()
+    assert abs(float(loss_out) - float(Lr)) < 1e-5 * max(abs(float(Lr)), 1e-3)
+    assert abs(float(out2[2]) - float(act)) < 1e-5 * max(1.0, abs(float(act)))
+    assert float(dy[2].abs().max()) == 0.0 and bool(torch.isfinite(dy).all())
+    assert rel_err(out2.cpu().numpy(), o.detach().reshape(-1).cpu().numpy()) < 1e-5
+    assert rel_err(dy.cpu().numpy(), yr.grad.cpu().numpy()) < 1e-5
+    assert rel_err(dw.cpu().numpy(), wr.grad.cpu().numpy()) < 1e-5
+    assert rel_err(db.cpu().numpy(), br.grad.cpu().numpy()) < 1e-5

@@ -117,7 +117,8 @@ def _sign_disagreements(neg, probe64, mask64):
     return out
 
 
-def _run_case(B, N, F, out, use_mask, sum_agg, seed, skip=True, alpha=0.2, control=None, flips=None, conditioned=None):
+def _run_case(B, N, F, out, use_mask, sum_agg, seed, skip=True, alpha=0.2, control=None, flips=None, conditioned=None, mask=None,
+              tensors=None):
     """HIP MPLayer vs fp64 oracle on the same inputs.  Returns per-tensor
     (max-norm error, fraction of elements off by more than 1e-3 of the max) and the oracle's
     kink margin = min |pre-activation| / max |pre-activation| over all LeakyReLU inputs.
@@ -127,7 +128,9 @@ def _run_case(B, N, F, out, use_mask, sum_agg, seed, skip=True, alpha=0.2, contr
     (``hip``) and of the fp32 oracle (``fp32``), per layer.
     ``conditioned`` (a dict): receives the errors against the SIGN-CONDITIONED fp64 oracle -- the same oracle with every
     LeakyReLU branch taken as the HIP forward took it (its own sign bits: ``_hip_signs``).  That is the gradient of the
-    function the kernels computed: it must match strictly (no kink left to flip), whatever the kink decisions were."""
+    function the kernels computed: it must match strictly (no kink left to flip), whatever the kink decisions were.
+    ``mask`` ([B, N, 1] of 0 / 1, with ``use_mask``): this mask instead of a drawn one -- jets without any particle included.
+    ``tensors`` (a dict): receives ``name -> (HIP tensor, oracle tensor)`` as float64 numpy arrays, for checks per jet."""
     import oracle
     from oracle import train_ref as T
     from mpgan_amd import ops
@@ -140,7 +143,10 @@ def _run_case(B, N, F, out, use_mask, sum_agg, seed, skip=True, alpha=0.2, contr
     x64 = torch.from_numpy(rs.normal(0, 0.5, size=(B, N, F)))
     g64 = torch.from_numpy(rs.normal(size=(B, N, out)))
     mask64 = None
-    if use_mask:
+    if use_mask and mask is not None:
+        mask64 = torch.as_tensor(np.asarray(mask), dtype=torch.float64).reshape(B, N, 1).clone()
+        assert bool(((mask64 == 0) | (mask64 == 1)).all())
+    elif use_mask:
         m = np.zeros((B, N, 1))
         for b in range(B):
             m[b, rs.permutation(N)[: rs.randint(1, N + 1)], 0] = 1
@@ -184,6 +190,8 @@ def _run_case(B, N, F, out, use_mask, sum_agg, seed, skip=True, alpha=0.2, contr
         b = b.numpy()
         errs[k] = rel_err(a, b)
         frac[k] = float((np.abs(a - b) > 1e-3 * np.abs(b).max()).mean())
+        if tensors is not None:
+            tensors[k] = (a, b)
     if conditioned is not None:
         sdc = {"L." + k: v.clone().requires_grad_(True) for k, v in sd64.items()}
         xc = x64.clone().requires_grad_(True)
@@ -571,7 +579,7 @@ def test_mplayer_dropout_exact(p_drop, F, alpha):
     from oracle import train_ref as T
     from mpgan_amd import ops
     from mpgan_amd.mpgan import MPLayer
-    B, N, out = 3, 30, 32
+    B, N, out = 5, 30, 32   # (three drawn masks, a jet without any particle, a jet with one)
     V = B * N
     sd64 = T.init_state_dict(_mplayer_shapes(F, out), seed=77, dtype=torch.float64)
     layer = MPLayer(F, [96, 160, 192], [256, 256], out, leaky_relu_alpha=alpha, dropout_p=p_drop).to(_dev())
@@ -582,6 +590,11 @@ def test_mplayer_dropout_exact(p_drop, F, alpha):
     g64 = torch.from_numpy(rs.normal(size=(B, N, out)))
     mask64 = torch.from_numpy((rs.uniform(size=(B, N, 1)) < 0.8).astype(np.float64))
     mask64[:, 0] = 1
+    # an empty jet and a one-particle jet: workgroups of the dropout kernels without a sender (three sender chunks at this size)
+    mask64[3] = 0
+    mask64[4] = 0
+    mask64[4, 17] = 1
+    assert ops.edge_plan(B, N, mask=True, need_grad=True).SC > 1
     ops.set_seed(4242)
     if F == 3:   # as MPDiscriminator hands it over: a column slice of the [B, N, 4] batch
         x4 = torch.cat([x64.float(), mask64.float() - 0.5], 2).to(_dev()).requires_grad_(True)
@@ -707,6 +720,9 @@ def test_edge_scalars_separable_case_equals_node_features(p_drop, use_mask, N, a
     if use_mask:
         mask = (torch.from_numpy(rs.uniform(size=(B, N, 1))) < 0.8).float().to(dev)
         mask[:, 0] = 1
+        if p_drop == 0.0:   # one case with a jet without any particle: workgroups of the four-wave kernels without a sender
+            mask[1] = 0
+            assert ops.edge_plan(B, N, es=True, mask=True, need_grad=True).SC > 1
     W1a, W1c, w = t(96, F, sc=0.2), t(96, F, sc=0.2), t(96, 1, sc=0.2)
     b1, W2, b2, W3, b3 = t(96, sc=0.1), t(160, 96, sc=0.1), t(160, sc=0.1), t(192, 160, sc=0.1), t(192, sc=0.1)
     V1a, V1x, c1, V2, c2, V3, c3 = t(256, 192, sc=0.1), t(256, F, sc=0.1), t(256, sc=0.1), t(256, 256, sc=0.1), t(256, sc=0.1), t(out, 256, sc=0.1), t(out, sc=0.1)
