@@ -682,6 +682,50 @@ int mpg_batch_feed(const float* particles, const float* labels_in, int64_t n, in
                    uint32_t* ticket, int B, uint64_t stride, float* data, float* labels, float* dcat, float* x3, float* mask2,
                    float* ign2, float* labels2, void* stream);
 
+/* Bulk generation as a stream of rows (gen.JetSampler; csrc/sampler.hip).  Row g = 0, 1, 2, ... of the stream is one generated
+ * jet; a launch of B jets (one CHUNK; B is fixed for a stream) covers rows *cursor .. *cursor + B - 1, and chunk c = rows
+ * c B .. c B + B - 1.  Everything a row holds is a function of (key, g) and the generator's weights:
+ *   its label   table[idx(g)],  idx(g) = ((uint64) word(MPG_PICK_TAG, (uint32) g, (uint32) (g >> 32)) * n) >> 32,  word the
+ *               project's counter-based hash as the keyed shuffle above spells it out, with the 64-bit key in place of the seed.
+ *               This is rng.choice(len(labels), size) of the reference's gen.py:105-107 as a keyed stream: a draw with
+ *               replacement from table [n], the data set's num_particles / N.  The multiply-shift is not exactly uniform:
+ *               an index is taken by floor(2^32 / n) or that plus one of the 2^32 words, a relative bias below n / 2^32.
+ *   its noise   drawn by mpg_normal / mpg_normal_rank_mask under the seed word of its chunk,
+ *               seed_c = key + c * 0x9E3779B97F4A7C15 (mod 2^64), at the row's place within the chunk.
+ * So the labels are a function of the row alone, the noise of (chunk index, place in the chunk): the same key and B give the
+ * same jets whatever ran before, and any row can be recomputed.  MPG_PICK_TAG stays clear of the dropout sites (below 2^27)
+ * and of the noise, augmentation, label and shuffle tags.
+ *
+ * mpg_label_pick: labels[b] = table[idx(*cursor + b)], b < B; table, *cursor and labels in device memory; the cursor is only
+ * read.  n < 1, n > 2^31 - 1, B < 1, a NULL table, cursor or labels: -1.
+ * mpg_label_pick_host: out[c] = idx(pos0 + c), c < count -- the same body compiled for the host, no HIP call.
+ * 1 <= n <= 2^31 - 1, count >= 0, out non-NULL when count > 0 (else -1). */
+#define MPG_PICK_TAG 0x50000000
+int mpg_label_pick(const float* table, int64_t n, uint64_t key, const uint64_t* cursor, int B, float* labels, void* stream);
+int mpg_label_pick_host(uint64_t key, uint64_t pos0, int64_t count, int64_t n, int32_t* out);
+
+/* mpg_jets_finish: the epilogue of the reference's gen.py:127-141 for one chunk, written into the final array.
+ * feat: the chunk's particle rows [B N, >= 3] at row stride ld_feat floats, past the generator's final activation
+ * (generate_parts(feat_out=...): ld_feat 3; a module's [B, N, 4] output: ld_feat 4).  mask [B, N] (1 real, 0 padded) or NULL
+ * for "all real".  maxes, norms, shifts: three floats each in HOST memory, read at the call (data.FEATURE_MAXES[jet_type],
+ * FEATURE_NORMS, FEATURE_SHIFTS).  out [total, N, 3] and mask_out [total, N] (or NULL) in device memory.
+ * Jet b < B is stream row g = *cursor + b and row r = g - row0 of out (row0: the stream row at which the caller's array
+ * begins; uint64 arithmetic).  r >= total: nothing is written for the jet -- the last chunk of a call may be short.  Otherwise,
+ * per particle i, with x = its feature row and m = mask[b, i]:
+ *   real = mask == NULL or (m - 0.5f) >= 0.5f          (gen.py's gen_jets[:, :, -1] >= 0.5 on the generator's mask - 0.5 column)
+ *   v_f  = real ? ((x_f - shift_f) / norm_f) * max_f : 0,  f = 0, 1, 2: a subtraction, a division and a product, each rounded
+ *          to fp32 on its own, in data.unnormalise_jets' order (nothing contracted);  then v_2 = v_2 < 0 ? 0 : v_2
+ *   out[r, i, :] = v;  mask_out[r, i] = real ? 1 : 0.
+ * One thread per particle; rows of out are 12 bytes: no alignment beyond a float's is assumed of out, feat or the masks.
+ * The same launch then moves the stream on, behind every workgroup's read of the cursor, as mpg_batch_feed does: the workgroup
+ * that arrives last on the agent-scope counter *ticket writes  *cursor += B,  *seed = key + (new cursor / B) * 0x9E3779B97F4A7C15
+ * (mod 2^64: the seed word seed_c of the next chunk) and leaves *ticket at zero, as it found it.  *cursor, *seed and *ticket
+ * live in device memory.  B < 1, N < 1, total < 0, ld_feat < 3, a NULL feat, out, cursor, seed, ticket, maxes, norms or
+ * shifts: -1. */
+int mpg_jets_finish(const float* feat, int ld_feat, const float* mask, int B, int N, const float* maxes, const float* norms,
+                    const float* shifts, float* out, float* mask_out, uint64_t row0, int64_t total, uint64_t key, uint64_t* cursor,
+                    uint64_t* seed, uint32_t* ticket, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -624,9 +624,11 @@ def evaluate_generator(G: torch.nn.Module, real_jets, jet_type: str, num_samples
                        num_w1_eval_samples: int = 10000, labels: Optional[torch.Tensor] = None, model: str = "mpgan",
                        model_args: Optional[dict] = None, batch_size: int = 4096, rng=None,
                        num_cov_mmd_eval_samples: int = 100, real_efps=None, fpd_args: Optional[dict] = None,
-                       kpd_args: Optional[dict] = None) -> dict:
+                       kpd_args: Optional[dict] = None, sampler=None) -> dict:
     """Generate ``num_samples`` jets with ``gen.generate_jets`` and ``evaluate`` them against ``real_jets`` ([n, N, >=3]
-    un-normalised), all on G's device.  ``labels`` (num_particles / N per generated jet) default to the multiplicities of
+    un-normalised), all on G's device.  ``sampler``: a ``gen.JetSampler`` built on ``G`` -- the generated jets are then the next
+    ``num_samples`` rows of its stream (labels drawn from its table; ``labels``, ``model``, ``model_args`` and ``batch_size``
+    are not used).  ``labels`` (num_particles / N per generated jet) default to the multiplicities of
     the real jets, taken in order and repeated as needed -- the reference conditions on the test set's ``jet_data``
     (train.py:712-723).  With ``"fpd"`` or ``"kpd"`` among the keys the 36 EFPs of degree <= 4 of the generated jets are computed
     on the device, and those of the real jets unless ``real_efps`` carries them (train.py:744-755 keeps them in a file per jet
@@ -636,11 +638,18 @@ def evaluate_generator(G: torch.nn.Module, real_jets, jet_type: str, num_samples
     real, _ = _as_tensor(real_jets)
     real = real.to(device)
     N = real.shape[1]
-    if labels is None:
-        idx = torch.arange(num_samples, device=device) % real.shape[0]
-        labels = ((real[idx, :, 2] != 0).sum(1).float() * np.float32(1.0 / N)).reshape(-1, 1)
-    gen_jets = generate_jets(G, num_samples, num_particles=N, labels=labels, jet_type=jet_type, model=model,
-                             model_args=model_args, batch_size=batch_size)
+    if sampler is not None:
+        if sampler.G is not G or sampler.N != N or sampler.jet_type != jet_type:
+            raise ValueError(f"evaluate_generator: the sampler generates {sampler.jet_type!r} jets of {sampler.N} particles from its own "
+                             f"generator; asked for {jet_type!r} jets of {N} particles from G")
+        gen_jets = sampler.sample(num_samples)
+        gen_jets = gen_jets[0] if isinstance(gen_jets, tuple) else gen_jets
+    else:
+        if labels is None:
+            idx = torch.arange(num_samples, device=device) % real.shape[0]
+            labels = ((real[idx, :, 2] != 0).sum(1).float() * np.float32(1.0 / N)).reshape(-1, 1)
+        gen_jets = generate_jets(G, num_samples, num_particles=N, labels=labels, jet_type=jet_type, model=model,
+                                 model_args=model_args, batch_size=batch_size)
     if losses is None:
         losses = {k: [] for k in keys}
     gen_efps = None

@@ -2,7 +2,8 @@
 (train.py:100-282) and the un-normalising epilogue of its ``gen.py`` (:85-145).
 
 Same function names and argument meaning as the reference, so ``train.py``'s evaluation loop and ``gen.py`` can call
-these instead of their own.  Differences, all results-neutral: generation runs under ``torch.no_grad()`` whenever the
+these instead of their own; ``JetSampler`` is the bulk path built for the device (a captured chunk replayed over a keyed
+stream of rows, labels drawn from the data set's multiplicities as gen.py:100-107 draws them).  Differences, all results-neutral: generation runs under ``torch.no_grad()`` whenever the
 caller asked for detached output (the reference builds and then drops the autograd graph, train.py:253-282; without it
 the fused MPLayer skips its sign words and saves nothing for a backward), and the default chunk is sized for the
 device (thousands of jets per launch keep all 256 CUs busy; the reference's default of 16 leaves 240 idle).
@@ -15,8 +16,19 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from .data import unnormalise_jets
+from .data import FEATURE_MAXES, FEATURE_NORMS, FEATURE_SHIFTS, unnormalise_jets
 from .mpgan.mask_utils import mask_manual
+
+
+def get_gen_noise_shape(model_args: dict, num_samples: int, num_particles: int, model: str = "mpgan") -> tuple:
+    """The shape of the generator's input noise per model family (train.py:100-140); see ``get_gen_noise``."""
+    if model in ("mpgan", "old_mpgan"):
+        if model_args.get("lfc"):
+            return (num_samples, model_args["lfc_latent_size"])
+        return (num_samples, num_particles + int(bool(model_args.get("mask_learn_sep"))), model_args["latent_node_size"])
+    if model == "gapt":
+        return (num_samples, num_particles, model_args["embed_dim"])
+    raise NotImplementedError(f"mpgan_amd generates for the mpgan and gapt model families only (got {model!r})")
 
 
 def get_gen_noise(model_args: dict, num_samples: int, num_particles: int, model: str = "mpgan", device=None,
@@ -93,3 +105,212 @@ def generate_jets(G: torch.nn.Module, num_samples: int, num_particles: int = 30,
     finally:
         G.train(was_training)
     return unnormalise_jets(jets, jet_type, mask=mask)
+
+
+SAMPLER_KEY_TERM = 0x8EBC6AF09C88C6E3   # tells a sampler's key from the loader's key and the device seed derived from the same torch seed
+
+
+def sampler_key(seed: int) -> int:
+    """The key of a ``JetSampler`` built with ``seed``: derived as ``DeviceJetLoader`` derives its own, with another term."""
+    return (int(seed) * 0x9E3779B97F4A7C15 + SAMPLER_KEY_TERM) & 0xFFFFFFFFFFFFFFFF
+
+
+def _parts_ok(G) -> bool:
+    """``G.generate_parts`` exists and takes this generator's options (it asserts mask_c without mask_feat_bin / use_mask)."""
+    if not hasattr(G, "generate_parts"):
+        return False
+    ma = getattr(G, "mask_args", None)
+    if ma is not None and (not ma.get("mask_c", True) or ma.get("mask_feat_bin", False)):
+        return False
+    return bool(getattr(G, "use_mask", True))
+
+
+class JetSampler:
+    """Bulk generation on the device: what the reference's ``gen.py`` does -- labels drawn from the data set's multiplicities
+    (:100-107), ``G`` in chunks (:111-125), the un-normalising epilogue (:127-141) -- as ONE chunk of ``chunk`` jets that is
+    captured once and replayed, with nothing drawn or sliced on the host.
+
+    The output is a stream of rows g = 0, 1, 2, ... (include/mpgan_amd.h states it): row g's label is ``table[idx(g)]``, a keyed
+    hash of the row alone (``ops.label_pick_indices`` recomputes it on the host); its noise is drawn under the seed word of its
+    chunk c = g // chunk, ``ops.chunk_seed(key, c)``, at its place within the chunk.  Labels are a function of the row, noise of
+    (chunk index, place in chunk): the same ``seed`` and ``chunk`` give the same jets whatever ran before.  ``sample`` always
+    consumes whole chunks: a call for a number of jets that ``chunk`` does not divide leaves the rest of its last chunk's rows
+    undelivered, and the next call goes on at the next chunk -- so two calls of 5 equal one call of 10 when ``chunk`` divides 5.
+
+    One chunk is, on the current stream: ``ops.label_pick``; the noise and the rank mask in one launch under the sampler's own
+    seed word; ``G.generate_parts`` under ``no_grad`` in eval mode; ``ops.jets_finish``, which writes the chunk's rows of the
+    result and moves the cursor and the seed word on.  With ``use_graphs`` the first three are one hipGraph; ``jets_finish``
+    stays outside it as the one eager launch per chunk, because the output array and its length are its arguments and differ
+    from call to call (no recapture for a caller-owned ``out``).  A generator without ``generate_parts`` (or whose options it
+    asserts against) runs as ``G(noise, labels)`` and ``jets_finish`` reads its [chunk, N, 4] rows in place.
+
+    ``table``: a ``JetArrayDataset``, a ``DeviceJetLoader`` (their ``jet_features`` = num_particles / N) or a 1-D array of
+    labels; kept on G's device.  ``seed`` (default ``torch.initial_seed()``) gives the key.  One rank, CUDA only (the product
+    has no CPU path), ``chunk`` fixed for the sampler's life."""
+
+    def __init__(self, G: torch.nn.Module, table, num_particles: int, jet_type: str = "g", chunk: int = 4096, model: str = "mpgan",
+                 model_args: Optional[dict] = None, noise_std: float = 0.2, seed: Optional[int] = None, use_graphs: bool = True,
+                 with_mask: bool = False):
+        from . import ops
+        dev = next(G.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError(f"JetSampler: the generator lives on {dev}; mpgan_amd has no CPU path (bulk generation runs on "
+                               "the GPU: move the generator there)")
+        if jet_type not in FEATURE_MAXES:
+            raise ValueError(f"JetSampler: unknown jet type {jet_type!r} (one of {sorted(FEATURE_MAXES)})")
+        if chunk < 1 or num_particles < 1:
+            raise ValueError(f"JetSampler: chunk {chunk} x num_particles {num_particles} is not a chunk of jets")
+        labels = table.jet_features if hasattr(table, "jet_features") else table
+        self.table = torch.as_tensor(labels, dtype=torch.float32).reshape(-1).to(dev).contiguous()
+        self.n = int(self.table.numel())
+        if not 1 <= self.n <= 0x7FFFFFFF:
+            raise ValueError(f"JetSampler: a table of 1 .. 2^31 - 1 labels expected, got {self.n}")
+        if model_args is None:
+            model_args = ({"lfc": False, "latent_node_size": getattr(G, "input_node_size", 32)} if model == "mpgan"
+                          else {"embed_dim": getattr(G, "embed_dim", 64)})
+        self.G, self.device, self.N, self.chunk, self.jet_type = G, dev, int(num_particles), int(chunk), jet_type
+        self.noise_std, self.use_graphs, self.with_mask = float(noise_std), bool(use_graphs), bool(with_mask)
+        self.key = sampler_key(torch.initial_seed() if seed is None else seed)
+        B, N = self.chunk, self.N
+        # the stream's state, in device memory: the launches read it and jets_finish moves it on (a replayed hipGraph holds
+        # these addresses: they are written in place, never replaced)
+        self.cursor = torch.zeros((1,), dtype=torch.int64, device=dev)
+        self.seed = torch.full((1,), ops.u64_as_i64(ops.chunk_seed(self.key, 0)), dtype=torch.int64, device=dev)
+        self._ticket = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self._pos = 0            # the cursor as the host knows it (every chunk adds ``chunk``): the row a call's array begins at
+        # the chunk's static buffers
+        noise_shape = get_gen_noise_shape(model_args, B, N, model)
+        self.labels = torch.zeros((B, 1), device=dev)
+        self.noise = torch.zeros(noise_shape, device=dev)
+        self.mask = torch.zeros((B, N), device=dev)
+        self.ignore = torch.zeros((B, N), device=dev)
+        self.parts = _parts_ok(G)
+        self.feat = torch.zeros((B, N, 3 if self.parts else 4), device=dev)
+        self.premask = (self.parts and len(noise_shape) == 3 and noise_shape[1] == N and (N * noise_shape[2]) % 2 == 0
+                        and getattr(G, "noise_mask_ok", lambda: False)())
+        self._graph, self._graph_key = None, None
+
+    # -- one chunk ------------------------------------------------------------------------------
+    def _front(self):
+        """Everything of a chunk in front of ``jets_finish``: labels, noise (+ masks), the generator.  Returns the mask
+        [chunk, N] that ``jets_finish`` reads.  Reads the stream's state, moves nothing: the warm-up may run it freely."""
+        from . import ops
+        B, N = self.chunk, self.N
+        ops.label_pick(self.table, self.key, self.cursor, B, self.labels)
+        if self.premask:
+            _, m, ig = ops.normal_noise_masked(tuple(self.noise.shape), self.noise_std, self.labels, device=self.device,
+                                               mask_out=self.mask, ignore_out=self.ignore, seed_t=self.seed, out=self.noise)
+            pm = (m, ig)
+        else:
+            ops.normal_noise(tuple(self.noise.shape), self.noise_std, device=self.device, seed_t=self.seed, out=self.noise)
+            pm = None
+        if self.parts:
+            _, mask, _ = self.G.generate_parts(self.noise, self.labels, feat_out=self.feat, premask=pm,
+                                               **({} if pm is not None else {"mask_out": self.mask}))
+            if mask.data_ptr() != self.mask.data_ptr():
+                self.mask.copy_(mask.reshape(B, N))
+        else:
+            self.feat.copy_(self.G(self.noise, self.labels))
+            torch.add(self.feat[:, :, 3], 0.5, out=self.mask)
+        return self.mask
+
+    def _param_key(self):
+        return tuple(p.data_ptr() for p in self.G.parameters())
+
+    def _ensure_packed(self):
+        """Weight images of the fused layers follow parameters that changed since the capture (an optimiser step,
+        ``load_state_dict``): the check is the layers' own, made on the host in front of the replays."""
+        for m in self.G.modules():
+            if hasattr(m, "packed_sets"):
+                for pk in m.packed_sets():
+                    pk.ensure()
+
+    def _capture(self, warmup: int = 2):
+        """A short eager warm-up on a side stream (kernels loaded, ticket buffers and the allocator's pools filled -- none of
+        which may happen during a capture), then the chunk's front as one hipGraph.  The warm-up reads the stream's state and
+        moves none of it; every tensor that outlives the capture (the chunk buffers) was allocated when the sampler was built."""
+        dev = self.device
+        s = torch.cuda.Stream(device=dev)
+        s.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                self._front()
+        torch.cuda.current_stream(dev).wait_stream(s)
+        torch.cuda.synchronize(dev)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._front()
+        self._graph, self._graph_key = g, self._param_key()
+
+    # -- the public face ------------------------------------------------------------------------
+    def sample(self, num_samples: int, out: Optional[Tensor] = None, mask_out: Optional[Tensor] = None):
+        """The next ``num_samples`` jets of the stream, un-normalised ``[num_samples, N, 3]`` = (eta_rel, phi_rel, pT_rel)
+        with masked particles zeroed -- what ``generate_jets`` returns --, plus their 0 / 1 masks ``[num_samples, N]`` when the
+        sampler was built ``with_mask``.  ``out`` (``mask_out``): a caller-owned contiguous array of at least that many rows to
+        write into (its first ``num_samples`` rows are returned)."""
+        from . import ops
+        num_samples = int(num_samples)
+        if num_samples < 0:
+            raise ValueError(f"sample: num_samples must be >= 0, got {num_samples}")
+        N, B, dev = self.N, self.chunk, self.device
+        if out is None:
+            out = torch.empty((num_samples, N, 3), device=dev)
+        if out.dim() != 3 or out.shape[0] < num_samples or tuple(out.shape[1:]) != (N, 3) or not out.is_contiguous() \
+                or out.device != dev or out.dtype != torch.float32:
+            raise ValueError(f"sample: out must be a contiguous float32 [>= {num_samples}, {N}, 3] tensor on {dev}, got {tuple(out.shape)}")
+        if self.with_mask and mask_out is None:
+            mask_out = torch.empty((num_samples, N), device=dev)
+        if mask_out is not None and (mask_out.numel() < num_samples * N or not mask_out.is_contiguous() or mask_out.device != dev
+                                     or mask_out.dtype != torch.float32):
+            raise ValueError(f"sample: mask_out must be a contiguous float32 [>= {num_samples}, {N}] tensor on {dev}")
+        was_training = self.G.training
+        self.G.eval()
+        try:
+            with torch.no_grad():
+                row0 = self._pos
+                chunks = -(-num_samples // B)
+                if chunks and self.use_graphs:
+                    if self._graph is None or self._graph_key != self._param_key():
+                        self._capture()
+                    self._ensure_packed()
+                for _ in range(chunks):
+                    if self.use_graphs:
+                        self._graph.replay()
+                        mask = self.mask
+                    else:
+                        mask = self._front()
+                    ops.jets_finish(self.feat, mask, out, maxes=FEATURE_MAXES[self.jet_type], norms=FEATURE_NORMS,
+                                    shifts=FEATURE_SHIFTS, key=self.key, cursor=self.cursor, seed=self.seed, ticket=self._ticket,
+                                    row0=row0, total=num_samples, mask_out=mask_out)
+                    self._pos += B
+        finally:
+            self.G.train(was_training)
+        jets = out[:num_samples]
+        return (jets, mask_out.reshape(-1, N)[:num_samples]) if self.with_mask else jets
+
+    @property
+    def position(self) -> int:
+        """The next stream row (reads the cursor: synchronises)."""
+        return int(self.cursor.item())
+
+    def state_dict(self) -> dict:
+        """The whole state of the stream (reads the cursor: synchronises)."""
+        return {"key": self.key, "cursor": self.position, "chunk": self.chunk, "n": self.n}
+
+    def load_state_dict(self, sd: dict):
+        """Go on where the saved sampler stopped.  The table must be the one saved (same n) and the chunk the same: the rows'
+        labels are indices into that table, and their noise is cut into chunks of that size."""
+        from . import ops
+        if int(sd["n"]) != self.n:
+            raise ValueError(f"JetSampler: the saved state belongs to a table of {int(sd['n'])} labels, this one has {self.n}")
+        if int(sd["chunk"]) != self.chunk:
+            raise ValueError(f"JetSampler: the saved state was cut into chunks of {int(sd['chunk'])} jets, this sampler's are {self.chunk}")
+        cursor = int(sd["cursor"])
+        if cursor < 0 or cursor % self.chunk:
+            raise ValueError(f"JetSampler: cursor {cursor} is not a whole number of chunks of {self.chunk}")
+        key = int(sd["key"]) & 0xFFFFFFFFFFFFFFFF
+        if key != self.key:       # (the key is an argument of the captured label_pick: capture again under the loaded one)
+            self.key, self._graph = key, None
+        self._pos = cursor
+        self.cursor.fill_(cursor)
+        self.seed.fill_(ops.u64_as_i64(ops.chunk_seed(self.key, cursor // self.chunk)))

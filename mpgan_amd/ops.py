@@ -205,14 +205,35 @@ def bump_seed(device="cuda"):
 NOISE_TAG = 0x4E000000   # site tags of ``normal_noise`` (dropout sites stay below 2^27: next_tag)
 
 
-def normal_noise(shape, std: float, site: int = 0, device="cuda", mean: float = 0.0) -> torch.Tensor:
+def _noise_target(shape, device, out):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=torch.float32)
+    _chk(out, "out")
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"noise: out must be a contiguous tensor of shape {tuple(shape)}, got {tuple(out.shape)}")
+    return out
+
+
+def normal_noise(shape, std: float, site: int = 0, device="cuda", mean: float = 0.0, seed_t: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """A fresh [*shape] tensor of N(mean, std^2) samples from the counter-based stream of ``mpg_normal``: keyed by the
     device's seed (``bump_seed`` once per iteration) and ``site`` (which draw of the iteration).  The generator's input noise
-    (train.py:100-141) inside a captured iteration: no torch generator state to carry through the graph."""
-    out = torch.empty(shape, device=device, dtype=torch.float32)
-    check(_lib.lib().mpg_normal(_p(out), out.numel(), _p(seed_tensor(out.device)), NOISE_TAG + int(site), mean, std, _stream()),
-          "mpg_normal")
+    (train.py:100-141) inside a captured iteration: no torch generator state to carry through the graph.
+    ``seed_t``: another 64-bit seed word in device memory (one int64; ``gen.JetSampler`` keys its chunks with its own) instead
+    of the device's; ``out``: the tensor to write into."""
+    out = _noise_target(shape, device, out)
+    seed_t = _seed_word(seed_t, out.device)
+    check(_lib.lib().mpg_normal(_p(out), out.numel(), _p(seed_t), NOISE_TAG + int(site), mean, std, _stream()), "mpg_normal")
     return out
+
+
+def _seed_word(seed_t: Optional[torch.Tensor], device) -> torch.Tensor:
+    """The seed word a noise launch reads: the caller's (one int64 on ``device``) or the device's own."""
+    if seed_t is None:
+        return seed_tensor(device)
+    if seed_t.dtype != torch.int64 or seed_t.numel() != 1 or seed_t.device != device:
+        raise ValueError(f"seed_t: one int64 on {device} expected, got {seed_t.dtype} {tuple(seed_t.shape)} on {seed_t.device}")
+    return seed_t
 
 
 def next_tag(device="cuda", kind: str = "", thr: int = 0) -> int:
@@ -447,18 +468,21 @@ def gate(g, H, *, gate_act, alpha, seed_t=None, tag=0, thr=0, scale=1.0):
 
 
 def normal_noise_masked(shape, std: float, labels: torch.Tensor, site: int = 0, device="cuda", mean: float = 0.0,
-                        mask_out: Optional[torch.Tensor] = None, ignore_out: Optional[torch.Tensor] = None):
+                        mask_out: Optional[torch.Tensor] = None, ignore_out: Optional[torch.Tensor] = None,
+                        seed_t: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
     """``normal_noise`` of a generator's input [B, N, L] AND ``rank_mask`` of its first feature (the jets' masks, mask_c of
-    mpgan/model.py:689-699) in one launch: (noise, mask [B, N], 1 - mask [B, N]).  Same values as the two calls."""
+    mpgan/model.py:689-699) in one launch: (noise, mask [B, N], 1 - mask [B, N]).  Same values as the two calls.
+    ``seed_t`` / ``out``: as ``normal_noise`` takes them."""
     B, N, L = shape
-    out = torch.empty(shape, device=device, dtype=torch.float32)
+    out = _noise_target(shape, device, out)
+    seed_t = _seed_word(seed_t, out.device)
     lab = labels[:, -1]
     if lab.dtype != torch.float32:
         lab = lab.float()
     mask = mask_out if mask_out is not None else torch.empty((B, N), device=device, dtype=torch.float32)
     ign = ignore_out if ignore_out is not None else torch.empty((B, N), device=device, dtype=torch.float32)
     assert mask.is_contiguous() and ign.is_contiguous() and mask.numel() == B * N and ign.numel() == B * N
-    check(_lib.lib().mpg_normal_rank_mask(_p(out), B, N, L, _p(seed_tensor(out.device)), NOISE_TAG + int(site), mean, std,
+    check(_lib.lib().mpg_normal_rank_mask(_p(out), B, N, L, _p(seed_t), NOISE_TAG + int(site), mean, std,
                                           _p(lab), lab.stride(0), _p(mask), _p(ign), _stream()), "mpg_normal_rank_mask")
     return out, mask.view(B, N), ign.view(B, N)
 
@@ -497,6 +521,91 @@ def batch_feed(particles: torch.Tensor, labels_in: torch.Tensor, key: int, curso
     check(_lib.lib().mpg_batch_feed(_p(particles), _p(labels_in), n, N, int(key) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(cursor.data_ptr()),
                                     C.c_void_p(ticket.data_ptr()), int(B), int(stride), _p(data), _p(labels), _p(dcat), _p(x3),
                                     _p(mask2), _p(ign2), _p(labels2), _stream()), "mpg_batch_feed")
+
+
+# ------------------------------------------------------------------------------------- bulk generation (gen.JetSampler)
+PICK_TAG = 0x50000000      # MPG_PICK_TAG of include/mpgan_amd.h (clear of NOISE_TAG, AUG_TAG, LABEL_TAG, SHUFFLE_TAG and the dropout sites)
+CHUNK_SEED_STEP = 0x9E3779B97F4A7C15   # what one chunk adds to a sampler's seed word: seed_c = key + c * CHUNK_SEED_STEP
+
+
+def chunk_seed(key: int, c: int) -> int:
+    """The seed word ``seed_c`` under which chunk ``c`` of a sampler's stream draws its noise (include/mpgan_amd.h)."""
+    return (int(key) + int(c) * CHUNK_SEED_STEP) & 0xFFFFFFFFFFFFFFFF
+
+
+def u64_as_i64(v: int) -> int:
+    """The 64-bit pattern ``v`` as the value an int64 tensor holds for it."""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def label_pick_indices(key: int, pos0: int, count: int, n: int) -> torch.Tensor:
+    """Table indices ``idx(g)`` of the stream rows ``pos0 .. pos0 + count - 1`` of a sampler keyed by ``key`` over a table of
+    ``n`` labels (``mpg_label_pick_host``: the kernel's own function compiled for the host, no device involved) as a CPU
+    int64 tensor."""
+    out = torch.empty(max(int(count), 0), dtype=torch.int32)
+    check(_lib.lib().mpg_label_pick_host(int(key) & 0xFFFFFFFFFFFFFFFF, int(pos0) & 0xFFFFFFFFFFFFFFFF, int(count), int(n),
+                                         C.c_void_p(out.data_ptr()) if out.numel() else None), "mpg_label_pick_host")
+    return out.long()
+
+
+def _stream_words(cursor, ticket, device, what, seed=None):
+    if cursor.dtype != torch.int64 or cursor.numel() != 1 or cursor.device != device:
+        raise ValueError(f"{what}: cursor is one int64 on {device}")
+    if ticket is not None and (ticket.dtype != torch.int32 or ticket.numel() != 1 or ticket.device != device):
+        raise ValueError(f"{what}: ticket is one int32 on {device}")
+    if seed is not None and (seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != device):
+        raise ValueError(f"{what}: seed is one int64 on {device}")
+
+
+def label_pick(table: torch.Tensor, key: int, cursor: torch.Tensor, B: int, out: torch.Tensor) -> torch.Tensor:
+    """``mpg_label_pick``: ``out[b] = table[idx(cursor + b)]`` for the ``B`` jets of a chunk -- labels drawn with replacement
+    from the resident 1-D ``table`` by a keyed hash of the stream row (``label_pick_indices`` is its host twin).  ``cursor``
+    (one int64 on the device) is read, not moved; ``out``: contiguous, at least ``B`` floats ([B, 1])."""
+    _chk(table, "table")
+    _chk(out, "out")
+    if table.dim() != 1 or not table.is_contiguous() or table.numel() < 1:
+        raise ValueError(f"label_pick: a contiguous 1-D table of at least one label expected, got {tuple(table.shape)}")
+    if not out.is_contiguous() or out.numel() < int(B) or out.device != table.device:
+        raise ValueError(f"label_pick: out must be contiguous with at least {B} elements on {table.device}, got {tuple(out.shape)}")
+    _stream_words(cursor, None, table.device, "label_pick")
+    check(_lib.lib().mpg_label_pick(_p(table), table.numel(), int(key) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(cursor.data_ptr()), int(B),
+                                    _p(out), _stream()), "mpg_label_pick")
+    return out
+
+
+def jets_finish(feat: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Tensor, *, maxes, norms, shifts, key: int,
+                cursor: torch.Tensor, seed: torch.Tensor, ticket: torch.Tensor, row0: int = 0, total: Optional[int] = None,
+                mask_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``mpg_jets_finish``: the un-normalising epilogue of the reference's gen.py:127-141 (``data.unnormalise_jets``, bit for
+    bit) on one chunk ``feat [B, N, >= 3]`` (unit feature stride, jets of whole rows: a [B, N, 4] module output is read in place)
+    with ``mask [B, N]`` (or None: all real), written into rows ``cursor - row0 ..`` of ``out [total, N, 3]`` (and the 0 / 1
+    verdicts into ``mask_out [total, N]``); jets at or beyond ``total`` (default: ``out``'s rows) are not written.  The launch
+    then moves ``cursor`` on by B, writes the next chunk's seed word ``chunk_seed(key, cursor / B)`` into ``seed`` and leaves
+    ``ticket`` at zero."""
+    B, N, F = _jet_layout(feat, "feat")
+    _chk(out, "out")
+    if feat.stride(0) != N * feat.stride(1) or F < 3:
+        raise ValueError(f"jets_finish: feat [B, N, >= 3] with evenly strided particle rows expected (shape {tuple(feat.shape)}, strides {feat.stride()})")
+    total = out.shape[0] if total is None else int(total)
+    if out.dim() != 3 or out.shape[1:] != (N, 3) or not out.is_contiguous() or not 0 <= total <= out.shape[0] or out.device != feat.device:
+        raise ValueError(f"jets_finish: out must be a contiguous [>= {total}, {N}, 3] tensor on {feat.device}, got {tuple(out.shape)}")
+    if mask is not None:
+        _chk(mask, "mask")
+        if not mask.is_contiguous() or mask.numel() != B * N or mask.device != feat.device:
+            raise ValueError(f"jets_finish: mask must be contiguous with {B * N} elements, got {tuple(mask.shape)}")
+    if mask_out is not None:
+        _chk(mask_out, "mask_out")
+        if not mask_out.is_contiguous() or mask_out.numel() < total * N or mask_out.device != feat.device:
+            raise ValueError(f"jets_finish: mask_out must be contiguous with at least {total * N} elements, got {tuple(mask_out.shape)}")
+    _stream_words(cursor, ticket, feat.device, "jets_finish", seed)
+    f3 = lambda v: (C.c_float * 3)(*[float(x) for x in list(v)[:3]])
+    mx, nr, sh = f3(maxes), f3(norms), f3(shifts)
+    check(_lib.lib().mpg_jets_finish(_p(feat), feat.stride(1), _p(mask), B, N, mx, nr, sh, _p(out), _p(mask_out),
+                                     int(row0) & 0xFFFFFFFFFFFFFFFF, total, int(key) & 0xFFFFFFFFFFFFFFFF,
+                                     C.c_void_p(cursor.data_ptr()), C.c_void_p(seed.data_ptr()), C.c_void_p(ticket.data_ptr()),
+                                     _stream()), "mpg_jets_finish")
+    return out
 
 
 # ------------------------------------------------------------------------------------- augmentation
