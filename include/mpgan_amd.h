@@ -648,6 +648,31 @@ int mpg_augment_bwd(const float* dy, float* dx, uint64_t jet_stride, int ld, int
 int mpg_label_targets(int B, int smoothing, float noise, const uint64_t* seed, uint32_t tag, float* targets, float* extra,
                       float* drawn, void* stream);
 
+/* mpg_ada_update: the adaptive augmentation probability (--adaptive-prob, setup_training.py:399; the reference reads
+ * augment_p[-1] under it, train.py:440, :510, and never fills it) -- ADA's rule (Karras et al. 2020) as ONE launch behind the D
+ * step's head: mpg_augment's *p moved by the discriminator's outputs on the real jets.  One workgroup; csrc/ada.hip.
+ * out [>= n_real] fp32: D's per-jet outputs of this D step, the real half first (MpgDiscHead.out); only out[0 .. n_real) is read.
+ * mid: the midpoint of the loss's two targets (0.5 for og / ls, 0 for w / hinge).  state: int32[2] = {sign sum, D steps counted};
+ * aug_p, r_out: one float each; all three in device memory.  One launch, all of it exact integer arithmetic up to the marked lines:
+ *   s = #{b < n_real : out[b] > mid} - #{b < n_real : out[b] < mid}        (an output equal to mid, or a NaN, counts on neither side)
+ *   state[0] += s;  state[1] += 1
+ *   if state[1] == interval:
+ *       r = (float) state[0] / (float) (n_real * interval)                 (two int32 -> fp32 conversions, ONE fp32 division)
+ *       if r > target: p = *aug_p + step;  else if r < target: p = *aug_p - step;  else p = *aug_p     (ONE fp32 add / subtract)
+ *       *aug_p = p < 0 ? 0 : (p > 1 ? 1 : p);  *r_out = r;  state[0] = state[1] = 0
+ * Conversions, division and sum round to nearest even; nothing is contracted.  The sign counts are added as integers (a lane's
+ * strided partial, shuffles within a wave, four words of LDS across the waves): the result does not depend on that order.  One
+ * thread writes state, *aug_p and *r_out with ordinary stores: no atomics.  r = +1: every real jet of the interval scored on
+ * the real side; p then moves by `step` towards 1 -- r > target says "D is overfitting, augment more".  A state whose count
+ * already stands at or beyond `interval` never closes its interval: callers keep 0 <= state[1] < interval.
+ * n_real < 1, n_real > 2^30, interval < 1, n_real * interval > 2^31 - 1, target outside [0, 1], step < 0 (a NaN in either), a
+ * NULL pointer: -1.
+ * mpg_ada_update_host: the same body compiled for the host on host memory, no HIP call. */
+int mpg_ada_update(const float* out, int n_real, float mid, float target, float step, int interval, int32_t* state, float* aug_p,
+                   float* r_out, void* stream);
+int mpg_ada_update_host(const float* out, int n_real, float mid, float target, float step, int interval, int32_t* state,
+                        float* aug_p, float* r_out);
+
 /* The keyed shuffle of a device-resident data set (csrc/shuffle.h: one body for the device and the host).
  * perm(key, epoch, i, n), 0 <= i < n <= 2^31 - 1, is a bijection of [0, n) computed from (key, epoch, i) alone -- a balanced
  * Feistel network with cycle walking, its round function the project's counter-based hash (the stream of the dropout masks, of

@@ -689,6 +689,35 @@ def label_targets(B: int, smoothing: bool, noise: float, device="cuda", site: in
     return targets, extra, drawn
 
 
+# ------------------------------------------------------------------------------------- adaptive augmentation probability
+def ada_update(out: torch.Tensor, n_real: int, mid: float, target: float, step: float, interval: int, state: torch.Tensor,
+               aug_p: torch.Tensor, r_out: torch.Tensor):
+    """``mpg_ada_update``: ADA's controller of ``augment``'s probability, ONE launch on the current stream.  ``out``: D's per-jet
+    outputs of a D step, the real half first (what ``disc_head_loss`` returns; its first ``n_real`` values are read); ``mid``: the
+    midpoint of the loss's two targets; ``state``: int32 [2] = (sign sum, D steps counted); ``aug_p`` and ``r_out``: one float32
+    each, all three on ``out``'s device.  Adds this step's count of sign(out - mid) to the state and, on the ``interval``-th call,
+    moves ``aug_p`` by ``step`` towards 1 (r > ``target``) or 0 (r < ``target``), clamps it to [0, 1], leaves r = sign sum /
+    (n_real * interval) in ``r_out`` and clears the state (include/mpgan_amd.h states the rule exactly)."""
+    _chk(out, "out")
+    n_real, interval = int(n_real), int(interval)
+    if not out.is_contiguous() or not 1 <= n_real <= out.numel():
+        raise ValueError(f"ada_update: out must be contiguous with at least n_real = {n_real} >= 1 elements, got {tuple(out.shape)}")
+    if interval < 1:
+        raise ValueError(f"ada_update: interval must be >= 1, got {interval}")
+    if n_real * interval > 2**31 - 1:
+        raise ValueError(f"ada_update: n_real * interval = {n_real * interval} does not fit the int32 sign sum")
+    if not 0.0 <= float(target) <= 1.0:
+        raise ValueError(f"ada_update: target must lie in [0, 1], got {target!r}")
+    if not float(step) >= 0.0:
+        raise ValueError(f"ada_update: step must be >= 0, got {step!r}")
+    for t, k, dt, name in ((state, 2, torch.int32, "state"), (aug_p, 1, torch.float32, "aug_p"), (r_out, 1, torch.float32, "r_out")):
+        if t.device != out.device or t.dtype != dt or not t.is_contiguous() or t.numel() != k:
+            raise ValueError(f"ada_update: {name} must be a contiguous {dt} tensor of {k} element(s) on {out.device}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    check(_lib.lib().mpg_ada_update(_p(out), n_real, float(mid), float(target), float(step), interval, _p(state), _p(aug_p), _p(r_out),
+                                    _stream()), "mpg_ada_update")
+
+
 def augment_apply_reference(x: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
     """The torch statement of what ``augment`` applies: y[b, i, :2] = A_b x[b, i, :2] + t_b with
     params[b] = (a00, a01, a10, a11, t0, t1), columns >= 2 unchanged.  Any device and dtype (tests, the CPU path)."""

@@ -16,6 +16,8 @@ Jet augmentation (``--aug-*``, train.py:438-442, :508-511; ``TrainStep(augment=.
 device inside the iteration (``ops.augment``), from the seed that keys the noise and the dropout masks.
 Label smoothing / label noise (``--label-smoothing`` / ``--label-noise``, train.py:341-363; ``TrainStep(label_smoothing=...,
 label_noise=...)``) are per-jet targets drawn on the device by one launch in front of D's head (``ops.label_targets``).
+The augmentation probability can follow the discriminator (``Augment(adaptive_prob=True)``, the reference's unimplemented
+``--adaptive-prob``): ADA's rule on D's outputs for the real jets, one launch behind D's head (``ops.ada_update``).
 The training data can live on the device as well (``TrainStep(loader=data.DeviceJetLoader(...))``): the batch is then gathered by
 one launch at the top of the iteration, inside the capture, in the order of a keyed shuffle.
 
@@ -154,6 +156,9 @@ class FlatParams:
         # outside a TrainStep.  (Not a reference back to the step: a cycle would leave the step's hipGraphs to the garbage
         # collector, which may run in the middle of another step's capture.)
         self.batch_ndx = None
+        # TrainStep with an adaptive augmentation probability: the controller's device words (``_ada_words``) are kept HERE, in D's
+        # FlatParams, and saved under ``ADA_KEY``; None otherwise
+        self.ada = None
 
     def zero_grad(self):
         self.grad.zero_()
@@ -199,6 +204,7 @@ class FlatParams:
     SEED_KEY = "mpgan_amd_seed"
     SEED_RANK_KEY = "mpgan_amd_seed_rank"
     BATCH_KEY = "mpgan_amd_batch_ndx"
+    ADA_KEY = "mpgan_amd_ada"
 
     def _torch_optimizer(self, lr):
         """A torch.optim instance over detached CPU stand-ins of the parameters: the source of truth for the
@@ -233,6 +239,8 @@ class FlatParams:
             sd["param_groups"][0][self.SEED_RANK_KEY] = int(self.seed_rank)
         if self.batch_ndx is not None:
             sd["param_groups"][0][self.BATCH_KEY] = int(self.batch_ndx)
+        if self.ada is not None:
+            sd["param_groups"][0][self.ADA_KEY] = _ada_read(self.ada)
         return sd
 
     def load_state_dict(self, sd: dict):
@@ -283,12 +291,32 @@ class FlatParams:
                          self.seed_device)
         if self.batch_ndx is not None:     # (a file without the field -- the reference's, an older one -- resumes at the top of an epoch)
             self.batch_ndx = int(groups[0].get(self.BATCH_KEY, 0))
+        if self.ada is not None:           # (a file without the field resumes at the starting probability with an empty interval)
+            _ada_write(self.ada, groups[0].get(self.ADA_KEY))
         return self.lr
 
     def versions(self) -> int:
         """Sum of the autograd version counters of the parameters: changes when anything but the fused optimiser (which
         works on the flat buffer, behind autograd's back) writes them -- ``load_state_dict``, an in-place edit."""
         return sum(p._version for p in self.params)
+
+
+def _ada_read(a) -> dict:
+    """{p, r, sign_sum, steps} of the controller's device words ``a`` (``TrainStep._ada_words``); synchronises.  p and r are fp32
+    values held exactly by the Python floats."""
+    s = a.state.tolist()
+    return {"p": float(a.p), "r": float(a.r), "sign_sum": int(s[0]), "steps": int(s[1])}
+
+
+def _ada_write(a, ent: Optional[dict]):
+    """Put a saved ``_ada_read`` back (None: the starting probability, an empty interval, r = 0)."""
+    if ent is None:
+        ent = {"p": a.p0, "r": 0.0, "sign_sum": 0, "steps": 0}
+    if not 0 <= int(ent["steps"]) < a.interval:
+        raise ValueError(f"saved adaptive-augmentation state counts {ent['steps']} D steps into an interval of {a.interval}")
+    a.p.fill_(float(ent["p"]))
+    a.r.fill_(float(ent["r"]))
+    a.state.copy_(torch.tensor([int(ent["sign_sum"]), int(ent["steps"])], dtype=torch.int32))
 
 
 def _set_requires_grad(flat: "FlatParams", flag: bool):
@@ -313,7 +341,13 @@ LOSSES = ("ls", "og", "w", "hinge")
 class Augment:
     """The reference's augmentation switches (``--aug-r90 / --aug-f / --aug-t / --aug-s``, ``--translate-ratio``, ``--scale-sd``,
     ``--aug-prob``; setup_training.py:385-402, its defaults) for ``TrainStep(augment=...)``; the reference's own argument
-    namespace has the same field names and is taken as it is."""
+    namespace has the same field names and is taken as it is.
+    ``adaptive_prob`` (``--adaptive-prob``, setup_training.py:399; the reference reads ``augment_p[-1]`` under it and never fills
+    it): the probability is moved on the device by ADA's rule (Karras et al. 2020) from D's outputs on the real jets -- every
+    ``ada_interval`` D steps by ``B * ada_interval / (1000 * ada_kimg)``, up while the mean sign of (D(real) - midpoint) exceeds
+    ``ada_target``, down while it falls short (``ops.ada_update``).  ``aug_prob`` is then the STARTING value: the paper starts at
+    0, and that is the usual choice -- the field's default of 1 is the reference's for a fixed probability and is not overridden.
+    The three ``ada_*`` fields are ADA's published defaults; a reference namespace lacks them and gets these."""
     aug_r90: bool = False
     aug_f: bool = False
     aug_t: bool = False
@@ -321,9 +355,37 @@ class Augment:
     translate_ratio: float = 0.125
     scale_sd: float = 0.125
     aug_prob: float = 1.0      # (rand_mix: p == 1 takes nothing)
+    adaptive_prob: bool = False
+    ada_target: float = 0.6
+    ada_interval: int = 4
+    ada_kimg: float = 500.0
 
 
 AUG_SITES = {"D_fake": 0, "G_fake": 1, "D_real": 2}   # ops.augment's sites within an iteration
+ADA_DEFAULTS = {f: Augment.__dataclass_fields__[f].default for f in ("ada_target", "ada_interval", "ada_kimg")}
+
+
+def _f32(v: float) -> float:
+    """``v`` rounded to fp32 (to nearest even), as a Python float"""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def ada_rule(out, n_real: int, mid: float, target: float, step: float, interval: int, sign_sum: int, steps: int, p: float, r: float):
+    """``mpg_ada_update`` (include/mpgan_amd.h) in Python on a host tensor ``out``: (sign_sum, steps, p, r) after one D step.  The
+    counts are integers; the one division and the one sum are torch's fp32 operations on fp32 operands.  The CPU path of
+    ``TrainStep`` (host-logic tests with toy modules)."""
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    o, mid, target = out.detach().reshape(-1)[:n_real].float(), f32(mid), float(f32(target))
+    sign_sum += int((o > mid).sum()) - int((o < mid).sum())
+    steps += 1
+    if steps != interval:
+        return sign_sum, steps, p, r
+    r = float(f32(sign_sum) / f32(n_real * interval))
+    if r > target:
+        p = float(f32(p) + f32(step))
+    elif r < target:
+        p = float(f32(p) - f32(step))
+    return 0, 0, min(1.0, max(0.0, p)), r
 
 
 def effective_targets(y_real: torch.Tensor, y_fake: torch.Tensor, smoothing: bool):
@@ -561,6 +623,33 @@ class TrainStep:
             if flags:      # (all four switches off: the step without augmentation, launch for launch)
                 self.aug = SimpleNamespace(flags=flags, translate_ratio=float(augment.translate_ratio), scale_sd=float(augment.scale_sd))
                 self.aug_params = [torch.zeros(batch_size, 6, device=dev) for _ in AUG_SITES]
+        # The adaptive probability (``Augment.adaptive_prob``): one launch behind the D step's head
+        # (ops.ada_update) adds the signs of D(real) - mid to ``ada_state`` = (sign sum, D steps counted) and, every ``interval`` D
+        # steps, moves ``aug_p`` by ``step`` and leaves the interval's r in ``ada_r`` -- all in device memory, inside the capture.
+        # With the four switches off there is nothing to adapt: no launch, no buffers.
+        self._ada = self.ada_state = self.ada_r = None
+        self.ada_keep_out = False    # tests: keep the D step's last ``out`` tensor in ``ada_last_out`` (no launch of its own)
+        self.ada_last_out = None
+        if self.aug is not None and getattr(augment, "adaptive_prob", False):
+            if world_size > 1:
+                raise ValueError(f"adaptive_prob with world_size = {world_size}: every rank would settle the probability from its own "
+                                 "batches and the ranks would drift apart (the sign sum is not all-reduced); adaptive augmentation "
+                                 "runs on one rank")
+            target, interval, kimg = (getattr(augment, k, v) for k, v in ADA_DEFAULTS.items())
+            if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
+                raise ValueError(f"ada_interval must be an integer >= 1, got {interval!r}")
+            if not 0.0 <= float(target) <= 1.0:
+                raise ValueError(f"ada_target must lie in [0, 1], got {target!r}")
+            if not float(kimg) > 0.0:
+                raise ValueError(f"ada_kimg must be > 0, got {kimg!r}")
+            # mid: the midpoint of the loss's two targets (sigmoid outputs against 1 / 0; raw scores either side of 0);
+            # step: p can cross [0, 1] in ada_kimg thousand real jets -- rounded to fp32 once, here
+            self._ada = SimpleNamespace(mid=0.5 if loss in ("og", "ls") else 0.0, target=_f32(target), interval=interval,
+                                        step=_f32(batch_size * interval / (1000.0 * float(kimg))))
+            self.ada_state = torch.zeros(2, device=dev, dtype=torch.int32)
+            self.ada_r = torch.zeros(1, device=dev)
+            self.fD.ada = self._ada_words = SimpleNamespace(p=self.aug_p, state=self.ada_state, r=self.ada_r, interval=interval,
+                                                            p0=_f32(augment.aug_prob))
         # the generator's noise and its jets' masks drawn by one launch (MPG_NOISE_MASK=0: mpg_normal, then mpg_rank_mask)
         self.noise_mask = gpu and on["MPG_NOISE_MASK"]
         self.fixed_noise = None  # tests: (noise_D, noise_G) used instead of fresh samples
@@ -632,10 +721,31 @@ class TrainStep:
 
     def set_aug_prob(self, p: float):
         """The augmentation probability from the next iteration on (the reference's ``aug_prob`` / ``augment_p[-1]``); a
-        captured graph reads it from device memory: no recapture."""
+        captured graph reads it from device memory: no recapture.  Under ``adaptive_prob`` the controller goes on from the value."""
         if self.aug_p is None:
             raise RuntimeError("TrainStep was built without augmentation")
         self.aug_p.fill_(float(p))
+
+    @property
+    def ada(self) -> dict:
+        """{p, r, sign_sum, steps} of the adaptive probability: the probability now, the last finished interval's r (0 before the
+        first), and the open interval's sign sum and count of D steps.  Read-only, and the one place that synchronises."""
+        if self._ada is None:
+            raise RuntimeError("TrainStep was built without adaptive_prob (or with every augmentation switch off)")
+        return _ada_read(self._ada_words)
+
+    def _ada_update(self, out: torch.Tensor):
+        """The controller's launch behind the D step's head; ``out``: D's outputs, the real half first.  Every augmentation
+        launch that follows in stream order reads the new probability."""
+        a, w = self._ada, self._ada_words
+        if self.ada_keep_out:
+            self.ada_last_out = out
+        if self.dev.type == "cuda":
+            ops.ada_update(out, self.B, a.mid, a.target, a.step, a.interval, w.state, w.p, w.r)
+            return
+        st = w.state.tolist()
+        sign_sum, steps, p, r = ada_rule(out, self.B, a.mid, a.target, a.step, a.interval, st[0], st[1], float(w.p), float(w.r))
+        _ada_write(w, {"p": p, "r": r, "sign_sum": sign_sum, "steps": steps})
 
     def _augment(self, x: torch.Tensor, site: int, in_place: bool = False) -> torch.Tensor:
         """``augment.augment(args, x, p)`` at ``site``; on the device with ``ops.AugmentFn``'s backward where ``x`` takes a
@@ -746,9 +856,11 @@ class TrainStep:
         w, b, mean, sigmoid, p = self.D.fused_head()
         # (train_D under label smoothing / noise: the targets ``_draw_labels`` left; calc_G_loss has neither)
         lab = {"targets": self.label_targets, "loss_extra": self.label_extra} if self.labels_on and not gen_step else {}
-        _, dy = ops.disc_head_loss(y, mask, w, b, mean=mean, sigmoid=sigmoid, p_drop=p, training=self.D.training, loss=self.loss,
-                                   n_real=self.B, gen_step=gen_step, count=self.B, loss_out=self.G_loss if gen_step else self.D_loss,
-                                   want_dy=True, wgrad=None if gen_step else (w.grad, None if b is None else b.grad), **lab)
+        out, dy = ops.disc_head_loss(y, mask, w, b, mean=mean, sigmoid=sigmoid, p_drop=p, training=self.D.training, loss=self.loss,
+                                     n_real=self.B, gen_step=gen_step, count=self.B, loss_out=self.G_loss if gen_step else self.D_loss,
+                                     want_dy=True, wgrad=None if gen_step else (w.grad, None if b is None else b.grad), **lab)
+        if self._ada is not None and not gen_step:     # (directly behind the head, on its stream: train_G's augmentation reads the new p)
+            self._ada_update(out)
         self._sum_epoch("G" if gen_step else "D")
         self._backward(y, dy, then)
 
@@ -819,6 +931,9 @@ class TrainStep:
             self.GP.copy_(gp.detach())
             self._sum_epoch("gp")
             loss = loss + gp
+        if self._ada is not None:
+            # behind the penalty's augmentation of the real batch: every augmentation launch of this D step has read the old p
+            self._ada_update(out.detach().reshape(-1))
         self._backward(loss, then=late_fork)
 
     def gradient_penalty(self, real: torch.Tensor, fake: torch.Tensor) -> torch.Tensor:
@@ -976,6 +1091,8 @@ class TrainStep:
             ts += list(f.module.buffers()) + [p for p in f.module.parameters() if not p.requires_grad]
         if self.loader is not None:      # (the data stream's cursor: the warm-up iterations of ``capture`` consume no jets)
             ts.append(self.loader.cursor)
+        if self._ada is not None:        # (the warm-up's D steps move neither the probability nor the open interval)
+            ts += [self.aug_p, self.ada_state, self.ada_r]
         return ts
 
     def capture(self, warmup: int = 3, kind: str = "DG"):

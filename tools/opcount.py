@@ -9,7 +9,10 @@ from mpgan_amd.data import synthetic_jets
 dev = torch.device("cuda:0")
 G, D = (train.default_gapt if os.environ.get("OPC_GAPT") else train.default_mpgan)(30, device=dev)
 BATCH = 512 if os.environ.get("OPC_GAPT") else 256
-ts = train.TrainStep(G, D, BATCH, 30, latent=64 if os.environ.get("OPC_GAPT") else 32, use_graphs=False)
+# (OPC_AUG=1: the step with the four augmentations at a fixed probability; OPC_ADA=1: the same with adaptive_prob)
+AUG = train.Augment(aug_r90=True, aug_f=True, aug_t=True, aug_s=True, aug_prob=0.5, adaptive_prob=bool(os.environ.get("OPC_ADA"))) \
+    if os.environ.get("OPC_AUG") or os.environ.get("OPC_ADA") else None
+ts = train.TrainStep(G, D, BATCH, 30, latent=64 if os.environ.get("OPC_GAPT") else 32, use_graphs=False, augment=AUG)
 data, labels = synthetic_jets(BATCH, 30, seed=1, dist="gluon")
 ts.set_batch(data.to(dev), labels.to(dev))
 for _ in range(3): ts.step()
