@@ -592,6 +592,25 @@ int mpg_jet_emd_host(const float* a, int ld_jet_a, const float* b, int ld_jet_b,
 int mpg_jet_emd_host_iters(const float* a, int ld_jet_a, const float* b, int ld_jet_b, int ld_part, int na, int nb, int N, float R,
                            double* out, int* status, int* iters, int threads);
 
+/* The tag table.  Every family of draws hashes (seed or key, tag, ...) under tags of its own: MPG_x_TAG + a site or round number
+ * below MPG_x_TAG_SPAN.  The spans are pairwise disjoint and lie at or above 2^27, the ceiling of the dropout sites' tags
+ * (csrc/draws.h asserts both at compile time).
+ *   NOISE    mpg_normal / mpg_normal_rank_mask: + the draw's site within an iteration (0 train_D's noise, 1 train_G's)
+ *   AUG      mpg_augment: + the site (0 train_D's generated jets, 1 train_G's, 2 the gradient penalty's real jets)
+ *   LABEL    mpg_label_targets: + the site (0)
+ *   SHUFFLE  the keyed shuffle: + the Feistel round (0 .. 3)
+ *   PICK     mpg_label_pick (0) */
+#define MPG_NOISE_TAG 0x4E000000
+#define MPG_NOISE_TAG_SPAN 0x100000
+#define MPG_AUG_TAG 0x41000000
+#define MPG_AUG_TAG_SPAN 0x100000
+#define MPG_LABEL_TAG 0x4C000000
+#define MPG_LABEL_TAG_SPAN 0x100000
+#define MPG_SHUFFLE_TAG 0x53000000
+#define MPG_SHUFFLE_TAG_SPAN 0x100000
+#define MPG_PICK_TAG 0x50000000
+#define MPG_PICK_TAG_SPAN 0x100000
+
 /* mpg_normal: out[i] = mean + std * z_i with z ~ N(0, 1) -- the generator's input noise (get_gen_noise, train.py:100-141:
  * torch.randn * sd) from a counter-based stream keyed by the device-resident 64-bit `seed` (the dropout seed, advanced
  * once per iteration) and a site `tag`: a captured hipGraph draws fresh values on every replay, and torch's generator
@@ -634,7 +653,7 @@ int mpg_augment_bwd(const float* dy, float* dx, uint64_t jet_stride, int ld, int
  * mpg_disc_head_loss / _bwd take (MpgDiscHead.targets, .loss_extra).  One workgroup; any B >= 1.
  * Draws: word(g) = the project's counter-based hash of (the 64-bit *seed, tag, jet b, group g) -- the stream of the dropout
  * masks, of mpg_normal and of the augmentation --, u_s = (word(0) >> 8) * 2^-24 and u_n = (word(1) >> 8) * 2^-24 in [0, 1).
- * tag = MPG_LABEL_TAG + site, clear of the dropout sites (below 2^27) and of the noise, augmentation and shuffle tags.
+ * tag = MPG_LABEL_TAG + site.
  *   Y_b = smoothing ? (real: 0.7f + 0.5f * u_s ~ U[0.7, 1.2);  generated: 0.3f * u_s ~ U[0, 0.3))  :  (real: 1;  generated: 0)
  *         -- one fp32 rounding each --, then, where u_n < noise, real: Y_b = 0, generated: Y_b = 1 (noise in [0, 1], else -1).
  * drawn [2B] (or NULL) receives Y.  What the loss makes of Y depends on its shape in the reference: without smoothing Y is
@@ -644,7 +663,6 @@ int mpg_augment_bwd(const float* dy, float* dx, uint64_t jet_stride, int ld, int
  * those shapes: smoothing has a meaning for ls only).  Per half the mean first, then sum (Y - mean)^2 / B, both summed in one
  * fixed order (a thread's strided partial, a tree over the 256 partials); no atomics.  *seed is read from device memory: a
  * replayed hipGraph draws fresh labels. */
-#define MPG_LABEL_TAG 0x4C000000
 int mpg_label_targets(int B, int smoothing, float noise, const uint64_t* seed, uint32_t tag, float* targets, float* extra,
                       float* drawn, void* stream);
 
@@ -688,10 +706,8 @@ int mpg_ada_update_host(const float* out, int n_real, float mid, float target, f
  *   again from the new x while x >= n (the walk); perm = the first x < n.  Only the low 32 bits of the epoch enter.
  * The stream is continuous: position g = 0, 1, 2, ... takes data-set row perm(key, g / n, g % n, n).  No batch is dropped or
  * short, a batch may straddle two epochs, and every n consecutive positions from a multiple of n visit every row once.
- * MPG_SHUFFLE_TAG stays clear of the dropout sites (below 2^27), of the noise tags and of the augmentation tags.
  *
  * mpg_shuffle_index_host: out[c] = the row of position pos0 + c, c < count; no HIP call.  1 <= n <= 2^31 - 1, count >= 0 (else -1). */
-#define MPG_SHUFFLE_TAG 0x53000000
 int mpg_shuffle_index_host(uint64_t key, uint64_t pos0, int64_t count, int64_t n, int32_t* out);
 
 /* mpg_batch_feed: one training batch gathered from the resident data set -- normalised particles [n, N, 4] fp32 (a particle row
@@ -718,14 +734,12 @@ int mpg_batch_feed(const float* particles, const float* labels_in, int64_t n, in
  *   its noise   drawn by mpg_normal / mpg_normal_rank_mask under the seed word of its chunk,
  *               seed_c = key + c * 0x9E3779B97F4A7C15 (mod 2^64), at the row's place within the chunk.
  * So the labels are a function of the row alone, the noise of (chunk index, place in the chunk): the same key and B give the
- * same jets whatever ran before, and any row can be recomputed.  MPG_PICK_TAG stays clear of the dropout sites (below 2^27)
- * and of the noise, augmentation, label and shuffle tags.
+ * same jets whatever ran before, and any row can be recomputed.
  *
  * mpg_label_pick: labels[b] = table[idx(*cursor + b)], b < B; table, *cursor and labels in device memory; the cursor is only
  * read.  n < 1, n > 2^31 - 1, B < 1, a NULL table, cursor or labels: -1.
  * mpg_label_pick_host: out[c] = idx(pos0 + c), c < count -- the same body compiled for the host, no HIP call.
  * 1 <= n <= 2^31 - 1, count >= 0, out non-NULL when count > 0 (else -1). */
-#define MPG_PICK_TAG 0x50000000
 int mpg_label_pick(const float* table, int64_t n, uint64_t key, const uint64_t* cursor, int B, float* labels, void* stream);
 int mpg_label_pick_host(uint64_t key, uint64_t pos0, int64_t count, int64_t n, int32_t* out);
 

@@ -7,41 +7,39 @@
 // FMAs per particle.  One workgroup (one wave) per jet: the map depends on blockIdx.x and kernel arguments alone, so the
 // hashes are wave-uniform work; the lanes do the particles.  Columns >= 2 (pT, a mask column) pass through; padded particles
 // are moved like any other, as the reference moves them.  The statement of the draws is in include/mpgan_amd.h.
-#include "common.h"
-#include "../../include/mpgan_amd.h"
+#include "draws.h"
 
 namespace {
 struct AugMap { float a00, a01, a10, a11, t0, t1; };
 
 // draw `i` of jet `b`: the 24 high bits of the word as u in [0, 1)
 MPG_DEV uint32_t aug_word(uint32_t lo, uint32_t hi, uint32_t tag, uint32_t b, uint32_t i) { return drop_word(lo, hi, tag, b, i); }
-MPG_DEV float aug_u(uint32_t w) { return (float)(w >> 8) * (1.f / 16777216.f); }
 
-MPG_DEV AugMap aug_map(uint64_t sd, uint32_t tag, uint32_t b, float p, int flags, float translate_ratio, float scale_sd) {
-    const uint32_t lo = (uint32_t)sd, hi = (uint32_t)(sd >> 32);
+MPG_DEV AugMap aug_map(SeedWords s, uint32_t tag, uint32_t b, float p, int flags, float translate_ratio, float scale_sd) {
+    const uint32_t lo = s.lo, hi = s.hi;
     AugMap m = {1.f, 0.f, 0.f, 1.f, 0.f, 0.f};
     // rand_mix: a stage is taken where u < p -- and never at p == 1 (the reference returns the untouched batch there)
     const bool on = p != 1.f;
-    auto take = [&](uint32_t i) { return on && aug_u(aug_word(lo, hi, tag, b, i)) < p; };
+    auto take = [&](uint32_t i) { return on && u24(aug_word(lo, hi, tag, b, i)) < p; };
     if ((flags & MPG_AUG_R90) && take(0)) {
         const uint32_t k = aug_word(lo, hi, tag, b, 1) >> 30;          // floor(4 u)
         const float c = k == 0 ? 1.f : (k == 2 ? -1.f : 0.f), s = k == 1 ? 1.f : (k == 3 ? -1.f : 0.f);
         m.a00 = c; m.a01 = 0.f - s; m.a10 = s; m.a11 = c;               // (first stage: A = R^k I, t = 0)
     }
     if ((flags & MPG_AUG_FLIP) && take(2)) {
-        const float sx = aug_u(aug_word(lo, hi, tag, b, 3)) >= 0.5f ? 1.f : -1.f;
-        const float sy = aug_u(aug_word(lo, hi, tag, b, 4)) >= 0.5f ? 1.f : -1.f;
+        const float sx = u24(aug_word(lo, hi, tag, b, 3)) >= 0.5f ? 1.f : -1.f;
+        const float sy = u24(aug_word(lo, hi, tag, b, 4)) >= 0.5f ? 1.f : -1.f;
         m.a00 *= sx; m.a01 *= sx; m.t0 *= sx;
         m.a10 *= sy; m.a11 *= sy; m.t1 *= sy;
     }
     if ((flags & MPG_AUG_TRANSLATE) && take(5)) {
-        m.t0 += (aug_u(aug_word(lo, hi, tag, b, 6)) - 0.5f) * translate_ratio;
-        m.t1 += (aug_u(aug_word(lo, hi, tag, b, 7)) - 0.5f) * translate_ratio;
+        m.t0 += (u24(aug_word(lo, hi, tag, b, 6)) - 0.5f) * translate_ratio;
+        m.t1 += (u24(aug_word(lo, hi, tag, b, 7)) - 0.5f) * translate_ratio;
     }
     if ((flags & MPG_AUG_SCALE) && take(8)) {
         // one standard normal from two uniforms in (0, 1), as mpg_normal forms its own
-        const float u1 = ((float)(aug_word(lo, hi, tag, b, 9) >> 8) + 0.5f) * (1.f / 16777216.f);
-        const float u2 = ((float)(aug_word(lo, hi, tag, b, 10) >> 8) + 0.5f) * (1.f / 16777216.f);
+        const float u1 = u24_open(aug_word(lo, hi, tag, b, 9));
+        const float u2 = u24_open(aug_word(lo, hi, tag, b, 10));
         const float z = sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
         const float f = expf(scale_sd * z);
         m.a00 *= f; m.a01 *= f; m.a10 *= f; m.a11 *= f; m.t0 *= f; m.t1 *= f;
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(64) void augment_kernel(const float* x, float* y, s
                                                      const uint64_t* __restrict__ seed, uint32_t tag, const float* __restrict__ p,
                                                      int flags, float translate_ratio, float scale_sd, float* __restrict__ params) {
     const uint32_t b = blockIdx.x;
-    const AugMap m = aug_map(*seed, tag, b, *p, flags, translate_ratio, scale_sd);
+    const AugMap m = aug_map(seed_words(seed), tag, b, *p, flags, translate_ratio, scale_sd);
     if (threadIdx.x == 0) {
         float* q = params + (size_t)b * 6;
         q[0] = m.a00; q[1] = m.a01; q[2] = m.a10; q[3] = m.a11; q[4] = m.t0; q[5] = m.t1;

@@ -6,16 +6,13 @@
 // pass recomputes it instead of parking it: pass 1 sums each half, pass 2 sums the squared distances to the half's mean, pass 3
 // writes.  Each sum is a thread's strided partial, then a tree over the 256 partials in LDS: one fixed order, no atomics.
 // The statement of the draws is in include/mpgan_amd.h.
-#include "common.h"
-#include "../../include/mpgan_amd.h"
+#include "draws.h"
 
 namespace {
 
-MPG_DEV float label_u(uint32_t w) { return (float)(w >> 8) * (1.f / 16777216.f); }   // as the augmentation's u
-
 // Y of jet b before any broadcasting: the smoothed (or 1 / 0) label, then the flip
 MPG_DEV float label_draw(uint32_t lo, uint32_t hi, uint32_t tag, uint32_t b, bool real, int smoothing, float noise) {
-    const float us = label_u(drop_word(lo, hi, tag, b, 0)), un = label_u(drop_word(lo, hi, tag, b, 1));
+    const float us = u24(drop_word(lo, hi, tag, b, 0)), un = u24(drop_word(lo, hi, tag, b, 1));
     float y = real ? 1.f : 0.f;
     if (smoothing) y = real ? fmaf(0.5f, us, 0.7f) : 0.3f * us;      // U[0.7, 1.2) / U[0, 0.3): one rounding each
     if (un < noise) y = real ? 0.f : 1.f;
@@ -39,10 +36,9 @@ __global__ __launch_bounds__(256) void label_targets_kernel(const uint64_t* __re
                                                             float noise, float* __restrict__ targets, float* __restrict__ extra,
                                                             float* __restrict__ drawn) {
     __shared__ float red[256];
-    const uint64_t sd = *seed;
-    const uint32_t lo = (uint32_t)sd, hi = (uint32_t)(sd >> 32);
+    const SeedWords s = seed_words(seed);
     const int tid = threadIdx.x, n = 2 * B;
-    auto y_of = [&](int b) { return label_draw(lo, hi, tag, (uint32_t)b, b < B, smoothing, noise); };
+    auto y_of = [&](int b) { return label_draw(s.lo, s.hi, tag, (uint32_t)b, b < B, smoothing, noise); };
     float mean_r = 0.f, mean_f = 0.f, ex = 0.f;
     if (smoothing) {
         // MSELoss(out [B, 1], Y [B]) broadcasts to [B, B]: mean_ij (out_i - Y_j)^2 = mean_i (out_i - mean Y)^2 + popvar(Y)

@@ -11,7 +11,7 @@
 // the workgroup that arrives last -- told by the value the add returns -- writes cursor + stride and puts the counter back to
 // zero for the next launch (the arrival counters of the sender-chunked edge launches work the same way).
 #include "shuffle.h"
-#include "../../include/mpgan_amd.h"
+#include "draws.h"
 
 namespace {
 struct FeedOut { float *data, *labels, *dcat, *x3, *mask2, *ign2, *labels2; };
@@ -42,8 +42,7 @@ __global__ __launch_bounds__(256) void batch_feed_kernel(const float4* __restric
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned int old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == gridDim.x - 1u) {
+        if (last_arrival(ticket)) {
             __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(cursor, cur + stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }

@@ -12,8 +12,7 @@
 // device memory (a captured hipGraph must see it advance on every replay).  `zero_grad` != 0: the gradient buffer is
 // cleared behind its last use (the next backward accumulates into zeros: optimizer.zero_grad() of train.py:419 / :494
 // without a launch of its own).
-#include "common.h"
-#include "../../include/mpgan_amd.h"
+#include "draws.h"
 
 namespace {
 __global__ void rmsprop_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ v, size_t n,
@@ -71,21 +70,13 @@ __global__ void adadelta_kernel(float* __restrict__ p, float* __restrict__ g, fl
 // out[i] = mean + std * z_i, z ~ N(0, 1): counter-based (two hashes of (seed, tag, pair index) -> Box-Muller, one pair of
 // values per thread), so a captured hipGraph draws fresh values on every replay from the device-resident seed alone
 __global__ void normal_kernel(float* __restrict__ out, size_t n, const uint64_t* __restrict__ seed, uint32_t tag, float mean, float std) {
-    const uint64_t sd = *seed;
-    const uint32_t lo = (uint32_t)sd, hi = (uint32_t)(sd >> 32);
+    const SeedWords s = seed_words(seed);
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x, npair = (n + 1) / 2;
     for (; i < npair; i += stride) {
-        // (the pair index goes through the mixer twice, the second time with the words swapped: two independent 32-bit streams)
-        uint32_t a = drop_word(lo, hi, tag, (uint32_t)i, (uint32_t)(i >> 32));
-        uint32_t b = drop_word(hi ^ 0x9E3779B9u, lo, tag + 0x7F4A7C15u, (uint32_t)i ^ a, (uint32_t)(i >> 32) + 1u);
-        const float u1 = ((float)(a >> 8) + 0.5f) * (1.f / 16777216.f);      // (0, 1)
-        const float u2 = ((float)(b >> 8) + 0.5f) * (1.f / 16777216.f);
-        const float r = sqrtf(-2.f * logf(u1)) * std;
-        float sn, cs;
-        sincosf(6.283185307179586f * u2, &sn, &cs);
-        out[2 * i] = mean + r * cs;
-        if (2 * i + 1 < n) out[2 * i + 1] = mean + r * sn;
+        const NormalPair z = normal_pair(s, tag, i, std);
+        out[2 * i] = mean + z.r * z.cs;
+        if (2 * i + 1 < n) out[2 * i + 1] = mean + z.r * z.sn;
     }
 }
 
@@ -96,20 +87,13 @@ __global__ __launch_bounds__(256) void normal_rank_mask_kernel(float* __restrict
                                                                uint32_t tag, float mean, float std, const float* __restrict__ labels,
                                                                int ld_lab, float* __restrict__ mask, float* __restrict__ ignore) {
     extern __shared__ float first[];   // [N]: the first feature of every particle
-    const uint64_t sd = *seed;
-    const uint32_t lo = (uint32_t)sd, hi = (uint32_t)(sd >> 32);
+    const SeedWords s = seed_words(seed);
     const int b = blockIdx.x;
     const size_t per_jet = (size_t)N * L, pair0 = (size_t)b * per_jet / 2, npair = per_jet / 2;   // (N L even: checked by the launcher)
     for (size_t q = threadIdx.x; q < npair; q += blockDim.x) {
         const size_t i = pair0 + q;
-        uint32_t a = drop_word(lo, hi, tag, (uint32_t)i, (uint32_t)(i >> 32));
-        uint32_t c = drop_word(hi ^ 0x9E3779B9u, lo, tag + 0x7F4A7C15u, (uint32_t)i ^ a, (uint32_t)(i >> 32) + 1u);
-        const float u1 = ((float)(a >> 8) + 0.5f) * (1.f / 16777216.f);
-        const float u2 = ((float)(c >> 8) + 0.5f) * (1.f / 16777216.f);
-        const float r = sqrtf(-2.f * logf(u1)) * std;
-        float sn, cs;
-        sincosf(6.283185307179586f * u2, &sn, &cs);
-        const float v0 = mean + r * cs, v1 = mean + r * sn;
+        const NormalPair z = normal_pair(s, tag, i, std);
+        const float v0 = mean + z.r * z.cs, v1 = mean + z.r * z.sn;
         out[2 * i] = v0;
         out[2 * i + 1] = v1;
         const size_t e0 = 2 * q;                       // element index within the jet

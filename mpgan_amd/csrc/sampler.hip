@@ -12,15 +12,13 @@
 // and its `row < total` branch depend on the value, so the read has returned -- and arrives on an agent-scope counter last; the
 // workgroup that arrives last, told by the value the add returns, writes cursor + B and the seed word of chunk (cursor + B) / B
 // and puts the counter back to zero.  Both launches are bound by latency (a chunk of 4096 jets of 30 particles moves 3.4 MB).
-#include "common.h"
-#include "../../include/mpgan_amd.h"
+#include "draws.h"
 
-constexpr uint32_t PICK_TAG = MPG_PICK_TAG;   // clear of the dropout sites (< 2^27) and of the noise, augmentation, label and shuffle tags
 constexpr uint64_t CHUNK_SEED_STEP = 0x9E3779B97F4A7C15ull;
 
 // table index of stream row g: multiply-shift of one hash word onto [0, n) (n <= 2^31 - 1)
 MPG_HD uint32_t pick_index(uint64_t key, uint64_t g, uint32_t n) {
-    const uint32_t w = drop_word((uint32_t)key, (uint32_t)(key >> 32), PICK_TAG, (uint32_t)g, (uint32_t)(g >> 32));
+    const uint32_t w = drop_word((uint32_t)key, (uint32_t)(key >> 32), MPG_PICK_TAG, (uint32_t)g, (uint32_t)(g >> 32));
     return (uint32_t)(((uint64_t)w * (uint64_t)n) >> 32);
 }
 
@@ -59,8 +57,7 @@ __global__ __launch_bounds__(256) void jets_finish_kernel(const float* __restric
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const unsigned int old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (old == gridDim.x - 1u) {
+        if (last_arrival(ticket)) {
             const uint64_t next = cur + (uint64_t)B;
             __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(seed, key + (next / (uint64_t)B) * CHUNK_SEED_STEP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

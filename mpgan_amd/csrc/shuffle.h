@@ -9,7 +9,6 @@
 #include "common.h"
 #include "../../include/mpgan_amd.h"
 
-constexpr uint32_t SHUFFLE_TAG = MPG_SHUFFLE_TAG;   // + round; clear of the dropout sites (< 2^27), NOISE_TAG and the augmentation tags
 constexpr int SHUFFLE_ROUNDS = 4;
 
 MPG_HD uint32_t shuffle_perm(uint64_t key, uint64_t epoch, uint32_t i, uint32_t n) {
@@ -23,7 +22,7 @@ MPG_HD uint32_t shuffle_perm(uint64_t key, uint64_t epoch, uint32_t i, uint32_t 
     do {
         uint32_t L = x >> h, R = x & half;
         for (int r = 0; r < SHUFFLE_ROUNDS; ++r) {
-            const uint32_t t = L ^ (drop_word(key_lo, key_hi, SHUFFLE_TAG + (uint32_t)r, R, ep) & half);
+            const uint32_t t = L ^ (drop_word(key_lo, key_hi, MPG_SHUFFLE_TAG + (uint32_t)r, R, ep) & half);
             L = R;
             R = t;
         }

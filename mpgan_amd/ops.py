@@ -202,7 +202,13 @@ def bump_seed(device="cuda"):
     seed_tensor(device).add_(SEED_STEP)
 
 
-NOISE_TAG = 0x4E000000   # site tags of ``normal_noise`` (dropout sites stay below 2^27: next_tag)
+# The tag table of include/mpgan_amd.h (MPG_*_TAG; a family's tags are its base + a site or round number): disjoint spans above
+# the dropout sites' tags, which ``next_tag`` keeps below 2^27 (csrc/draws.h asserts it; tests/test_cabi_cpu.py compares the two)
+NOISE_TAG = 0x4E000000     # ``normal_noise``: + site
+AUG_TAG = 0x41000000       # ``augment``: + site
+LABEL_TAG = 0x4C000000     # ``label_targets``: + site
+SHUFFLE_TAG = 0x53000000   # the keyed shuffle: + Feistel round
+PICK_TAG = 0x50000000      # ``label_pick``
 
 
 def _noise_target(shape, device, out):
@@ -488,7 +494,6 @@ def normal_noise_masked(shape, std: float, labels: torch.Tensor, site: int = 0, 
 
 
 # ------------------------------------------------------------------------------------- data feed
-SHUFFLE_TAG = 0x53000000   # MPG_SHUFFLE_TAG of include/mpgan_amd.h (+ the Feistel round; clear of NOISE_TAG, AUG_TAG and the dropout sites)
 
 
 def shuffle_indices(key: int, pos0: int, count: int, n: int) -> torch.Tensor:
@@ -524,7 +529,6 @@ def batch_feed(particles: torch.Tensor, labels_in: torch.Tensor, key: int, curso
 
 
 # ------------------------------------------------------------------------------------- bulk generation (gen.JetSampler)
-PICK_TAG = 0x50000000      # MPG_PICK_TAG of include/mpgan_amd.h (clear of NOISE_TAG, AUG_TAG, LABEL_TAG, SHUFFLE_TAG and the dropout sites)
 CHUNK_SEED_STEP = 0x9E3779B97F4A7C15   # what one chunk adds to a sampler's seed word: seed_c = key + c * CHUNK_SEED_STEP
 
 
@@ -609,7 +613,6 @@ def jets_finish(feat: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Ten
 
 
 # ------------------------------------------------------------------------------------- augmentation
-AUG_TAG = 0x41000000  # site tags of ``augment`` (clear of NOISE_TAG and of the dropout sites below 2^27)
 AUG_R90, AUG_FLIP, AUG_TRANSLATE, AUG_SCALE = 1, 2, 4, 8   # MPG_AUG_* of include/mpgan_amd.h
 
 
@@ -663,7 +666,6 @@ def augment(x: torch.Tensor, p_tensor: torch.Tensor, flags: int, translate_ratio
 
 
 # ------------------------------------------------------------------------------------- label smoothing / noise
-LABEL_TAG = 0x4C000000  # MPG_LABEL_TAG of include/mpgan_amd.h (+ site; clear of NOISE_TAG, AUG_TAG, SHUFFLE_TAG and the dropout sites below 2^27)
 
 
 def label_targets(B: int, smoothing: bool, noise: float, device="cuda", site: int = 0, out=None):

@@ -1,0 +1,288 @@
+"""The options of the captured training iteration (``train.TrainStep``) as objects, and the step state that outlives an iteration.
+
+Each option owns its configuration, its device words and its one launch with the CPU statement beside it (the host-logic tests run
+toy modules on the CPU): ``Augmenter`` (``--aug-*``), ``AdaController`` (``Augment.adaptive_prob``), ``LabelDraw``
+(``--label-smoothing`` / ``--label-noise``).  ``train`` re-exports the public names.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import Optional
+
+import torch
+
+from . import ops
+from .mpgan import augment as maugment
+
+
+@dataclass
+class Augment:
+    """The reference's augmentation switches (``--aug-r90 / --aug-f / --aug-t / --aug-s``, ``--translate-ratio``, ``--scale-sd``,
+    ``--aug-prob``; setup_training.py:385-402, its defaults) for ``TrainStep(augment=...)``; the reference's own argument
+    namespace has the same field names and is taken as it is.
+    ``adaptive_prob`` (``--adaptive-prob``, setup_training.py:399; the reference reads ``augment_p[-1]`` under it and never fills
+    it): the probability is moved on the device by ADA's rule (Karras et al. 2020) from D's outputs on the real jets -- every
+    ``ada_interval`` D steps by ``B * ada_interval / (1000 * ada_kimg)``, up while the mean sign of (D(real) - midpoint) exceeds
+    ``ada_target``, down while it falls short (``ops.ada_update``).  ``aug_prob`` is then the STARTING value: the paper starts at
+    0, and that is the usual choice -- the field's default of 1 is the reference's for a fixed probability and is not overridden.
+    The three ``ada_*`` fields are ADA's published defaults; a reference namespace lacks them and gets these."""
+    aug_r90: bool = False
+    aug_f: bool = False
+    aug_t: bool = False
+    aug_s: bool = False
+    translate_ratio: float = 0.125
+    scale_sd: float = 0.125
+    aug_prob: float = 1.0      # (rand_mix: p == 1 takes nothing)
+    adaptive_prob: bool = False
+    ada_target: float = 0.6
+    ada_interval: int = 4
+    ada_kimg: float = 500.0
+
+
+AUG_SITES = {"D_fake": 0, "G_fake": 1, "D_real": 2}   # ops.augment's sites within an iteration
+ADA_DEFAULTS = {f: Augment.__dataclass_fields__[f].default for f in ("ada_target", "ada_interval", "ada_kimg")}
+
+
+def _f32(v: float) -> float:
+    """``v`` rounded to fp32 (to nearest even), as a Python float"""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def ada_rule(out, n_real: int, mid: float, target: float, step: float, interval: int, sign_sum: int, steps: int, p: float, r: float):
+    """``mpg_ada_update`` (include/mpgan_amd.h) in Python on a host tensor ``out``: (sign_sum, steps, p, r) after one D step.  The
+    counts are integers; the one division and the one sum are torch's fp32 operations on fp32 operands.  The CPU path of
+    ``TrainStep`` (host-logic tests with toy modules)."""
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    o, mid, target = out.detach().reshape(-1)[:n_real].float(), f32(mid), float(f32(target))
+    sign_sum += int((o > mid).sum()) - int((o < mid).sum())
+    steps += 1
+    if steps != interval:
+        return sign_sum, steps, p, r
+    r = float(f32(sign_sum) / f32(n_real * interval))
+    if r > target:
+        p = float(f32(p) + f32(step))
+    elif r < target:
+        p = float(f32(p) - f32(step))
+    return 0, 0, min(1.0, max(0.0, p)), r
+
+
+def effective_targets(y_real: torch.Tensor, y_fake: torch.Tensor, smoothing: bool):
+    """(t [2B], extra): calc_D_loss's labels ``Y_real`` / ``Y_fake`` (train.py:353-363, after the noise) as ``d_loss`` and the fused
+    head take them -- loss = sum_b term(out_b, t_b) / B + extra.  Without smoothing the labels are [B, 1] like D's outputs: t = Y,
+    extra = 0.  With smoothing they are [B] and ``MSELoss(out [B, 1], Y [B])`` broadcasts to [B, B] (train.py:369-370):
+    mean_ij (out_i - Y_j)^2 = mean_i (out_i - mean(Y))^2 + popvar(Y) per half, so t is each half's mean and extra the two
+    population variances.  Any device and dtype."""
+    y_real, y_fake = y_real.reshape(-1), y_fake.reshape(-1)
+    if not smoothing:
+        return torch.cat([y_real, y_fake]), torch.zeros((), device=y_real.device, dtype=y_real.dtype)
+    t = torch.cat([y_real.mean().expand(y_real.numel()), y_fake.mean().expand(y_fake.numel())])
+    return t, y_real.var(unbiased=False) + y_fake.var(unbiased=False)
+
+
+# -- step state that outlives an iteration, and the options that own some ------------------------------------------------------
+# A carried entry has ``tensors()`` -- the device words an iteration moves: ``TrainStep.capture`` snapshots them before its warm-up
+# and puts them back after -- and ``save(group)`` / ``load(group)`` -- its keys in an optimizer file's parameter group (torch.optim's
+# own load_state_dict carries unknown group keys along untouched); a missing key loads the entry's default.
+# ``FlatParams.carried`` lists the entries that travel with that optimizer's file.  No entry refers back to the TrainStep: a cycle
+# would leave the step's hipGraphs to the garbage collector, which may run in the middle of another step's capture.
+
+class DeviceWords:
+    """Carried device words that no optimizer file holds: the epoch's loss sums, the loader's cursor (the loader has a
+    ``state_dict`` of its own)."""
+
+    def __init__(self, tensors):
+        self._tensors = list(tensors)
+
+    def tensors(self):
+        return self._tensors
+
+    def save(self, group: dict):
+        pass
+
+    def load(self, group: dict):
+        pass
+
+
+class SeedState(DeviceWords):
+    """The dropout / noise seed of ``device`` and this process's rank in the data-parallel group, in G's file."""
+    KEY, RANK_KEY = "mpgan_amd_seed", "mpgan_amd_seed_rank"
+
+    def __init__(self, device, rank: int):
+        super().__init__([ops.seed_tensor(device)])
+        self.device, self.rank = device, rank
+
+    def save(self, group):
+        group[self.KEY] = ops.get_seed(self.device)
+        group[self.RANK_KEY] = int(self.rank)
+
+    def load(self, group):
+        if self.KEY in group:    # (a file without the field leaves the seed alone)
+            # a resumed run goes on with the noise / dropout stream where the saved one stopped, not from its start -- on the rank
+            # that wrote the file.  The reference's checkpoint is ONE file per epoch (train.py:534-535): every other rank of a
+            # resumed data-parallel run moves the saved value by its distance in rank (ops.rerank_seed), so that no two ranks
+            # share noise or masks behind a resume either.
+            ops.set_seed(ops.rerank_seed(int(group[self.KEY]), int(group.get(self.RANK_KEY, 0)), self.rank), self.device)
+
+
+class Schedule(DeviceWords):
+    """``batch_ndx`` of the num_critic / num_gen schedule -- a host integer -- in G's file."""
+    KEY = "mpgan_amd_batch_ndx"
+
+    def __init__(self):
+        super().__init__([])
+        self.batch_ndx = 0
+
+    def save(self, group):
+        group[self.KEY] = int(self.batch_ndx)
+
+    def load(self, group):    # (a file without the field -- the reference's, an older one -- resumes at the top of an epoch)
+        self.batch_ndx = int(group.get(self.KEY, 0))
+
+
+class AdaController:
+    """The adaptive augmentation probability (``Augment.adaptive_prob``), in D's file: one launch behind the D
+    step's head (``update``) adds the signs of D(real) - mid to ``state`` = (sign sum, D steps counted) and, every ``interval`` D
+    steps, moves ``p`` -- the augmenter's own probability word -- by ``step`` and leaves the interval's r in ``r``: all in device
+    memory, inside the capture."""
+    KEY = "mpgan_amd_ada"
+
+    def __init__(self, p: torch.Tensor, mid: float, target: float, interval: int, step: float):
+        self.mid, self.target, self.interval, self.step = mid, target, interval, step
+        self.p, self.p0 = p, float(p)
+        self.state = torch.zeros(2, device=p.device, dtype=torch.int32)
+        self.r = torch.zeros(1, device=p.device)
+        self.keep_out = False    # tests: keep the D step's last ``out`` tensor in ``last_out`` (no launch of its own)
+        self.last_out = None
+
+    @classmethod
+    def from_args(cls, augment, p: torch.Tensor, loss: str, batch_size: int, world_size: int):
+        """The controller ``augment`` (an ``Augment`` or the reference's namespace) asks for, or None."""
+        if not getattr(augment, "adaptive_prob", False):
+            return None
+        if world_size > 1:
+            raise ValueError(f"adaptive_prob with world_size = {world_size}: every rank would settle the probability from its own "
+                             "batches and the ranks would drift apart (the sign sum is not all-reduced); adaptive augmentation "
+                             "runs on one rank")
+        target, interval, kimg = (getattr(augment, k, v) for k, v in ADA_DEFAULTS.items())
+        if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
+            raise ValueError(f"ada_interval must be an integer >= 1, got {interval!r}")
+        if not 0.0 <= float(target) <= 1.0:
+            raise ValueError(f"ada_target must lie in [0, 1], got {target!r}")
+        if not float(kimg) > 0.0:
+            raise ValueError(f"ada_kimg must be > 0, got {kimg!r}")
+        # mid: the midpoint of the loss's two targets (sigmoid outputs against 1 / 0; raw scores either side of 0);
+        # step: p can cross [0, 1] in ada_kimg thousand real jets -- rounded to fp32 once, here
+        return cls(p, 0.5 if loss in ("og", "ls") else 0.0, _f32(target), interval, _f32(batch_size * interval / (1000.0 * float(kimg))))
+
+    def read(self) -> dict:
+        """{p, r, sign_sum, steps}; synchronises.  p and r are fp32 values held exactly by the Python floats."""
+        s = self.state.tolist()
+        return {"p": float(self.p), "r": float(self.r), "sign_sum": int(s[0]), "steps": int(s[1])}
+
+    def write(self, ent: Optional[dict]):
+        """Put a saved ``read`` back (None: the starting probability, an empty interval, r = 0)."""
+        if ent is None:
+            ent = {"p": self.p0, "r": 0.0, "sign_sum": 0, "steps": 0}
+        if not 0 <= int(ent["steps"]) < self.interval:
+            raise ValueError(f"saved adaptive-augmentation state counts {ent['steps']} D steps into an interval of {self.interval}")
+        self.p.fill_(float(ent["p"]))
+        self.r.fill_(float(ent["r"]))
+        self.state.copy_(torch.tensor([int(ent["sign_sum"]), int(ent["steps"])], dtype=torch.int32))
+
+    def update(self, out: torch.Tensor, n_real: int):
+        """The launch behind the D step's head; ``out``: D's outputs, the real half first.  Every augmentation launch that follows
+        in stream order reads the new probability.  CPU (host-logic tests with toy modules): ``ada_rule``."""
+        if self.keep_out:
+            self.last_out = out
+        if self.p.is_cuda:
+            ops.ada_update(out, n_real, self.mid, self.target, self.step, self.interval, self.state, self.p, self.r)
+            return
+        now = self.read()
+        sign_sum, steps, p, r = ada_rule(out, n_real, self.mid, self.target, self.step, self.interval, now["sign_sum"], now["steps"],
+                                         now["p"], now["r"])
+        self.write({"p": p, "r": r, "sign_sum": sign_sum, "steps": steps})
+
+    def tensors(self):    # (the warm-up's D steps move neither the probability nor the open interval)
+        return [self.p, self.state, self.r]
+
+    def save(self, group):
+        group[self.KEY] = self.read()
+
+    def load(self, group):    # (a file without the field resumes at the starting probability with an empty interval)
+        self.write(group.get(self.KEY))
+
+
+class Augmenter:
+    """Jet augmentation (train.py:438-442, :508-511): one affine map of (eta, phi) per jet, drawn on the device from the seed that
+    keys the noise and the dropout masks (``ops.augment``).  The probability ``p`` lives in device memory -- a captured graph
+    follows ``TrainStep.set_aug_prob`` and the controller's updates; ``params[site]``: the last maps drawn at each of ``AUG_SITES``."""
+
+    def __init__(self, flags: int, translate_ratio: float, scale_sd: float, p: torch.Tensor, batch_size: int):
+        self.flags, self.translate_ratio, self.scale_sd, self.p = flags, float(translate_ratio), float(scale_sd), p
+        self.params = [torch.zeros(batch_size, 6, device=p.device) for _ in AUG_SITES]
+
+    @classmethod
+    def from_args(cls, augment, p: torch.Tensor, batch_size: int):
+        """None with all four switches off: the step without augmentation, launch for launch."""
+        flags = ops.augment_flags(augment.aug_r90, augment.aug_f, augment.aug_t, augment.aug_s)
+        return cls(flags, augment.translate_ratio, augment.scale_sd, p, batch_size) if flags else None
+
+    def apply(self, x: torch.Tensor, site: int, in_place: bool = False) -> torch.Tensor:
+        """``augment.augment(args, x, p)`` at ``site``; on the device with ``ops.AugmentFn``'s backward where ``x`` takes a
+        gradient.  CPU (host-logic tests with toy modules): the torch statement with torch's generator."""
+        if not self.p.is_cuda:
+            args = SimpleNamespace(device=self.p.device, aug_r90=self.flags & ops.AUG_R90, aug_f=self.flags & ops.AUG_FLIP,
+                                   aug_t=self.flags & ops.AUG_TRANSLATE, aug_s=self.flags & ops.AUG_SCALE,
+                                   translate_ratio=self.translate_ratio, scale_sd=self.scale_sd)
+            return maugment.augment(args, x, float(self.p))
+        if torch.is_grad_enabled() and x.requires_grad:
+            return ops.AugmentFn.apply(x, self.p, self.flags, self.translate_ratio, self.scale_sd, site, self.params[site])
+        return ops.augment(x, self.p, self.flags, self.translate_ratio, self.scale_sd, site, out=x if in_place else None,
+                           params=self.params[site])[0]
+
+
+class LabelDraw:
+    """Label smoothing / label noise of calc_D_loss (train.py:353-363, ``--label-smoothing`` / ``--label-noise``): the D step's
+    per-jet targets, drawn by one small launch in front of the head (``ops.label_targets``) from the seed that keys the noise and
+    the dropout masks.  ``drawn``: the labels Y of the last D step as drawn; ``targets`` / ``extra``: what the loss made of them
+    (``effective_targets``)."""
+
+    def __init__(self, smoothing: bool, noise: float, batch_size: int, dev):
+        self.smoothing, self.noise, self.B = smoothing, noise, batch_size
+        self.targets = torch.zeros(2 * batch_size, device=dev)
+        self.extra = torch.zeros(1, device=dev)
+        self.drawn = torch.zeros(2 * batch_size, device=dev)
+
+    @classmethod
+    def from_args(cls, loss: str, label_smoothing, label_noise, batch_size: int, dev):
+        """None with neither option on, and for ``w`` / ``hinge``, which never look at them (as in the reference): no launch, no
+        buffers, the step as it was."""
+        if isinstance(label_noise, bool) or not 0.0 <= float(label_noise) <= 1.0:
+            raise ValueError(f"label_noise is a probability in [0, 1], got {label_noise!r}")
+        if label_smoothing and loss == "og":
+            raise ValueError("label_smoothing with loss = 'og': the reference draws the smoothed labels with shape [B] "
+                             "(train.py:354-355) and its nn.BCELoss refuses them against outputs [B, 1] (\"Using a target size ... "
+                             "that is different to the input size\", train.py:366); smoothing runs with loss = 'ls' only")
+        on = loss in ("og", "ls") and (bool(label_smoothing) or float(label_noise) > 0.0)
+        return cls(bool(label_smoothing), float(label_noise), batch_size, dev) if on else None
+
+    def draw(self):
+        """calc_D_loss's ``Y_real`` / ``Y_fake`` of this D step into the three buffers.  CPU (host-logic tests with toy modules):
+        the reference's own four calls in its order, from torch's generator."""
+        B = self.B
+        if self.targets.is_cuda:
+            ops.label_targets(B, self.smoothing, self.noise, self.targets.device, out=(self.targets, self.extra, self.drawn))
+            return
+        if self.smoothing:
+            y_real = torch.empty(B).uniform_(0.7, 1.2)
+            y_fake = torch.empty(B).uniform_(0.0, 0.3)
+        else:
+            y_real, y_fake = torch.ones(B), torch.zeros(B)
+        if self.noise:
+            y_real[torch.rand(B) < self.noise] = 0
+            y_fake[torch.rand(B) < self.noise] = 1
+        t, extra = effective_targets(y_real, y_fake, self.smoothing)
+        self.targets.copy_(t)
+        self.extra.copy_(extra.reshape(1))
+        self.drawn.copy_(torch.cat([y_real, y_fake]))

@@ -33,15 +33,15 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from dataclasses import dataclass
-from types import SimpleNamespace
 from typing import Optional
 
 import torch
 from torch import nn
 
 from . import _lib, ops, dist as mdist
-from .mpgan import MPGenerator, MPDiscriminator, augment as maugment
+from .mpgan import MPGenerator, MPDiscriminator
+from .step_options import (ADA_DEFAULTS, AUG_SITES, AdaController, Augment, Augmenter, DeviceWords, LabelDraw, Schedule,  # noqa: F401
+                           SeedState, ada_rule, effective_targets)
 
 LR = {  # setup_training.py:848-872 (lr_disc, lr_gen) per jet type for model = mpgan
     "g": (3e-5, 1e-5), "t": (6e-5, 2e-5), "q": (1.5e-5, 0.5e-5),
@@ -148,17 +148,7 @@ class FlatParams:
             off += k
         self.n = n
         self.lr = None  # last learning rate used (for state_dict's param_groups)
-        # TrainStep: the device whose dropout / noise seed travels with this optimizer's state dict (``SEED_KEY`` in its
-        # parameter group: torch.optim's own load_state_dict carries unknown group keys along untouched)
-        self.seed_device = None
-        self.seed_rank = 0     # this process's rank in the data-parallel group (TrainStep sets it): saved beside the seed
-        # TrainStep: its ``batch_ndx`` (num_critic / num_gen schedule) is kept HERE, in G's FlatParams, and saved beside the seed; None
-        # outside a TrainStep.  (Not a reference back to the step: a cycle would leave the step's hipGraphs to the garbage
-        # collector, which may run in the middle of another step's capture.)
-        self.batch_ndx = None
-        # TrainStep with an adaptive augmentation probability: the controller's device words (``_ada_words``) are kept HERE, in D's
-        # FlatParams, and saved under ``ADA_KEY``; None otherwise
-        self.ada = None
+        self.carried = []   # the carried entries (step_options.py) that travel with this optimizer's state dict; TrainStep fills it
 
     def zero_grad(self):
         self.grad.zero_()
@@ -201,10 +191,8 @@ class FlatParams:
 
     # -- torch.optim-compatible state ---------------------------------------------------------------
     _STATE_KEYS = {"rmsprop": ("square_avg", None), "adam": ("exp_avg_sq", "exp_avg"), "adadelta": ("square_avg", "acc_delta")}
-    SEED_KEY = "mpgan_amd_seed"
-    SEED_RANK_KEY = "mpgan_amd_seed_rank"
-    BATCH_KEY = "mpgan_amd_batch_ndx"
-    ADA_KEY = "mpgan_amd_ada"
+    # (the carried entries' keys, under the names they had here)
+    SEED_KEY, SEED_RANK_KEY, BATCH_KEY, ADA_KEY = SeedState.KEY, SeedState.RANK_KEY, Schedule.KEY, AdaController.KEY
 
     def _torch_optimizer(self, lr):
         """A torch.optim instance over detached CPU stand-ins of the parameters: the source of truth for the
@@ -234,13 +222,8 @@ class FlatParams:
                 if k_aux is not None:
                     ent[k_aux] = self.aux[off:off + k].view(shape).clone()
                 sd["state"][i if filtered else self._trained_idx[i]] = ent
-        if self.seed_device is not None:
-            sd["param_groups"][0][self.SEED_KEY] = ops.get_seed(self.seed_device)
-            sd["param_groups"][0][self.SEED_RANK_KEY] = int(self.seed_rank)
-        if self.batch_ndx is not None:
-            sd["param_groups"][0][self.BATCH_KEY] = int(self.batch_ndx)
-        if self.ada is not None:
-            sd["param_groups"][0][self.ADA_KEY] = _ada_read(self.ada)
+        for c in self.carried:
+            c.save(sd["param_groups"][0])
         return sd
 
     def load_state_dict(self, sd: dict):
@@ -282,41 +265,14 @@ class FlatParams:
         self.step_count.fill_(steps)
         self._host_steps = int(steps)
         self.lr = groups[0].get("lr", self.lr)
-        if self.seed_device is not None and self.SEED_KEY in groups[0]:
-            # a resumed run goes on with the noise / dropout stream where the saved one stopped, not from its start -- on the rank
-            # that wrote the file.  The reference's checkpoint is ONE file per epoch (train.py:534-535): every other rank of a
-            # resumed data-parallel run moves the saved value by its distance in rank (ops.rerank_seed), so that no two ranks
-            # share noise or masks behind a resume either.
-            ops.set_seed(ops.rerank_seed(int(groups[0][self.SEED_KEY]), int(groups[0].get(self.SEED_RANK_KEY, 0)), self.seed_rank),
-                         self.seed_device)
-        if self.batch_ndx is not None:     # (a file without the field -- the reference's, an older one -- resumes at the top of an epoch)
-            self.batch_ndx = int(groups[0].get(self.BATCH_KEY, 0))
-        if self.ada is not None:           # (a file without the field resumes at the starting probability with an empty interval)
-            _ada_write(self.ada, groups[0].get(self.ADA_KEY))
+        for c in self.carried:
+            c.load(groups[0])
         return self.lr
 
     def versions(self) -> int:
         """Sum of the autograd version counters of the parameters: changes when anything but the fused optimiser (which
         works on the flat buffer, behind autograd's back) writes them -- ``load_state_dict``, an in-place edit."""
         return sum(p._version for p in self.params)
-
-
-def _ada_read(a) -> dict:
-    """{p, r, sign_sum, steps} of the controller's device words ``a`` (``TrainStep._ada_words``); synchronises.  p and r are fp32
-    values held exactly by the Python floats."""
-    s = a.state.tolist()
-    return {"p": float(a.p), "r": float(a.r), "sign_sum": int(s[0]), "steps": int(s[1])}
-
-
-def _ada_write(a, ent: Optional[dict]):
-    """Put a saved ``_ada_read`` back (None: the starting probability, an empty interval, r = 0)."""
-    if ent is None:
-        ent = {"p": a.p0, "r": 0.0, "sign_sum": 0, "steps": 0}
-    if not 0 <= int(ent["steps"]) < a.interval:
-        raise ValueError(f"saved adaptive-augmentation state counts {ent['steps']} D steps into an interval of {a.interval}")
-    a.p.fill_(float(ent["p"]))
-    a.r.fill_(float(ent["r"]))
-    a.state.copy_(torch.tensor([int(ent["sign_sum"]), int(ent["steps"])], dtype=torch.int32))
 
 
 def _set_requires_grad(flat: "FlatParams", flag: bool):
@@ -335,70 +291,6 @@ def _forward_writes_no_state(module: nn.Module) -> bool:
 
 
 LOSSES = ("ls", "og", "w", "hinge")
-
-
-@dataclass
-class Augment:
-    """The reference's augmentation switches (``--aug-r90 / --aug-f / --aug-t / --aug-s``, ``--translate-ratio``, ``--scale-sd``,
-    ``--aug-prob``; setup_training.py:385-402, its defaults) for ``TrainStep(augment=...)``; the reference's own argument
-    namespace has the same field names and is taken as it is.
-    ``adaptive_prob`` (``--adaptive-prob``, setup_training.py:399; the reference reads ``augment_p[-1]`` under it and never fills
-    it): the probability is moved on the device by ADA's rule (Karras et al. 2020) from D's outputs on the real jets -- every
-    ``ada_interval`` D steps by ``B * ada_interval / (1000 * ada_kimg)``, up while the mean sign of (D(real) - midpoint) exceeds
-    ``ada_target``, down while it falls short (``ops.ada_update``).  ``aug_prob`` is then the STARTING value: the paper starts at
-    0, and that is the usual choice -- the field's default of 1 is the reference's for a fixed probability and is not overridden.
-    The three ``ada_*`` fields are ADA's published defaults; a reference namespace lacks them and gets these."""
-    aug_r90: bool = False
-    aug_f: bool = False
-    aug_t: bool = False
-    aug_s: bool = False
-    translate_ratio: float = 0.125
-    scale_sd: float = 0.125
-    aug_prob: float = 1.0      # (rand_mix: p == 1 takes nothing)
-    adaptive_prob: bool = False
-    ada_target: float = 0.6
-    ada_interval: int = 4
-    ada_kimg: float = 500.0
-
-
-AUG_SITES = {"D_fake": 0, "G_fake": 1, "D_real": 2}   # ops.augment's sites within an iteration
-ADA_DEFAULTS = {f: Augment.__dataclass_fields__[f].default for f in ("ada_target", "ada_interval", "ada_kimg")}
-
-
-def _f32(v: float) -> float:
-    """``v`` rounded to fp32 (to nearest even), as a Python float"""
-    return float(torch.tensor(float(v), dtype=torch.float32))
-
-
-def ada_rule(out, n_real: int, mid: float, target: float, step: float, interval: int, sign_sum: int, steps: int, p: float, r: float):
-    """``mpg_ada_update`` (include/mpgan_amd.h) in Python on a host tensor ``out``: (sign_sum, steps, p, r) after one D step.  The
-    counts are integers; the one division and the one sum are torch's fp32 operations on fp32 operands.  The CPU path of
-    ``TrainStep`` (host-logic tests with toy modules)."""
-    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
-    o, mid, target = out.detach().reshape(-1)[:n_real].float(), f32(mid), float(f32(target))
-    sign_sum += int((o > mid).sum()) - int((o < mid).sum())
-    steps += 1
-    if steps != interval:
-        return sign_sum, steps, p, r
-    r = float(f32(sign_sum) / f32(n_real * interval))
-    if r > target:
-        p = float(f32(p) + f32(step))
-    elif r < target:
-        p = float(f32(p) - f32(step))
-    return 0, 0, min(1.0, max(0.0, p)), r
-
-
-def effective_targets(y_real: torch.Tensor, y_fake: torch.Tensor, smoothing: bool):
-    """(t [2B], extra): calc_D_loss's labels ``Y_real`` / ``Y_fake`` (train.py:353-363, after the noise) as ``d_loss`` and the fused
-    head take them -- loss = sum_b term(out_b, t_b) / B + extra.  Without smoothing the labels are [B, 1] like D's outputs: t = Y,
-    extra = 0.  With smoothing they are [B] and ``MSELoss(out [B, 1], Y [B])`` broadcasts to [B, B] (train.py:369-370):
-    mean_ij (out_i - Y_j)^2 = mean_i (out_i - mean(Y))^2 + popvar(Y) per half, so t is each half's mean and extra the two
-    population variances.  Any device and dtype."""
-    y_real, y_fake = y_real.reshape(-1), y_fake.reshape(-1)
-    if not smoothing:
-        return torch.cat([y_real, y_fake]), torch.zeros((), device=y_real.device, dtype=y_real.dtype)
-    t = torch.cat([y_real.mean().expand(y_real.numel()), y_fake.mean().expand(y_fake.numel())])
-    return t, y_real.var(unbiased=False) + y_fake.var(unbiased=False)
 
 
 def d_loss(loss: str, out: torch.Tensor, B: int, real: Optional[torch.Tensor] = None,
@@ -490,12 +382,14 @@ class TrainStep:
                  track_epoch_losses: bool = False, label_smoothing: bool = False, label_noise: float = 0.0):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
-        if isinstance(label_noise, bool) or not 0.0 <= float(label_noise) <= 1.0:
-            raise ValueError(f"label_noise is a probability in [0, 1], got {label_noise!r}")
-        if label_smoothing and loss == "og":
-            raise ValueError("label_smoothing with loss = 'og': the reference draws the smoothed labels with shape [B] "
-                             "(train.py:354-355) and its nn.BCELoss refuses them against outputs [B, 1] (\"Using a target size ... "
-                             "that is different to the input size\", train.py:366); smoothing runs with loss = 'ls' only")
+        self.dev = dev = next(G.parameters()).device
+        gpu = dev.type == "cuda"
+        # Label smoothing / label noise (``LabelDraw``), ``og`` / ``ls`` only: ``label_drawn``, ``label_targets`` and ``label_extra``
+        # are its three buffers
+        self._labels = LabelDraw.from_args(loss, label_smoothing, label_noise, batch_size, dev)
+        self.label_smoothing, self.label_noise, self.labels_on = bool(label_smoothing), float(label_noise), self._labels is not None
+        if self.labels_on:
+            self.label_targets, self.label_extra, self.label_drawn = self._labels.targets, self._labels.extra, self._labels.drawn
         for name, v in (("num_critic", num_critic), ("num_gen", num_gen)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
@@ -507,8 +401,6 @@ class TrainStep:
         # ``last_ran`` names what the last ``step()`` ran.
         self.num_critic, self.num_gen = num_critic, num_gen
         self.last_ran = ()
-        self.dev = dev = next(G.parameters()).device
-        gpu = dev.type == "cuda"
 
         # Every MPG_* switch of this file is read HERE, once, as the step is built: a change of the environment afterwards
         # reaches neither a later iteration nor ``capture``.  What each one does is said where its attribute is set, below.
@@ -540,7 +432,8 @@ class TrainStep:
         self.state = ops.dev_state(dev)
         self.fG = FlatParams(G, optimizer, betas)
         self.fD = FlatParams(D, optimizer, betas)
-        self.fG.batch_ndx = 0      # (the schedule's batch index: saved with G's optimizer state, see ``batch_ndx``)
+        self._schedule = Schedule()      # (the schedule's batch index: saved with G's optimizer state, see ``batch_ndx``)
+        self._seed = None
         if gpu:
             # The generator's noise and every dropout mask come from counter-based streams keyed by the DEVICE seed, which
             # torch.manual_seed does not reach.  Unless the caller has set it (ops.set_seed), derive it here from torch's
@@ -556,8 +449,7 @@ class TrainStep:
             if self.state.seed_is_default and self.state.auto_seed_key != key:
                 ops.set_seed(ops.derived_seed(*key), dev, _auto=True)
                 self.state.auto_seed_key = key
-            self.fG.seed_device = dev
-            self.fG.seed_rank = rank
+            self._seed = SeedState(dev, rank)
             # arrival counters of the sender-chunked launches (ops._tickets): allocated and zeroed HERE, on the default stream, for
             # the step's largest launch (the D step's 2B jets) -- never inside a capture, never first on a side stream
             ops.reserve_tickets(dev, 2 * batch_size * ((num_particles + 31) // 32))
@@ -612,44 +504,17 @@ class TrainStep:
         # are small or latency-bound launches that leave most CUs idle, and two full-chip forwards fill them
         self.gen_ahead_late = self.gen_ahead and self.wgrad_side and on["MPG_GEN_AHEAD_LATE"]
         self.bridge = gpu and on["MPG_BRIDGE"]      # (see ``_bridge``)
-        # Jet augmentation (train.py:438-442, :508-511): one affine map of (eta, phi) per jet, drawn on the device from the seed
-        # that keys the noise and the dropout masks (ops.augment) -- one launch on the generated half of the D step's batch, one
-        # each way between the generator's jets and the discriminator in the G step.  The probability lives in device memory:
-        # ``set_aug_prob`` reaches a captured graph.  ``aug_params[site]`` holds the last maps drawn at each site (AUG_SITES).
-        self.aug = self.aug_p = None
+        # Jet augmentation (``Augmenter``): one launch on the generated half of the D step's batch, one each way between the
+        # generator's jets and the discriminator in the G step -- and its adaptive probability (``AdaController``), which moves
+        # the augmenter's probability word ``aug_p``.  With the four switches off there is nothing to adapt: no launch, no buffers.
+        self.aug = self.aug_p = self._ada = None
         if augment is not None:
-            flags = ops.augment_flags(augment.aug_r90, augment.aug_f, augment.aug_t, augment.aug_s)
             self.aug_p = torch.full((1,), float(augment.aug_prob), device=dev)
-            if flags:      # (all four switches off: the step without augmentation, launch for launch)
-                self.aug = SimpleNamespace(flags=flags, translate_ratio=float(augment.translate_ratio), scale_sd=float(augment.scale_sd))
-                self.aug_params = [torch.zeros(batch_size, 6, device=dev) for _ in AUG_SITES]
-        # The adaptive probability (``Augment.adaptive_prob``): one launch behind the D step's head
-        # (ops.ada_update) adds the signs of D(real) - mid to ``ada_state`` = (sign sum, D steps counted) and, every ``interval`` D
-        # steps, moves ``aug_p`` by ``step`` and leaves the interval's r in ``ada_r`` -- all in device memory, inside the capture.
-        # With the four switches off there is nothing to adapt: no launch, no buffers.
-        self._ada = self.ada_state = self.ada_r = None
-        self.ada_keep_out = False    # tests: keep the D step's last ``out`` tensor in ``ada_last_out`` (no launch of its own)
-        self.ada_last_out = None
-        if self.aug is not None and getattr(augment, "adaptive_prob", False):
-            if world_size > 1:
-                raise ValueError(f"adaptive_prob with world_size = {world_size}: every rank would settle the probability from its own "
-                                 "batches and the ranks would drift apart (the sign sum is not all-reduced); adaptive augmentation "
-                                 "runs on one rank")
-            target, interval, kimg = (getattr(augment, k, v) for k, v in ADA_DEFAULTS.items())
-            if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
-                raise ValueError(f"ada_interval must be an integer >= 1, got {interval!r}")
-            if not 0.0 <= float(target) <= 1.0:
-                raise ValueError(f"ada_target must lie in [0, 1], got {target!r}")
-            if not float(kimg) > 0.0:
-                raise ValueError(f"ada_kimg must be > 0, got {kimg!r}")
-            # mid: the midpoint of the loss's two targets (sigmoid outputs against 1 / 0; raw scores either side of 0);
-            # step: p can cross [0, 1] in ada_kimg thousand real jets -- rounded to fp32 once, here
-            self._ada = SimpleNamespace(mid=0.5 if loss in ("og", "ls") else 0.0, target=_f32(target), interval=interval,
-                                        step=_f32(batch_size * interval / (1000.0 * float(kimg))))
-            self.ada_state = torch.zeros(2, device=dev, dtype=torch.int32)
-            self.ada_r = torch.zeros(1, device=dev)
-            self.fD.ada = self._ada_words = SimpleNamespace(p=self.aug_p, state=self.ada_state, r=self.ada_r, interval=interval,
-                                                            p0=_f32(augment.aug_prob))
+            self.aug = Augmenter.from_args(augment, self.aug_p, batch_size)
+        if self.aug is not None:
+            self.aug_params = self.aug.params
+            self._ada = AdaController.from_args(augment, self.aug_p, loss, batch_size, world_size)
+        self.ada_state, self.ada_r = (None, None) if self._ada is None else (self._ada.state, self._ada.r)    # (the controller's words)
         # the generator's noise and its jets' masks drawn by one launch (MPG_NOISE_MASK=0: mpg_normal, then mpg_rank_mask)
         self.noise_mask = gpu and on["MPG_NOISE_MASK"]
         self.fixed_noise = None  # tests: (noise_D, noise_G) used instead of fresh samples
@@ -658,17 +523,11 @@ class TrainStep:
         # (FlatParams.step(zero_grad=True)): no memset of its own at the top of train_D / train_G.  A caller that accumulates
         # into the networks' .grad between iterations calls ``mark_grads_dirty()``.
         self._clean = {"D": True, "G": True}
-        # Label smoothing / label noise of calc_D_loss (train.py:353-363, ``--label-smoothing`` / ``--label-noise``): the D
-        # step's per-jet targets, drawn by one small launch in front of the head (ops.label_targets) from the seed that keys the
-        # noise and the dropout masks.  ``og`` / ``ls`` only, as in the reference (w / hinge never look at the two options);
-        # with neither on: no launch, no buffers, the step as it was.  ``label_drawn``: the labels Y of the last D step as
-        # drawn; ``label_targets`` / ``label_extra``: what the loss made of them (``effective_targets``).
-        self.label_smoothing, self.label_noise = bool(label_smoothing), float(label_noise)
-        self.labels_on = loss in ("og", "ls") and (self.label_smoothing or self.label_noise > 0.0)
-        if self.labels_on:
-            self.label_targets = torch.zeros(2 * batch_size, device=dev)
-            self.label_extra = torch.zeros(1, device=dev)
-            self.label_drawn = torch.zeros(2 * batch_size, device=dev)
+        # what outlives an iteration, by the optimizer file that carries it (the keys' order in G's file: seed, rank, batch_ndx)
+        self.fG.carried = [c for c in (self._seed, self._schedule) if c is not None]
+        self.fD.carried = [c for c in (self._ada,) if c is not None]
+        if self.epoch_sums is not None:
+            self.fG.carried.append(DeviceWords(self.epoch_sums.values()))
         # a device-resident data set (data.DeviceJetLoader): its feed launch is the first thing of every iteration
         self.loader = None
         if loader is not None:
@@ -690,6 +549,7 @@ class TrainStep:
         if loader.device != self.data.device:
             raise ValueError(f"loader lives on {loader.device}, the step on {self.data.device}")
         self.loader = loader
+        self.fG.carried.append(DeviceWords([loader.cursor]))     # (the warm-up iterations of ``capture`` consume no jets)
 
     # -- the three segments between collectives ------------------------------------------------
     def _noise(self, which: int = 0):
@@ -732,55 +592,22 @@ class TrainStep:
         first), and the open interval's sign sum and count of D steps.  Read-only, and the one place that synchronises."""
         if self._ada is None:
             raise RuntimeError("TrainStep was built without adaptive_prob (or with every augmentation switch off)")
-        return _ada_read(self._ada_words)
+        return self._ada.read()
 
-    def _ada_update(self, out: torch.Tensor):
-        """The controller's launch behind the D step's head; ``out``: D's outputs, the real half first.  Every augmentation
-        launch that follows in stream order reads the new probability."""
-        a, w = self._ada, self._ada_words
-        if self.ada_keep_out:
-            self.ada_last_out = out
-        if self.dev.type == "cuda":
-            ops.ada_update(out, self.B, a.mid, a.target, a.step, a.interval, w.state, w.p, w.r)
-            return
-        st = w.state.tolist()
-        sign_sum, steps, p, r = ada_rule(out, self.B, a.mid, a.target, a.step, a.interval, st[0], st[1], float(w.p), float(w.r))
-        _ada_write(w, {"p": p, "r": r, "sign_sum": sign_sum, "steps": steps})
+    @property
+    def ada_keep_out(self) -> bool:      # (tests: the controller's hook)
+        return self._ada.keep_out
+
+    @ada_keep_out.setter
+    def ada_keep_out(self, keep: bool):
+        self._ada.keep_out = keep
+
+    @property
+    def ada_last_out(self):
+        return self._ada.last_out
 
     def _augment(self, x: torch.Tensor, site: int, in_place: bool = False) -> torch.Tensor:
-        """``augment.augment(args, x, p)`` at ``site``; on the device with ``ops.AugmentFn``'s backward where ``x`` takes a
-        gradient.  CPU (host-logic tests with toy modules): the torch statement with torch's generator."""
-        a = self.aug
-        if self.dev.type != "cuda":
-            args = SimpleNamespace(device=self.dev, aug_r90=a.flags & ops.AUG_R90, aug_f=a.flags & ops.AUG_FLIP,
-                                   aug_t=a.flags & ops.AUG_TRANSLATE, aug_s=a.flags & ops.AUG_SCALE,
-                                   translate_ratio=a.translate_ratio, scale_sd=a.scale_sd)
-            return maugment.augment(args, x, float(self.aug_p))
-        if torch.is_grad_enabled() and x.requires_grad:
-            return ops.AugmentFn.apply(x, self.aug_p, a.flags, a.translate_ratio, a.scale_sd, site, self.aug_params[site])
-        return ops.augment(x, self.aug_p, a.flags, a.translate_ratio, a.scale_sd, site, out=x if in_place else None,
-                           params=self.aug_params[site])[0]
-
-    def _draw_labels(self):
-        """calc_D_loss's ``Y_real`` / ``Y_fake`` (train.py:353-363) of this D step into the static label buffers.  CPU (host-logic
-        tests with toy modules): the reference's own four calls in its order, from torch's generator."""
-        B = self.B
-        if self.dev.type == "cuda":
-            ops.label_targets(B, self.label_smoothing, self.label_noise, self.dev,
-                              out=(self.label_targets, self.label_extra, self.label_drawn))
-            return
-        if self.label_smoothing:
-            y_real = torch.empty(B).uniform_(0.7, 1.2)
-            y_fake = torch.empty(B).uniform_(0.0, 0.3)
-        else:
-            y_real, y_fake = torch.ones(B), torch.zeros(B)
-        if self.label_noise:
-            y_real[torch.rand(B) < self.label_noise] = 0
-            y_fake[torch.rand(B) < self.label_noise] = 1
-        t, extra = effective_targets(y_real, y_fake, self.label_smoothing)
-        self.label_targets.copy_(t)
-        self.label_extra.copy_(extra.reshape(1))
-        self.label_drawn.copy_(torch.cat([y_real, y_fake]))
+        return self.aug.apply(x, site, in_place)
 
     def _bridge(self) -> bool:
         """GAPT: gen's ``final_fc`` + tanh and disc's ``input_embedding`` as one launch each way (``ops.GenDiscBridgeFn``;
@@ -854,13 +681,13 @@ class TrainStep:
     def _head_loss_backward(self, y, mask, gen_step: bool, then=None):
         """The fused head with its loss (train_D: with the head's own weight gradients), then the backward from (y, dy)."""
         w, b, mean, sigmoid, p = self.D.fused_head()
-        # (train_D under label smoothing / noise: the targets ``_draw_labels`` left; calc_G_loss has neither)
+        # (train_D under label smoothing / noise: the targets ``LabelDraw.draw`` left; calc_G_loss has neither)
         lab = {"targets": self.label_targets, "loss_extra": self.label_extra} if self.labels_on and not gen_step else {}
         out, dy = ops.disc_head_loss(y, mask, w, b, mean=mean, sigmoid=sigmoid, p_drop=p, training=self.D.training, loss=self.loss,
                                      n_real=self.B, gen_step=gen_step, count=self.B, loss_out=self.G_loss if gen_step else self.D_loss,
                                      want_dy=True, wgrad=None if gen_step else (w.grad, None if b is None else b.grad), **lab)
         if self._ada is not None and not gen_step:     # (directly behind the head, on its stream: train_G's augmentation reads the new p)
-            self._ada_update(out)
+            self._ada.update(out, self.B)
         self._sum_epoch("G" if gen_step else "D")
         self._backward(y, dy, then)
 
@@ -871,13 +698,7 @@ class TrainStep:
     def _seg_D(self, join: bool = True, fork: bool = True):  # train_D up to and including backward (train.py:419-460)
         # (join=False: the generator-ahead branch stays open for a _seg_G that follows in the same graph / eager run;
         # fork=False: a batch on which the generator does not train -- no _seg_G follows, so the branch is never opened)
-        # parameter gradients are added straight into the flat buffers (no AccumulateGrad kernel per parameter)
-        if self.loader is not None:     # (first: the generator-ahead branch reads self.labels)
-            self.loader.feed(self)
-        self.state.grad_into_param = True
-        self.state.order_cache = None   # (ops.jet_order: the masks of this iteration live where last iteration's did)
-        # (the dropout / noise seed of this iteration was set by the last launch of the iteration before: _seg_end)
-        self.D.train()
+        self._open_batch()
         if fork and self.gen_ahead and not self.gen_ahead_late:
             self._fork_generator()
         self.G.eval()
@@ -890,6 +711,23 @@ class TrainStep:
         finally:
             if join:     # everything of this segment is ordered before whatever follows it
                 self._ahead.join("seg_D")
+
+    def _open_batch(self):   # the top of every batch, whichever network trains on it
+        if self.loader is not None:     # (first: the generator-ahead branch reads self.labels)
+            self.loader.feed(self)
+        # parameter gradients are added straight into the flat buffers (no AccumulateGrad kernel per parameter)
+        self.state.grad_into_param = True
+        self.state.order_cache = None   # (ops.jet_order: the masks of this iteration live where last iteration's did)
+        # (the dropout / noise seed of this iteration was set by the last launch of the iteration before: _close_batch)
+        self.D.train()
+
+    def _close_batch(self, net: str):   # the batch's last optimizer step ("D" | "G"), which also moves the seed on
+        # (what ops.bump_seed at the head of the next train_D would do in a launch of its own)
+        flat, lr = (self.fD, self.lr_disc) if net == "D" else (self.fG, self.lr_gen)
+        flat.step(lr, gscale=1.0 / self.world, zero_grad=True, advance_seed=ops.seed_tensor(self.dev))
+        self._clean[net] = True
+        self._refresh_packed(flat.module)
+        self.state.grad_into_param = False
 
     def _fork_generator(self):
         """train_G's ``gen_data = gen(...)`` (train.py:500-511) on the side stream, in training mode."""
@@ -908,7 +746,7 @@ class TrainStep:
         fake, jets = self._generate_for_D(route)
         if route != "module":
             if self.labels_on:
-                self._draw_labels()
+                self._labels.draw()
             # real jets sit in the first half of the static batch; the generator has written the second half itself
             return self._head_loss_backward(*self._features(route, jets, self._labels2, False), False, late_fork)
         if self.batch_real_fake:
@@ -916,7 +754,7 @@ class TrainStep:
         else:
             out = torch.cat([self.D(self.data.clone(), self.labels).reshape(-1), self.D(fake, self.labels).reshape(-1)])
         if self.labels_on:     # (drawn where calc_D_loss draws them: behind both passes of D, in front of the penalty)
-            self._draw_labels()
+            self._labels.draw()
             loss = d_loss(self.loss, out, self.B, self.label_targets, self.label_extra)
         else:
             loss = d_loss(self.loss, out, self.B, self._real)
@@ -933,7 +771,7 @@ class TrainStep:
             loss = loss + gp
         if self._ada is not None:
             # behind the penalty's augmentation of the real batch: every augmentation launch of this D step has read the old p
-            self._ada_update(out.detach().reshape(-1))
+            self._ada.update(out.detach().reshape(-1), self.B)
         self._backward(loss, then=late_fork)
 
     def gradient_penalty(self, real: torch.Tensor, fake: torch.Tensor) -> torch.Tensor:
@@ -990,20 +828,13 @@ class TrainStep:
     def _seg_D_end(self):  # D_optimizer.step() (train.py:461) of a batch on which the generator does not train
         # the seed moves on HERE, as it does in G's optimizer launch otherwise (_seg_end): the next critic step would redraw this
         # one's generator noise, dropout masks and augmentation maps without it
-        self.fD.step(self.lr_disc, gscale=1.0 / self.world, zero_grad=True, advance_seed=ops.seed_tensor(self.dev))
-        self._clean["D"] = True
-        self._refresh_packed(self.D)
-        self.state.grad_into_param = False
+        self._close_batch("D")
 
     def _seg_G(self, alone: bool = False):  # D_optimizer.step() (train.py:461) + train_G up to backward (:494-520)
         if alone:
             # a batch on which the discriminator does not train (num_gen > 1): what the top of _seg_D sets up, and train_G --
             # the data loader yields the batch all the same, and train_G takes its labels (train.py:832-835, :872)
-            if self.loader is not None:
-                self.loader.feed(self)
-            self.state.grad_into_param = True
-            self.state.order_cache = None
-            self.D.train()
+            self._open_batch()
         else:
             # optimizer.zero_grad() of the next train_D (train.py:419) rides in this launch: the buffer is cleared behind its last use
             self.fD.step(self.lr_disc, gscale=1.0 / self.world, zero_grad=True)
@@ -1033,11 +864,7 @@ class TrainStep:
         _set_requires_grad(self.fD, True)
 
     def _seg_end(self):  # G_optimizer.step() (train.py:521)
-        # ... and so does the next iteration's seed (what ops.bump_seed at the head of train_D would do in a launch of its own)
-        self.fG.step(self.lr_gen, gscale=1.0 / self.world, zero_grad=True, advance_seed=ops.seed_tensor(self.dev))
-        self._clean["G"] = True
-        self._refresh_packed(self.G)
-        self.state.grad_into_param = False
+        self._close_batch("G")
 
     def mark_grads_dirty(self):
         """Tell the step that something outside it wrote the networks' .grad buffers (they are views of the flat gradient
@@ -1080,19 +907,15 @@ class TrainStep:
                 self._allreduce(flat)
 
     def _training_state(self):
-        """Everything an iteration changes: parameters, optimiser moments and step counters, the dropout seed, the losses --
-        and what a FORWARD changes: the modules' buffers (batch norm's running statistics and batch counter) and frozen
-        parameters (spectral norm's power-iteration vectors, written in place by ``SpectralNorm.weight``)."""
-        ts = [self.D_loss, self.G_loss, self.GP, ops.seed_tensor(self.dev)]
-        if self.epoch_sums is not None:
-            ts += list(self.epoch_sums.values())
+        """Everything an iteration changes: the losses; parameters, optimiser moments and step counters; what a FORWARD
+        changes -- the modules' buffers (batch norm's running statistics and batch counter) and frozen parameters (spectral
+        norm's power-iteration vectors, written in place by ``SpectralNorm.weight``); and the device words of every carried
+        entry (the dropout seed, the epoch's sums, the loader's cursor, the adaptive probability)."""
+        ts = [self.D_loss, self.G_loss, self.GP]
         for f in (self.fD, self.fG):
             ts += [f.flat, f.sq, f.step_count] + ([f.aux] if f.aux is not None else [])
             ts += list(f.module.buffers()) + [p for p in f.module.parameters() if not p.requires_grad]
-        if self.loader is not None:      # (the data stream's cursor: the warm-up iterations of ``capture`` consume no jets)
-            ts.append(self.loader.cursor)
-        if self._ada is not None:        # (the warm-up's D steps move neither the probability nor the open interval)
-            ts += [self.aug_p, self.ada_state, self.ada_r]
+            ts += [t for c in f.carried for t in c.tensors()]
         return ts
 
     def capture(self, warmup: int = 3, kind: str = "DG"):
@@ -1196,21 +1019,17 @@ class TrainStep:
     @property
     def batch_ndx(self) -> int:
         """The reference's ``batch_ndx`` (train.py:829) of the batch the next ``step()`` is: steps since ``start_epoch``."""
-        return self.fG.batch_ndx
+        return self._schedule.batch_ndx
 
-    @property
-    def _batch_ndx(self) -> int:
-        return self.fG.batch_ndx
-
-    @_batch_ndx.setter
-    def _batch_ndx(self, b: int):
-        self.fG.batch_ndx = int(b)
+    @batch_ndx.setter
+    def batch_ndx(self, b: int):
+        self._schedule.batch_ndx = int(b)
 
     def start_epoch(self):
         """Where the reference's ``for batch_ndx, data in enumerate(...)`` begins (train.py:829): the schedule restarts -- batch
         0 trains D whatever ``num_gen`` is, and G only with ``num_critic`` = 1 -- and so do the epoch's loss sums (train.py:940-941).
         With ``num_critic = num_gen = 1`` every batch runs both and nothing depends on the index."""
-        self._batch_ndx = 0
+        self.batch_ndx = 0
         self._epoch_steps = 0
         if self.epoch_sums is not None:
             for t in self.epoch_sums.values():
@@ -1238,7 +1057,7 @@ class TrainStep:
         """One batch of the reference's epoch loop (train.py:829-878): train_D and / or train_G as ``num_critic`` / ``num_gen``
         say for ``batch_ndx``, which it moves on."""
         self.sync_external_writes()
-        kind = self._kind(self._batch_ndx)
+        kind = self._kind(self.batch_ndx)
         if not self.use_graphs:
             self._eager(kind)
         else:
@@ -1256,7 +1075,7 @@ class TrainStep:
             for net in self.KINDS[kind]:     # (only the networks this replay stepped)
                 (self.fD if net == "D" else self.fG).note_step()
         self.last_ran = self.KINDS[kind]
-        self._batch_ndx += 1
+        self.batch_ndx += 1
         self._epoch_steps += 1
 
     # -- optimiser state in the reference's checkpoint format (train.py:534-535, setup_training.py:1525-1535) -----

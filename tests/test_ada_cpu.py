@@ -233,7 +233,7 @@ def test_refusals_and_the_switches_off():
             _toy_step(train.Augment(**dict(ADA, **bad)))
     # all four switches off: adaptive_prob does nothing, as Augment without switches does nothing today
     off = _toy_step(train.Augment(adaptive_prob=True, aug_prob=0.25), world_size=1)
-    assert off.aug is None and off._ada is None and off.ada_state is None and off.fD.ada is None
+    assert off.aug is None and off._ada is None and off.ada_state is None and off.fD.carried == []
     with pytest.raises(RuntimeError, match="adaptive_prob"):
         off.ada
     fixed = _toy_step(train.Augment(aug_t=True, aug_prob=0.25))

@@ -32,8 +32,7 @@ def test_symbols_are_exported_with_the_documented_signatures():
                                                     "MPG_AUG_TRANSLATE": ops.AUG_TRANSLATE, "MPG_AUG_SCALE": ops.AUG_SCALE}
     assert (ops.AUG_R90, ops.AUG_FLIP, ops.AUG_TRANSLATE, ops.AUG_SCALE) == (1, 2, 4, 8)
     assert ops.augment_flags(aug_r90=True, aug_s=True) == 9 and ops.augment_flags() == 0
-    # the site tags stay clear of the noise's and of the dropout sites'
-    assert all(ops.AUG_TAG + s not in (ops.NOISE_TAG, ops.NOISE_TAG + 1) and ops.AUG_TAG + s >= (1 << 27) + 8 for s in range(3))
+    # (the site tags: test_cabi_cpu.py::test_tag_table)
 
 
 ARGS = SimpleNamespace(device="cpu", aug_r90=True, aug_f=True, aug_t=True, aug_s=True, translate_ratio=0.3, scale_sd=0.2)

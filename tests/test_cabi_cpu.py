@@ -62,6 +62,30 @@ def test_header_constants_match_their_python_mirrors():
     assert lim(bwd, "B2_LIST_MAX_Q") == ops.MAX_CHUNK_SENDERS_ES
 
 
+def test_tag_table():
+    """The five families of draws (include/mpgan_amd.h's tag table): ops.py's constants equal the header's defines, the spans are
+    pairwise disjoint -- also when every family is given at least 2^20 tags --, all lie above the dropout sites' tags (next_tag:
+    (< 2^24) * 8 + a site < 8, so below 2^27 + 8) and inside 32 bits, and the sites / rounds in use lie inside their spans."""
+    from mpgan_amd import ops
+    txt = open(HEADER).read()
+    defs = {k: int(v, 16) for k, v in re.findall(r"^#define\s+(MPG_\w+_TAG(?:_SPAN)?)\s+(0x[0-9A-Fa-f]+)\s*$", txt, flags=re.M)}
+    used = {"NOISE": 2, "AUG": 3, "LABEL": 1, "SHUFFLE": 4, "PICK": 1}     # sites 0-1, sites 0-2 (train.AUG_SITES), site 0, rounds 0-3, 0
+    assert set(defs) == {f"MPG_{n}_TAG{s}" for n in used for s in ("", "_SPAN")}
+    from mpgan_amd import train
+    assert sorted(train.AUG_SITES.values()) == list(range(used["AUG"]))
+    spans = {}
+    for name, n_used in used.items():
+        tag, span = defs[f"MPG_{name}_TAG"], defs[f"MPG_{name}_TAG_SPAN"]
+        assert tag == getattr(ops, name + "_TAG"), name
+        assert n_used <= span and tag >= (1 << 27) + 8 and tag + max(span, 1 << 20) <= (1 << 32), name
+        spans[name] = (tag, tag + max(span, 1 << 20))
+    assert ops.LABEL_TAG == 0x4C000000
+    for a in spans:
+        for b in spans:
+            if a < b:
+                assert spans[a][1] <= spans[b][0] or spans[b][1] <= spans[a][0], (a, b)
+
+
 def test_host_helpers():
     from mpgan_amd import ops
     assert ops.drop_params(0.0) == (0, 1.0)

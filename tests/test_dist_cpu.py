@@ -132,7 +132,7 @@ def _resume_worker(rank, world, port, out):
     G, D = ToyG(), ToyD()
     ts = train.TrainStep(G, D, 4, N, latent=LAT, use_graphs=False, process_group=pg, world_size=world)
     # (the device seed belongs to the GPU path; its host logic -- what is saved, what a rank makes of it -- is device-agnostic)
-    ts.fG.seed_device, ts.fG.seed_rank = cpu, rank
+    ts.fG.carried.insert(0, train.SeedState(cpu, rank))
     ops.set_seed(ops.derived_seed(torch.initial_seed(), rank), cpu, _auto=True)
     data, labels, nD, nG = _inputs(8)
     ts.set_batch(data[rank * 4:rank * 4 + 4], labels[rank * 4:rank * 4 + 4])

@@ -290,7 +290,7 @@ def test_without_adaptive_prob_the_step_has_no_such_launch(monkeypatch):
             _reset_tags()
             ts = _ada_step(aug, use_graphs=False, fixed=True)
             ts.step()
-            assert ts._ada is None and ts.ada_state is None and ts.ada_r is None and ts.fD.ada is None
+            assert ts._ada is None and ts.ada_state is None and ts.ada_r is None and ts.fD.carried == []
             assert train.FlatParams.ADA_KEY not in ts.optimizer_state_dicts()[0]["param_groups"][0]
             res.append(_state(ts))
     assert _all_equal(res[0], res[2]) and len(res[1]) == len(res[0])

@@ -1145,7 +1145,7 @@ def test_device_seed_follows_torch_seed_and_travels_with_the_checkpoint():
         ts.load_optimizer_state_dicts(sdD, sdG)
         assert ops.get_seed(dev) == now
         # another rank reading the same file gets a stream of its own (tests/test_dist_cpu.py runs it on two ranks)
-        ts.fG.seed_rank = 3
+        ts._seed.rank = 3
         ts.load_optimizer_state_dicts(sdD, sdG)
         assert ops.get_seed(dev) == ops.rerank_seed(now, 0, 3) != now
     finally:
@@ -1230,3 +1230,81 @@ def test_a_backward_that_raises_leaves_no_branch_and_no_weight_gradient_state_op
     torch.cuda.synchronize()
     assert ts.gen_join == "seg_G" and ts._ahead.jets is None and not ts._ahead.open
     assert np.isfinite(float(ts.D_loss)) and np.isfinite(float(ts.G_loss))
+
+
+def test_every_option_at_once_capture_restores_graphs_equal_eager_resume_equals_the_run():
+    """The four augmentations at p = 0.5 under ``adaptive_prob`` (interval 2), label noise 0.1, ``num_critic=2``, the epoch's loss
+    sums and a ``DeviceJetLoader`` over 16 jets in ONE step, MPGAN defaults at N = 30, B = 4, D's dropout on:
+    (i) ``capture`` of both kinds of batch leaves every tensor of ``_training_state``, the seed, ``ada``, ``batch_ndx`` and the
+    loader's position where they were; (ii) six captured steps equal six eager ones bit for bit; (iii) the optimizer state dicts and
+    the loader's state saved after step 3, loaded into a fresh step over other weights with a fresh loader, give the same six.
+    (The dropout sites of an eager step are numbered anew on every step, a graph keeps those of its capture: the counter is put back
+    before each eager step and before the captures that are compared with them.)"""
+    import itertools
+    from mpgan_amd import ops, train
+    from mpgan_amd.data import DeviceJetLoader, synthetic_jets
+    B, N, dev = 4, 30, torch.device("cuda", torch.cuda.current_device())
+    st = ops.dev_state(dev)
+    particles, labels = synthetic_jets(16, N, seed=4)
+
+    def build(use_graphs, loader_seed=13, **seeds):
+        G, D = _setup(B, N, disc_dropout=0.5, **seeds)
+        aug = train.Augment(aug_r90=True, aug_f=True, aug_t=True, aug_s=True, aug_prob=0.5, adaptive_prob=True, ada_interval=2)
+        loader = DeviceJetLoader((particles, labels), B, "cuda", seed=loader_seed)
+        ts = train.TrainStep(G, D, B, N, use_graphs=use_graphs, augment=aug, label_noise=0.1, num_critic=2, track_epoch_losses=True,
+                             loader=loader)
+        ops.set_seed(0x5EED, dev)
+        return ts
+
+    def result(ts):
+        torch.cuda.synchronize()
+        return ([t.clone() for t in (ts.fD.flat, ts.fG.flat, ts.fD.sq, ts.fG.sq, ts.D_loss, ts.G_loss)], ts.ada, ops.get_seed(dev),
+                ts.batch_ndx, ts.loader.position)
+
+    def eager_step(ts):
+        st.tags = itertools.count(1)
+        ts.step()
+
+    def same(a, b):
+        return all(torch.equal(x, y) for x, y in zip(a[0], b[0])) and a[1:] == b[1:]
+
+    try:
+        eager = build(False)
+        for _ in range(3):
+            eager_step(eager)
+        torch.cuda.synchronize()
+        clone = lambda sd: {k: v.clone() for k, v in sd.items()}
+        saved = (eager.optimizer_state_dicts(), eager.loader.state_dict(), clone(eager.G.state_dict()), clone(eager.D.state_dict()))
+        assert eager.last_ran == ("D",) and saved[0][0]["param_groups"][0]["mpgan_amd_ada"]["steps"] == 1    # (mid-interval)
+        for _ in range(3):
+            eager_step(eager)
+        want = result(eager)
+        assert want[3] == 6 and want[4] == 6 * B
+        # (i), (ii)
+        ts = build(True)
+        before = ([t.clone() for t in ts._training_state()], result(ts))
+        ts.capture(kind="DG")
+        ts.capture(kind="D")
+        torch.cuda.synchronize()
+        after = ts._training_state()
+        assert len(after) == len(before[0]) and all(torch.equal(a, b) for a, b in zip(after, before[0]))
+        assert same(result(ts), before[1]) and before[1][2] == 0x5EED and before[1][3:] == (0, 0)
+        for kind in ("DG", "D"):       # (captured again without a warm-up, from the first dropout site on)
+            st.tags = itertools.count(1)
+            ts.capture(warmup=0, kind=kind)
+        for _ in range(6):
+            ts.step()
+        assert same(result(ts), want)
+        assert eager.epoch_losses(reset=False) == ts.epoch_losses(reset=False)
+        # (iii)
+        again = build(False, loader_seed=99, seedG=77, seedD=78)
+        ops.set_seed(999, dev)
+        again.G.load_state_dict(saved[2]); again.D.load_state_dict(saved[3])
+        again.loader.load_state_dict(saved[1])
+        again.load_optimizer_state_dicts(*saved[0])
+        assert again.batch_ndx == 3 and again.loader.position == 3 * B
+        for _ in range(3):
+            eager_step(again)
+        assert same(result(again), want)
+    finally:
+        st.seed_is_default, st.auto_seed_key = True, None

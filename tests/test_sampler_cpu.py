@@ -31,8 +31,7 @@ def test_pick_is_the_headers_statement():
     from mpgan_amd import ops
     tag = int(re.search(r"^#define\s+MPG_PICK_TAG\s+(0x[0-9A-Fa-f]+)\s*$", open(HEADER).read(), flags=re.M).group(1), 16)
     assert tag == ops.PICK_TAG
-    others = {int(v, 16) for v in re.findall(r"^#define\s+MPG_(?:LABEL|SHUFFLE)_TAG\s+(0x[0-9A-Fa-f]+)", open(HEADER).read(), flags=re.M)}
-    assert tag >= (1 << 27) and tag not in others | {ops.NOISE_TAG, ops.AUG_TAG}
+    # (clear of every other family: test_cabi_cpu.py::test_tag_table)
     for n, pos0 in ((7, 0), (1000, 123), (2**31 - 1, 2**32 - 3), (30, 5 * 2**32 + 1)):
         got = ops.label_pick_indices(KEY, pos0, 6, n).tolist()
         want = [(_word(KEY, tag, (pos0 + c) & 0xFFFFFFFF, (pos0 + c) >> 32) * n) >> 32 for c in range(6)]

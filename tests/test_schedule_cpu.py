@@ -107,7 +107,7 @@ def test_batch_ndx_travels_with_the_generators_optimizer_state(monkeypatch):
     again.step()
     assert again.last_ran == ("D",)         # (batch 2 of num_critic = 3; batch 0 would be D alone as well, batch 1 both:)
     again.load_optimizer_state_dicts(sdD, sdG)
-    again._batch_ndx = 1
+    again.batch_ndx = 1
     again.step()
     assert again.last_ran == ("D", "G")
     del sdG["param_groups"][0][train.FlatParams.BATCH_KEY]     # a file without the field: the top of an epoch

@@ -1,0 +1,171 @@
+"""What one option of the captured training iteration costs next to the step without it, on one GPU.  One JSON object per line on
+stdout and in --out.
+
+    python tools/step_option_bench.py --option {labels,ada,critic} [--reps 10] [--out profiles/<option>_bench.jsonl]
+
+MPGAN at N = 30, B = 256, the captured iteration, one process.  Two steps over the same weights and batch -- a baseline and the
+same with the option on -- and, where the option adds one launch to the D segment, that launch on its own outside any graph:
+
+labels   baseline: the default step.  Option: ``label_smoothing=True, label_noise=0.1`` (+ ``mpg_label_targets``, and the head
+         reads its targets from memory).  Rows: a default_step, b labels_step, c label_launch.
+ada      baseline: the four augmentations at p = 0.5.  Option: the same with ``adaptive_prob=True`` (+ ``mpg_ada_update`` behind
+         the head).  Rows: a fixed_p_step, b adaptive_step, c ada_launch.
+critic   baseline: the default step.  Option: ``num_critic=5`` (--num-critic).  Rows: a default_step, b d_only_replay (a batch
+         on which only D trains), c dg_replay (both train: the launches of a), d mean_per_batch (over two full cycles).
+
+Every ``step()`` and every lone launch sits between two HIP events of its own -- in all rows alike, so that what an event pair
+costs cancels between them.  A repetition is --batches steps of each kind (critic: two full cycles of the schedule) taken
+alternately, then as many lone launches; the rows are the means within a repetition, reported as median / min / max over --reps
+repetitions behind a warm-up that captures every graph.  No speed claim is made.  The last line states what the option is held to.
+labels, ada: (b) - (a) is at most the run-to-run spread of (a) (max - min of its repetitions) plus (c).  critic: (c) within
+the spread of (a), and (b) <= (a).
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mpgan_amd import data as mdata, ops, train  # noqa: E402
+
+N, B = 30, 256
+SMOOTHING, NOISE, P0 = True, 0.1, 0.5
+
+
+def build(**kw):
+    G, D = train.default_mpgan(N)
+    lrs = train.LR["g"]
+    ts = train.TrainStep(G, D, B, N, lr_disc=lrs[0], lr_gen=lrs[1], use_graphs=True, **kw)
+    x, labels = mdata.synthetic_jets(B, N, seed=1)
+    ts.set_batch(x.cuda(), labels.cuda())
+    return ts
+
+
+def timed(fn):
+    """microseconds between an event before and an event behind ``fn()``"""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return 1e3 * a.elapsed_time(b)
+
+
+def jsonl_sink(path):
+    """emit(record): one JSON line on stdout and, with a path, appended to that file"""
+    sink = open(path, "a") if path else None
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if sink:
+            sink.write(line + "\n")
+            sink.flush()
+    return emit
+
+
+def _augment(**kw):
+    return train.Augment(aug_r90=True, aug_f=True, aug_t=True, aug_s=True, aug_prob=P0, **kw)
+
+
+def _label_launch(opt):
+    out = tuple(torch.empty(k, device="cuda") for k in (2 * B, 1, 2 * B))
+    return lambda: ops.label_targets(B, SMOOTHING, NOISE, "cuda", out=out)
+
+
+def _ada_launch(opt):
+    a = opt._ada
+    out = torch.rand(2 * B, device="cuda")
+    words = (torch.zeros(2, dtype=torch.int32, device="cuda"), torch.full((1,), P0, device="cuda"), torch.zeros(1, device="cuda"))
+    return lambda: ops.ada_update(out, B, a.mid, a.target, a.step, a.interval, *words)
+
+
+def _launch_condition(opt_name, base_name, launch_name):
+    """(b) - (a) at most the spread of (a) plus (c), under the field names of the option's earlier lines"""
+    def condition(med, us, rows):
+        diff = med[rows[1]] - med[rows[0]]
+        spread = float(np.max(us[rows[0]]) - np.min(us[rows[0]]))
+        return {"row": "condition", f"{opt_name}_minus_{base_name}_us": diff, f"spread_{base_name}_us": spread,
+                f"{launch_name}_launch_us": med[rows[2]], "within_spread_plus_launch": bool(diff <= spread + med[rows[2]])}
+    return condition
+
+
+def _critic_condition(med, us, rows):
+    a, d_only, dg = (med[r] for r in rows[:3])
+    spread = float(np.max(us[rows[0]]) - np.min(us[rows[0]]))
+    return {"row": "conditions", "dg_minus_default_us": dg - a, "spread_default_us": spread,
+            "dg_within_spread_of_default": bool(abs(dg - a) <= spread), "d_only_minus_default_us": d_only - a,
+            "d_only_le_default": bool(d_only <= a)}
+
+
+# option -> baseline step's arguments, option step's arguments, the lone launch (or None), row names, fields of every row, the
+# condition line, fields that close the condition line
+OPTIONS = {
+    "labels": dict(base=lambda a: {}, opt=lambda a: dict(label_smoothing=SMOOTHING, label_noise=NOISE), launch=_label_launch,
+                   rows=("a default_step", "b labels_step", "c label_launch"),
+                   fields=lambda a, opt: {"label_smoothing": SMOOTHING, "label_noise": NOISE},
+                   condition=_launch_condition("labels", "default", "label"), tail=lambda opt: {"label_extra": float(opt.label_extra)}),
+    "ada": dict(base=lambda a: dict(augment=_augment()), opt=lambda a: dict(augment=_augment(adaptive_prob=True)), launch=_ada_launch,
+                rows=("a fixed_p_step", "b adaptive_step", "c ada_launch"),
+                fields=lambda a, opt: {"aug_prob": P0, "ada_interval": opt._ada.interval, "ada_step": opt._ada.step},
+                condition=_launch_condition("adaptive", "fixed", "ada"), tail=lambda opt: {"ada": opt.ada}),
+    "critic": dict(base=lambda a: {}, opt=lambda a: dict(num_critic=a.num_critic), launch=None,
+                   rows=("a default_step", "b d_only_replay", "c dg_replay", "d mean_per_batch"),
+                   fields=lambda a, opt: {"num_critic": a.num_critic}, condition=_critic_condition, tail=lambda opt: {}),
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--option", choices=sorted(OPTIONS), required=True)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--batches", type=int, default=10, help="steps of each kind per repetition (critic: two cycles of the schedule)")
+    ap.add_argument("--num-critic", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit(f"{args.option}_bench: no GPU visible (timings are taken on the device or not at all)")
+    emit = jsonl_sink(args.out)
+    o = OPTIONS[args.option]
+    critic = args.option == "critic"
+    batches = 2 * args.num_critic if critic else args.batches
+    torch.manual_seed(0)
+    base, opt = build(**o["base"](args)), build(**o["opt"](args))
+    launch = o["launch"](opt) if o["launch"] else None
+    for _ in range(batches + 1 if critic else 3):   # warm-up: captures every graph (critic: leaves the schedule on batch 1, both train)
+        base.step()
+        opt.step()
+        if launch:
+            launch()
+    torch.cuda.synchronize()
+    assert not critic or opt.batch_ndx % args.num_critic == 1
+    rows = o["rows"]
+    us = {r: [] for r in rows}
+    for _ in range(args.reps):
+        ta, by_kind = [], {("D", "G"): [], ("D",): []}
+        for _ in range(batches):        # (alternated: the rows share whatever the box does meanwhile)
+            ta.append(timed(base.step))
+            t = timed(opt.step)
+            by_kind[opt.last_ran].append(t)
+        us[rows[0]].append(float(np.mean(ta)))
+        if critic:
+            assert len(by_kind[("D", "G")]) == 2 and len(by_kind[("D",)]) == batches - 2
+            for r, ts in zip(rows[1:], (by_kind[("D",)], by_kind[("D", "G")], by_kind[("D",)] + by_kind[("D", "G")])):
+                us[r].append(float(np.mean(ts)))
+        else:
+            us[rows[1]].append(float(np.mean(by_kind[("D", "G")])))
+            us[rows[2]].append(float(np.mean([timed(launch) for _ in range(batches)])))
+    med = {}
+    for name, v in us.items():
+        med[name] = float(np.median(v))
+        emit({"model": "mpgan", "B": B, "N": N, **o["fields"](args, opt), "row": name, "reps": args.reps, "batches_per_rep": batches,
+              "median_us": med[name], "min_us": float(np.min(v)), "max_us": float(np.max(v))})
+    emit({"model": "mpgan", "B": B, **({"num_critic": args.num_critic} if critic else {}), **o["condition"](med, us, rows),
+          "D_loss": float(opt.D_loss), "G_loss": float(opt.G_loss), **o["tail"](opt)})
+
+
+if __name__ == "__main__":
+    main()
