@@ -765,6 +765,44 @@ int mpg_jets_finish(const float* feat, int ld_feat, const float* mask, int B, in
                     const float* shifts, float* out, float* mask_out, uint64_t row0, int64_t total, uint64_t key, uint64_t* cursor,
                     uint64_t* seed, uint32_t* ticket, void* stream);
 
+/* ---- spectral normalisation of Linear layers (mpgan/spectral_normalization.py:29-46), grouped; csrc/spectral.hip ----------------
+ * One job per wrapped layer, one workgroup per job, up to MPG_SPECTRAL_MAX_JOBS jobs per launch.  Everything is fp32 and
+ * contiguous (W, W_eff, G, dW row-major [R, C]); no alignment beyond a float's is assumed: W is a view into a flat parameter buffer.
+ *
+ * mpg_spectral_norm, per job, with P = power_iterations >= 0, u' = u and v' = v to start with:
+ *   P times:   t = W^T u';  v' = t / (||t||_2 + 1e-12);  s = W v';  u' = s / (||s||_2 + 1e-12)
+ *   sigma = u' . (W v')                 (P >= 1: W v' is the s of the last pass; P = 0: formed from u and v as they stand)
+ *   inv = 1 / (sigma + 1e-12);  W_eff = W * inv;  u_out = u';  v_out = v';  *inv_sigma = inv
+ *   P >= 1:    u = u', v = v' stored in place, at the caller's (the parameters') own addresses, last of all; P = 0 writes neither.
+ * u_out, v_out and inv_sigma are fresh copies for the backward: a later launch that moves u and v on does not touch them.
+ * Every sum -- the two products, the two norms, the dot product -- is added in a fixed order (a lane's strided partial, shuffles
+ * within a wave, the waves' partials in wave order): no atomics, the same bits on every run from the same inputs.
+ * -1: a NULL pointer, R < 1, C < 1, P < 0, njobs outside [1, MPG_SPECTRAL_MAX_JOBS];  -2: two jobs of the launch name the same u or
+ * the same v;  -3: u_out == u or v_out == v.
+ *
+ * mpg_spectral_norm_bwd, per job: the gradient with respect to W of a loss whose gradient with respect to W_eff is G, with u_out and
+ * v_out constants of the differentiation (as the reference's wrapper has them: they are .data there):
+ *   dW (+)= (G - <G, W_eff> u v^T) * inv_sigma,   <G, W_eff> = sum_ij G_ij W_eff_ij,   (+)= when accumulate, = otherwise
+ * (u, v, inv_sigma: the forward's u_out, v_out, inv_sigma).  -1: a NULL pointer, R < 1, C < 1, njobs out of range.
+ *
+ * mpg_spectral_norm_host / mpg_spectral_norm_bwd_host: the same per-layer routines compiled for the host, on host memory, one job
+ * after the other; no HIP call. */
+#define MPG_SPECTRAL_MAX_JOBS 16
+typedef struct MpgSpectralJob {
+    const float* W; float* u; float* v;
+    float* W_eff; float* u_out; float* v_out; float* inv_sigma;
+    int R, C;
+} MpgSpectralJob;
+typedef struct MpgSpectralBwdJob {
+    const float* G; const float* W_eff; const float* u; const float* v; const float* inv_sigma;
+    float* dW;
+    int R, C, accumulate;
+} MpgSpectralBwdJob;
+int mpg_spectral_norm(const MpgSpectralJob* jobs, int njobs, int power_iterations, void* stream);
+int mpg_spectral_norm_bwd(const MpgSpectralBwdJob* jobs, int njobs, void* stream);
+int mpg_spectral_norm_host(const MpgSpectralJob* jobs, int njobs, int power_iterations);
+int mpg_spectral_norm_bwd_host(const MpgSpectralBwdJob* jobs, int njobs);
+
 #ifdef __cplusplus
 }
 #endif

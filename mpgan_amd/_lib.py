@@ -190,7 +190,23 @@ class MpgMab(C.Structure):
     ]
 
 
-MPG_FN_NA = -100   # mpg_edge_fwd_fn: "not one of my shapes" (include/mpgan_amd.h)
+class MpgSpectralJob(C.Structure):
+    _fields_ = [
+        ("W", _fp), ("u", _fp), ("v", _fp),
+        ("W_eff", _fp), ("u_out", _fp), ("v_out", _fp), ("inv_sigma", _fp),
+        ("R", C.c_int), ("C", C.c_int),
+    ]
+
+
+class MpgSpectralBwdJob(C.Structure):
+    _fields_ = [
+        ("G", _fp), ("W_eff", _fp), ("u", _fp), ("v", _fp), ("inv_sigma", _fp),
+        ("dW", _fp),
+        ("R", C.c_int), ("C", C.c_int), ("accumulate", C.c_int),
+    ]
+
+
+MPG_FN_NA = -100  # mpg_edge_fwd_fn: "not one of my shapes" (include/mpgan_amd.h)
 
 MAB_CHAIN_MAX = 4   # MPG_MAB_CHAIN_MAX of include/mpgan_amd.h
 
@@ -267,6 +283,10 @@ SIGNATURES = {
     "mpg_label_pick_host": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, _fp]),
     "mpg_jets_finish": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_uint64, C.c_int64, C.c_uint64,
                                   _fp, _fp, _fp, C.c_void_p]),
+    "mpg_spectral_norm": (C.c_int, [C.POINTER(MpgSpectralJob), C.c_int, C.c_int, C.c_void_p]),
+    "mpg_spectral_norm_bwd": (C.c_int, [C.POINTER(MpgSpectralBwdJob), C.c_int, C.c_void_p]),
+    "mpg_spectral_norm_host": (C.c_int, [C.POINTER(MpgSpectralJob), C.c_int, C.c_int]),
+    "mpg_spectral_norm_bwd_host": (C.c_int, [C.POINTER(MpgSpectralBwdJob), C.c_int]),
 }
 
 

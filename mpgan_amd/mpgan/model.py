@@ -9,9 +9,10 @@ libmpgan_amd.so (HIP, gfx950); there is no CPU fallback.
 Fused (``ops.FusedMPLayerFn``: the reference's default and every published ``mp_*`` configuration): edge network
 [96, 160, 192], two hidden node layers, fully connected or ``fully_connected=False`` with ``num_knn`` / ``self_loops``,
 and up to ``ops.EDGE_SCALARS`` scalars per edge -- the distance column of ``pos_diffs``, ``clabels``, ``mask_fne_np`` --
-plus coordinate differences (``delta_coords``, folded into the layer-1 projection); ``mask_c`` masking, ``dea`` pooling.
+plus coordinate differences (``delta_coords``, folded into the layer-1 projection); ``mask_c`` masking, ``dea`` pooling;
+spectral norm (``ops.spectral_weights``: the wrapped layers' W_bar / sigma from one grouped launch, packed per call).
 Every other constructor option of the reference (more edge scalars, conditioning columns on the k-NN graph, other layer
-widths, batch / spectral norm) runs un-fused, layer by layer on the HIP GEMM (``MPLayer._forward_edges``); the few options
+widths, batch norm) runs un-fused, layer by layer on the HIP GEMM (``MPLayer._forward_edges``); the few options
 the reference itself cannot run (``int_diffs``, ``mask_learn*``, ``mask_feat_bin``) raise ``NotImplementedError`` at
 construction.  ``MPLayer.fused`` says which route a layer takes.
 """
@@ -37,7 +38,9 @@ class SpectralNorm(nn.Module):
     wrapped module keeps ``weight_bar`` (trained), ``weight_u`` / ``weight_v`` (power-iteration vectors, no gradient) and
     ``bias`` -- same state-dict keys (``module.weight_bar`` ...).  ``weight()`` runs one power iteration and
     returns  W_bar / (u' W_bar v + 1e-12)  with the gradient flowing through W_bar only, which the caller feeds to the
-    fused Linear launch."""
+    fused Linear launch.  On the GPU that is one ``mpg_spectral_norm`` launch (``ops.spectral_weights``); ``LinearNet`` and
+    ``MPLayer`` put all their wrapped layers into one such launch (``job()``).  CPU tensors and the twice-differentiable route
+    (``ops.double_backward_route``) keep the torch formula."""
 
     def __init__(self, module: nn.Linear, power_iterations: int = 1):
         super().__init__()
@@ -54,9 +57,18 @@ class SpectralNorm(nn.Module):
     def bias(self):
         return self.module.bias
 
+    def job(self):
+        """(weight_bar, weight_u, weight_v): this layer's entry of a grouped ``ops.spectral_weights`` call."""
+        mod = self.module
+        return mod.weight_bar, mod.weight_u, mod.weight_v
+
     def weight(self) -> Tensor:
         mod = self.module
         u, v, w = mod.weight_u, mod.weight_v, mod.weight_bar
+        if w.is_cuda and not ops.double_backward_on(w.device):
+            # one launch (mpg_spectral_norm) with the contract of the lines below: the iteration out of place, u / v stored in place
+            # at their own addresses, the backward on the launch's own copies of the vectors (ops.SpectralWeightsFn)
+            return ops.spectral_weights([self.job()], self.power_iterations)[0]
         # The power iteration runs OUT OF PLACE and sigma is built from the fresh vectors, so autograd never saves u / v
         # themselves (train_D runs D(real) and D(fake) before one backward: writing u in place must not touch what an
         # earlier forward saved).  The new vectors are then stored IN PLACE, at the parameters' fixed addresses: a captured
@@ -76,6 +88,18 @@ class SpectralNorm(nn.Module):
                 un, vn = u.clone(), v.clone()
         sigma = un.dot(w.mv(vn))
         return w / (sigma + 1e-12)
+
+
+def _spectral_group(layers) -> list:
+    """The weight of every layer of ``layers`` as its launch takes it -- ``weight`` of a plain Linear, W_bar / sigma of a
+    ``SpectralNorm`` -- with ALL the wrapped layers' power iterations in one grouped launch (``ops.spectral_weights``; layers with
+    different iteration counts, which no constructor here builds, get a launch per count)."""
+    out = [None if isinstance(l, SpectralNorm) else l.weight for l in layers]
+    for P in sorted({l.power_iterations for l in layers if isinstance(l, SpectralNorm)}):
+        idx = [k for k, l in enumerate(layers) if isinstance(l, SpectralNorm) and l.power_iterations == P]
+        for k, W in zip(idx, ops.spectral_weights([layers[k].job() for k in idx], P)):
+            out[k] = W
+    return out
 
 
 class LinearNet(nn.Module):
@@ -145,10 +169,11 @@ class LinearNet(nn.Module):
         if x.is_cuda and ops.double_backward_on(x.device):
             return self._forward_dd(x, resid)
         last = len(self.net) - 1
+        eff = _spectral_group(self.net) if (self.spectral_norm and x.is_cuda and ops.OPTIONS["sn_fused"]) else None
         for k, lin in enumerate(self.net):
             act = not (self.final_linear and k == last)
             fuse = resid if (k == last and not act) else None
-            W = lin.weight() if isinstance(lin, SpectralNorm) else lin.weight
+            W = eff[k] if eff is not None else (lin.weight() if isinstance(lin, SpectralNorm) else lin.weight)
             if self.batch_norm and act:   # the norm sits between the activation and the dropout (:78-83)
                 x = ops.FusedLinearFn.apply(x, W, lin.bias, True, self.leaky_relu_alpha, 0.0, self.training, None)
                 x = self._bn(k, x.reshape(-1, x.shape[-1])).reshape(x.shape)
@@ -167,8 +192,9 @@ class MPLayer(nn.Module):
     """One message-passing iteration.  The reference's default configuration -- edge network [96, 160, 192] on
     [x_i ; x_j], two hidden node layers, fully connected or k-NN graph -- runs on ``ops.FusedMPLayerFn`` (fused edge
     kernels + chained node network).  Every other option of the reference's constructor (edge features ``pos_diffs`` /
-    ``delta_r`` / ``delta_coords``, conditioning columns ``clabels`` / ``mask_fne_np``, other layer widths) takes the
-    un-fused route of ``_forward_edges``: the edge matrix is materialised as the reference builds it and the two
+    ``delta_r`` / ``delta_coords``, conditioning columns ``clabels`` / ``mask_fne_np``, other layer widths, batch norm) takes
+    the un-fused route of ``_forward_edges`` -- spectral norm too when ``ops.OPTIONS["sn_fused"]`` is off; with it on (the
+    default) the wrapped layers' normalised weights come from one grouped ``mpg_spectral_norm`` launch and feed the fused kernels --: the edge matrix is materialised as the reference builds it and the two
     networks run layer by layer on the HIP GEMM -- same results, none of the fused kernels' speed."""
 
     def __init__(self, input_node_size: int, fe_layers: list, fn_layers: list, output_node_size: int,
@@ -210,10 +236,13 @@ class MPLayer(nn.Module):
         self._diff_cols = nc if (has_diffs and not self.all_ef) else 0
         self.n_es = int(self._dist_col) + extra
         consistent = num_ef == self._diff_cols + int(self._dist_col) and not (has_diffs and self.all_ef)
+        # Spectral norm stays on the fused kernels: the five wrapped layers' W_bar / sigma are computed tensors, packed per call like a
+        # folded W1 (forward).  Batch norm sits between a layer's activation and its dropout: not a form the fused kernels have.
+        self.spectral_norm = bool(linear_args.get("spectral_norm"))
         self.fused = (list(self.fe_layers) == [ops.H1, ops.H2, ops.H3] and len(self.fn_layers) == 2
                       and consistent and self.n_es <= ops.EDGE_SCALARS
                       and (self.fully_connected or (not self._diff_cols and extra == 0))
-                      and not (linear_args.get("batch_norm") or linear_args.get("spectral_norm")))
+                      and not linear_args.get("batch_norm"))
         self.fe = LinearNet(self.fe_layers, input_size=2 * input_node_size + num_ef + extra, final_linear=False, **linear_args)
         self.fn = LinearNet(self.fn_layers, input_size=self.fe_layers[-1] + input_node_size + extra,
                             output_size=output_node_size, final_linear=True, **linear_args)
@@ -280,7 +309,8 @@ class MPLayer(nn.Module):
         assert not (use_mask and mask is None), "need ``mask`` tensor if using ``use_mask`` option"
         assert not (self.clabels and labels is None), "need ``labels`` tensor if using ``clabels`` option"
         assert not (self.mask_fne_np and num_jet_particles is None), "need ``num_jet_particles`` tensor if using ``mask_fne_np`` option"
-        if not self.fused or (x.is_cuda and ops.double_backward_on(x.device)):
+        if (not self.fused or (x.is_cuda and ops.double_backward_on(x.device))
+                or (self.spectral_norm and not ops.OPTIONS["sn_fused"])):
             return self._forward_edges(x, use_mask, mask, labels, num_jet_particles)
         fe, fn = self.fe.net, self.fn.net
         nbr = None
@@ -291,10 +321,13 @@ class MPLayer(nn.Module):
                 xr = x[..., :(3 if self.coords == "cartesian" else 2)] if (self.pos_diffs and not self.all_ef) else x
                 nbr = ops.knn_sets(xr, mask if use_mask else None, self.num_knn, self.self_loops)
         es, xfn = self._edge_scalars(x, labels, num_jet_particles, mask if (use_mask and not self.fully_connected) else None)
-        W1, packed = fe[0].weight, None
+        # the six weights as the launches take them: with spectral norm, fe.net.0..2 and fn.net.0..1 are W_bar / sigma out of ONE
+        # grouped launch (a wrapped layer's ``.weight`` is a method, not a tensor); fn.net.2, the final linear layer, is not wrapped
+        W1, W2, W3, V1, V2, V3 = _spectral_group([*fe, *fn])
+        packed = None
         if self._diff_cols:
             W1 = self._folded_w1(W1)   # (not a parameter: its images are packed for this call)
-        else:
+        elif not self.spectral_norm:   # (nor are W_bar / sigma: they change with every forward)
             packed = self._packed()
         # consecutive fused layers of a network hand each other the layer-1 node terms a | c (ops.LayerHandoff): the launch
         # that produces a layer's output rows also projects them for the layer above
@@ -302,12 +335,13 @@ class MPLayer(nn.Module):
             nxt = handoff.above
             if packed is None:   # (images packed for this call: nothing from below fits them; the layer above may still take its chain)
                 handoff.below = None
-            elif nxt is not None and nxt.fused and not nxt._diff_cols and nxt.training == self.training and nxt.n_es == 0:
+            elif (nxt is not None and nxt.fused and not nxt._diff_cols and not nxt.spectral_norm and nxt.training == self.training
+                  and nxt.n_es == 0):
                 handoff.next = (nxt._packed(), nxt.fe.net[0].bias)
         return ops.FusedMPLayerFn.apply(
             x, mask if use_mask else None,
-            W1, fe[0].bias, fe[1].weight, fe[1].bias, fe[2].weight, fe[2].bias,
-            fn[0].weight, fn[0].bias, fn[1].weight, fn[1].bias, fn[2].weight, fn[2].bias, es, xfn,
+            W1, fe[0].bias, W2, fe[1].bias, W3, fe[2].bias,
+            V1, fn[0].bias, V2, fn[1].bias, V3, fn[2].bias, es, xfn,
             ops.MPLayerSettings(self.sum, self.fe.leaky_relu_alpha, self.fe.dropout_p, self.training, packed, nbr, self.num_knn,
                                 self.n_es, handoff, not torch.is_grad_enabled()))
 
@@ -351,7 +385,9 @@ class MPLayer(nn.Module):
 
     def _packed(self) -> "ops.PackedMPLayer":
         """Persistent weight images of this layer for the current mode (dropout scale) -- rebuilt when a
-        parameter changes (``PackedMPLayer.ensure``) or on ``refresh_packed()``."""
+        parameter changes (``PackedMPLayer.ensure``) or on ``refresh_packed()``.  Not for a spectral-norm layer: its weights are
+        new tensors on every forward, packed by that call."""
+        assert not self.spectral_norm, "MPLayer._packed: a spectral-norm layer has no persistent weight images"
         dscale = ops.drop_params(self.fe.dropout_p)[1] if self.training else 1.0
         params = tuple(l.weight for l in (*self.fe.net, *self.fn.net))
         # keyed by the DEVICE of the weights as well: ``nn.DataParallel`` (the reference's multi-GPU mode,

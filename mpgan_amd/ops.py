@@ -51,6 +51,9 @@ OPTIONS = {
     # (its input E2 as the one fp16 value that is parked for the backward anyway): -15 % per launch, pre-activations of fe.net.2 to
     # ~1e-4 of their scale instead of ~5e-7.  MPG_FWD_TWO_TERM.
     "fwd_two_term": int(os.environ.get("MPG_FWD_TWO_TERM", "0")),
+    # spectral-norm networks: the normalised weights of all wrapped layers of a LinearNet / an MPLayer from ONE grouped launch
+    # (mpg_spectral_norm) and such MPLayers on the fused edge kernels; False = a launch per wrapped layer and MPLayer._forward_edges
+    "sn_fused": os.environ.get("MPG_SN_FUSED", "1") != "0",
 }
 NUM_CUS = 256
 # Forward products (they decide LeakyReLU signs) are split as fp16 hi/lo with the operand scales below (~2^-21 per
@@ -753,6 +756,105 @@ def dropout_mask(rows: int, F: int, tag: int, thr: int, device="cuda"):
     check(_lib.lib().mpg_dropout_mask(_p(out), rows, F, _p(seed_tensor(device)), tag, thr, _stream()),
           "mpg_dropout_mask")
     return out
+
+
+# ------------------------------------------------------------------------------------- spectral norm
+SPECTRAL_MAX = 16    # MPG_SPECTRAL_MAX_JOBS of include/mpgan_amd.h
+
+
+def _spectral_run(entry, name, jobs, *tail):
+    # ``jobs``: filled ``MpgSpectralJob`` / ``MpgSpectralBwdJob`` structs; as many launches as the job limit asks for.
+    for i0 in range(0, len(jobs), SPECTRAL_MAX):
+        chunk = jobs[i0:i0 + SPECTRAL_MAX]
+        check(entry((type(chunk[0]) * len(chunk))(*chunk), len(chunk), *tail), name)
+
+
+def spectral_norm_launch(layers, power_iterations: int, host: bool = False):
+    """``mpg_spectral_norm`` over ``layers`` = [(W_bar [R, C], u [R], v [C]), ...] (``mpg_spectral_norm_host`` on CPU tensors with
+    ``host``): power iteration, sigma and W_eff = W_bar / sigma of every layer in ONE launch per ``SPECTRAL_MAX`` layers.  ``u``
+    and ``v`` are advanced IN PLACE (``power_iterations`` >= 1).  Returns [(W_eff, u_out, v_out, inv_sigma), ...]: the normalised
+    weight and the fresh copies of the vectors and of 1 / sigma that belong to it (include/mpgan_amd.h states the arithmetic)."""
+    seen, jobs, outs = set(), [], []
+    for W, u, v in layers:
+        if W.dim() != 2:
+            raise ValueError(f"spectral_norm_launch: W_bar must be a matrix, got {tuple(W.shape)}")
+        for t, n, what in ((W, W.numel(), "W_bar"), (u, W.shape[0], "u"), (v, W.shape[1], "v")):
+            if t.dtype != torch.float32 or t.is_cuda == host or not t.is_contiguous() or t.numel() != n or t.device != W.device:
+                raise ValueError(f"spectral_norm_launch: {what} must be a contiguous float32 tensor of {n} elements on "
+                                 f"{'the host' if host else 'the GPU'}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        if u.data_ptr() in seen or v.data_ptr() in seen:
+            raise ValueError("spectral_norm_launch: two layers of one call share a power-iteration vector")
+        seen.update((u.data_ptr(), v.data_ptr()))
+        out = (torch.empty_like(W), torch.empty_like(u), torch.empty_like(v), W.new_empty(1))
+        j = _lib.MpgSpectralJob()
+        j.W, j.u, j.v, j.R, j.C = _p(W), _p(u), _p(v), W.shape[0], W.shape[1]
+        j.W_eff, j.u_out, j.v_out, j.inv_sigma = (_p(t) for t in out)
+        jobs.append(j)
+        outs.append(out)
+    if jobs:
+        if host:
+            _spectral_run(_lib.lib().mpg_spectral_norm_host, "mpg_spectral_norm_host", jobs, int(power_iterations))
+        else:
+            _spectral_run(_lib.lib().mpg_spectral_norm, "mpg_spectral_norm", jobs, int(power_iterations), _stream())
+    return outs
+
+
+def spectral_norm_bwd_launch(layers, host: bool = False):
+    """``mpg_spectral_norm_bwd`` over ``layers`` = [(G, W_eff, u_out, v_out, inv_sigma, dW, accumulate), ...]:
+    dW (+)= (G - <G, W_eff> u v^T) * inv_sigma of every layer in ONE launch per ``SPECTRAL_MAX`` layers."""
+    jobs = []
+    for G, W_eff, u, v, inv, dW, acc in layers:
+        for t in (G, W_eff, u, v, inv, dW):
+            if t.dtype != torch.float32 or t.is_cuda == host or not t.is_contiguous():
+                raise ValueError("spectral_norm_bwd_launch: contiguous float32 tensors on %s expected" % ("the host" if host else "the GPU"))
+        if G.shape != W_eff.shape or dW.shape != W_eff.shape or u.numel() != W_eff.shape[0] or v.numel() != W_eff.shape[1]:
+            raise ValueError("spectral_norm_bwd_launch: G, dW [R, C], u [R], v [C] must fit W_eff %s" % (tuple(W_eff.shape),))
+        j = _lib.MpgSpectralBwdJob()
+        j.G, j.W_eff, j.u, j.v, j.inv_sigma, j.dW = (_p(t) for t in (G, W_eff, u, v, inv, dW))
+        j.R, j.C, j.accumulate = W_eff.shape[0], W_eff.shape[1], int(bool(acc))
+        jobs.append(j)
+    if jobs:
+        if host:
+            _spectral_run(_lib.lib().mpg_spectral_norm_bwd_host, "mpg_spectral_norm_bwd_host", jobs)
+        else:
+            _spectral_run(_lib.lib().mpg_spectral_norm_bwd, "mpg_spectral_norm_bwd", jobs, _stream())
+
+
+class SpectralWeightsFn(torch.autograd.Function):
+    """The normalised weights of several spectral-norm layers: ``apply(uv, power_iterations, *W_bars)`` with ``uv`` =
+    ((u, v), ...) returns one W_eff per W_bar (``mpg_spectral_norm``, one grouped launch).  The backward (one grouped
+    ``mpg_spectral_norm_bwd``) reaches the W_bars only, with the vectors as constants.  It keeps W_eff and the launch's OWN copies
+    of u, v and 1 / sigma, never the live vectors: train_D runs two forwards before one backward, and the second forward's power
+    iteration writes the parameters' u and v in place."""
+
+    @staticmethod
+    def forward(ctx, uv, power_iterations, *Ws):
+        outs = spectral_norm_launch([(W.contiguous(), u, v) for W, (u, v) in zip(Ws, uv)], power_iterations)
+        ctx.save_for_backward(*(t for out in outs for t in out))
+        return tuple(out[0] for out in outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gs):
+        saved = ctx.saved_tensors
+        grads, jobs = [None] * len(gs), []
+        for i, g in enumerate(gs):
+            if g is None or not ctx.needs_input_grad[2 + i]:
+                continue
+            W_eff, u, v, inv = saved[4 * i:4 * i + 4]
+            grads[i] = torch.empty_like(W_eff)
+            jobs.append((g.contiguous(), W_eff, u, v, inv, grads[i], False))
+        spectral_norm_bwd_launch(jobs)
+        return (None, None, *grads)
+
+
+def spectral_weights(layers, power_iterations: int = 1):
+    """W_eff = W_bar / sigma of every layer of ``layers`` = [(W_bar, u, v), ...] after ``power_iterations`` steps of the power
+    iteration (which advance u and v in place): one launch forwards, one backwards (``SpectralWeightsFn``)."""
+    layers = list(layers)
+    for W, u, v in layers:
+        _chk(W, "W_bar")
+    return list(SpectralWeightsFn.apply(tuple((u, v) for _, u, v in layers), int(power_iterations), *(W for W, _, _ in layers)))
 
 
 # ------------------------------------------------------------------------------------- edge

@@ -1,7 +1,7 @@
 """What one option of the captured training iteration costs next to the step without it, on one GPU.  One JSON object per line on
 stdout and in --out.
 
-    python tools/step_option_bench.py --option {labels,ada,critic} [--reps 10] [--out profiles/<option>_bench.jsonl]
+    python tools/step_option_bench.py --option {labels,ada,critic,sn} [--reps 10] [--out profiles/<option>_bench.jsonl]
 
 MPGAN at N = 30, B = 256, the captured iteration, one process.  Two steps over the same weights and batch -- a baseline and the
 same with the option on -- and, where the option adds one launch to the D segment, that launch on its own outside any graph:
@@ -12,6 +12,8 @@ ada      baseline: the four augmentations at p = 0.5.  Option: the same with ``a
          the head).  Rows: a fixed_p_step, b adaptive_step, c ada_launch.
 critic   baseline: the default step.  Option: ``num_critic=5`` (--num-critic).  Rows: a default_step, b d_only_replay (a batch
          on which only D trains), c dg_replay (both train: the launches of a), d mean_per_batch (over two full cycles).
+sn       three steps: a default_step (for scale), and spectral norm in G and D with ``ops.OPTIONS["sn_fused"]`` off (b
+         sn_unfused_step) and on (c sn_fused_step).  Held to: the median of (c) is not above the median of (b).
 
 Every ``step()`` and every lone launch sits between two HIP events of its own -- in all rows alike, so that what an event pair
 costs cancels between them.  A repetition is --batches steps of each kind (critic: two full cycles of the schedule) taken
@@ -118,9 +120,47 @@ OPTIONS = {
 }
 
 
+def sn_bench(args, emit):
+    """--option sn: three captured steps in one process -- the default step (for scale), and spectral norm in G and D built under
+    ``ops.OPTIONS["sn_fused"]`` off (a launch per wrapped layer, MPLayer._forward_edges) and on (one grouped launch per network
+    part, the fused edge kernels) -- alternated, every ``step()`` between two HIP events."""
+    rows = ("a default_step", "b sn_unfused_step", "c sn_fused_step")
+    torch.manual_seed(0)
+    steps = []
+    for sn, on in ((False, True), (True, False), (True, True)):
+        ops.OPTIONS["sn_fused"] = on
+        G, D = train.default_mpgan(N, spectral_norm_gen=sn, spectral_norm_disc=sn)
+        lrs = train.LR["g"]
+        ts = train.TrainStep(G, D, B, N, lr_disc=lrs[0], lr_gen=lrs[1], use_graphs=True)
+        x, labels = mdata.synthetic_jets(B, N, seed=1)
+        ts.set_batch(x.cuda(), labels.cuda())
+        for _ in range(3):   # warm-up: captures the graph, under this leg's switch
+            ts.step()
+        torch.cuda.synchronize()
+        steps.append(ts)
+    ops.OPTIONS["sn_fused"] = True
+    assert all(l.fused for ts in steps for l in (*ts.G.mp_layers, *ts.D.mp_layers))
+    us = {r: [] for r in rows}
+    for _ in range(args.reps):
+        t = {r: [] for r in rows}
+        for _ in range(args.batches):        # (alternated: the rows share whatever the box does meanwhile)
+            for r, ts in zip(rows, steps):
+                t[r].append(timed(ts.step))
+        for r in rows:
+            us[r].append(float(np.mean(t[r])))
+    med = {}
+    for name, v in us.items():
+        med[name] = float(np.median(v))
+        emit({"model": "mpgan", "B": B, "N": N, "spectral_norm": name != rows[0], "row": name, "reps": args.reps,
+              "batches_per_rep": args.batches, "median_us": med[name], "min_us": float(np.min(v)), "max_us": float(np.max(v))})
+    emit({"model": "mpgan", "B": B, "row": "condition", "fused_minus_unfused_us": med[rows[2]] - med[rows[1]],
+          "fused_le_unfused": bool(med[rows[2]] <= med[rows[1]]),
+          **{f"{k}_loss_{r[2:]}": float(getattr(ts, k + "_loss")) for r, ts in zip(rows[1:], steps[1:]) for k in ("D", "G")}})
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--option", choices=sorted(OPTIONS), required=True)
+    ap.add_argument("--option", choices=sorted([*OPTIONS, "sn"]), required=True)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--batches", type=int, default=10, help="steps of each kind per repetition (critic: two cycles of the schedule)")
     ap.add_argument("--num-critic", type=int, default=5)
@@ -129,6 +169,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit(f"{args.option}_bench: no GPU visible (timings are taken on the device or not at all)")
     emit = jsonl_sink(args.out)
+    if args.option == "sn":
+        return sn_bench(args, emit)
     o = OPTIONS[args.option]
     critic = args.option == "critic"
     batches = 2 * args.num_critic if critic else args.batches
