@@ -145,6 +145,18 @@ typedef struct MpgChain {
     MpgChainLayer L[3];
 } MpgChain;
 int mpg_chain(const MpgChain* p, void* stream);
+/* mpg_chain_route: which kernel mpg_chain would run for `p`, without launching anything (host only: struct fields and
+ * pointer VALUES are read, nothing is dereferenced).  The checks are mpg_chain's own, in its order -- mpg_chain decides
+ * through this function -- so a refusal returns mpg_chain's negative code; otherwise one of
+ *   MPG_CHAIN_ROUTE_CHAIN2    the fixed shape table of chain2.hip (the MPLayer shapes),
+ *   MPG_CHAIN_ROUTE_STRAIGHT  the general kernel of chain.hip, one of its instantiations with straight-line k loops
+ *                             (the same k-steps as the MPLayer shapes: what MPG_CHAIN_GENERAL=1 in the environment,
+ *                             read on every call, sends them to),
+ *   MPG_CHAIN_ROUTE_LOOPS     the general kernel with run-time k loops (every other shape). */
+#define MPG_CHAIN_ROUTE_CHAIN2 1
+#define MPG_CHAIN_ROUTE_STRAIGHT 2
+#define MPG_CHAIN_ROUTE_LOOPS 3
+int mpg_chain_route(const MpgChain* p);
 
 /* mpg_edge_fwd: replaces MPLayer._getA_fully_connected + self.fe(A) + mask multiply + sum/mean
  * (mpgan/model.py:241, :256-267, :284-317).  Inputs are the layer-1 node terms

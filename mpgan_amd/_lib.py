@@ -207,6 +207,8 @@ class MpgSpectralBwdJob(C.Structure):
 
 
 MPG_FN_NA = -100  # mpg_edge_fwd_fn: "not one of my shapes" (include/mpgan_amd.h)
+# what mpg_chain_route answers (MPG_CHAIN_ROUTE_* of include/mpgan_amd.h)
+CHAIN_ROUTE_CHAIN2, CHAIN_ROUTE_STRAIGHT, CHAIN_ROUTE_LOOPS = 1, 2, 3
 
 MAB_CHAIN_MAX = 4   # MPG_MAB_CHAIN_MAX of include/mpgan_amd.h
 
@@ -229,6 +231,7 @@ SIGNATURES = {
     "mpg_pack_weights": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp, C.c_void_p]),
     "mpg_pack_many": (C.c_int, [C.POINTER(MpgPackJob), C.c_int, C.c_void_p]),
     "mpg_chain": (C.c_int, [C.POINTER(MpgChain), C.c_void_p]),
+    "mpg_chain_route": (C.c_int, [C.POINTER(MpgChain)]),
     "mpg_edge_fwd": (C.c_int, [C.POINTER(MpgEdgeFwd), C.c_void_p]),
     "mpg_edge_fwd_fn": (C.c_int, [C.POINTER(MpgEdgeFwd), C.POINTER(MpgChain), C.POINTER(MpgChain), C.c_void_p]),
     "mpg_edge_bwd": (C.c_int, [C.POINTER(MpgEdgeBwd), C.c_void_p]),

@@ -390,7 +390,13 @@ extern "C" int mpg_debug_chain_stamps(unsigned long long* host_out) {
 }
 #endif
 
-extern "C" int mpg_chain(const MpgChain* p, void* stream) {
+namespace {
+
+// The one decision of mpg_chain and mpg_chain_route (host only, nothing launched): a refusal's negative code, or the route
+// with what its launch needs -- chain2's plan, or the general kernel's instantiation (`shape`: column of GO below).
+struct ChainPlan { MpgChain2Plan c2; int shape; };
+
+int chain_decide(const MpgChain* p, ChainPlan* plan) {
     if (p->M <= 0 || p->nlayers < 1 || p->nlayers > 3) return -1;
     if (!(p->alpha >= 0.f && p->alpha <= 1.f)) return -4;
     for (int l = 0; l < p->nlayers; ++l) {
@@ -398,15 +404,30 @@ extern "C" int mpg_chain(const MpgChain* p, void* stream) {
         if (l + 1 < p->nlayers && (p->L[l].N > 16 * CH_MAXKS || p->L[l + 1].K != p->L[l].N)) return -2;
     }
     if (p->a_slabs < 1 || p->K1 > p->L[0].K || (p->K1 < p->L[0].K && p->A2 == nullptr)) return -2;
-    hipStream_t st = (hipStream_t)stream;
-    {   // the MPLayer shapes have their own schedule (chain2.hip)
-        const int rc = mpg_chain2_try(p, st);
-        if (rc != MPG_CHAIN2_NA) return rc;
-    }
-    dim3 grid((p->M + 31) / 32), block(512);
+    // the MPLayer shapes have their own schedule (chain2.hip)
+    if (mpg_chain2_decide(p, &plan->c2) != MPG_CHAIN2_NA) return MPG_CHAIN_ROUTE_CHAIN2;
     // k-steps per layer; the shapes MPLayer uses have straight-line instantiations, anything else the run-time loops
     int ks[3] = {0, 0, 0};
     for (int l = 0; l < p->nlayers; ++l) ks[l] = 2 * ((p->L[l].K + 31) / 32);
+    const bool f16 = p->f16 != 0;
+    plan->shape = (ks[0] == (f16 ? 14 : 2) && ks[1] == 16 && ks[2] == 16) ? 0 : ((ks[0] == (f16 ? 2 : 12) && p->nlayers == 1) ? 1 : 2);
+    return plan->shape == 2 ? MPG_CHAIN_ROUTE_LOOPS : MPG_CHAIN_ROUTE_STRAIGHT;
+}
+
+}  // namespace
+
+extern "C" int mpg_chain_route(const MpgChain* p) {
+    ChainPlan plan;
+    return chain_decide(p, &plan);
+}
+
+extern "C" int mpg_chain(const MpgChain* p, void* stream) {
+    ChainPlan plan;
+    const int route = chain_decide(p, &plan);
+    if (route < 0) return route;
+    hipStream_t st = (hipStream_t)stream;
+    if (route == MPG_CHAIN_ROUTE_CHAIN2) return mpg_chain2_launch(p, plan.c2, st);
+    dim3 grid((p->M + 31) / 32), block(512);
     using Go = int (*)(dim3, dim3, int, hipStream_t, const MpgChain&);
     static constexpr Go GO[2][3] = {   // [f16][shape]
         {mpg_go<chain_kernel<false, 2, 16, 16>, MpgChain>,   // fn input-gradient chain
@@ -415,9 +436,7 @@ extern "C" int mpg_chain(const MpgChain* p, void* stream) {
         {mpg_go<chain_kernel<true, 14, 16, 16>, MpgChain>,   // fn forward
          mpg_go<chain_kernel<true, 2, 0, 0>, MpgChain>,      // a | c projection
          mpg_go<chain_kernel<true, 0, 0, 0>, MpgChain>}};
-    const bool f16 = p->f16 != 0;
-    const int shape = (ks[0] == (f16 ? 14 : 2) && ks[1] == 16 && ks[2] == 16) ? 0 : ((ks[0] == (f16 ? 2 : 12) && p->nlayers == 1) ? 1 : 2);
-    return GO[f16][shape](grid, block, CH_LDS_BYTES, st, *p);
+    return GO[p->f16 != 0][plan.shape](grid, block, CH_LDS_BYTES, st, *p);
 }
 
 extern "C" int mpg_pack_many(const MpgPackJob* jobs, int njobs, void* stream) {

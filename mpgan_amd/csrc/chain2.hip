@@ -80,7 +80,7 @@ extern "C" int mpg_debug_chain2_stamps(unsigned long long* host_out) {
 #define C2_NA(why) do { if (dbg) fprintf(stderr, "mpg_chain: general kernel (%s; M %d, layers %d, K %d %d %d, N %d %d %d)\n", why, p->M, p->nlayers, \
         p->L[0].K, p->L[1].K, p->L[2].K, p->L[0].N, p->L[1].N, p->L[2].N); return MPG_CHAIN2_NA; } while (0)
 
-int mpg_chain2_try(const MpgChain* p, hipStream_t st) {
+int mpg_chain2_decide(const MpgChain* p, MpgChain2Plan* plan) {
     if (getenv("MPG_CHAIN_GENERAL")) return MPG_CHAIN2_NA;
     static const bool dbg = getenv("MPG_CHAIN_DEBUG") != nullptr;
     int ks[3] = {0, 0, 0};
@@ -114,14 +114,24 @@ int mpg_chain2_try(const MpgChain* p, hipStream_t st) {
         gates |= (p->L[l].gateH != nullptr) << l;
         resid |= (p->L[l].resid != nullptr) << l;
     }
+    plan->drop = drop;
+    plan->sl = sl;
     if (p->f16) {
-        if (p->nlayers == 3 && ks[0] == 14 && ks[1] == 16 && ks[2] == 16 && !gates && !resid)
-            return c2_launch_drop<true, 14, 16, 16, 0, 0>(p, drop, sl, st);                                                   // fn forward
-        if (p->nlayers == 1 && ks[0] == 2 && drop == 0 && !gates && !resid && !sl) return c2_launch<true, 2, 0, 0, 0, 0, 0, false>(p, st);  // a | c projection
+        if (p->nlayers == 3 && ks[0] == 14 && ks[1] == 16 && ks[2] == 16 && !gates && !resid) { plan->shape = C2_FN_FWD; return 0; }
+        if (p->nlayers == 1 && ks[0] == 2 && drop == 0 && !gates && !resid && !sl) { plan->shape = C2_AC_PROJ; return 0; }
         C2_NA("f16 shape");
     }
-    if (p->nlayers == 3 && ks[0] == 2 && ks[1] == 16 && ks[2] == 16 && gates == 3 && !resid)
-        return c2_launch_drop<false, 2, 16, 16, 3, 0>(p, drop, sl, st);                                                       // fn input gradients
-    if (p->nlayers == 1 && ks[0] == 12 && drop == 0 && !gates && resid == 1) return c2_launch_sl<false, 12, 0, 0, 0, 0, 1>(p, sl, st);   // dx from da | dc
+    if (p->nlayers == 3 && ks[0] == 2 && ks[1] == 16 && ks[2] == 16 && gates == 3 && !resid) { plan->shape = C2_FN_GRAD; return 0; }
+    if (p->nlayers == 1 && ks[0] == 12 && drop == 0 && !gates && resid == 1) { plan->shape = C2_DX; return 0; }
     C2_NA("shape");
+}
+
+int mpg_chain2_launch(const MpgChain* p, const MpgChain2Plan& plan, hipStream_t st) {
+    switch (plan.shape) {
+    case C2_FN_FWD: return c2_launch_drop<true, 14, 16, 16, 0, 0>(p, plan.drop, plan.sl, st);      // fn forward
+    case C2_AC_PROJ: return c2_launch<true, 2, 0, 0, 0, 0, 0, false>(p, st);                       // a | c projection
+    case C2_FN_GRAD: return c2_launch_drop<false, 2, 16, 16, 3, 0>(p, plan.drop, plan.sl, st);     // fn input gradients
+    case C2_DX: return c2_launch_sl<false, 12, 0, 0, 0, 0, 1>(p, plan.sl, st);                     // dx from da | dc
+    }
+    return -1;
 }

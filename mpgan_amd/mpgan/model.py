@@ -239,7 +239,11 @@ class MPLayer(nn.Module):
         # Spectral norm stays on the fused kernels: the five wrapped layers' W_bar / sigma are computed tensors, packed per call like a
         # folded W1 (forward).  Batch norm sits between a layer's activation and its dropout: not a form the fused kernels have.
         self.spectral_norm = bool(linear_args.get("spectral_norm"))
-        self.fused = (list(self.fe_layers) == [ops.H1, ops.H2, ops.H3] and len(self.fn_layers) == 2
+        # Every layer input of the node network's forward and input-gradient chains has to fit mpg_chain's fragment buffer
+        # (ops.CHAIN_MAX_K): the first layer's [agg | x | conditioning] columns, both hidden widths, and the output width
+        # (the first K of the backward chain).  A wider node network runs un-fused.
+        chain_fits = max([self.fe_layers[-1] + input_node_size + extra, output_node_size] + self.fn_layers) <= ops.CHAIN_MAX_K
+        self.fused = (list(self.fe_layers) == [ops.H1, ops.H2, ops.H3] and len(self.fn_layers) == 2 and chain_fits
                       and consistent and self.n_es <= ops.EDGE_SCALARS
                       and (self.fully_connected or (not self._diff_cols and extra == 0))
                       and not linear_args.get("batch_norm"))

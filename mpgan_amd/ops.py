@@ -956,6 +956,17 @@ def run_chain(c):   # (c: an ``MpgChain`` block, see ``chain_struct``)
     check(_lib.lib().mpg_chain(C.byref(c), _stream()), "mpg_chain")
 
 
+# = CH_MAXKS * 16 of csrc/chain.hip: the widest layer INPUT (K of any layer, so also N of every layer but the last) a fragment
+# buffer of mpg_chain holds -- beyond it the entry point refuses (-2)
+CHAIN_MAX_K = 256
+
+
+def chain_route(c) -> int:
+    """Which kernel ``mpg_chain`` would run for the block ``c`` (``_lib.CHAIN_ROUTE_*``), or its negative refusal code;
+    host only, nothing is launched."""
+    return _lib.lib().mpg_chain_route(C.byref(c))
+
+
 def chain_struct(M, layers, *, A, lda, K1, A2=None, lda2=0, a_slabs=1, a_slab_stride=0, in_gate=None, in_out=None,
                  alpha=0.2, seed_t=None, f16=False, ascale=1.0):
     """The ``MpgChain`` argument block of ``chain`` (also what ``mpg_edge_fwd_fn`` takes for its epilogue)."""

@@ -78,9 +78,9 @@ def test_gemm_two_segments_and_slices():
     assert rel_err(y2.cpu().numpy(), (x.double() @ w[:, K1:].double().t()).cpu().numpy()) < TIGHT
 
 
-def _mplayer_shapes(F, out):
+def _mplayer_shapes(F, out, fn=(256, 256)):
     from test_oracle_golden import mplayer_shapes
-    return mplayer_shapes(F, out)
+    return mplayer_shapes(F, out, fn=fn)
 
 
 def _fused_node(y):
@@ -118,7 +118,7 @@ def _sign_disagreements(neg, probe64, mask64):
 
 
 def _run_case(B, N, F, out, use_mask, sum_agg, seed, skip=True, alpha=0.2, control=None, flips=None, conditioned=None, mask=None,
-              tensors=None):
+              tensors=None, fn=(256, 256), route=None):
     """HIP MPLayer vs fp64 oracle on the same inputs.  Returns per-tensor
     (max-norm error, fraction of elements off by more than 1e-3 of the max) and the oracle's
     kink margin = min |pre-activation| / max |pre-activation| over all LeakyReLU inputs.
@@ -130,15 +130,17 @@ def _run_case(B, N, F, out, use_mask, sum_agg, seed, skip=True, alpha=0.2, contr
     LeakyReLU branch taken as the HIP forward took it (its own sign bits: ``_hip_signs``).  That is the gradient of the
     function the kernels computed: it must match strictly (no kink left to flip), whatever the kink decisions were.
     ``mask`` ([B, N, 1] of 0 / 1, with ``use_mask``): this mask instead of a drawn one -- jets without any particle included.
-    ``tensors`` (a dict): receives ``name -> (HIP tensor, oracle tensor)`` as float64 numpy arrays, for checks per jet."""
+    ``tensors`` (a dict): receives ``name -> (HIP tensor, oracle tensor)`` as float64 numpy arrays, for checks per jet.
+    ``fn``: the node network's hidden widths.  ``route`` (a dict): receives ``fused`` (the layer's own answer) and the C-ABI edge /
+    chain entry points its forward (``fwd``) and backward (``bwd``) called, in order."""
     import oracle
     from oracle import train_ref as T
     from mpgan_amd import ops
     from mpgan_amd.mpgan import MPLayer
     ops.OPTIONS["skip_masked"] = skip
     rs = np.random.RandomState(1000 + seed)
-    sd64 = T.init_state_dict(_mplayer_shapes(F, out), seed=seed, dtype=torch.float64)
-    layer = MPLayer(F, [96, 160, 192], [256, 256], out, sum=sum_agg, leaky_relu_alpha=alpha).to(_dev())
+    sd64 = T.init_state_dict(_mplayer_shapes(F, out, fn), seed=seed, dtype=torch.float64)
+    layer = MPLayer(F, [96, 160, 192], list(fn), out, sum=sum_agg, leaky_relu_alpha=alpha).to(_dev())
     layer.load_state_dict({k: v.float() for k, v in sd64.items()})
     x64 = torch.from_numpy(rs.normal(0, 0.5, size=(B, N, F)))
     g64 = torch.from_numpy(rs.normal(size=(B, N, out)))
@@ -174,12 +176,22 @@ def _run_case(B, N, F, out, use_mask, sum_agg, seed, skip=True, alpha=0.2, contr
             control[k] = (rel_err(a, b), float((np.abs(a - b) > 1e-3 * np.abs(b).max()).mean()))
     x = x64.float().to(_dev()).requires_grad_(True)
     mask = None if mask64 is None else mask64.float().to(_dev())
-    y = layer(x, use_mask, mask)
-    hip_neg = _hip_signs(y, B, N) if (flips is not None or conditioned is not None) else None
-    if flips is not None:
-        flips["hip"] = _sign_disagreements(hip_neg, probe, mask64)
-    (y * g64.float().to(_dev())).sum().backward()
-    torch.cuda.synchronize()
+    calls = _count_calls(ops) if route is not None else None
+    try:
+        y = layer(x, use_mask, mask)
+        if route is not None:
+            route["fused"], route["fwd"] = layer.fused, [k for k in calls.names if k in _KEEP]
+            del calls.names[:]
+        hip_neg = _hip_signs(y, B, N) if (flips is not None or conditioned is not None) else None
+        if flips is not None:
+            flips["hip"] = _sign_disagreements(hip_neg, probe, mask64)
+        (y * g64.float().to(_dev())).sum().backward()
+        torch.cuda.synchronize()
+        if route is not None:
+            route["bwd"] = [k for k in calls.names if k in _KEEP]
+    finally:
+        if calls is not None:
+            calls.restore()
     ops.OPTIONS["skip_masked"] = True
     pairs = {"y": (y.detach(), yo.detach()), "dx": (x.grad, xo.grad)}
     for k, p in layer.named_parameters():
@@ -276,6 +288,78 @@ def test_mplayer_vs_oracle(case):
     errs, frac, margin = _run_case(*case, seed=CASES.index(case), control=control, flips=flips, conditioned=cond)
     assert errs["y"] < TIGHT, errs
     _assert_gradients_up_to_kink_flips(errs, cond, flips, margin)
+
+
+WIDTH_CASES = [  # group, B, N, F, fn, out (mask on, sum on)
+    # ragged last tiles in every node layer, still the special kernels' k-steps: the node network as the edge launches' epilogue
+    ("ragged", 3, 30, 20, (228, 252), 20), ("ragged", 2, 33, 20, (228, 252), 20),
+    # none of the special kernels' shapes: mpg_edge_fwd_fn declines, the node network runs on mpg_chain's general kernel
+    ("general", 3, 30, 64, (128, 64), 64), ("general", 2, 33, 64, (128, 64), 64), ("general", 2, 5, 64, (128, 64), 64),
+    ("general", 3, 30, 6, (250, 131), 7),    # widths that are no multiples of 4
+    # a layer input beyond mpg_chain's 256 columns: un-fused
+    ("unfused", 2, 5, 128, (256, 256), 32), ("unfused", 2, 5, 32, (512, 256), 32), ("unfused", 2, 5, 32, (256, 256), 300),
+]
+_WIDTH_IDS = ["%s-B%d-N%d-F%d-fn%d-%d-out%d" % (g, B, N, F, fn[0], fn[1], out) for g, B, N, F, fn, out in WIDTH_CASES]
+_default_routes = {}
+
+
+def _default_route(B, N):
+    """The entry points a default-width layer (32, [256, 256], 32) calls at this size, forward and backward."""
+    if (B, N) not in _default_routes:
+        route = {}
+        _run_case(B, N, 32, 32, True, True, seed=0, alpha=1.0, route=route)
+        _default_routes[(B, N)] = route
+    return _default_routes[(B, N)]
+
+
+def _follows(names, first, then):
+    return any(a == first and b == then for a, b in zip(names, names[1:]))
+
+
+def _assert_width_route(group, B, N, route):
+    """``MPLayer.fused`` and the launches of one WIDTH_CASES run: the ragged widths stay on the epilogue kernels exactly as the default
+    widths do at that size; the other fused widths fall back inside the fused route to mpg_edge_fwd + mpg_chain; beyond the chain's
+    limits nothing of the fused route runs."""
+    assert route["fused"] == (group != "unfused"), route
+    if group == "ragged":
+        ref = _default_route(B, N)
+        assert route["fwd"] == ref["fwd"] and route["bwd"] == ref["bwd"], (route, ref)
+        assert "mpg_edge_fwd_fn" in route["fwd"] and "mpg_edge_fwd" not in route["fwd"], route
+        assert ("mpg_edge_bwd_fn" in route["bwd"]) == (N == 30) and ("mpg_edge_bwd" in route["bwd"]) == (N != 30), route
+    elif group == "general":
+        assert _follows(route["fwd"], "mpg_edge_fwd", "mpg_chain"), route   # (mpg_edge_fwd_fn is asked first and answers MPG_FN_NA)
+    else:
+        assert not route["fwd"] and not route["bwd"], route   # (LinearNet's launches are mpg_gemm)
+
+
+@pytest.mark.parametrize("case", WIDTH_CASES, ids=_WIDTH_IDS)
+def test_mplayer_other_widths_slope1_strict(case, monkeypatch):
+    """``test_mplayer_slope1_strict`` at node-network widths other than [256, 256] -> 3 / 5 / 32, and their routes.  One sender chunk
+    per jet (at these batch sizes the plan would cut three): the form in which both epilogue kernels run -- the ticketed chunks are
+    what ``test_mplayer_other_widths_vs_oracle`` takes."""
+    group, B, N, F, fn, out = case
+    monkeypatch.setenv("MPG_FORCE_SC", "1")
+    route = {}
+    errs, _, _ = _run_case(B, N, F, out, True, True, seed=20 + WIDTH_CASES.index(case), alpha=1.0, fn=fn, route=route)
+    print("errs", errs, "\nroute", route)
+    _assert_width_route(group, B, N, route)
+    _assert_smooth_bars(errs, case)
+
+
+@pytest.mark.parametrize("case", WIDTH_CASES, ids=_WIDTH_IDS)
+def test_mplayer_other_widths_vs_oracle(case):
+    """``test_mplayer_vs_oracle`` at those widths: forward strict, gradients up to kink flips (the fused layers keep the sign words that
+    check needs; the un-fused ones are held to the forward bar here and to the smooth bars above)."""
+    group, B, N, F, fn, out = case
+    seed = 40 + WIDTH_CASES.index(case)
+    if group == "unfused":
+        errs, _, _ = _run_case(B, N, F, out, True, True, seed=seed, fn=fn)
+        assert errs["y"] < TIGHT, errs
+        return
+    control, flips, cond = {}, {}, {}
+    errs, frac, margin = _run_case(B, N, F, out, True, True, seed=seed, control=control, flips=flips, conditioned=cond, fn=fn)
+    assert errs["y"] < TIGHT, errs
+    _assert_gradients_up_to_kink_flips(errs, cond, flips, margin, what=case)
 
 
 @pytest.mark.parametrize("case", [(4, 30, 32, 32, True, True), (3, 30, 3, 32, True, False), (2, 33, 32, 32, False, True)])
@@ -565,9 +649,14 @@ def test_mplayer_gradient_units_across_binades_and_zero_jets():
     _assert_smooth_bars(dict(errs, dx=worst))
 
 
-@pytest.mark.parametrize("p_drop,F,alpha", [(0.5, 32, 1.0), (0.3, 32, 1.0), (0.5, 3, 1.0), (0.3, 3, 1.0),
-                                            (0.5, 3, 0.2), (0.5, 32, 0.2), (0.3, 3, 0.2)])
-def test_mplayer_dropout_exact(p_drop, F, alpha):
+_DROPOUT_CASES = [pytest.param(p, F, (256, 256), 32, a, id="%s-%s-%s" % (p, F, a))
+                  for p, F, a in [(0.5, 32, 1.0), (0.3, 32, 1.0), (0.5, 3, 1.0), (0.3, 3, 1.0), (0.5, 3, 0.2), (0.5, 32, 0.2), (0.3, 3, 0.2)]]
+# other widths: the node network on mpg_chain's general kernel (its own choice of dropout words), both modes
+_DROPOUT_CASES += [pytest.param(p, 64, (128, 64), 64, 1.0, id="%s-64-128-64-64-1.0" % p) for p in (0.5, 0.3)]
+
+
+@pytest.mark.parametrize("p_drop,F,fn,out,alpha", _DROPOUT_CASES)
+def test_mplayer_dropout_exact(p_drop, F, fn, out, alpha):
     """Dropout on (training mode): the kernels' counter-based keep masks are dumped with
     mpg_dropout_mask and fed to the oracle, so forward AND backward can be compared exactly
     (p = 0.5 takes the one-bit fast path, p = 0.3 the byte-threshold path).  F = 3 is the discriminator's first layer -- the
@@ -579,10 +668,11 @@ def test_mplayer_dropout_exact(p_drop, F, alpha):
     from oracle import train_ref as T
     from mpgan_amd import ops
     from mpgan_amd.mpgan import MPLayer
-    B, N, out = 5, 30, 32   # (three drawn masks, a jet without any particle, a jet with one)
+    B, N = 5, 30   # (three drawn masks, a jet without any particle, a jet with one)
     V = B * N
-    sd64 = T.init_state_dict(_mplayer_shapes(F, out), seed=77, dtype=torch.float64)
-    layer = MPLayer(F, [96, 160, 192], [256, 256], out, leaky_relu_alpha=alpha, dropout_p=p_drop).to(_dev())
+    sd64 = T.init_state_dict(_mplayer_shapes(F, out, fn), seed=77, dtype=torch.float64)
+    layer = MPLayer(F, [96, 160, 192], list(fn), out, leaky_relu_alpha=alpha, dropout_p=p_drop).to(_dev())
+    assert layer.fused
     layer.load_state_dict({k: v.float() for k, v in sd64.items()})
     layer.train()
     rs = np.random.RandomState(5)
@@ -607,7 +697,9 @@ def test_mplayer_dropout_exact(p_drop, F, alpha):
     (y * g64.float().to(_dev())).sum().backward()
     dx = x4.grad[..., :F]
     thr, scale = ops.drop_params(p_drop)
-    widths = {"e0": 96, "e1": 160, "e2": 192, "n0": 256, "n1": 256, "n2": out}
+    widths = {"e%d" % i: l.out_features for i, l in enumerate(layer.fe.net)}
+    widths.update({"n%d" % i: l.out_features for i, l in enumerate(layer.fn.net)})
+    assert widths == {"e0": 96, "e1": 160, "e2": 192, "n0": fn[0], "n1": fn[1], "n2": out}
     sites = {"e0": ops.TAG_E0, "e1": ops.TAG_E1, "e2": ops.TAG_E2, "n0": ops.TAG_N0, "n1": ops.TAG_N1, "n2": ops.TAG_N2}
     keeps = {}
     for k, wdt in widths.items():
@@ -1008,8 +1100,8 @@ def test_layers_hand_over_their_node_terms(which, train, two_term):
 _KEEP = ("mpg_chain", "mpg_edge_fwd", "mpg_edge_fwd_fn", "mpg_edge_bwd", "mpg_edge_bwd_fn")
 
 
-def _layer_pair_runs(N, shift=None):
-    """Two fused MPLayers 32 -> 32 -> 32 (default widths, dropout 0.5, training mode) on B = 2 jets, one sender chunk: the pair
+def _layer_pair_runs(N, shift=None, F=32):
+    """Two fused MPLayers F -> F -> F (F = 32: default widths; dropout 0.5, training mode) on B = 2 jets, one sender chunk: the pair
     run through ``MPNet._run_layers`` (each layer with its ``ops.LayerHandoff``) and called by hand (no handoff), same seed and
     tags.  ``shift``: a forward pre-hook on the second layer replaces its x by x + shift in the coupled pass; the by-hand pass
     is given that input.  Returns ((results, forward launches, backward launches) coupled, the same by hand)."""
@@ -1018,7 +1110,7 @@ def _layer_pair_runs(N, shift=None):
     from mpgan_amd import ops
     from mpgan_amd.mpgan import MPNet
     dev = _dev()
-    B, F = 2, 32
+    B = 2
     torch.manual_seed(11)
     net = MPNet(N, F, mp_iters=2, hidden_node_size=F, linear_args={"dropout_p": 0.5}).to(dev).train()
     lo, hi = net.mp_layers
@@ -1079,6 +1171,18 @@ def test_coupled_and_uncoupled_layer_pairs_give_the_same_bits(N):
         assert fb == ["mpg_chain", "mpg_edge_fwd_fn"] * 2, fb
         assert ba == ["mpg_chain", "mpg_edge_bwd_fn", "mpg_edge_bwd_fn"], ba
         assert bb == ["mpg_chain", "mpg_edge_bwd_fn"] * 2, bb
+
+
+def test_layer_pair_at_64_features_declines_the_hand_off_with_the_same_bits():
+    """``MPNet(N, 64, mp_iters=2, hidden_node_size=64)``: both layers are fused, but none of the epilogue kernels' shapes (the node
+    network's first layer has 192 + 64 = 256 columns, dx 64) -- ``_next_node_terms`` declines (out_f > 32), every piece takes its own
+    launch with the node network on mpg_chain's general kernel, coupled and by hand alike, and the bits agree."""
+    (a, fa, ba), (b_, fb, bb) = _layer_pair_runs(30, F=64)
+    for k in a:
+        assert torch.equal(a[k], b_[k]), (k, float((a[k] - b_[k]).abs().max()))
+    ran = lambda names: [k for k in names if not k.endswith("_fn")]   # (the epilogue entry points are asked, and answer MPG_FN_NA)
+    assert ran(fa) == ran(fb) == ["mpg_chain", "mpg_edge_fwd", "mpg_chain"] * 2, (fa, fb)
+    assert ran(ba) == ran(bb) == ["mpg_chain", "mpg_edge_bwd", "mpg_chain"] * 2, (ba, bb)
 
 
 def test_forward_pre_hook_between_layers_breaks_the_coupling_safely():
