@@ -86,7 +86,7 @@ MPG_DEV uint32_t cvt_pk_bf16(float a, float b) {
     uint32_t r;
     // The conversion as the compiler's own instruction (a pair converts to ONE v_cvt_pk_bf16_f32), not inline assembly: behind
     // assembly the hazard recognizer sees neither the write that an MFMA reads two instructions later nor the read of an MFMA's
-    // result.  csrc/mab.hip's large-set backward lost the lo halves of some heads' fragments that way -- 1e-3 of dQ / dK on those
+    // result.  csrc/mab_bwds.hip's large-set backward lost the lo halves of some heads' fragments that way -- 1e-3 of dQ / dK on those
     // heads, gone with `s_nop 3` behind the instruction -- until the instruction was visible to the compiler.  Same values; the
     // headline and GAPT benches are unchanged (128.9k / 129.0k, 986k / 981k jets/s, old and new library alternated on one box).
     typedef float f32x2_t __attribute__((ext_vector_type(2)));

@@ -1,4 +1,4 @@
-"""GPU parity of the one-launch attention block (mpg_mab_fwd / mpg_mab_bwd, csrc/mab.hip) against the reference goldens,
+"""GPU parity of the one-launch attention block (mpg_mab_fwd / mpg_mab_bwd, csrc/mab_fwd.hip, csrc/mab_bwd.hip) against the reference goldens,
 the fp64 oracle (exact dropout masks) and the block-by-block path."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""The one-launch attention blocks (mpg_mab_fwd / mpg_mab_bwd / mpg_mab_chain_fwd, csrc/mab.hip) on the key masks a network
+"""The one-launch attention blocks (mpg_mab_fwd / mpg_mab_bwd / mpg_mab_chain_fwd, csrc/mab_fwd.hip and mab_bwd.hip) on the key masks a network
 meets in use -- whole key tiles of 32 without a real key (leading, middle, last), single real keys at a tile's first and last
 slot, the jet with no real key at all -- at every tile and route edge, through every schedule that can take the shape.
 
@@ -25,7 +25,7 @@ from test_mab_masks_cpu import (catalogue, tiled_catalogue, worst_jet, DEAD, FLO
 pytestmark = pytest.mark.gpu
 TIGHT = 1e-4
 LA = {"leaky_relu_alpha": 0.2, "dropout_p": 0.0, "batch_norm": False, "spectral_norm": False}
-SCHEDULES = {   # (read at every launch, csrc/mab.hip: mab_split_mode, mpg_mab_fwd)
+SCHEDULES = {   # (read at every launch, csrc/mab_common.h: mab_split_mode; mpg_mab_fwd)
     "default": {},
     "split0": {"MPG_MAB_SPLIT": "0"},     # one wave per jet
     "split1": {"MPG_MAB_SPLIT": "1"},     # two waves per jet up to 512 jets (the default, spelled out)

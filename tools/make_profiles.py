@@ -156,7 +156,7 @@ if os.path.isfile(sq_path):
 gp = os.path.join(F, "pmc_gapt_summary.txt")
 if os.path.isfile(gp):
     open(os.path.join(P, f"{tag}_pmc_gapt_mab_counters.txt"), "w").write(
-        "# One-launch attention blocks (csrc/mab.hip) under rocprofv3 --kernel-trace --pmc, one pass per counter set, workload\n"
+        "# One-launch attention blocks (csrc/mab_fwd.hip, csrc/mab_bwd.hip) under rocprofv3 --kernel-trace --pmc, one pass per counter set, workload\n"
         "# bench.py --model gapt --steps 3 --warmup 2 --no-graphs (B = 512: launches of 512 and 1,024 jets), per dispatch.\n"
         "# SQ_* units as in the edge-kernel table (quad-cycles summed over waves; MFMA_BUSY in cycles summed over SIMDs);\n"
         "# HBM bytes = 2 x FETCH_SIZE + WRITE_SIZE (KiB).  One wave per jet: MFMA busy / (4 x WAVE_CYCLES) is the share of a\n"

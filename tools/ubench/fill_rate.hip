@@ -1,4 +1,4 @@
-// How fast does a workgroup get a weight image into LDS when every CU wants one at once?  (mab.hip's prologue: 80 KiB forward,
+// How fast does a workgroup get a weight image into LDS when every CU wants one at once?  (the prologue of the mab_fwd.hip / mab_bwd.hip kernels: 80 KiB forward,
 // 144 KiB backward.)  Variants: LDS-DMA (global_load_lds_dwordx4) vs registers + ds_write_b128; 4 / 8 / 16 waves issuing; the
 // same image for every workgroup vs one image each; 256 / 128 / 64 workgroups.  Prints clocks (s_memtime) from the first
 // issue to the barrier behind the last piece, workgroup 0 and the median workgroup.

@@ -1,6 +1,6 @@
 // The first large-set backward of round 5 (every wave projects the other tiles' rows itself: 1,950 MFMAs per wave against 1,050 of
 // mab_bwdS_kernel, 157 against 120 us per launch) -- it lost its A/B and left the product library in round 6.  Text of the kernel as it
-// stood inside csrc/mab.hip's anonymous namespace (it uses that file's helpers); to build it again, include this file there in front of
+// stood inside the anonymous namespace of what is now csrc/mab_bwds.hip (it uses mab_common.h's helpers); to build it again, include this file there in front of
 // mab_bwdS_kernel and add the launch branch (MPG_MAB_BWDN=recompute) to mpg_mab_bwd.
 // ---- LARGE SETS, backward (33 ... 160 tokens; the forward is mab_fwdN_kernel).  One workgroup per jet; wave w owns query tile w
 // (its rows of dout, z, x: the feed-forward half, dq, the query side of dx) AND key tile w (dk, dv, the key side of dx / dy).
