@@ -58,7 +58,9 @@ OPTIONS = {
 NUM_CUS = 256
 # Forward products (they decide LeakyReLU signs) are split as fp16 hi/lo with the operand scales below (~2^-21 per
 # product); the fused edge backward works in fp16 as well (csrc/edge_bwd2_impl.h).  Range: |e2| < 1023, node activations
-# < 8188, |W * dscale| < 1023 -- see INTEGRATION.md.
+# < 8188, |W * dscale| < 1023 -- see INTEGRATION.md.  ``mpg_gemm`` (``linear_fwd``) has no operand scales: its fp16 route holds
+# 1e-4 (TIGHT) for operand magnitudes down to about 2^-10 and 1e-3 (TOL) down to about 2^-16; below that the product fades
+# out, above 65504 it is inf.  The bf16 route has no such range (tests/split_ref.py).
 FWD_F16 = True
 
 
@@ -353,7 +355,9 @@ def gemm(A, lda, B, ldb, Cout, ldc, M, N, K, *, ak=True, bk=True, a_off=0, b_off
 
 def linear_fwd(x, W, bias=None, *, act=False, alpha=0.2, drop=None, x2=None, w_col0=0, w_cols=None, resid=None, f16=None):
     """y = drop(act([x | x2] @ W[:, w_col0:w_col0+K]^T + bias)) (+ resid).  x [M,K1], W [N,ldw].  ``f16``: fp16 hi/lo
-    operands (the forward's default: ~2^-21 per product, magnitudes below 65504) or bf16 hi/lo (~2^-17, any magnitude)."""
+    operands (the forward's default: ~2^-21 per product at unit magnitude) or bf16 hi/lo (~2^-17, any magnitude).  The fp16 route
+    carries no operand scales: it holds 1e-4 (TIGHT) for operand magnitudes down to about 2^-10 and 1e-3 (TOL) down to about
+    2^-16; below that the product fades out, and above 65504 it is inf.  The bf16 route has no such range."""
     M, K1 = x.shape
     K2 = 0 if x2 is None else x2.shape[1]
     K = K1 + K2 if w_cols is None else w_cols

@@ -14,6 +14,7 @@ gradients and outputs are stored in full.
 Run:  python tests/gen_golden.py          (no-op with a message if /root/reference is absent)
       python tests/gen_golden.py fixtures (published weights, drop-in records: see ``fixtures``)
       python tests/gen_golden.py mab_masks (the attention block on the key-mask catalogue alone: see ``mab_masks``)
+      python tests/gen_golden.py mplayer_bn (MPLayer with batch norm alone: see ``mplayer_bn``)
 """
 import json
 import os
@@ -555,7 +556,7 @@ def main():
                     f"{loss}_G_loss": G_loss.item(), f"{loss}_dG_df": gg.numpy()})
         print("loss", loss, D_loss.item(), G_loss.item())
     np.savez_compressed(os.path.join(OUT, "losses.npz"), **rec)
-    return mab_masks()
+    return mplayer_bn() or mab_masks()
 
 
 PART_BYTES = 900 * 1024   # a committed file stays below 1 MiB: larger fixtures are split into <stem>.npz, <stem>.part1.npz, ...
@@ -636,6 +637,47 @@ def mab_masks():
                 rec[f"{tag}__{k}"] = v
             print("mab masks", tag, "dead jet finite on the reference's route:", dead_ok, float(np.abs(r["out"]).max()))
     save_parts("mab_masks_f64", rec)
+    return 0
+
+
+MPLAYER_BN_SEED = 65
+
+
+def mplayer_bn():
+    """The reference's own ``MPLayer(32, [96, 160, 192], [256, 256], 32, batch_norm=True)`` in fp64, training mode, B = 3, N = 10,
+    jet 1 without any particle: ``mplayer_bn_f64.npz`` (inputs, output, input gradient, summaries of the parameter gradients --
+    the norms' among them -- and the running statistics after the one call).  The edge network's norms see all B N N edge rows:
+    the reference multiplies by the sender's mask only after the edge network (mpgan/model.py:256-262)."""
+    if not os.path.isdir(REF):
+        print(f"reference not found at {REF}; nothing generated")
+        return 0
+    sys.path.insert(0, REF)
+    import mpgan as rmp  # reference
+    os.makedirs(OUT, exist_ok=True)
+    dt, ci, B, N, F, out = torch.float64, MPLAYER_BN_SEED, 3, 10, 32, 32
+    layer = rmp.MPLayer(F, [96, 160, 192], [256, 256], out, batch_norm=True).to(dt)
+    shapes = {k: tuple(v.shape) for k, v in layer.state_dict().items() if "running" not in k and "num_batches" not in k}
+    sd = layer.state_dict()
+    sd.update(init_state_dict(shapes, seed=ci, dtype=dt))   # running statistics keep their defaults (0, 1, 0)
+    layer.load_state_dict(sd)
+    layer.train()
+    f32 = lambda t: t.float().to(dt)      # (inputs are float32 values, stored as such: exact in fp64)
+    x = f32(seeded((B, N, F), 100 + ci, 0.5)).requires_grad_(True)
+    mask = rand_mask(B, N, 200 + ci).to(dt)
+    mask[1] = 0
+    g = f32(seeded((B, N, out), 300 + ci))
+    y = layer(x, True, mask)
+    (y * g).sum().backward()
+    rec = dict(x=x.detach().numpy().astype(np.float32), g=g.numpy().astype(np.float32), mask=mask.numpy().astype(np.float32),
+               y=y.detach().numpy(), dx=x.grad.numpy(), seed=ci)
+    for k, p in layer.named_parameters():
+        if p.grad is not None:      # (the node network registers a norm for its final linear layer and never runs it)
+            rec["grad__" + k] = summarize(k, p.grad)
+    for k, v in layer.state_dict().items():
+        if "running" in k or "num_batches" in k:
+            rec["state__" + k] = v.detach().numpy()
+    np.savez_compressed(os.path.join(OUT, "mplayer_bn_f64.npz"), **rec)
+    print("mplayer batch norm", float(y.abs().max()), int(mask.sum()))
     return 0
 
 
@@ -721,4 +763,5 @@ def fixtures():
 
 
 if __name__ == "__main__":
-    sys.exit(fixtures() if sys.argv[1:] == ["fixtures"] else mab_masks() if sys.argv[1:] == ["mab_masks"] else main())
+    sys.exit(fixtures() if sys.argv[1:] == ["fixtures"] else mab_masks() if sys.argv[1:] == ["mab_masks"]
+             else mplayer_bn() if sys.argv[1:] == ["mplayer_bn"] else main())
