@@ -1328,15 +1328,12 @@ def _taken_fn_grads(ctx, gy2):
 
 
 def _grad_targets(call, need_w):
-    # DeviceState.grad_into_param: add into the parameters' .grad buffers directly and return None for them.
+    # DeviceState.grad_into_param: add into the parameters' .grad buffers directly (the layer must know its twelve Parameters:
+    # ``pk.plist``) and return None for them.  Returns (the MPGradTargets, the ParamGrads whose slots autograd gets).
     sv, pk = call.sv, call.pk
-    if not need_w:
-        return MPGradTargets(*(None,) * 12, direct=False)
-    if (dev_state(sv.x2.device).grad_into_param and pk.plist is not None
-            and all(q.grad is not None and q.grad.is_contiguous() for q in pk.plist)):
-        return MPGradTargets(*(q.grad for q in pk.plist), direct=True)
-    W1, W2, W3, V1, V2, V3 = sv.W1, sv.W2, sv.W3, sv.V1, sv.V2, sv.V3
-    return MPGradTargets(*(t for W in (W1, W2, W3, V1, V2, V3) for t in (torch.empty_like(W), W.new_empty(W.shape[0]))), direct=False)
+    pg = ParamGrads(dev_state(sv.x2.device), pk.plist or (None,) * 12, (need_w,) * 12, eligible=pk.plist is not None)
+    tg, direct = pg.written(lambda: [t for W in (sv.W1, sv.W2, sv.W3, sv.V1, sv.V2, sv.V3) for t in (torch.empty_like(W), W.new_empty(W.shape[0]))])
+    return MPGradTargets(*tg, direct=bool(direct)), pg
 
 
 def _edge_grad_bufs(call, need_w):
@@ -1534,7 +1531,7 @@ class FusedMPLayerFn(torch.autograd.Function):
         # node network fn (mpgan/model.py:279): its input-gradient chain -- already run by the layer above as the epilogue of its
         # data-gradient launch, or launched by _edge_backward
         fng = _taken_fn_grads(ctx, gy2) or _fn_grad_chain(ctx, gy2)
-        tg = _grad_targets(call, any(need_p))   # (no parameter wants one in the G step: D's weights get no update there)
+        tg, pg = _grad_targets(call, any(need_p))   # (no parameter wants one in the G step: D's weights get no update there)
         dx = torch.empty((V, F), device=dev, dtype=torch.float32) if need_x else None
         route, sums, des = _edge_backward(ctx, call, gy2, fng, tg, dx)
         if need_x:
@@ -1547,7 +1544,7 @@ class FusedMPLayerFn(torch.autograd.Function):
             # tail of dh0; the x columns of xfn are the same nodes as x, whose node-path gradient is already in dx above
             dxfn = torch.cat((torch.zeros((V, F), device=dev, dtype=torch.float32), fng.dh0[:, H3 + F:]), dim=1).reshape(B, N, -1)
         # (parameter gradients already in .grad: autograd gets nothing to accumulate)
-        return (dx, None, *((None,) * 12 if tg.direct else tg[:12]), des, dxfn, None)
+        return (dx, None, *pg.slots(), des, dxfn, None)
 
 
 def _grad_target(t):
@@ -1564,14 +1561,83 @@ def _grad_target(t):
     return base.grad.as_strided(t.size(), t.stride(), t.storage_offset() - base.storage_offset() + base.grad.storage_offset())
 
 
-def _deferred_targets(st, params):
-    """May the gradients of ``params`` be queued for the grouped weight-gradient launches?  (their ``.grad`` targets in order, the
-    ``WgradBatch``) while a TrainStep backward is collecting on ``st`` (a ``DeviceState``) and EVERY parameter has a target; else
-    None -- the caller then computes the gradients itself and returns them to autograd."""
-    if not st.grad_into_param or st.deferred_wgrad is None:
+def _deferred_targets(st, params, queue_only=True):
+    """The decision step of ``ParamGrads``: may the gradients of ``params`` go into their ``.grad`` buffers?  (the targets in order,
+    ``st.deferred_wgrad``) while ``st.grad_into_param`` is on and EVERY parameter has a target, else None.  ``queue_only``: only
+    while a backward is collecting as well (a ``WgradBatch`` in ``st.deferred_wgrad``)."""
+    if not st.grad_into_param or (queue_only and st.deferred_wgrad is None):
         return None
     targets = [_grad_target(q) for q in params]
     return None if any(t is None for t in targets) else (targets, st.deferred_wgrad)
+
+
+class ParamGrads:
+    """Where the parameter gradients of ONE backward node go: decided here, once, all or nothing over ``params`` (the node's
+    parameters in autograd's order; ``wanted``: which of them get a gradient; ``st``: the ``DeviceState``).
+      queued    ``st.grad_into_param``, a collecting ``st.deferred_wgrad`` and a ``_grad_target`` for EVERY wanted parameter (a
+                wanted None has none): ``gemm`` and ``colsum`` add jobs to that ``WgradBatch``, whose grouped launch adds into
+                .grad at ``flush()``;
+      direct    the flag and every target: a kernel that forms the gradients itself adds into .grad (``written``);
+      returned  otherwise: fresh tensors, handed to autograd.
+    ``eligible``: what else the node needs to leave the returned route.  ``slots()`` is the node's answer to autograd: None
+    wherever the gradient went into .grad, so none can be returned and accumulated as well.
+    One per node, but for ``FusedMABFn``: its six GEMM-shaped gradients share one, while each norm parameter and the seed row
+    decide alone, as they always have (``_colsum_grad``: one helper of one parameter each)."""
+
+    __slots__ = ("wanted", "out", "targets", "batch")
+
+    def __init__(self, st, params, wanted, eligible=True):
+        self.wanted, self.out = wanted, [None] * len(params)
+        self.targets = self.batch = None
+        found = _deferred_targets(st, [q for q, w in zip(params, wanted) if w], queue_only=False) if (eligible and any(wanted)) else None
+        if found is not None:
+            tg = iter(found[0])
+            self.targets, self.batch = [next(tg) if w else None for w in wanted], found[1]
+
+    def slots(self):
+        return tuple(self.out)
+
+    def _give(self, i, t):   # (row blocks of one parameter -- cross-attention's Win[:E] / Win[E:] -- one under the other)
+        self.out[i] = t if self.out[i] is None else torch.cat([self.out[i], t], 0)
+
+    def gemm(self, iw, ib, dy, x, *, rows=None, col0=0):
+        """dW[rows, col0:col0+K] = dy^T x for parameter ``iw`` and its column sums for the bias ``ib`` (or None), as far as
+        they are wanted: a job of the batch when queued, else ``linear_bwd_weight`` into fresh tensors; a bias alone is summed
+        here and returned on every route (there is no GEMM for it to ride in).  ``col0`` (``WgradBatch.add``'s ``out_col0``) is
+        for the queued route only and no site passes it yet; ``out_scale`` is not offered: no site scales."""
+        want_b = ib is not None and self.wanted[ib]
+        if not self.wanted[iw]:
+            if want_b:
+                self._give(ib, dy.sum(0))
+        elif self.batch is not None:
+            W, b = self.targets[iw], self.targets[ib] if want_b else None
+            self.batch.add(dy, x, out=W if rows is None else W[rows], out_col0=col0,
+                           bias_out=b if (b is None or rows is None) else b[rows], accumulate=True)
+        else:
+            assert col0 == 0, "a column block of dW is formed on the queued route only"
+            db = torch.empty(dy.shape[1], device=dy.device, dtype=torch.float32) if want_b else None
+            self._give(iw, linear_bwd_weight(dy, x, bias_out=db))
+            if want_b:
+                self._give(ib, db)
+
+    def colsum(self, i, rows):
+        """The column sums of ``rows`` [M, E] for the vector parameter ``i``: queued, a bias-sum job (its one-column GEMM goes
+        into a throw-away ``out``); else summed here."""
+        if self.wanted[i] and self.batch is not None:
+            self.batch.add(rows, rows[:, :1], out=rows.new_empty((rows.shape[1], 1)), bias_out=self.targets[i].reshape(-1), accumulate=True)
+        elif self.wanted[i]:
+            self.out[i] = rows.sum(0)
+
+    def written(self, fresh, scratch=False):
+        """For a kernel that writes the gradients itself: (the tensors it writes, its ``accumulate`` flag) -- the .grad targets and
+        1, what ``fresh()`` allocates and 0, or Nones and 0 when nothing is wanted.  ``scratch``: the launch needs its buffers
+        even then (``mpg_batchnorm_bwd``): ``fresh()`` as well, but autograd still gets Nones."""
+        if self.targets is not None:
+            return self.targets, 1
+        if any(self.wanted):
+            self.out = list(fresh())
+            return self.out, 0
+        return (list(fresh()) if scratch else self.out), 0
 
 
 class FusedLinearFn(torch.autograd.Function):
@@ -1603,28 +1669,16 @@ class FusedLinearFn(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy):
         x2, W, y = ctx.saved_tensors
-        shp, act, alpha, thr, dscale, tag, has_b = ctx.cfg
+        shp, act, alpha, thr, dscale, tag, _ = ctx.cfg
         g2 = gy.reshape(-1, W.shape[0]).contiguous()
         if act or thr:
             g2 = gate(g2, y, gate_act=act, alpha=alpha, seed_t=seed_tensor(g2.device), tag=tag + TAG_GENERIC,
                       thr=thr, scale=dscale)
-        dW = db = None
-        want_b = has_b and ctx.needs_input_grad[2]
-        queue = None
-        if ctx.needs_input_grad[1]:
-            queue = _deferred_targets(dev_state(g2.device), [ctx.wparam, ctx.bias] if want_b else [ctx.wparam])
-        if queue is not None:
-            # TrainStep: queue dW (+ db) for the grouped launch at the end of the backward; it adds into .grad
-            targets, batch = queue
-            batch.add(g2, x2, out=targets[0], bias_out=targets[1] if want_b else None, accumulate=True)
-        elif ctx.needs_input_grad[1]:
-            if want_b:
-                db = torch.empty(W.shape[0], device=g2.device, dtype=torch.float32)
-            dW = linear_bwd_weight(g2, x2, bias_out=db)
-        elif want_b:
-            db = g2.sum(0)
+        # (TrainStep: dW (+ db) queued for the grouped launch at the end of the backward, which adds into .grad)
+        pg = ParamGrads(dev_state(g2.device), (ctx.wparam, ctx.bias), ctx.needs_input_grad[1:3])
+        pg.gemm(0, 1, g2, x2)
         dx = linear_bwd_data(g2, W).reshape(shp) if ctx.needs_input_grad[0] else None
-        return dx, dW, db, None, None, None, None, (gy if ctx.has_resid else None)
+        return dx, *pg.slots(), None, None, None, None, (gy if ctx.has_resid else None)
 
 
 class MatMulFn(torch.autograd.Function):
@@ -1914,23 +1968,13 @@ def mab_block(x, y, ignore, pk, prm, ln, H, alpha, ff_act, p_mab, p_ff, training
     return FusedMABFn.apply(x, y, ignore, *prm, *(ln if ln is not None else (None,) * 5), H, alpha, ff_act, p_mab, p_ff, training, pk)
 
 
-def _ln_param_grads(dn, gn, w, b, need_w, need_b):
-    """(d weight, d bias) of a LayerNorm from the rows the block's backward left -- dn = gradient with respect to the norm's
-    output, gn = dn times the normalised input: their column sums.  Inside a TrainStep backward they ride in the grouped
-    weight-gradient launch as bias-sum jobs (and Nones are returned); otherwise summed here."""
-    st = dev_state(dn.device)
-    E = dn.shape[1]
-    out = [None, None]
-    for k, (rows, prm, need) in enumerate(((gn, w, need_w), (dn, b, need_b))):
-        if not need:
-            continue
-        queue = _deferred_targets(st, [prm])
-        if queue is not None:
-            queue[1].add(rows, rows[:, :1], out=torch.empty((E, 1), device=dn.device, dtype=torch.float32),
-                         bias_out=queue[0][0].reshape(-1), accumulate=True)
-        else:
-            out[k] = rows.sum(0)
-    return out
+def _colsum_grad(st, prm, need, rows):
+    """The gradient of ONE vector parameter that is the column sums of ``rows`` -- a LayerNorm's weight or bias from the rows the
+    block's backward left, the seed row all jets share from dx: a bias-sum job of the grouped launch inside a TrainStep
+    backward (then None), else summed here.  Each such parameter decides for itself."""
+    pg = ParamGrads(st, (prm,), (need,))
+    pg.colsum(0, rows)
+    return pg.slots()[0]
 
 
 def _mab_backward_block(cfg, sv, prm, pk, gout, need_x, need_y, need_w, eps=None, need_ln=False):
@@ -1968,30 +2012,16 @@ def _mab_backward_block(cfg, sv, prm, pk, gout, need_x, need_y, need_w, eps=None
         lnrows = tuple(torch.empty((B * L, E), device=dev, dtype=torch.float32) for _ in range(4))
         m.dn1, m.gn1, m.dn2, m.gn2 = (_p(t) for t in lnrows)
     check(_lib.lib().mpg_mab_bwd(C.byref(m), _stream()), "mpg_mab_bwd")
-    grads = [None] * 6
-    if need_w:
-        queue = _deferred_targets(dev_state(dev), prm)
-        if queue is not None:      # TrainStep: queued for the grouped launches, added into the flat gradient buffers
-            g, wb = MABParams(*queue[0]), queue[1]
-            if cross:
-                wb.add(dq, x2, out=g.Win[:E], bias_out=g.bin[:E], accumulate=True)
-                wb.add(dkv, y2, out=g.Win[E:], bias_out=g.bin[E:], accumulate=True)
-            else:
-                wb.add(dqkv, x2, out=g.Win, bias_out=g.bin, accumulate=True)
-            wb.add(dza, o, out=g.Wo, bias_out=g.bo, accumulate=True)
-            wb.add(du, z, out=g.Wf, bias_out=g.bf, accumulate=True)
-        else:
-            def wgrad(dyv, xv):
-                db = torch.empty(dyv.shape[1], device=dev, dtype=torch.float32)
-                return linear_bwd_weight(dyv, xv, bias_out=db), db
-            if cross:
-                (wq, bq), (wkv, bkv) = wgrad(dq, x2), wgrad(dkv, y2)
-                grads[0], grads[1] = torch.cat([wq, wkv], 0), torch.cat([bq, bkv], 0)
-            else:
-                grads[0], grads[1] = wgrad(dqkv, x2)
-            grads[2], grads[3] = wgrad(dza, o)
-            grads[4], grads[5] = wgrad(du, z)
-    return dx, dy, grads, lnrows
+    # (TrainStep: queued for the grouped launches, added into the flat gradient buffers; nothing happens without ``need_w``)
+    pg = ParamGrads(dev_state(dev), prm, (need_w,) * 6)
+    if cross:
+        pg.gemm(0, 1, dq, x2, rows=slice(0, E))
+        pg.gemm(0, 1, dkv, y2, rows=slice(E, None))
+    else:
+        pg.gemm(0, 1, dqkv, x2)
+    pg.gemm(2, 3, dza, o)
+    pg.gemm(4, 5, du, z)
+    return dx, dy, pg.slots(), lnrows
 
 
 def sab_chain_forward(x, ignore, H, alpha, ff_act, p_mab, p_ff, training, pks, blocks, save=False):
@@ -2052,7 +2082,7 @@ class FusedMABFn(torch.autograd.Function):
     the grouped weight-gradient launches (``TrainStep``) or computes the weight gradients itself.  ``n1w`` ... ``eps``: norm1 /
     norm2 of a block with ``layer_norm=True`` (gapt/model.py:118-120, :131-136), which then run inside the same launches (one wave
     per jet); None without.  The backward then leaves, per row, the gradients with respect to the norms' outputs and those times
-    the normalised inputs: their column sums are the norms' parameter gradients (``_ln_param_grads``)."""
+    the normalised inputs: their column sums are the norms' parameter gradients (``_colsum_grad``)."""
 
     @staticmethod
     def forward(ctx, x, y, ignore, Win, bin_, Wo, bo, Wf, bf, n1w, n1b, n2w, n2b, eps, H, alpha, ff_act, p_mab, p_ff, training, pk):
@@ -2071,19 +2101,15 @@ class FusedMABFn(torch.autograd.Function):
         sv, cfg, need = MABSaved(*ctx.saved_tensors), ctx.cfg, ctx.needs_input_grad
         dx, dy, grads, rows = _mab_backward_block(cfg, sv, ctx.params, ctx.pk, gout, need[0], need[1], any(need[3:9]),
                                                   eps=ctx.eps, need_ln=any(need[9:13]))
-        gln = [None] * 4
+        st, gln = dev_state(gout.device), [None] * 4
         if rows is not None:
-            gln = (_ln_param_grads(rows[0], rows[1], sv.n1w, sv.n1b, need[9], need[10])
-                   + _ln_param_grads(rows[2], rows[3], sv.n2w, sv.n2b, need[11], need[12]))
-        if ctx.shared and dx is not None:
-            # a bias-sum job of the grouped weight-gradient launch when there is one, instead of a reduction launch of its own
-            queue = _deferred_targets(dev_state(dx.device), [ctx.seed]) if ctx.seed is not None else None
-            if queue is not None:
-                queue[1].add(dx, dx[:, :1], out=torch.empty((cfg.E, 1), device=dx.device, dtype=torch.float32),
-                             bias_out=queue[0][0].reshape(-1), accumulate=True)
-                dx = None
-            else:
-                dx = dx.sum(0).reshape(1, 1, cfg.E)
+            # (rows = dn1, gn1, dn2, gn2: dn = the gradient with respect to the norm's output (its bias's), gn = dn times the
+            # normalised input (its weight's))
+            gln = [_colsum_grad(st, prm, nd, r) for prm, nd, r in zip((sv.n1w, sv.n1b, sv.n2w, sv.n2b), need[9:13],
+                                                                      (rows[1], rows[0], rows[3], rows[2]))]
+        if ctx.shared and dx is not None:   # (ctx.seed: the row as a leaf parameter, else None -- then it has no .grad to add into)
+            dx = _colsum_grad(st, ctx.seed, True, dx)
+            dx = None if dx is None else dx.reshape(1, 1, cfg.E)
         elif dx is not None:
             dx = dx.reshape(cfg.B, cfg.L, cfg.E)
         return (dx, None if dy is None else dy.reshape(cfg.B, cfg.S, cfg.E), None, *grads, *gln, None, None, None, None, None, None, None, None)
@@ -2247,25 +2273,11 @@ class GenDiscBridgeFn(torch.autograd.Function):
         q.g2, q.ldg2, q.g1, q.ldg1, q.dx, q.lddx = _p(g2), E, _p(g1), F, _p(dx), K
         if want1 or want2 or need[0]:
             check(_lib.lib().mpg_bridge_bwd(q, _stream()), "mpg_bridge_bwd")
-        st = dev_state(dev)
-        outs = {}
-        for key, g, xin, W, b, nW, nb in (("1", g1, pre2, W1, b1, need[1], b1 is not None and need[2]),
-                                          ("2", g2, feat.reshape(M, F), W2, b2, need[4], b2 is not None and need[5])):
-            dW = db = None
-            if g is not None:
-                queue = _deferred_targets(st, [W, b] if nb else [W]) if nW else None
-                if queue is not None:
-                    targets, batch = queue
-                    batch.add(g, xin, out=targets[0], bias_out=targets[1] if nb else None, accumulate=True)
-                elif nW:
-                    if nb:
-                        db = torch.empty(W.shape[0], device=dev, dtype=torch.float32)
-                    dW = linear_bwd_weight(g, xin, bias_out=db)
-                elif nb:
-                    db = g.sum(0)
-            outs[key] = (dW, db)
-        return (None if dx is None else dx.reshape(Bg, N, K), outs["1"][0], outs["1"][1], None, outs["2"][0], outs["2"][1],
-                None, None, None, None, None)
+        st = dev_state(dev)   # (each layer decides for itself, as two FusedLinearFn nodes would)
+        pg1, pg2 = ParamGrads(st, (W1, b1), need[1:3]), ParamGrads(st, (W2, b2), need[4:6])
+        pg1.gemm(0, 1, g1, pre2)
+        pg2.gemm(0, 1, g2, feat.reshape(M, F))
+        return (None if dx is None else dx.reshape(Bg, N, K), *pg1.slots(), None, *pg2.slots(), None, None, None, None, None)
 
 
 LOSS_CODES = {"ls": 0, "og": 1, "w": 2, "hinge": 3}
@@ -2327,19 +2339,12 @@ class DiscHeadFn(torch.autograd.Function):
         h.gout = _p(gout)
         dy = torch.empty((B, N, F), device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
         h.dy, h.ld_dy = _p(dy), F
-        dw = db = None
-        if ctx.needs_input_grad[2]:
-            st = dev_state(dev)
-            gw = _grad_target(w) if st.grad_into_param else None
-            gb = _grad_target(b) if (st.grad_into_param and b is not None) else None
-            if gw is not None and (b is None or gb is not None):
-                h.dw, h.db, h.accumulate = _p(gw), _p(gb), 1
-            else:
-                dw = torch.empty_like(w)
-                db = None if b is None else torch.empty_like(b)
-                h.dw, h.db, h.accumulate = _p(dw), _p(db), 0
+        need_w = ctx.needs_input_grad[2]   # (w decides for both; a head without bias has one target)
+        pg = ParamGrads(dev_state(dev), (w, b), (need_w, need_w and b is not None))
+        (tw, tb), h.accumulate = pg.written(lambda: (torch.empty_like(w), None if b is None else torch.empty_like(b)))
+        h.dw, h.db = _p(tw), _p(tb)
         check(_lib.lib().mpg_disc_head_bwd(C.byref(h), _stream()), "mpg_disc_head_bwd")
-        return dy, None, dw, db, None, None, None, None
+        return dy, None, *pg.slots(), None, None, None, None
 
 
 def disc_head_loss(y, mask, w, b, *, mean, sigmoid, p_drop, training, loss, n_real, gen_step, count, loss_out,
@@ -2406,18 +2411,13 @@ class BatchNormFn(torch.autograd.Function):
         part = torch.empty((2 * nchunk, F), device=g.device, dtype=torch.float32)
         sums = torch.empty(2 * F, device=g.device, dtype=torch.float32)
         dx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
-        wp, bp = ctx.params
-        st = dev_state(g.device)
-        # (a frozen norm -- the discriminator's inside train_G -- keeps its .grad buffer as the optimizer launch left it: cleared)
-        wanted = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        gw = _grad_target(wp) if (st.grad_into_param and wanted) else None
-        gb = _grad_target(bp) if (st.grad_into_param and wanted) else None
-        direct = gw is not None and gb is not None
-        dw = gw if direct else torch.empty(F, device=g.device, dtype=torch.float32)
-        db = gb if direct else torch.empty(F, device=g.device, dtype=torch.float32)
+        # (a frozen norm -- the discriminator's inside train_G -- keeps its .grad buffer as the optimizer launch left it: cleared;
+        # the launch then writes its two sums into scratch, as it always has)
+        pg = ParamGrads(dev_state(g.device), ctx.params, (ctx.needs_input_grad[1] or ctx.needs_input_grad[2],) * 2)
+        (dw, db), acc = pg.written(lambda: (sums.new_empty(F), sums.new_empty(F)), scratch=True)
         check(_lib.lib().mpg_batchnorm_bwd(_p(g2), g2.stride(0), _p(x2), x2.stride(0), _p(mean), _p(var), _p(w), ctx.eps, _p(part), nchunk,
-                                           _p(sums), _p(dx), F, _p(dw), _p(db), int(direct), M, F, _stream()), "mpg_batchnorm_bwd")
-        return dx, (None if direct else dw), (None if direct else db), None
+                                           _p(sums), _p(dx), F, _p(dw), _p(db), acc, M, F, _stream()), "mpg_batchnorm_bwd")
+        return dx, *pg.slots(), None
 
 
 def batchnorm_eval(x, w, b, mean, var, eps):
@@ -2463,22 +2463,10 @@ class LayerNormFn(torch.autograd.Function):
         dx = torch.empty((M, E), device=g.device, dtype=torch.float32)
         nwaves = 4 * min(256, (M + 3) // 4)
         part = torch.empty((nwaves, 2, E), device=g.device, dtype=torch.float32)
-        st = dev_state(g.device)
-        wp, bp = ctx.params
-        dw = db = None
-        if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
-            # frozen norm (the discriminator's inside train_G): no parameter gradient is formed at all -- its .grad buffer was
-            # cleared by the optimizer launch before and must stay clean for the next train_D (TrainStep has no zero_grad there)
-            tw = tb = None
-            acc = 0
-        else:
-            gw = _grad_target(wp) if st.grad_into_param else None
-            gb = _grad_target(bp) if st.grad_into_param else None
-            if gw is not None and gb is not None:
-                tw, tb, acc = gw, gb, 1
-            else:
-                dw, db = torch.empty_like(w), torch.empty_like(w)
-                tw, tb, acc = dw, db, 0
+        # (a frozen norm -- the discriminator's inside train_G -- forms no parameter gradient at all: its .grad buffer was cleared by the
+        # optimizer launch before and must stay clean for the next train_D, TrainStep has no zero_grad there)
+        pg = ParamGrads(dev_state(g.device), ctx.params, (ctx.needs_input_grad[1] or ctx.needs_input_grad[2],) * 2)
+        (tw, tb), acc = pg.written(lambda: (torch.empty_like(w), torch.empty_like(w)))
         check(_lib.lib().mpg_layernorm_bwd(_p(g2), g2.stride(0), _p(x2), x2.stride(0), _p(w), _p(stats), _p(dx), E, _p(part),
                                            nwaves, _p(tw), _p(tb), acc, M, E, _stream()), "mpg_layernorm_bwd")
-        return dx.reshape(ctx.shp), dw, db, None
+        return dx.reshape(ctx.shp), *pg.slots(), None

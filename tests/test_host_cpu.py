@@ -320,6 +320,146 @@ def test_deferred_targets_only_inside_a_collecting_backward_with_every_target():
     assert ops._deferred_targets(st, [b, W])[0][0] is b.grad
 
 
+def test_param_grads_queue_only_inside_a_collecting_backward_with_every_target():
+    """``ops.ParamGrads`` queues -- the ``.grad`` targets in order plus the batch -- while ``grad_into_param`` is on, a batch is
+    collecting and EVERY wanted parameter has a target; not otherwise."""
+    from mpgan_amd import ops
+    st = ops.DeviceState(-1)
+    W = torch.nn.Parameter(torch.randn(6, 4))
+    b = torch.nn.Parameter(torch.randn(6))
+    bare = torch.nn.Parameter(torch.randn(3))          # no .grad buffer
+    W.grad, b.grad = torch.zeros_like(W), torch.zeros_like(b)
+    batch = object()
+
+    def queued(params):
+        pg = ops.ParamGrads(st, params, (True,) * len(params))
+        assert (pg.batch is None) or (pg.targets is not None)     # (a batch only ever beside every target)
+        return None if pg.batch is None else (pg.targets, pg.batch)
+    assert queued([W, b]) is None                       # nothing switched on
+    st.deferred_wgrad = batch
+    assert queued([W, b]) is None                       # grad_into_param off
+    st.grad_into_param, st.deferred_wgrad = True, None
+    assert queued([W, b]) is None                       # no batch
+    st.deferred_wgrad = batch
+    assert queued([W, bare]) is None                    # one parameter without a target
+    assert queued([W, None]) is None
+    targets, got = queued([W, b])
+    assert got is batch and len(targets) == 2 and targets[0] is W.grad and targets[1] is b.grad
+    rows = W[2:5]                                                          # a row slice of a leaf: the matching view of its .grad
+    (t,), _ = queued([rows])
+    assert t.shape == (3, 4) and t.data_ptr() == W.grad[2:5].data_ptr()
+    assert queued([b, W])[0][0] is b.grad
+
+
+class _RecordingBatch:
+    """Stands in for ``ops.WgradBatch``: keeps the arguments of every ``add``."""
+
+    def __init__(self):
+        self.jobs = []
+
+    def add(self, dy, x, **kw):
+        self.jobs.append((dy, x, kw))
+
+
+def _route(pg):
+    # which way the gradients of one ``ops.ParamGrads`` go, read off its decision
+    if not any(pg.wanted):
+        return "none"
+    return "returned" if pg.targets is None else "direct" if pg.batch is None else "queued"
+
+
+def _linear_params(with_b=True, grads=True):
+    W = torch.nn.Parameter(torch.randn(6, 4))
+    b = torch.nn.Parameter(torch.randn(6)) if with_b else None
+    if grads:
+        W.grad = torch.zeros_like(W)
+        if with_b:
+            b.grad = torch.zeros_like(b)
+    return W, b
+
+
+@pytest.mark.parametrize("flag", [False, True])
+@pytest.mark.parametrize("has_batch", [False, True])
+@pytest.mark.parametrize("grads", [False, True])
+@pytest.mark.parametrize("with_b", [False, True])
+def test_param_grads_decision_table(flag, has_batch, grads, with_b):
+    """The route of ``ops.ParamGrads`` for every combination of (flag, batch present, targets present, b is None), and nothing
+    wanted; ``written`` and ``slots`` on each: None for autograd exactly where the gradient goes into .grad."""
+    from mpgan_amd import ops
+    st = ops.DeviceState(-1)
+    st.grad_into_param, st.deferred_wgrad = flag, (_RecordingBatch() if has_batch else None)
+    W, b = _linear_params(with_b, grads)
+    wanted = (True, with_b)                               # (as DiscHeadFn asks: a head without bias has one target)
+    pg = ops.ParamGrads(st, (W, b), wanted)
+    expect = "returned" if not (flag and grads) else "queued" if has_batch else "direct"
+    assert _route(pg) == expect
+    fresh = (torch.empty(6, 4), torch.empty(6) if with_b else None)
+    (tw, tb), acc = pg.written(lambda: fresh)
+    if expect == "returned":
+        assert acc == 0 and tw is fresh[0] and tb is fresh[1]
+        assert pg.slots()[0] is fresh[0] and pg.slots()[1] is fresh[1]
+    else:                                                 # (a kernel that writes the gradients itself adds into .grad, batch or not)
+        assert acc == 1 and tw is W.grad and (tb is b.grad if with_b else tb is None)
+        assert pg.slots() == (None, None)
+    # nothing wanted: no target is looked up, nothing is allocated, nothing is returned -- a frozen norm's .grad stays as it is
+    calls = []
+    none = ops.ParamGrads(st, (W, b), (False, False))
+    assert _route(none) == "none" and none.targets is None and none.batch is None
+    assert none.written(lambda: calls.append(1)) == ([None, None], 0) and not calls and none.slots() == (None, None)
+    none.gemm(0, 1, None, None)
+    none.colsum(1, None)
+    assert none.slots() == (None, None) and (not has_batch or not st.deferred_wgrad.jobs)
+    # a wanted parameter that is None has no target: returned, whatever is switched on (FusedMABFn's seed row that is no leaf)
+    assert _route(ops.ParamGrads(st, (None,), (True,))) == "returned"
+    # ``eligible``: what else a node needs (FusedMPLayerFn: its PackedMPLayer knows the twelve Parameters)
+    assert _route(ops.ParamGrads(st, (W, b), wanted, eligible=False)) == "returned"
+
+
+def test_param_grads_queued_jobs_and_autograd_slots():
+    """The jobs ``gemm`` and ``colsum`` add on the queued route -- with and without bias, a row block, ``out_col0``, a column
+    sum -- and the tuple autograd gets: None for everything queued."""
+    from mpgan_amd import ops
+    st = ops.DeviceState(-1)
+    st.grad_into_param, st.deferred_wgrad = True, _RecordingBatch()
+    jobs = st.deferred_wgrad.jobs
+    W, b = _linear_params()
+    dy, x = torch.randn(9, 6), torch.randn(9, 4)
+    pg = ops.ParamGrads(st, (W, b), (True, True))
+    pg.gemm(0, 1, dy, x)
+    assert len(jobs) == 1 and jobs[0][0] is dy and jobs[0][1] is x
+    kw = jobs[0][2]
+    assert sorted(kw) == ["accumulate", "bias_out", "out", "out_col0"]
+    assert kw["out"] is W.grad and kw["bias_out"] is b.grad and kw["out_col0"] == 0 and kw["accumulate"] is True
+    assert pg.slots() == (None, None)
+    pg = ops.ParamGrads(st, (W, b), (True, False))         # the bias is not wanted: no bias_out, no target looked up for it
+    pg.gemm(0, 1, dy, x[:, :2], col0=2)
+    assert jobs[1][2]["out"] is W.grad and jobs[1][2]["bias_out"] is None and jobs[1][2]["out_col0"] == 2 and jobs[1][2]["accumulate"] is True
+    assert pg.targets[1] is None and pg.slots() == (None, None)
+    pg = ops.ParamGrads(st, (W, b), (True, True))          # a row block (cross-attention's Win[:E] / Win[E:]): the same rows of both targets
+    pg.gemm(0, 1, dy[:, :2], x, rows=slice(4, None))
+    kw = jobs[2][2]
+    assert kw["out"].shape == (2, 4) and kw["out"].data_ptr() == W.grad[4:].data_ptr()
+    assert kw["bias_out"].shape == (2,) and kw["bias_out"].data_ptr() == b.grad[4:].data_ptr() and kw["accumulate"] is True
+    pg = ops.ParamGrads(st, (W, b), (False, True))         # a bias alone rides in no GEMM: summed at once and returned
+    pg.gemm(0, 1, dy, x)
+    assert len(jobs) == 3 and pg.slots()[0] is None and torch.equal(pg.slots()[1], dy.sum(0))
+    # a column sum: the bias-sum job -- a one-column GEMM into a throw-away out, the sums into the flattened target
+    g = torch.nn.Parameter(torch.randn(1, 1, 6))
+    g.grad = torch.zeros_like(g)
+    rows = torch.randn(9, 6)
+    pg = ops.ParamGrads(st, (g,), (True,))
+    pg.colsum(0, rows)
+    dy4, x4, kw = jobs[3]
+    assert dy4 is rows and x4.shape == (9, 1) and x4.data_ptr() == rows.data_ptr() and x4.stride() == rows[:, :1].stride()
+    assert kw["out"].shape == (6, 1) and kw["bias_out"].shape == (6,) and kw["bias_out"].data_ptr() == g.grad.data_ptr()
+    assert kw["accumulate"] is True and pg.slots() == (None,)
+    # not queued (no batch): summed here and returned, whatever the flag says
+    st.deferred_wgrad = None
+    pg = ops.ParamGrads(st, (g,), (True,))
+    pg.colsum(0, rows)
+    assert torch.equal(pg.slots()[0], rows.sum(0)) and not g.grad.any()
+
+
 @pytest.mark.parametrize("switches", ["1", "0"])
 def test_cpu_and_gradient_penalty_steps_take_the_module_route(monkeypatch, switches):
     """``TrainStep._route()`` names how the generator's jets reach the discriminator.  A step on the CPU (toy modules) and a
