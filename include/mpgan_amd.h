@@ -524,6 +524,41 @@ int mpg_adam(float* p, float* g, float* m, float* v, float* step, uint64_t n, fl
 int mpg_adadelta(float* p, float* g, float* v, float* u, uint64_t n, float lr, float rho, float eps,
                  float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, void* stream);
 
+/* The averaged forms: the same launch also folds the new parameters into an exponential moving average e [n] of them (Yazici
+ * et al. 2019; the G_ema of StyleGAN2-ADA).  The reference has no such option (its answer to an oscillating generator is
+ * G_best_epoch.pt, train.py:794-797): this statement is the specification.
+ * state: uint32[2] = {t, ticket} in device memory -- t counts the averaged launches made so far; the ticket is the launch's
+ * arrival counter and reads 0 between launches.  For every element i, with p_new the value the optimiser stores in p[i] and t
+ * the step word as it stood before the launch:
+ *   if t < start:   e[i] = p_new                                        (the average follows the weights until averaging begins)
+ *   else:
+ *       k      = (float) min(t - start, 2^24)                           (exact)
+ *       beta_t = warmup ? min(beta, (1 + k) / (10 + k)) : beta           (two fp32 sums, ONE fp32 division)
+ *       om     = 1 - beta_t                                             (ONE fp32 subtraction)
+ *       d = p_new - e[i];  m = om * d;  e[i] = e[i] + m                 (THREE fp32 operations)
+ * Every operation rounds to nearest even on its own; nothing is contracted into a fused multiply-add.  p, the optimiser's
+ * moments, g and *counter come out bit for bit as from the entry point without the average.
+ * Every workgroup reads t before anything else and arrives on the ticket last; the one that arrives last writes t + 1 and puts
+ * the ticket back to 0: exactly one write per launch, behind every read of the old value, and no launch of its own.
+ * A NULL block, ema or state, beta outside [0, 1) or a NaN, start < 0, n == 0: -1.
+ * mpg_ema_update_host: the rule alone, compiled from the same body for the host, on host memory: e[i] <- rule(e[i], p_new[i])
+ * for i < n at step word t.  No HIP call; the same refusals. */
+typedef struct MpgEma {
+    float* ema;
+    uint32_t* state;   /* t, ticket */
+    float beta;
+    int start;
+    int warmup;
+} MpgEma;
+int mpg_rmsprop_ema(float* p, float* g, float* v, uint64_t n, float lr, float alpha, float eps, float gscale, int zero_grad,
+                    uint64_t* counter, uint64_t counter_add, const MpgEma* ema, void* stream);
+int mpg_adam_ema(float* p, float* g, float* m, float* v, float* step, uint64_t n, float lr, float beta1,
+                 float beta2, float eps, float weight_decay, float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add,
+                 const MpgEma* ema, void* stream);
+int mpg_adadelta_ema(float* p, float* g, float* v, float* u, uint64_t n, float lr, float rho, float eps,
+                     float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, const MpgEma* ema, void* stream);
+int mpg_ema_update_host(float* e, const float* p_new, uint64_t n, uint32_t t, float beta, int start, int warmup);
+
 /* ---- evaluation metrics --------------------------------------------------------------------------
  * mpg_jet_obs: per-jet observables of the metrics the reference's evaluate (train.py:543-606) draws from jetnet / energyflow:
  * jetnet.utils.jet_features (for w1m) and the EFPs of jetnet.evaluation.w1efp (energyflow ("n==",4), ("d==",4), ("p==",1)).

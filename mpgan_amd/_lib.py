@@ -206,6 +206,10 @@ class MpgSpectralBwdJob(C.Structure):
     ]
 
 
+class MpgEma(C.Structure):
+    _fields_ = [("ema", _fp), ("state", _fp), ("beta", C.c_float), ("start", C.c_int), ("warmup", C.c_int)]
+
+
 MPG_FN_NA = -100  # mpg_edge_fwd_fn: "not one of my shapes" (include/mpgan_amd.h)
 # what mpg_chain_route answers (MPG_CHAIN_ROUTE_* of include/mpgan_amd.h)
 CHAIN_ROUTE_CHAIN2, CHAIN_ROUTE_STRAIGHT, CHAIN_ROUTE_LOOPS = 1, 2, 3
@@ -262,6 +266,13 @@ SIGNATURES = {
                            C.c_float, C.c_int, _fp, C.c_uint64, C.c_void_p]),
     "mpg_adadelta": (C.c_int, [_fp, _fp, _fp, _fp, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _fp, C.c_uint64,
                                C.c_void_p]),
+    "mpg_rmsprop_ema": (C.c_int, [_fp, _fp, _fp, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _fp, C.c_uint64,
+                                  C.POINTER(MpgEma), C.c_void_p]),
+    "mpg_adam_ema": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                               C.c_float, C.c_int, _fp, C.c_uint64, C.POINTER(MpgEma), C.c_void_p]),
+    "mpg_adadelta_ema": (C.c_int, [_fp, _fp, _fp, _fp, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _fp, C.c_uint64,
+                                   C.POINTER(MpgEma), C.c_void_p]),
+    "mpg_ema_update_host": (C.c_int, [_fp, _fp, C.c_uint64, C.c_uint32, C.c_float, C.c_int, C.c_int]),
     "mpg_bridge_fwd": (C.c_int, [C.POINTER(MpgBridge), C.c_void_p]),
     "mpg_bridge_bwd": (C.c_int, [C.POINTER(MpgBridgeBwd), C.c_void_p]),
     "mpg_normal": (C.c_int, [_fp, C.c_uint64, _fp, C.c_uint32, C.c_float, C.c_float, C.c_void_p]),

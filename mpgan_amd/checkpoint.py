@@ -2,6 +2,8 @@
 
 * ``save_models``  -- ``<models_path>/{D,G}_<epoch>.pt`` (module state dicts) and ``{D,G}_optim_<epoch>.pt``
   (``torch.optim`` state dicts), train.py:526-537;
+* ``save_models(..., G_ema=)`` / ``load_ema`` -- ``G_ema_<epoch>.pt``: the averaged generator of ``TrainStep(ema=...)``, a plain G
+  state dict (the reference's ``gen.py`` loads it as a generator); the reference has no such file;
 * ``load_models`` / ``load_optimizers`` -- their readers, setup_training.py:1406-1416 and :1525-1535;
 * ``latest_epoch`` -- the newest epoch for which both networks were saved, setup_training.py:1140-1156;
 * ``save_losses`` / ``load_losses`` -- one ``<key>.txt`` per loss or metric (``np.savetxt`` / ``np.loadtxt``),
@@ -23,12 +25,16 @@ def _plain(module: torch.nn.Module) -> torch.nn.Module:
     return module.module if hasattr(module, "module") and isinstance(module.module, torch.nn.Module) else module
 
 
-def save_models(D, G, D_optimizer, G_optimizer, models_path: str, epoch: int, multi_gpu: bool = False):
-    """train.py:526-537.  ``multi_gpu`` (a DataParallel / DDP wrapper) is also detected from ``.module``."""
+def save_models(D, G, D_optimizer, G_optimizer, models_path: str, epoch: int, multi_gpu: bool = False, G_ema=None):
+    """train.py:526-537.  ``multi_gpu`` (a DataParallel / DDP wrapper) is also detected from ``.module``.  ``G_ema``
+    (``TrainStep.ema_generator()``): the averaged generator's state dict goes to ``G_ema_<epoch>.pt``; the step word of the
+    average travels in G's optimizer file."""
     os.makedirs(models_path, exist_ok=True)
     for tag, net, opt in (("D", D, D_optimizer), ("G", G, G_optimizer)):
         torch.save(_plain(net).state_dict(), os.path.join(models_path, f"{tag}_{epoch}.pt"))
         torch.save(opt.state_dict(), os.path.join(models_path, f"{tag}_optim_{epoch}.pt"))
+    if G_ema is not None:
+        torch.save(_plain(G_ema).state_dict(), os.path.join(models_path, f"G_ema_{epoch}.pt"))
 
 
 def latest_epoch(models_path: str) -> int:
@@ -56,6 +62,25 @@ def load_models(D, G, models_path: str, epoch: int, map_location=None):
             _plain(net).load_state_dict(obj)
         out.append(net)
     return out[0], out[1]
+
+
+def load_ema(ts_or_module, models_path: str, epoch: int, map_location=None) -> bool:
+    """Read ``G_ema_<epoch>.pt`` back into the averaged generator: ``ts_or_module`` is the ``TrainStep`` (its
+    ``ema_generator()`` twin is loaded, and through the twin's parameters ``fG.ema``) or a generator module.  Call it after
+    ``load_models`` / ``load_optimizers``.  Returns whether the file was there; without it a ``TrainStep`` restarts the average
+    as it does from an optimizer file without the average's key: the average set to the loaded weights, its step count to 0."""
+    path = os.path.join(models_path, f"G_ema_{epoch}.pt")
+    is_step = hasattr(ts_or_module, "ema_generator")
+    if not os.path.isfile(path):
+        if is_step:
+            ts_or_module.fG.ema_carried.restart(0)
+        return False
+    sd = torch.load(path, map_location=map_location, weights_only=False)
+    target = ts_or_module.ema_generator() if is_step else _plain(ts_or_module)
+    target.load_state_dict(sd)
+    if is_step:        # (buffers and frozen parameters are G's own again, the weight images those of the loaded average)
+        ts_or_module.ema_generator()
+    return True
 
 
 def load_optimizers(D_optimizer, G_optimizer, models_path: str, epoch: int, map_location=None):

@@ -12,27 +12,103 @@
 // device memory (a captured hipGraph must see it advance on every replay).  `zero_grad` != 0: the gradient buffer is
 // cleared behind its last use (the next backward accumulates into zeros: optimizer.zero_grad() of train.py:419 / :494
 // without a launch of its own).
+//
+// The averaged form (mpg_*_ema; the rule is stated in include/mpgan_amd.h): the same loops with the exponential moving average
+// of the parameters as two more memory streams -- the new parameter value is in a register when it is stored.  The kernels are
+// templates on a bool; the instantiation without the average reads and writes what it always did.  The average's step word t
+// is read by every workgroup at the top and moved on by the workgroup that arrives last on the ticket beside it
+// (last_arrival, csrc/draws.h -- the loader's cursor moves the same way): no workgroup of the launch can still be about to read
+// the old value when the new one is written, and there is no launch for it.  ema_coef / ema_fold are one body for the device and
+// for mpg_ema_update_host.
 #include "draws.h"
 
+// What a launch at step word t does with every element: `track` (t < start: the average follows the weights) or the fold with
+// om = 1 - beta_t.  Every operation is one fp32 operation rounded to nearest even, and none is contracted: the bodies are plain
+// operators under `fp contract(off)`, the same text for the device and the host.  (Not __fsub_rn / __fmul_rn / __fadd_rn: the
+// compiler's headers define them as the plain operators, compiled under the header's own contraction setting, and inlined here
+// the multiply and the sum came out as one v_fmac_f32.  The quotient is __fdiv_rn's on the device, as in csrc/ada.hip: correctly
+// rounded whatever the build's division flags.)
+struct EmaCoef { bool track; float om; };
+
+MPG_HD float ema_div(float a, float b) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __fdiv_rn(a, b);
+#else
+    return a / b;
+#endif
+}
+
+MPG_HD EmaCoef ema_coef(uint32_t t, float beta, int start, int warmup) {
+#pragma clang fp contract(off)
+    if (t < (uint32_t)start) return {true, 0.f};
+    float beta_t = beta;
+    if (warmup) {
+        const uint32_t since = t - (uint32_t)start;
+        const float k = (float)(since < (1u << 24) ? since : (1u << 24));     // (exact: an integer <= 2^24)
+        const float num = 1.f + k, den = 10.f + k;
+        const float ramp = ema_div(num, den);
+        beta_t = ramp < beta ? ramp : beta;
+    }
+    const float om = 1.f - beta_t;
+    return {false, om};
+}
+
+MPG_HD float ema_fold(EmaCoef c, float e, float p_new) {
+#pragma clang fp contract(off)
+    if (c.track) return p_new;
+    const float d = p_new - e;
+    const float m = c.om * d;
+    return e + m;
+}
+
 namespace {
+// the head and the tail of an averaged launch: every workgroup reads t first and arrives last
+template <bool EMA>
+MPG_DEV EmaCoef ema_begin(const MpgEma& a, uint32_t& t) {
+    if constexpr (!EMA) return {true, 0.f};
+    t = __hip_atomic_load(a.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return ema_coef(t, a.beta, a.start, a.warmup);
+}
+template <bool EMA>
+MPG_DEV void ema_end(const MpgEma& a, uint32_t t) {
+    if constexpr (EMA) {
+        // (behind the barrier every lane of the workgroup has used t: its stores to the average carry values made from it)
+        __syncthreads();
+        if (threadIdx.x == 0 && last_arrival(a.state + 1)) {
+            __hip_atomic_store(a.state + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(a.state, t + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+template <bool EMA>
 __global__ void rmsprop_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ v, size_t n,
-                               float lr, float alpha, float eps, float gscale, int zero_grad, uint64_t* __restrict__ counter, uint64_t counter_add) {
+                               float lr, float alpha, float eps, float gscale, int zero_grad, uint64_t* __restrict__ counter, uint64_t counter_add,
+                               MpgEma ema) {
     if (counter != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *counter += counter_add;
+    uint32_t t = 0;
+    const EmaCoef ec = ema_begin<EMA>(ema, t);
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
         const float gi = g[i] * gscale;
         const float vi = alpha * v[i] + (1.f - alpha) * gi * gi;
         v[i] = vi;
-        p[i] -= lr * gi / (sqrtf(vi) + eps);
+        const float pn = p[i] - lr * gi / (sqrtf(vi) + eps);
+        p[i] = pn;
+        if constexpr (EMA) ema.ema[i] = ema_fold(ec, ema.ema[i], pn);
         if (zero_grad) g[i] = 0.f;
     }
+    ema_end<EMA>(ema, t);
 }
 
+template <bool EMA>
 __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             const float* __restrict__ step, size_t n, float lr, float b1, float b2, float eps, float wd,
-                            float gscale, int zero_grad, uint64_t* __restrict__ counter, uint64_t counter_add) {
+                            float gscale, int zero_grad, uint64_t* __restrict__ counter, uint64_t counter_add, MpgEma ema) {
     if (counter != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *counter += counter_add;
+    uint32_t te = 0;
+    const EmaCoef ec = ema_begin<EMA>(ema, te);
     const float t = *step + 1.f;
     const float bc1 = 1.f - powf(b1, t), bc2s = sqrtf(1.f - powf(b2, t));
     const float step_size = lr / bc1;
@@ -45,15 +121,22 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
         const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
         m[i] = mi;
         v[i] = vi;
-        p[i] = pi - step_size * mi / (sqrtf(vi) / bc2s + eps);
+        const float pn = pi - step_size * mi / (sqrtf(vi) / bc2s + eps);
+        p[i] = pn;
+        if constexpr (EMA) ema.ema[i] = ema_fold(ec, ema.ema[i], pn);
         if (zero_grad) g[i] = 0.f;
     }
+    ema_end<EMA>(ema, te);
 }
 __global__ void step_inc_kernel(float* step) { *step += 1.f; }
 
+template <bool EMA>
 __global__ void adadelta_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ v, float* __restrict__ u,
-                                size_t n, float lr, float rho, float eps, float gscale, int zero_grad, uint64_t* __restrict__ counter, uint64_t counter_add) {
+                                size_t n, float lr, float rho, float eps, float gscale, int zero_grad, uint64_t* __restrict__ counter, uint64_t counter_add,
+                                MpgEma ema) {
     if (counter != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *counter += counter_add;
+    uint32_t t = 0;
+    const EmaCoef ec = ema_begin<EMA>(ema, t);
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
@@ -62,9 +145,12 @@ __global__ void adadelta_kernel(float* __restrict__ p, float* __restrict__ g, fl
         const float d = sqrtf(u[i] + eps) / sqrtf(vi + eps) * gi;
         v[i] = vi;
         u[i] = rho * u[i] + (1.f - rho) * d * d;
-        p[i] -= lr * d;
+        const float pn = p[i] - lr * d;
+        p[i] = pn;
+        if constexpr (EMA) ema.ema[i] = ema_fold(ec, ema.ema[i], pn);
         if (zero_grad) g[i] = 0.f;
     }
+    ema_end<EMA>(ema, t);
 }
 
 // out[i] = mean + std * z_i, z ~ N(0, 1): counter-based (two hashes of (seed, tag, pair index) -> Box-Muller, one pair of
@@ -115,14 +201,56 @@ __global__ __launch_bounds__(256) void normal_rank_mask_kernel(float* __restrict
 }
 
 inline int nblocks(uint64_t n) { return (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048); }
+// The averaged launches: at most one workgroup per CU of an MI355X.  Every workgroup arrives once on the ticket, the arrivals on
+// one word are served one after the other, and the launch ends with the last: over G's 361 123 parameters (1411 workgroups under
+// nblocks) the launch took 19.2 us against 4.1 us without the average, 9.2 us capped at 512 workgroups, 7.0 us at 256 or 128,
+// 9.1 us at 64 (too few waves for the loop's loads).  The elements' arithmetic does not depend on the grid.
+constexpr int EMA_MAX_BLOCKS = 256;
+template <bool EMA>
+inline int nblocks_for(uint64_t n) { return EMA && nblocks(n) > EMA_MAX_BLOCKS ? EMA_MAX_BLOCKS : nblocks(n); }
+
+// an MpgEma block the averaged entry points take (n: the launch's element count)
+bool ema_args_ok(const MpgEma* a, uint64_t n) {
+    if (a == nullptr || a->ema == nullptr || a->state == nullptr || n == 0) return false;
+    return a->beta >= 0.f && a->beta < 1.f && a->start >= 0;      // (a NaN fails both comparisons)
+}
+
+template <bool EMA>
+int rmsprop_launch(float* p, float* g, float* v, uint64_t n, float lr, float alpha, float eps, float gscale, int zero_grad,
+                   uint64_t* counter, uint64_t counter_add, const MpgEma& ema, void* stream) {
+    hipLaunchKernelGGL(rmsprop_kernel<EMA>, dim3(nblocks_for<EMA>(n)), dim3(256), 0, (hipStream_t)stream, p, g, v, (size_t)n, lr, alpha,
+                       eps, gscale, zero_grad, counter, counter_add, ema);
+    return (int)hipGetLastError();
+}
+
+template <bool EMA>
+int adam_launch(float* p, float* g, float* m, float* v, float* step, uint64_t n, float lr, float beta1, float beta2, float eps,
+                float weight_decay, float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, const MpgEma& ema, void* stream) {
+    hipLaunchKernelGGL(adam_kernel<EMA>, dim3(nblocks_for<EMA>(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, step, (size_t)n, lr,
+                       beta1, beta2, eps, weight_decay, gscale, zero_grad, counter, counter_add, ema);
+    hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
+    return (int)hipGetLastError();
+}
+
+template <bool EMA>
+int adadelta_launch(float* p, float* g, float* v, float* u, uint64_t n, float lr, float rho, float eps, float gscale, int zero_grad,
+                    uint64_t* counter, uint64_t counter_add, const MpgEma& ema, void* stream) {
+    hipLaunchKernelGGL(adadelta_kernel<EMA>, dim3(nblocks_for<EMA>(n)), dim3(256), 0, (hipStream_t)stream, p, g, v, u, (size_t)n, lr, rho,
+                       eps, gscale, zero_grad, counter, counter_add, ema);
+    return (int)hipGetLastError();
+}
 }  // namespace
 
 extern "C" int mpg_rmsprop(float* p, float* g, float* v, uint64_t n, float lr, float alpha, float eps,
                            float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, void* stream) {
     if (n == 0) return counter != nullptr ? -1 : 0;
-    hipLaunchKernelGGL(rmsprop_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, v, (size_t)n, lr, alpha,
-                       eps, gscale, zero_grad, counter, counter_add);
-    return (int)hipGetLastError();
+    return rmsprop_launch<false>(p, g, v, n, lr, alpha, eps, gscale, zero_grad, counter, counter_add, MpgEma{}, stream);
+}
+
+extern "C" int mpg_rmsprop_ema(float* p, float* g, float* v, uint64_t n, float lr, float alpha, float eps,
+                               float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, const MpgEma* ema, void* stream) {
+    if (!ema_args_ok(ema, n)) return -1;
+    return rmsprop_launch<true>(p, g, v, n, lr, alpha, eps, gscale, zero_grad, counter, counter_add, *ema, stream);
 }
 
 extern "C" int mpg_adam(float* p, float* g, float* m, float* v, float* step, uint64_t n, float lr, float beta1,
@@ -130,18 +258,35 @@ extern "C" int mpg_adam(float* p, float* g, float* m, float* v, float* step, uin
                         void* stream) {
     if (n == 0) return counter != nullptr ? -1 : 0;
     if (step == nullptr) return -1;
-    hipLaunchKernelGGL(adam_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, step, (size_t)n, lr,
-                       beta1, beta2, eps, weight_decay, gscale, zero_grad, counter, counter_add);
-    hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
-    return (int)hipGetLastError();
+    return adam_launch<false>(p, g, m, v, step, n, lr, beta1, beta2, eps, weight_decay, gscale, zero_grad, counter, counter_add,
+                              MpgEma{}, stream);
+}
+
+extern "C" int mpg_adam_ema(float* p, float* g, float* m, float* v, float* step, uint64_t n, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, float gscale, int zero_grad, uint64_t* counter,
+                            uint64_t counter_add, const MpgEma* ema, void* stream) {
+    if (!ema_args_ok(ema, n) || step == nullptr) return -1;
+    return adam_launch<true>(p, g, m, v, step, n, lr, beta1, beta2, eps, weight_decay, gscale, zero_grad, counter, counter_add,
+                             *ema, stream);
 }
 
 extern "C" int mpg_adadelta(float* p, float* g, float* v, float* u, uint64_t n, float lr, float rho, float eps,
                             float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, void* stream) {
     if (n == 0) return counter != nullptr ? -1 : 0;
-    hipLaunchKernelGGL(adadelta_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, v, u, (size_t)n, lr, rho,
-                       eps, gscale, zero_grad, counter, counter_add);
-    return (int)hipGetLastError();
+    return adadelta_launch<false>(p, g, v, u, n, lr, rho, eps, gscale, zero_grad, counter, counter_add, MpgEma{}, stream);
+}
+
+extern "C" int mpg_adadelta_ema(float* p, float* g, float* v, float* u, uint64_t n, float lr, float rho, float eps,
+                                float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, const MpgEma* ema, void* stream) {
+    if (!ema_args_ok(ema, n)) return -1;
+    return adadelta_launch<true>(p, g, v, u, n, lr, rho, eps, gscale, zero_grad, counter, counter_add, *ema, stream);
+}
+
+extern "C" int mpg_ema_update_host(float* e, const float* p_new, uint64_t n, uint32_t t, float beta, int start, int warmup) {
+    if (e == nullptr || p_new == nullptr || n == 0 || !(beta >= 0.f && beta < 1.f) || start < 0) return -1;
+    const EmaCoef c = ema_coef(t, beta, start, warmup);
+    for (uint64_t i = 0; i < n; ++i) e[i] = ema_fold(c, e[i], p_new[i]);
+    return 0;
 }
 
 extern "C" int mpg_normal(float* out, uint64_t n, const uint64_t* seed, uint32_t tag, float mean, float std, void* stream) {

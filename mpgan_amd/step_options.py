@@ -140,6 +140,77 @@ class Schedule(DeviceWords):
         self.batch_ndx = int(group.get(self.KEY, 0))
 
 
+class Ema:
+    """The averaged generator of ``TrainStep(ema=...)``: an exponential moving average of G's weights, folded inside G's optimizer
+    launch (``mpg_*_ema``; include/mpgan_amd.h states the rule).  Exactly one of ``beta`` -- the decay per G
+    step, in [0, 1) -- and ``kimg`` -- StyleGAN's parametrisation: the average's half-life in thousands of jets,
+    ``beta = 0.5 ** (jets per G step / (1000 * kimg))``, computed once on the host in fp64 and rounded to fp32 (``beta_for``).
+    ``start``: G steps before averaging begins -- until then the average follows the weights.  ``warmup``: the decay ramps up as
+    ``min(beta, (1 + k) / (10 + k))`` over the k averaged steps so far, so that the early average forgets the starting weights."""
+
+    def __init__(self, beta: Optional[float] = None, kimg: Optional[float] = None, start: int = 0, warmup: bool = False):
+        if (beta is None) == (kimg is None):
+            raise ValueError(f"Ema: give exactly one of beta and kimg, got beta = {beta!r}, kimg = {kimg!r}")
+        if beta is not None and (isinstance(beta, bool) or not 0.0 <= float(beta) < 1.0):      # (a NaN fails both comparisons)
+            raise ValueError(f"Ema: beta must lie in [0, 1), got {beta!r}")
+        if kimg is not None and (isinstance(kimg, bool) or not float(kimg) > 0.0):
+            raise ValueError(f"Ema: kimg must be > 0, got {kimg!r}")
+        if isinstance(start, bool) or not isinstance(start, int) or not 0 <= start <= 0x7FFFFFFF:
+            raise ValueError(f"Ema: start must be an integer >= 0 (and below 2^31), got {start!r}")
+        self.beta = None if beta is None else float(beta)
+        self.kimg = None if kimg is None else float(kimg)
+        self.start, self.warmup = start, bool(warmup)
+
+    def beta_for(self, batch_size: Optional[int]) -> float:
+        """The decay per G step as the kernel takes it: an fp32 value held by a Python float.  ``batch_size``: the jets one G
+        step consumes (all ranks together); only ``kimg`` needs it."""
+        if self.beta is not None:
+            return _f32(self.beta)
+        if batch_size is None or batch_size < 1:
+            raise ValueError(f"Ema(kimg = {self.kimg}): the decay depends on the batch size, got {batch_size!r}")
+        beta = _f32(0.5 ** (batch_size / (1000.0 * self.kimg)))
+        if not 0.0 <= beta < 1.0:      # (a half-life so long that the decay rounds to 1 in fp32: the average would never move)
+            raise ValueError(f"Ema(kimg = {self.kimg}) at {batch_size} jets per step gives a decay of {beta} in fp32, outside [0, 1)")
+        return beta
+
+    def __repr__(self):
+        which = f"beta={self.beta}" if self.beta is not None else f"kimg={self.kimg}"
+        return f"Ema({which}, start={self.start}, warmup={self.warmup})"
+
+
+class EmaState(DeviceWords):
+    """The averaged generator's state, in G's file: the average itself and its two words (t, ticket) are what an iteration
+    moves; the file carries ``{t, beta, start, warmup}`` -- the average's values travel as ``G_ema_<epoch>.pt``
+    (``checkpoint.save_models`` / ``load_ema``).  Loading sets the average to the weights as they stand (the loaded ones, after
+    ``checkpoint.load_models``) until ``load_ema`` brings the saved average; a file without the key also restarts t at 0.
+    ``beta``, ``start`` and ``warmup`` are the step's own, as built; the saved ones are a record."""
+    KEY = "mpgan_amd_ema"
+
+    def __init__(self, flat: torch.Tensor, ema: torch.Tensor, state: torch.Tensor, beta: float, start: int, warmup: bool):
+        super().__init__([ema, state])
+        self.flat, self.ema, self.state = flat, ema, state
+        self.beta, self.start, self.warmup = beta, start, warmup
+
+    @property
+    def t(self) -> int:
+        """Averaged G steps counted so far (reads the word: synchronises)."""
+        return int(self.state[0].item())
+
+    def restart(self, t: int = 0):
+        """The average set to the weights as they stand, the step word to ``t``, the ticket to 0."""
+        if not 0 <= int(t) <= 0xFFFFFFFF:
+            raise ValueError(f"saved averaged-generator state counts {t} steps: not a 32-bit count")
+        self.ema.copy_(self.flat)
+        self.state.copy_(torch.tensor([int(t), 0], dtype=torch.int64).to(torch.uint32))
+
+    def save(self, group):
+        group[self.KEY] = {"t": self.t, "beta": self.beta, "start": self.start, "warmup": self.warmup}
+
+    def load(self, group):
+        ent = group.get(self.KEY)
+        self.restart(0 if ent is None else int(ent["t"]))
+
+
 class AdaController:
     """The adaptive augmentation probability (``Augment.adaptive_prob``), in D's file: one launch behind the D
     step's head (``update``) adds the signs of D(real) - mid to ``state`` = (sign sum, D steps counted) and, every ``interval`` D

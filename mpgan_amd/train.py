@@ -20,6 +20,8 @@ The augmentation probability can follow the discriminator (``Augment(adaptive_pr
 ``--adaptive-prob``): ADA's rule on D's outputs for the real jets, one launch behind D's head (``ops.ada_update``).
 The training data can live on the device as well (``TrainStep(loader=data.DeviceJetLoader(...))``): the batch is then gathered by
 one launch at the top of the iteration, inside the capture, in the order of a keyed shuffle.
+An averaged generator (``TrainStep(ema=Ema(...))``; Yazici et al. 2019, StyleGAN's ``G_ema``) is kept by G's optimizer launch
+itself -- two more memory streams in its loop -- and handed out as a module by ``ema_generator()``.
 
 Two pieces of work the reference does and throws away are not done (results-neutral, SURVEY.md
 section 3.1): the D step does not back-propagate into G (its gradients are zeroed before use,
@@ -31,6 +33,7 @@ captured into hipGraphs (three segments, split at the two gradient all-reduces) 
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import os
 from typing import Optional
@@ -40,8 +43,8 @@ from torch import nn
 
 from . import _lib, ops, dist as mdist
 from .mpgan import MPGenerator, MPDiscriminator
-from .step_options import (ADA_DEFAULTS, AUG_SITES, AdaController, Augment, Augmenter, DeviceWords, LabelDraw, Schedule,  # noqa: F401
-                           SeedState, ada_rule, effective_targets)
+from .step_options import (ADA_DEFAULTS, AUG_SITES, AdaController, Augment, Augmenter, DeviceWords, Ema, EmaState, LabelDraw,  # noqa: F401
+                           Schedule, SeedState, ada_rule, effective_targets)
 
 LR = {  # setup_training.py:848-872 (lr_disc, lr_gen) per jet type for model = mpgan
     "g": (3e-5, 1e-5), "t": (6e-5, 2e-5), "q": (1.5e-5, 0.5e-5),
@@ -110,9 +113,14 @@ class FlatParams:
     "adadelta" -- the three choices of ``setup_training.optimizers`` (setup_training.py:1511-1523), each ONE fused
     launch over the flat buffer.  ``state_dict()`` / ``load_state_dict()`` speak the matching ``torch.optim``
     class's own format, so the reference's ``*_optim_<epoch>.pt`` files (train.py:534-535, reloaded at
-    setup_training.py:1525-1535) are read and written as they are."""
+    setup_training.py:1525-1535) are read and written as they are.
 
-    def __init__(self, module: nn.Module, optimizer: str = "rmsprop", betas=(0.9, 0.999), weight_decay: float = 5e-4):
+    ``ema`` (a ``step_options.Ema``; ``batch_size``: the jets one step consumes, which ``Ema(kimg=...)`` needs): the launch also
+    folds the new parameters into their exponential moving average ``self.ema`` (``mpg_*_ema``); ``self.ema_state`` holds its
+    step word and the launch's ticket."""
+
+    def __init__(self, module: nn.Module, optimizer: str = "rmsprop", betas=(0.9, 0.999), weight_decay: float = 5e-4,
+                 ema: Optional[Ema] = None, batch_size: Optional[int] = None):
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         # Only what is TRAINED goes into the flat buffers: frozen parameters (spectral norm's power-iteration vectors,
@@ -149,6 +157,15 @@ class FlatParams:
         self.n = n
         self.lr = None  # last learning rate used (for state_dict's param_groups)
         self.carried = []   # the carried entries (step_options.py) that travel with this optimizer's state dict; TrainStep fills it
+        # the averaged parameters: a copy of ``flat`` to start from, the words (t, ticket) and the block the launch takes
+        self.ema = self.ema_state = self._ema_block = self.ema_carried = None
+        if ema is not None:
+            beta = ema.beta_for(batch_size)
+            self.ema = self.flat.clone()
+            self.ema_state = torch.zeros(2, device=dev, dtype=torch.uint32)
+            self._ema_block = _lib.MpgEma(C.c_void_p(self.ema.data_ptr()), C.c_void_p(self.ema_state.data_ptr()), beta, ema.start,
+                                          int(ema.warmup))
+            self.ema_carried = EmaState(self.flat, self.ema, self.ema_state, beta, ema.start, ema.warmup)
 
     def zero_grad(self):
         self.grad.zero_()
@@ -165,15 +182,17 @@ class FlatParams:
         L = _lib.lib()
         z = int(zero_grad)
         cnt, add = (None, 0) if advance_seed is None else (vp(advance_seed), ops.SEED_STEP)
+        # (the averaged entry point takes the same arguments with the MpgEma block in front of the stream)
+        name = "mpg_" + self.optimizer + ("" if self._ema_block is None else "_ema")
+        tail = (st,) if self._ema_block is None else (C.byref(self._ema_block), st)
         if self.optimizer == "rmsprop":
-            _lib.check(L.mpg_rmsprop(vp(self.flat), vp(self.grad), vp(self.sq), self.n, lr, 0.99, 1e-8, gscale, z, cnt, add, st),
-                       "mpg_rmsprop")
+            args = (vp(self.flat), vp(self.grad), vp(self.sq), self.n, lr, 0.99, 1e-8, gscale, z, cnt, add)
         elif self.optimizer == "adam":
-            _lib.check(L.mpg_adam(vp(self.flat), vp(self.grad), vp(self.aux), vp(self.sq), vp(self.step_count), self.n,
-                                  lr, self.betas[0], self.betas[1], 1e-8, self.weight_decay, gscale, z, cnt, add, st), "mpg_adam")
+            args = (vp(self.flat), vp(self.grad), vp(self.aux), vp(self.sq), vp(self.step_count), self.n,
+                    lr, self.betas[0], self.betas[1], 1e-8, self.weight_decay, gscale, z, cnt, add)
         else:
-            _lib.check(L.mpg_adadelta(vp(self.flat), vp(self.grad), vp(self.sq), vp(self.aux), self.n, lr, 0.9, 1e-6,
-                                      gscale, z, cnt, add, st), "mpg_adadelta")
+            args = (vp(self.flat), vp(self.grad), vp(self.sq), vp(self.aux), self.n, lr, 0.9, 1e-6, gscale, z, cnt, add)
+        _lib.check(getattr(L, name)(*args, *tail), name)
         if not (self.flat.is_cuda and torch.cuda.is_current_stream_capturing()):  # a capture records the launch, it does not run it
             self._host_steps += 1
 
@@ -372,14 +391,18 @@ class TrainStep:
     say for ``batch_ndx`` (``start_epoch()`` where the reference's ``for batch_ndx, ...`` begins); ``last_ran`` names what ran.
     ``track_epoch_losses``: the epoch's loss sums on the device, read by ``epoch_losses()``.  ``label_smoothing`` / ``label_noise``:
     calc_D_loss's two options (train.py:341-363) for ``og`` / ``ls`` -- ``ls`` + smoothing in the reference's [B, B] broadcast
-    form, ``og`` + smoothing refused as the reference's BCELoss refuses it, ``w`` / ``hinge`` untouched by either."""
+    form, ``og`` + smoothing refused as the reference's BCELoss refuses it, ``w`` / ``hinge`` untouched by either.
+    ``ema`` (``step_options.Ema``): an exponential moving average of G's weights, folded by G's optimizer launch (so it moves on
+    the batches that train G and on no other; identical on every rank, as the weights are); ``ema_generator()`` hands it out as
+    a module, ``fG.ema`` / ``fG.ema_state`` are its buffers."""
 
     def __init__(self, G: nn.Module, D: nn.Module, batch_size: int, num_particles: int, latent: int = 32,
                  lr_disc: float = 3e-5, lr_gen: float = 1e-5, noise_std: float = 0.2, use_graphs: bool = True,
                  process_group=None, world_size: int = 1, batch_real_fake: bool = True, loss: str = "ls",
                  optimizer: str = "rmsprop", betas=(0.9, 0.999), gp_lambda: float = 0.0,
                  graph_collectives: Optional[bool] = None, augment=None, loader=None, num_critic: int = 1, num_gen: int = 1,
-                 track_epoch_losses: bool = False, label_smoothing: bool = False, label_noise: float = 0.0):
+                 track_epoch_losses: bool = False, label_smoothing: bool = False, label_noise: float = 0.0,
+                 ema: Optional[Ema] = None):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
         self.dev = dev = next(G.parameters()).device
@@ -430,7 +453,11 @@ class TrainStep:
         # the default keeps the all-reduces as ordinary calls between three graph segments.
         self.graph_collectives = bool(graph_collectives) and process_group is not None
         self.state = ops.dev_state(dev)
-        self.fG = FlatParams(G, optimizer, betas)
+        if ema is not None and not isinstance(ema, Ema):
+            raise TypeError(f"ema must be a step_options.Ema, got {type(ema).__name__}")
+        # (Ema(kimg=...): the half-life counts the jets of all ranks)
+        self.fG = FlatParams(G, optimizer, betas, ema=ema, batch_size=batch_size * world_size)
+        self._ema_twin = None        # (``ema_generator`` builds it on first use)
         self.fD = FlatParams(D, optimizer, betas)
         self._schedule = Schedule()      # (the schedule's batch index: saved with G's optimizer state, see ``batch_ndx``)
         self._seed = None
@@ -528,6 +555,8 @@ class TrainStep:
         self.fD.carried = [c for c in (self._ada,) if c is not None]
         if self.epoch_sums is not None:
             self.fG.carried.append(DeviceWords(self.epoch_sums.values()))
+        if self.fG.ema_carried is not None:      # (the average and its words: the warm-up of ``capture`` puts both back)
+            self.fG.carried.append(self.fG.ema_carried)
         # a device-resident data set (data.DeviceJetLoader): its feed launch is the first thing of every iteration
         self.loader = None
         if loader is not None:
@@ -1003,6 +1032,36 @@ class TrainStep:
                 self._refresh_packed(self.D)
                 self._refresh_packed(self.G)
             self._seen_versions = seen
+
+    def ema_generator(self) -> nn.Module:
+        """The averaged generator as a module of G's class with G's state-dict keys, in eval mode: its trained parameters are
+        views into ``fG.ema``, everything else (buffers; frozen parameters: spectral norm's u / v, batch norm's running
+        statistics) is copied from G by every call, and its packed weight images are rebuilt by every call -- the optimizer
+        launch writes the average behind autograd's back.  Take it for ``gen.JetSampler``, ``gen.generate_jets``,
+        ``evaluation.evaluate_generator`` and ``checkpoint.save_models(..., G_ema=)``.  The twin is built once and every call
+        returns the same object; it does not synchronise.  Once further steps have run, call it AGAIN before sampling: the
+        parameters follow by themselves, the weight images only through this call."""
+        if self.fG.ema is None:
+            raise RuntimeError("TrainStep was built without ema")
+        fG = self.fG
+        if self._ema_twin is None:
+            twin = copy.deepcopy(self.G)
+            ps = list(twin.parameters())
+            for (off, k, shape), i in zip(fG._spans, fG._trained_idx):
+                ps[i].data = fG.ema[off:off + k].view(shape)
+                ps[i].grad = None
+            self._ema_twin = twin
+        twin = self._ema_twin
+        with torch.no_grad():
+            for dst, src in zip(twin.buffers(), self.G.buffers()):
+                dst.copy_(src)
+            for dst, src in zip(twin.parameters(), self.G.parameters()):
+                if not src.requires_grad:
+                    dst.copy_(src)
+        twin.eval()
+        if self.dev.type == "cuda":
+            self._refresh_packed(twin)
+        return twin
 
     def check_range(self):
         """Raise ``FloatingPointError`` if the run has left the numeric range of the fused path (fp16 operands

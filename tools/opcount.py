@@ -14,6 +14,8 @@ AUG = train.Augment(aug_r90=True, aug_f=True, aug_t=True, aug_s=True, aug_prob=0
 # (OPC_SN=1: spectral norm in G and D, counted twice -- ops.OPTIONS["sn_fused"] on, then off: the grouped power-iteration launch and
 # the fused edge kernels against a launch per wrapped layer and the un-fused route)
 SN = bool(os.environ.get("OPC_SN"))
+# (OPC_EMA=1: the averaged generator, folded by G's optimizer launch -- the default step's counts, launch for launch)
+EMA = train.Ema(kimg=10) if os.environ.get("OPC_EMA") else None
 
 
 def count(title):
@@ -22,7 +24,7 @@ def count(title):
         G, D = train.default_gapt(30, device=dev)
     else:
         G, D = train.default_mpgan(30, device=dev, spectral_norm_gen=SN, spectral_norm_disc=SN)
-    ts = train.TrainStep(G, D, BATCH, 30, latent=64 if os.environ.get("OPC_GAPT") else 32, use_graphs=False, augment=AUG)
+    ts = train.TrainStep(G, D, BATCH, 30, latent=64 if os.environ.get("OPC_GAPT") else 32, use_graphs=False, augment=AUG, ema=EMA)
     data, labels = synthetic_jets(BATCH, 30, seed=1, dist="gluon")
     ts.set_batch(data.to(dev), labels.to(dev))
     for _ in range(3): ts.step()

@@ -1,7 +1,7 @@
 """What one option of the captured training iteration costs next to the step without it, on one GPU.  One JSON object per line on
 stdout and in --out.
 
-    python tools/step_option_bench.py --option {labels,ada,critic,sn} [--reps 10] [--out profiles/<option>_bench.jsonl]
+    python tools/step_option_bench.py --option {labels,ada,critic,sn,ema} [--reps 10] [--out profiles/<option>_bench.jsonl]
 
 MPGAN at N = 30, B = 256, the captured iteration, one process.  Two steps over the same weights and batch -- a baseline and the
 same with the option on -- and, where the option adds one launch to the D segment, that launch on its own outside any graph:
@@ -15,12 +15,15 @@ critic   baseline: the default step.  Option: ``num_critic=5`` (--num-critic).  
 sn       three steps: a default_step (for scale), and spectral norm in G and D with ``ops.OPTIONS["sn_fused"]`` off (b
          sn_unfused_step) and on (c sn_fused_step).  Held to: the median of (c) is not above the median of (b).
 
+ema      baseline: the default step.  Option: ``ema=Ema(kimg=10)`` -- G's optimizer launch also folds the averaged generator; no
+         launch is added, so there is no lone launch to time.  Rows: a default_step, b ema_step.
+
 Every ``step()`` and every lone launch sits between two HIP events of its own -- in all rows alike, so that what an event pair
 costs cancels between them.  A repetition is --batches steps of each kind (critic: two full cycles of the schedule) taken
 alternately, then as many lone launches; the rows are the means within a repetition, reported as median / min / max over --reps
 repetitions behind a warm-up that captures every graph.  No speed claim is made.  The last line states what the option is held to.
 labels, ada: (b) - (a) is at most the run-to-run spread of (a) (max - min of its repetitions) plus (c).  critic: (c) within
-the spread of (a), and (b) <= (a).
+the spread of (a), and (b) <= (a).  ema: (b) - (a) is at most the run-to-run spread of (a).
 """
 import argparse
 import json
@@ -103,6 +106,12 @@ def _critic_condition(med, us, rows):
             "d_only_le_default": bool(d_only <= a)}
 
 
+def _ema_condition(med, us, rows):
+    diff = med[rows[1]] - med[rows[0]]
+    spread = float(np.max(us[rows[0]]) - np.min(us[rows[0]]))
+    return {"row": "condition", "ema_minus_default_us": diff, "spread_default_us": spread, "within_spread": bool(diff <= spread)}
+
+
 # option -> baseline step's arguments, option step's arguments, the lone launch (or None), row names, fields of every row, the
 # condition line, fields that close the condition line
 OPTIONS = {
@@ -117,6 +126,9 @@ OPTIONS = {
     "critic": dict(base=lambda a: {}, opt=lambda a: dict(num_critic=a.num_critic), launch=None,
                    rows=("a default_step", "b d_only_replay", "c dg_replay", "d mean_per_batch"),
                    fields=lambda a, opt: {"num_critic": a.num_critic}, condition=_critic_condition, tail=lambda opt: {}),
+    "ema": dict(base=lambda a: {}, opt=lambda a: dict(ema=train.Ema(kimg=10)), launch=None, rows=("a default_step", "b ema_step"),
+                fields=lambda a, opt: {"ema_kimg": 10, "ema_beta": opt.fG.ema_carried.beta}, condition=_ema_condition,
+                tail=lambda opt: {"ema_t": opt.fG.ema_carried.t}),
 }
 
 
@@ -199,7 +211,8 @@ def main():
                 us[r].append(float(np.mean(ts)))
         else:
             us[rows[1]].append(float(np.mean(by_kind[("D", "G")])))
-            us[rows[2]].append(float(np.mean([timed(launch) for _ in range(batches)])))
+            if launch:
+                us[rows[2]].append(float(np.mean([timed(launch) for _ in range(batches)])))
     med = {}
     for name, v in us.items():
         med[name] = float(np.median(v))
