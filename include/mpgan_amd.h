@@ -313,6 +313,54 @@ int mpg_edge_dw(const MpgEdgeDw* p, void* stream);
  * in the same order as mpg_edge_dw's own reduction + mpg_splitk_reduce_group. */
 int mpg_splitk_reduce_group_dw(const MpgReduceJob* jobs, int n, const MpgEdgeDw* p, void* stream);
 
+/* ---- the edge network on the k-nearest-neighbour graph's own rows ---------------------------------
+ * mpg_knn_edge_fwd: replaces MPLayer._getA_knn's gather + self.fe(A) + mask multiply + sum/mean for fully_connected=False
+ * (mpgan/model.py:319-381, :256-267) on the B*N*k edge ROWS the reference builds there -- not on all N*N pairs with the neighbour
+ * bit as a factor, as mpg_edge_fwd does with MpgEdgeFwd.nbr.  Row (b, i, r), global index (b N + i) k + r, pairs receiver i with
+ * the r-th set bit (ascending sender index) of nbr[(b N + i) ceil(N/32) ..] as mpg_knn_sets writes them:
+ *   agg[b,i,:] = agg_scale * sum_{r < k} mask[b, j(i, r)] * fe([x_i ; x_j(i, r)])     (rows added in ascending r, no atomics)
+ * a, c, the W2 / W3 images, biases, scales, product form (three fp16 terms) and dropout draws (keyed by the DENSE edge row
+ * (b N + i) N + j) are those of mpg_edge_fwd: a dense and a sparse launch of one call keep the same elements.
+ * A workgroup takes RW consecutive receivers of a jet (RW * k rows in tiles of 32; RW * k * 784 bytes of LDS <= 160 KiB, error -6).
+ * With E1 != NULL it parks, row-major and in fp32, what the backward and the weight-gradient GEMMs read: E1 [B*N*k, 96] and
+ * E2 [B*N*k, 160] = the inputs of fe.net.1 / fe.net.2 as the reference has them (dropout scale included; rows of zero-masked
+ * senders are zero), and sign3 [B*N*k][6][2] 16-bit words: bit 4g + t of word (tile m, lane half h) set <=> Z3[32m + 8g + 4h + t] <= 0.
+ * N <= 192 (mpg_knn_sets), 0 < k <= N. */
+typedef struct MpgKnnEdgeFwd {
+    const float* a; const float* c; int ld_ac;   /* as MpgEdgeFwd                                    */
+    const float* mask;                           /* [B*N] or NULL                                    */
+    const unsigned int* nbr;                     /* [B*N][ceil(N/32)] from mpg_knn_sets (required)   */
+    const void* W2img; const void* W3img;        /* the fp16 images of MpgEdgeFwd                    */
+    const float* b2; const float* b3;
+    float* agg;                                  /* [B*N, 192]                                       */
+    int B, N, k, RW;
+    float alpha, agg_scale;
+    const uint64_t* seed; uint32_t tag_base, thr; float dscale;
+    float* E1; float* E2; unsigned short* sign3; /* parked for the backward: all three or none       */
+} MpgKnnEdgeFwd;
+int mpg_knn_edge_fwd(const MpgKnnEdgeFwd* p, void* stream);
+
+/* mpg_knn_edge_bwd: autograd backward of the same span (the backward of mpgan/model.py:256-267 and of the gather of :319-381),
+ * data path, from dagg and what mpg_knn_edge_fwd parked.  Per row: dZ3, dZ2 = W3^T dZ3, dZ1 = W2^T dZ2 through the parked gates
+ * and the regenerated dropout keeps (W3Timg / W2Timg as MpgEdgeBwd's; three fp16 terms, the gradient split hi + lo in a
+ * power-of-two unit per row).  dZ1 [B*N*k, 96] is always written (scratch of the launch), dZ2 [B*N*k, 160] and dZ3 [B*N*k, 192]
+ * when non-NULL (both or none): with E1 / E2 they are the operands of the weight-gradient GEMMs of fe.net.1 / fe.net.2; rows
+ * of zero-masked senders are zero.  A second kernel of the same call then writes dadc [B*N, 192] = da | dc:
+ *   da[b,i,:] = sum_{r < k} dZ1(b, i, r)  in ascending r;   dc[b,j,:] = sum over the receivers i that list j, in ascending i
+ * (it walks column j of the bit words) -- fixed orders, no atomics. */
+typedef struct MpgKnnEdgeBwd {
+    const float* mask; const unsigned int* nbr;
+    const void* W3Timg; const void* W2Timg;
+    const float* dagg; int ld_dagg;              /* [B*N, >= 192], row stride ld_dagg                */
+    int B, N, k, RW;
+    float alpha, agg_scale;
+    const uint64_t* seed; uint32_t tag_base, thr; float dscale;
+    const float* E1; const float* E2; const unsigned short* sign3;   /* from mpg_knn_edge_fwd       */
+    float* dZ1; float* dZ2; float* dZ3;
+    float* dadc;
+} MpgKnnEdgeBwd;
+int mpg_knn_edge_bwd(const MpgKnnEdgeBwd* p, void* stream);
+
 /* ---- attention core of GAPT's MAB ---------------------------------------------------------------
  * mpg_attn_fwd / mpg_attn_bwd: per (jet b, head h), d = E / H:
  *     P = softmax_s( q_h k_h^T / sqrt(d)  with keys s where ignore[b,s] != 0 at -inf ),   o_h = P v_h

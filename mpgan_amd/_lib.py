@@ -87,6 +87,30 @@ class MpgEdgeDw(C.Structure):
     ]
 
 
+class MpgKnnEdgeFwd(C.Structure):
+    _fields_ = [
+        ("a", _fp), ("c", _fp), ("ld_ac", C.c_int), ("mask", _fp), ("nbr", _fp),
+        ("W2img", _fp), ("W3img", _fp), ("b2", _fp), ("b3", _fp),
+        ("agg", _fp),
+        ("B", C.c_int), ("N", C.c_int), ("k", C.c_int), ("RW", C.c_int),
+        ("alpha", C.c_float), ("agg_scale", C.c_float),
+        ("seed", _fp), ("tag_base", C.c_uint32), ("thr", C.c_uint32), ("dscale", C.c_float),
+        ("E1", _fp), ("E2", _fp), ("sign3", _fp),
+    ]
+
+
+class MpgKnnEdgeBwd(C.Structure):
+    _fields_ = [
+        ("mask", _fp), ("nbr", _fp), ("W3Timg", _fp), ("W2Timg", _fp),
+        ("dagg", _fp), ("ld_dagg", C.c_int),
+        ("B", C.c_int), ("N", C.c_int), ("k", C.c_int), ("RW", C.c_int),
+        ("alpha", C.c_float), ("agg_scale", C.c_float),
+        ("seed", _fp), ("tag_base", C.c_uint32), ("thr", C.c_uint32), ("dscale", C.c_float),
+        ("E1", _fp), ("E2", _fp), ("sign3", _fp),
+        ("dZ1", _fp), ("dZ2", _fp), ("dZ3", _fp), ("dadc", _fp),
+    ]
+
+
 class MpgReduceJob(C.Structure):
     _fields_ = [
         ("part", _fp), ("S", C.c_int), ("N", C.c_int), ("K", C.c_int), ("has_bias", C.c_int),
@@ -246,6 +270,8 @@ SIGNATURES = {
     "mpg_mab_fwd": (C.c_int, [C.POINTER(MpgMab), C.c_void_p]),
     "mpg_mab_bwd": (C.c_int, [C.POINTER(MpgMab), C.c_void_p]),
     "mpg_mab_chain_fwd": (C.c_int, [C.POINTER(MpgMabChain), C.c_void_p]),
+    "mpg_knn_edge_fwd": (C.c_int, [C.POINTER(MpgKnnEdgeFwd), C.c_void_p]),
+    "mpg_knn_edge_bwd": (C.c_int, [C.POINTER(MpgKnnEdgeBwd), C.c_void_p]),
     "mpg_knn_sets": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_void_p]),
     "mpg_rank_mask": (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_void_p]),
     "mpg_jet_order": (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_void_p]),

@@ -212,7 +212,8 @@ class MPLayer(nn.Module):
         self.delta_coords, self.delta_r = bool(delta_coords), bool(delta_r)
         self.clabels, self.mask_fne_np = int(clabels), bool(mask_fne_np)
         # fully_connected=False: every receiver aggregates over its num_knn nearest senders only (reference _getA_knn);
-        # the fused kernels still walk all N senders with the neighbour sets as a per-edge 0/1 factor
+        # the fused kernels walk all N senders with the neighbour sets as a per-edge 0/1 factor -- or, with
+        # ops.OPTIONS["knn_sparse"], the sparse kernels work on the N * num_knn rows of the sets themselves (ops.knn_sparse_route)
         self.fully_connected, self.num_knn, self.self_loops = fully_connected, int(num_knn), bool(self_loops)
         num_ef = 0   # edge features appended to [x_i ; x_j] (:169-178)
         if self.pos_diffs:
@@ -335,6 +336,9 @@ class MPLayer(nn.Module):
             packed = self._packed()
         # consecutive fused layers of a network hand each other the layer-1 node terms a | c (ops.LayerHandoff): the launch
         # that produces a layer's output rows also projects them for the layer above
+        # (a layer on the sparse k-NN route -- ops.knn_sparse_route -- takes and offers no hand-off; spectral-norm layers stay dense)
+        if ops.knn_sparse_route(nbr is not None, self.n_es, x.shape[1], self.num_knn, spectral_norm=self.spectral_norm):
+            handoff = None
         if handoff is not None:
             nxt = handoff.above
             if packed is None:   # (images packed for this call: nothing from below fits them; the layer above may still take its chain)
@@ -347,7 +351,7 @@ class MPLayer(nn.Module):
             W1, fe[0].bias, W2, fe[1].bias, W3, fe[2].bias,
             V1, fn[0].bias, V2, fn[1].bias, V3, fn[2].bias, es, xfn,
             ops.MPLayerSettings(self.sum, self.fe.leaky_relu_alpha, self.fe.dropout_p, self.training, packed, nbr, self.num_knn,
-                                self.n_es, handoff, not torch.is_grad_enabled()))
+                                self.n_es, handoff, not torch.is_grad_enabled(), not self.spectral_norm))
 
     def _folded_w1(self, W1: Tensor) -> Tensor:
         """fe.net.0.weight with the coordinate-difference columns folded into the node columns: the reference appends

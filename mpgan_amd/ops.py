@@ -19,7 +19,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import MpgGemm, MpgEdgeFwd, MpgEdgeBwd, MpgEdgeDw, MpgPackJob, MpgChain, MpgReduceJob, check
+from ._lib import MpgGemm, MpgEdgeFwd, MpgEdgeBwd, MpgEdgeDw, MpgKnnEdgeFwd, MpgKnnEdgeBwd, MpgPackJob, MpgChain, MpgReduceJob, check
 
 H1, H2, H3 = 96, 160, 192
 # Exact power-of-two operand scales of the forward products (csrc/edge_common.h): fp16 hi/lo pairs keep their 22 bits
@@ -54,6 +54,10 @@ OPTIONS = {
     # spectral-norm networks: the normalised weights of all wrapped layers of a LinearNet / an MPLayer from ONE grouped launch
     # (mpg_spectral_norm) and such MPLayers on the fused edge kernels; False = a launch per wrapped layer and MPLayer._forward_edges
     "sn_fused": os.environ.get("MPG_SN_FUSED", "1") != "0",
+    # fused MPLayers on a k-nearest-neighbour graph (fully_connected=False) on the SPARSE edge kernels (mpg_knn_edge_fwd / _bwd: the
+    # B * N * k rows of the neighbour sets) instead of the dense kernels with the neighbour bit as a factor over all N * N pairs;
+    # see ``knn_sparse_route`` for what it covers.  Off unless asked for: MPG_KNN_SPARSE=1.
+    "knn_sparse": os.environ.get("MPG_KNN_SPARSE", "0") not in ("", "0"),
 }
 NUM_CUS = 256
 # Forward products (they decide LeakyReLU signs) are split as fp16 hi/lo with the operand scales below (~2^-21 per
@@ -1063,13 +1067,22 @@ MPLayerSaved = namedtuple("MPLayerSaved", "x2 m1 ac agg h1 h2 W1 b2 b3 W2 W3 V1 
 # ... and the non-tensor state of the call that the backward needs (``ctx.cfg``)
 MPLayerCfg = namedtuple("MPLayerCfg", "B N F agg_scale alpha thr dscale tag SC f16 nq")
 # Everything ``FusedMPLayerFn.apply`` takes that is not a tensor with a gradient (see its ``forward``)
-MPLayerSettings = namedtuple("MPLayerSettings", "sum_agg alpha p_drop training packed nbr num_knn nq handoff no_grad",
-                             defaults=(None, None, 0, 0, None, False))
+MPLayerSettings = namedtuple("MPLayerSettings", "sum_agg alpha p_drop training packed nbr num_knn nq handoff no_grad sparse_ok",
+                             defaults=(None, None, 0, 0, None, False, True))
+# ... and what a call on the sparse k-NN route saves BEHIND those entries: the rows parked by ``mpg_knn_edge_fwd`` (``knn_saved``)
+KnnSaved = namedtuple("KnnSaved", "E1 E2 sign3")
 
 
 def mplayer_saved(node):
     """The saved tensors of a ``FusedMPLayerFn`` backward node (the ``grad_fn`` behind a fused MPLayer's output), by name."""
-    return MPLayerSaved(*node.saved_tensors)
+    return MPLayerSaved(*node.saved_tensors[:len(MPLayerSaved._fields)])
+
+
+def knn_saved(node):
+    """What a ``FusedMPLayerFn`` backward node of the sparse k-NN route holds beside ``mplayer_saved``: a ``KnnSaved`` (``E1`` [B*N*k, 96]
+    and ``E2`` [B*N*k, 160], the inputs of fe.net.1 / fe.net.2 row by row, ``sign3`` [B*N*k, 6, 2] int16); None on the dense routes."""
+    tail = node.saved_tensors[len(MPLayerSaved._fields):]
+    return KnnSaved(*tail) if tail else None
 
 
 # The node network's input gradients of one layer -- dz3, dz2, dz1 (at its three pre-activations) and dh0 = [dagg | dx(node path)
@@ -1178,6 +1191,127 @@ def _fill_edge_grad(e, sv, dh0, park):
     e.dagg, e.ld_dagg = _p(dh0), dh0.stride(0)
     e.sign3, e.stageE2, e.stageZ2, e.gexp = _p(sv.sign3), _p(sv.stE2), _p(park.stZ2), _p(park.gexp)
     return e
+
+
+# ---- the sparse k-NN route
+KNN_MAX_N = 192            # mpg_knn_sets' limit: six neighbour words per receiver
+KNN_STAGE_BYTES = 784      # LDS per edge row of mpg_knn_edge_fwd (192 floats + 16 bytes of padding: KNN_STAGE_LD of csrc/knn_edge_impl.h)
+KNN_LDS_BYTES = 160 * 1024
+KNN_WG_ROWS = int(os.environ.get("MPG_KNN_WG_ROWS", "128"))   # edge rows a workgroup aims for: four tiles of 32, one per wave
+KNN_PARK_ROW_BYTES = (H1 + H2) * 4 + 6 * 2 * 2   # E1, E2 in fp32 and the sign words of Z3: what the forward parks per edge row
+KNN_GRAD_ROW_BYTES = (H1 + H2 + H3) * 4          # dZ1, dZ2, dZ3 in fp32: what the backward writes per edge row
+KnnPlan = namedtuple("KnnPlan", "rows tiles RW workgroups parked_bytes grad_bytes")
+
+
+def knn_sparse_route(has_nbr, nq, N, k, *, spectral_norm=False, fused=True, double_backward=False, options=None):
+    """Does a fused MPLayer call take the sparse k-NN launches?  Only with neighbour sets, the option on, no edge scalars and k < N (k
+    = N is the fully connected layer); never a spectral-norm layer, a layer of other widths than [96, 160, 192] with two hidden node
+    layers (``fused`` False) or the double-backward route: those stay on the routes they take today.  Host only."""
+    opt = OPTIONS if options is None else options
+    return bool(has_nbr and opt["knn_sparse"] and nq == 0 and 0 < k < N <= KNN_MAX_N and fused and not spectral_norm and not double_backward)
+
+
+def knn_block_tiles(N, k, RW):
+    """The tiles of one jet under ``RW`` receivers per workgroup: (first edge row, rows) per tile, in workgroup order.  A workgroup's rows
+    -- those of its receivers, k each -- are cut into tiles of 32; the last tile of a workgroup may be short."""
+    tiles = []
+    for i0 in range(0, N, RW):
+        r0, nrows = i0 * k, min(RW, N - i0) * k
+        tiles += [(r0 + t, min(32, nrows - t)) for t in range(0, nrows, 32)]
+    return tiles
+
+
+def knn_plan(B, N, k, need_grad):
+    """What one sparse k-NN MPLayer call decides from sizes alone (no tensor, no launch), as a ``KnnPlan``: ``rows`` = N * k edge rows
+    per jet, ``tiles`` of 32 rows per jet, ``RW`` receivers per workgroup, ``workgroups`` of the launch, ``parked_bytes`` the forward
+    writes for a backward (0 without one) and ``grad_bytes`` that backward's gradient rows take.  A workgroup takes whole receivers
+    -- RW * k rows, about ``KNN_WG_ROWS`` -- and fewer when the launch would otherwise leave CUs idle (2 jets of 150: one receiver
+    each).  Raises, before any allocation, when the call would park more than 2 GiB (the dense route's bound) or k is out of range."""
+    if not (0 < k <= N <= KNN_MAX_N):
+        raise ValueError(f"knn_plan: k = {k} neighbours of N = {N} nodes (0 < k <= N <= {KNN_MAX_N})")
+    if B <= 0:
+        raise ValueError(f"knn_plan: B = {B}")
+    rw_max = max(1, min(N, min(KNN_WG_ROWS, KNN_LDS_BYTES // KNN_STAGE_BYTES) // k))
+    fill = [rw for rw in range(1, rw_max + 1) if B * -(-N // rw) >= NUM_CUS]
+    RW = max(fill) if fill else min(rw_max, -(-32 // k))   # (too few rows for every CU: at least a tile per workgroup)
+    rows = N * k
+    parked = B * rows * KNN_PARK_ROW_BYTES if need_grad else 0
+    grad = B * rows * KNN_GRAD_ROW_BYTES if need_grad else 0
+    if max(parked, grad) > 0x7fffffff:
+        raise RuntimeError(f"FusedMPLayerFn (sparse k-NN): {B} jets x {N} particles x {k} neighbours park {max(parked, grad) / 2**30:.1f} GiB "
+                           f"of edge rows for the backward, beyond 2 GiB per launch; split the batch "
+                           f"(at most {0x7fffffff // (rows * KNN_GRAD_ROW_BYTES)} jets per call at this size)")
+    return KnnPlan(rows, len(knn_block_tiles(N, k, RW)), RW, B * -(-N // RW), parked, grad)
+
+
+def _knn_fwd_desc(call, kp, k, agg, ks):
+    # ``MpgKnnEdgeFwd`` of ``call``; ``ks``: the ``KnnSaved`` to park into (entries None: nothing is parked)
+    sv, cfg, pk, seed_t = call
+    e = MpgKnnEdgeFwd()
+    e.a, e.c, e.ld_ac, e.mask, e.nbr = _p(sv.ac), _p(sv.ac, H1), 2 * H1, _p(sv.m1), _p(sv.nbr)
+    e.W2img, e.W3img, e.b2, e.b3, e.agg = pk.ptr("W2"), pk.ptr("W3"), _p(sv.b2), _p(sv.b3), _p(agg)
+    e.B, e.N, e.k, e.RW, e.alpha, e.agg_scale = cfg.B, cfg.N, k, kp.RW, cfg.alpha, cfg.agg_scale
+    e.seed, e.tag_base, e.thr, e.dscale = _p(seed_t), cfg.tag, cfg.thr, cfg.dscale
+    e.E1, e.E2, e.sign3 = _p(ks.E1), _p(ks.E2), _p(ks.sign3)
+    return e
+
+
+def _knn_forward(ctx, call, kp, k, biases, y, need_grad):
+    # The sparse route's forward launches: ``mpg_knn_edge_fwd`` on the neighbour rows, then the node network (``mpg_chain``) as
+    # ``_fwd_two_launches`` runs it.  Returns (agg, the ``KnnSaved``).
+    sv, cfg = call.sv, call.cfg
+    V, dev = cfg.B * cfg.N, sv.x2.device
+    ks = KnnSaved(None, None, None)
+    if need_grad:   # (what only a backward reads is not written without one)
+        ks = KnnSaved(torch.empty((V * k, H1), device=dev, dtype=torch.float32), torch.empty((V * k, H2), device=dev, dtype=torch.float32),
+                      torch.empty((V * k, 6, 2), device=dev, dtype=torch.int16))
+    agg = torch.empty((V, H3), device=dev, dtype=torch.float32)
+    check(_lib.lib().mpg_knn_edge_fwd(C.byref(_knn_fwd_desc(call, kp, k, agg, ks)), _stream()), "mpg_knn_edge_fwd")
+    run_chain(_fn_fwd_chain(call, _fn_fwd_layers(call, biases, y), agg))
+    return agg, ks
+
+
+def _knn_backward(ctx, call, ks, gy2, fng, tg, dx):
+    # The sparse route's backward launches: fn's input-gradient chain, ``mpg_knn_edge_bwd`` (the rows' dZ3, dZ2, dZ1, then da | dc in
+    # fixed orders), the weight gradients -- fe.net.1 / fe.net.2 from the parked rows as two more jobs of the layer's ONE grouped
+    # launch -- and dx through the existing chain.
+    sv, cfg, pk, seed_t = call
+    kp, k = ctx.knn
+    V, dev, need_w = cfg.B * cfg.N, sv.x2.device, tg.W1 is not None
+    if fng.chain is not None:
+        run_chain(fng.chain)
+    dZ1 = torch.empty((V * k, H1), device=dev, dtype=torch.float32)
+    dZ2 = torch.empty((V * k, H2), device=dev, dtype=torch.float32) if need_w else None
+    dZ3 = torch.empty((V * k, H3), device=dev, dtype=torch.float32) if need_w else None
+    dadc = torch.empty((V, 2 * H1), device=dev, dtype=torch.float32)
+    e = MpgKnnEdgeBwd()
+    e.mask, e.nbr, e.W3Timg, e.W2Timg = _p(sv.m1), _p(sv.nbr), pk.ptr("W3T"), pk.ptr("W2T")
+    e.dagg, e.ld_dagg = _p(fng.dh0), fng.dh0.stride(0)
+    e.B, e.N, e.k, e.RW, e.alpha, e.agg_scale = cfg.B, cfg.N, k, kp.RW, cfg.alpha, cfg.agg_scale
+    e.seed, e.tag_base, e.thr, e.dscale = _p(seed_t), cfg.tag, cfg.thr, cfg.dscale
+    e.E1, e.E2, e.sign3 = _p(ks.E1), _p(ks.E2), _p(ks.sign3)
+    e.dZ1, e.dZ2, e.dZ3, e.dadc = _p(dZ1), _p(dZ2), _p(dZ3), _p(dadc)
+    check(_lib.lib().mpg_knn_edge_bwd(C.byref(e), _stream()), "mpg_knn_edge_bwd")
+    sums = SlabSums(dadc[:, :H1], dadc[:, H1:], dadc)
+    if need_w:
+        acc, wb = tg.direct, WgradBatch()
+        wb.add(fng.dz3, sv.h2, out=tg.V3, bias_out=tg.c3, accumulate=acc)
+        wb.add(fng.dz2, sv.h1, out=tg.V2, bias_out=tg.c2, accumulate=acc)
+        wb.add(fng.dz1, sv.agg, out=tg.V1, out_col0=0, bias_out=tg.c1, accumulate=acc)
+        wb.add(fng.dz1, sv.xf2, out=tg.V1, out_col0=H3, accumulate=acc)
+        wb.add(sums.da, sv.x2, out=tg.W1, out_col0=0, bias_out=tg.b1, accumulate=acc)
+        wb.add(sums.dc, sv.x2, out=tg.W1, out_col0=cfg.F, accumulate=acc)
+        wb.add(dZ3, ks.E2, out=tg.W3, bias_out=tg.b3, accumulate=acc)
+        wb.add(dZ2, ks.E1, out=tg.W2, bias_out=tg.b2, accumulate=acc)
+        st = dev_state(dev)
+        side = st.wgrad_stream if acc else None
+        if side is not None:   # (as ``_weight_grads``: everything the side stream touches stays referenced until TrainStep joins it)
+            st.wgrad_keep.append((sv, ks, gy2, fng[:4], dZ1, dZ2, dZ3, dadc, list(wb.jobs)))
+            side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+            wb.flush()
+    if dx is not None:
+        run_chain(_dx_chain(call, fng.dh0, dx, dadc))
 
 
 # ---- forward
@@ -1479,7 +1613,7 @@ class FusedMPLayerFn(torch.autograd.Function):
         columns of the reference (mpgan/model.py:247-253, :297-313), one scalar per edge each; they multiply the columns
         ``W1[:, 2F : 2F + nq]`` (``Z1 = a_i + c_j + sum_q es_q w_q``) and get a gradient.  ``xfn`` [B, N, F + E]: the node
         network's view of the nodes when conditioning columns are appended to it (:270-276); ``V1`` then has E more columns."""
-        sum_agg, alpha, p_drop, training, packed, nbr, num_knn, nq, handoff, no_grad = settings
+        sum_agg, alpha, p_drop, training, packed, nbr, num_knn, nq, handoff, no_grad, sparse_ok = settings
         _chk(x, "x")
         B, N, F = x.shape
         V, dev, out_f = B * N, x.device, V3.shape[0]
@@ -1487,17 +1621,31 @@ class FusedMPLayerFn(torch.autograd.Function):
         # always off and needs_input_grad still says what the PARAMETERS want, so without the flag such a call would write
         # everything a backward reads -- sign words, 10 KB of parked fragments per block, agg, h1, h2 -- for nothing
         need_grad = any(ctx.needs_input_grad) and not no_grad
-        plan = edge_plan(B, N, es=es is not None, mask=mask is not None, need_grad=need_grad)   # (raises before any allocation or launch)
+        sparse = bool(sparse_ok and es is None and knn_sparse_route(nbr is not None, nq, N, num_knn))
+        if sparse:   # (a sparse layer takes and offers no hand-off, like a spectral-norm layer)
+            kp, handoff = knn_plan(B, N, num_knn, need_grad), None   # (raises before any allocation or launch)
+        plan = edge_plan(B, N, es=es is not None, mask=mask is not None, need_grad=need_grad and not sparse)   # (raises likewise)
         thr, dscale = drop_params(p_drop) if training else (0, 1.0)
         seed_t = seed_tensor(dev)
         agg_scale = 1.0 if sum_agg else 1.0 / (num_knn if nbr is not None else N)
-        cfg = MPLayerCfg(B, N, F, agg_scale, alpha, thr, dscale, next_tag(dev, "mplayer", thr), plan.SC, FWD_F16, nq)
+        cfg = MPLayerCfg(B, N, F, agg_scale, alpha, thr, dscale, next_tag(dev, "mplayer", thr), 1 if sparse else plan.SC, FWD_F16, nq)
         if packed is None or packed.dscale != dscale or packed.f16 != cfg.f16:  # direct callers: pack for this call
             packed = PackedMPLayer((W1, W2, W3, V1, V2, V3), F, out_f, dscale, cfg.f16)
         pk = packed.ensure()
         x2, m1, xf2 = _row_views(x, mask, xfn)
         assert V1.shape[1] == H3 + xf2.shape[1]
         ac = _node_terms(handoff.below if handoff is not None else None, pk, x2, b1, cfg)
+        if sparse:
+            h1 = torch.empty((V, V1.shape[0]), device=dev, dtype=torch.float32) if need_grad else None
+            h2 = torch.empty((V, V2.shape[0]), device=dev, dtype=torch.float32) if need_grad else None
+            sv = MPLayerSaved(x2, m1, ac, None, h1, h2, W1, b2, b3, W2, W3, V1, V2, V3, None, nbr, None, None, None, xf2, None)
+            y = torch.empty((V, out_f), device=dev, dtype=torch.float32)
+            agg, ks = _knn_forward(ctx, MPCall(sv, cfg, pk, seed_t), kp, num_knn, (c1, c2, c3), y, need_grad)
+            _leave_offers(ctx, None, x, need_grad)
+            ctx.packed, ctx.cfg, ctx.knn = pk, cfg, (kp, num_knn)
+            ctx.save_for_backward(*sv._replace(agg=agg), *ks)
+            return y.reshape(B, N, out_f)
+        ctx.knn = None
         es, wq = _edge_scalar_terms(es, W1, cfg)
         order = jet_order(m1.view(B, N)) if plan.lpt else None
         # (what only a backward reads -- the sign words of the third edge layer, the parked E2, the hidden activations, and agg for
@@ -1533,7 +1681,11 @@ class FusedMPLayerFn(torch.autograd.Function):
         fng = _taken_fn_grads(ctx, gy2) or _fn_grad_chain(ctx, gy2)
         tg, pg = _grad_targets(call, any(need_p))   # (no parameter wants one in the G step: D's weights get no update there)
         dx = torch.empty((V, F), device=dev, dtype=torch.float32) if need_x else None
-        route, sums, des = _edge_backward(ctx, call, gy2, fng, tg, dx)
+        if ctx.knn is not None:
+            _knn_backward(ctx, call, knn_saved(ctx), gy2, fng, tg, dx)
+            route, des = "knn", None
+        else:
+            route, sums, des = _edge_backward(ctx, call, gy2, fng, tg, dx)
         if need_x:
             if route == "plain":   # (not done by the data-gradient launch: its own launch)
                 run_chain(_dx_chain(call, fng.dh0, dx, *((sums.dadc,) if sums.dadc is not None else (sums.da, sums.dc))))
