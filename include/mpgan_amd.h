@@ -786,6 +786,28 @@ int mpg_ada_update(const float* out, int n_real, float mid, float target, float 
 int mpg_ada_update_host(const float* out, int n_real, float mid, float target, float step, int interval, int32_t* state,
                         float* aug_p, float* r_out);
 
+/* mpg_ada_count / mpg_ada_settle: mpg_ada_update in two launches, for data-parallel ranks that settle ONE probability from the
+ * sign sum of all their real jets.  The sum travels in the discriminator's gradient all-reduce: `slot` is one float at the tail
+ * of the flat gradient buffer (TrainStep: FlatParams(tail=1)), no collective is added.
+ * mpg_ada_count:   slot[0] = (float) s, s the count of mpg_ada_update over out[0 .. n_real) of THIS rank (an output equal to mid,
+ *                  or a NaN, counts on neither side).  A store, not an add: what the slot held is gone.  One workgroup.
+ *                  n_real < 1, n_real > 2^24, a NULL out or slot: -1.
+ * mpg_ada_settle:  s = (int32) slot[0], then the rule of mpg_ada_update from `state[0] += s` onward with n_real_total -- the real
+ *                  jets of all ranks -- in the division.  One thread.  If slot[0] is not an integer value (a NaN, an infinity, a
+ *                  fraction) or |slot[0]| > n_real_total, the collective is broken: state and *aug_p stay untouched and
+ *                  *r_out = NaN.  Refusals as mpg_ada_update's, with slot in out's place and n_real_total in n_real's.
+ * The identity: mpg_ada_update(out, n, ...) leaves the same state, *aug_p and *r_out as mpg_ada_count(out, n, mid, slot)
+ * followed by mpg_ada_settle(slot, n, ...), bit for bit.  With the outputs split over W ranks -- n = n_1 + ... + n_W <= 2^24 --
+ * the W counts added in fp32 give (float) s in any order and any association: every partial sum is an integer of magnitude
+ * <= 2^24, which fp32 holds exactly.  So every rank reads the same slot behind a SUM all-reduce and settles the same p.
+ * mpg_ada_count_host / mpg_ada_settle_host: the same bodies compiled for the host on host memory, no HIP call. */
+int mpg_ada_count(const float* out, int n_real, float mid, float* slot, void* stream);
+int mpg_ada_count_host(const float* out, int n_real, float mid, float* slot);
+int mpg_ada_settle(const float* slot, int n_real_total, float target, float step, int interval, int32_t* state, float* aug_p,
+                   float* r_out, void* stream);
+int mpg_ada_settle_host(const float* slot, int n_real_total, float target, float step, int interval, int32_t* state, float* aug_p,
+                        float* r_out);
+
 /* The keyed shuffle of a device-resident data set (csrc/shuffle.h: one body for the device and the host).
  * perm(key, epoch, i, n), 0 <= i < n <= 2^31 - 1, is a bijection of [0, n) computed from (key, epoch, i) alone -- a balanced
  * Feistel network with cycle walking, its round function the project's counter-based hash (the stream of the dropout masks, of
@@ -859,6 +881,16 @@ int mpg_label_pick_host(uint64_t key, uint64_t pos0, int64_t count, int64_t n, i
 int mpg_jets_finish(const float* feat, int ld_feat, const float* mask, int B, int N, const float* maxes, const float* norms,
                     const float* shifts, float* out, float* mask_out, uint64_t row0, int64_t total, uint64_t key, uint64_t* cursor,
                     uint64_t* seed, uint32_t* ticket, void* stream);
+
+/* mpg_jets_finish_stride: mpg_jets_finish for a rank of W data-parallel ranks that share ONE stream (gen.JetSampler(rank=,
+ * world_size=)): chunk c of the global stream goes to rank c mod W, so a rank's cursor starts at rank * B and the launch moves
+ * it by stride = W B:  *cursor += stride,  *seed = key + (new cursor / B) * 0x9E3779B97F4A7C15 (mod 2^64) -- the seed word of
+ * the rank's next chunk of the global stream.  Everything else, the row arithmetic included, is mpg_jets_finish: the caller
+ * passes each launch the row0 that lands the chunk at its place in the rank's own array.  mpg_jets_finish is this entry with
+ * stride = B.  stride < 1: -1. */
+int mpg_jets_finish_stride(const float* feat, int ld_feat, const float* mask, int B, int N, const float* maxes, const float* norms,
+                           const float* shifts, float* out, float* mask_out, uint64_t row0, int64_t total, uint64_t key,
+                           int64_t stride, uint64_t* cursor, uint64_t* seed, uint32_t* ticket, void* stream);
 
 /* ---- spectral normalisation of Linear layers (mpgan/spectral_normalization.py:29-46), grouped; csrc/spectral.hip ----------------
  * One job per wrapped layer, one workgroup per job, up to MPG_SPECTRAL_MAX_JOBS jobs per launch.  Everything is fp32 and

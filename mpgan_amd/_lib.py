@@ -319,10 +319,16 @@ SIGNATURES = {
     "mpg_label_targets": (C.c_int, [C.c_int, C.c_int, C.c_float, _fp, C.c_uint32, _fp, _fp, _fp, C.c_void_p]),
     "mpg_ada_update": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _fp, _fp, _fp, C.c_void_p]),
     "mpg_ada_update_host": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _fp, _fp, _fp]),
+    "mpg_ada_count": (C.c_int, [_fp, C.c_int, C.c_float, _fp, C.c_void_p]),
+    "mpg_ada_count_host": (C.c_int, [_fp, C.c_int, C.c_float, _fp]),
+    "mpg_ada_settle": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float, C.c_int, _fp, _fp, _fp, C.c_void_p]),
+    "mpg_ada_settle_host": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float, C.c_int, _fp, _fp, _fp]),
     "mpg_label_pick": (C.c_int, [_fp, C.c_int64, C.c_uint64, _fp, C.c_int, _fp, C.c_void_p]),
     "mpg_label_pick_host": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, _fp]),
     "mpg_jets_finish": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_uint64, C.c_int64, C.c_uint64,
                                   _fp, _fp, _fp, C.c_void_p]),
+    "mpg_jets_finish_stride": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_uint64, C.c_int64,
+                                         C.c_uint64, C.c_int64, _fp, _fp, _fp, C.c_void_p]),
     "mpg_spectral_norm": (C.c_int, [C.POINTER(MpgSpectralJob), C.c_int, C.c_int, C.c_void_p]),
     "mpg_spectral_norm_bwd": (C.c_int, [C.POINTER(MpgSpectralBwdJob), C.c_int, C.c_void_p]),
     "mpg_spectral_norm_host": (C.c_int, [C.POINTER(MpgSpectralJob), C.c_int, C.c_int]),

@@ -11,7 +11,9 @@
 // exactly as mpg_batch_feed moves its cursor (csrc/loader.hip): every workgroup reads the cursor first -- its stores' addresses
 // and its `row < total` branch depend on the value, so the read has returned -- and arrives on an agent-scope counter last; the
 // workgroup that arrives last, told by the value the add returns, writes cursor + B and the seed word of chunk (cursor + B) / B
-// and puts the counter back to zero.  Both launches are bound by latency (a chunk of 4096 jets of 30 particles moves 3.4 MB).
+// and puts the counter back to zero.  mpg_jets_finish_stride moves the cursor by `stride` instead of B: rank r of W data-parallel
+// ranks owns the chunks c = r (mod W) of the one global stream and strides by W B.  Both launches are bound by latency (a chunk
+// of 4096 jets of 30 particles moves 3.4 MB).
 #include "draws.h"
 
 constexpr uint64_t CHUNK_SEED_STEP = 0x9E3779B97F4A7C15ull;
@@ -34,8 +36,8 @@ __global__ __launch_bounds__(256) void label_pick_kernel(const float* __restrict
 
 __global__ __launch_bounds__(256) void jets_finish_kernel(const float* __restrict__ feat, int ld_feat, const float* __restrict__ mask,
                                                           int B, int N, Unnorm u, float* __restrict__ out, float* __restrict__ mask_out,
-                                                          uint64_t row0, uint64_t total, uint64_t key, uint64_t* cursor,
-                                                          uint64_t* seed, unsigned int* ticket) {
+                                                          uint64_t row0, uint64_t total, uint64_t key, uint64_t stride,
+                                                          uint64_t* cursor, uint64_t* seed, unsigned int* ticket) {
 #pragma clang fp contract(off)   // subtract, divide, multiply: three roundings, as data.unnormalise_jets makes them
     const uint64_t cur = __hip_atomic_load(cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;          // particle of the chunk
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(256) void jets_finish_kernel(const float* __restric
     __syncthreads();
     if (threadIdx.x == 0) {
         if (last_arrival(ticket)) {
-            const uint64_t next = cur + (uint64_t)B;
+            const uint64_t next = cur + stride;      // (a rank of W: W B, its next chunk of the global stream)
             __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(seed, key + (next / (uint64_t)B) * CHUNK_SEED_STEP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(cursor, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -81,10 +83,11 @@ extern "C" int mpg_label_pick_host(uint64_t key, uint64_t pos0, int64_t count, i
     return 0;
 }
 
-extern "C" int mpg_jets_finish(const float* feat, int ld_feat, const float* mask, int B, int N, const float* maxes,
-                               const float* norms, const float* shifts, float* out, float* mask_out, uint64_t row0, int64_t total,
-                               uint64_t key, uint64_t* cursor, uint64_t* seed, uint32_t* ticket, void* stream) {
-    if (B < 1 || N < 1 || total < 0 || ld_feat < 3) return -1;
+extern "C" int mpg_jets_finish_stride(const float* feat, int ld_feat, const float* mask, int B, int N, const float* maxes,
+                                      const float* norms, const float* shifts, float* out, float* mask_out, uint64_t row0,
+                                      int64_t total, uint64_t key, int64_t stride, uint64_t* cursor, uint64_t* seed, uint32_t* ticket,
+                                      void* stream) {
+    if (B < 1 || N < 1 || total < 0 || ld_feat < 3 || stride < 1) return -1;
     if (feat == nullptr || out == nullptr || cursor == nullptr || seed == nullptr || ticket == nullptr) return -1;
     if (maxes == nullptr || norms == nullptr || shifts == nullptr) return -1;
     if ((uint64_t)B * (uint64_t)N > 0x7fffffffull * 256ull) return -1;       // (the grid's x extent)
@@ -92,6 +95,13 @@ extern "C" int mpg_jets_finish(const float* feat, int ld_feat, const float* mask
     for (int f = 0; f < 3; ++f) { u.mx[f] = maxes[f]; u.nrm[f] = norms[f]; u.sh[f] = shifts[f]; }
     const unsigned int grid = (unsigned int)(((uint64_t)B * N + 255) / 256);
     hipLaunchKernelGGL(jets_finish_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feat, ld_feat, mask, B, N, u, out, mask_out,
-                       row0, (uint64_t)total, key, cursor, seed, ticket);
+                       row0, (uint64_t)total, key, (uint64_t)stride, cursor, seed, ticket);
     return (int)hipGetLastError();
+}
+
+extern "C" int mpg_jets_finish(const float* feat, int ld_feat, const float* mask, int B, int N, const float* maxes,
+                               const float* norms, const float* shifts, float* out, float* mask_out, uint64_t row0, int64_t total,
+                               uint64_t key, uint64_t* cursor, uint64_t* seed, uint32_t* ticket, void* stream) {
+    return mpg_jets_finish_stride(feat, ld_feat, mask, B, N, maxes, norms, shifts, out, mask_out, row0, total, key, (int64_t)B, cursor,
+                                  seed, ticket, stream);
 }

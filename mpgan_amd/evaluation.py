@@ -628,7 +628,8 @@ def evaluate_generator(G: torch.nn.Module, real_jets, jet_type: str, num_samples
     """Generate ``num_samples`` jets with ``gen.generate_jets`` and ``evaluate`` them against ``real_jets`` ([n, N, >=3]
     un-normalised), all on G's device.  ``sampler``: a ``gen.JetSampler`` built on ``G`` -- the generated jets are then the next
     ``num_samples`` rows of its stream (labels drawn from its table; ``labels``, ``model``, ``model_args`` and ``batch_size``
-    are not used).  ``labels`` (num_particles / N per generated jet) default to the multiplicities of
+    are not used); a sampler with a process group generates them over its ranks (``sample_all``: every rank calls this function
+    and gets the same result).  ``labels`` (num_particles / N per generated jet) default to the multiplicities of
     the real jets, taken in order and repeated as needed -- the reference conditions on the test set's ``jet_data``
     (train.py:712-723).  With ``"fpd"`` or ``"kpd"`` among the keys the 36 EFPs of degree <= 4 of the generated jets are computed
     on the device, and those of the real jets unless ``real_efps`` carries them (train.py:744-755 keeps them in a file per jet
@@ -642,7 +643,8 @@ def evaluate_generator(G: torch.nn.Module, real_jets, jet_type: str, num_samples
         if sampler.G is not G or sampler.N != N or sampler.jet_type != jet_type:
             raise ValueError(f"evaluate_generator: the sampler generates {sampler.jet_type!r} jets of {sampler.N} particles from its own "
                              f"generator; asked for {jet_type!r} jets of {N} particles from G")
-        gen_jets = sampler.sample(num_samples)
+        # (a sampler of several ranks: every rank generates its chunks and all of them evaluate the gathered rows -- a collective)
+        gen_jets = sampler.sample_all(num_samples) if getattr(sampler, "pg", None) is not None else sampler.sample(num_samples)
         gen_jets = gen_jets[0] if isinstance(gen_jets, tuple) else gen_jets
     else:
         if labels is None:

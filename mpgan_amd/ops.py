@@ -591,13 +591,14 @@ def label_pick(table: torch.Tensor, key: int, cursor: torch.Tensor, B: int, out:
 
 def jets_finish(feat: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Tensor, *, maxes, norms, shifts, key: int,
                 cursor: torch.Tensor, seed: torch.Tensor, ticket: torch.Tensor, row0: int = 0, total: Optional[int] = None,
-                mask_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                mask_out: Optional[torch.Tensor] = None, stride: Optional[int] = None) -> torch.Tensor:
     """``mpg_jets_finish``: the un-normalising epilogue of the reference's gen.py:127-141 (``data.unnormalise_jets``, bit for
     bit) on one chunk ``feat [B, N, >= 3]`` (unit feature stride, jets of whole rows: a [B, N, 4] module output is read in place)
     with ``mask [B, N]`` (or None: all real), written into rows ``cursor - row0 ..`` of ``out [total, N, 3]`` (and the 0 / 1
     verdicts into ``mask_out [total, N]``); jets at or beyond ``total`` (default: ``out``'s rows) are not written.  The launch
     then moves ``cursor`` on by B, writes the next chunk's seed word ``chunk_seed(key, cursor / B)`` into ``seed`` and leaves
-    ``ticket`` at zero."""
+    ``ticket`` at zero.  ``stride`` (``mpg_jets_finish_stride``; default B): what the cursor moves by instead -- W B for a rank
+    of W that share one stream."""
     B, N, F = _jet_layout(feat, "feat")
     _chk(out, "out")
     if feat.stride(0) != N * feat.stride(1) or F < 3:
@@ -616,10 +617,15 @@ def jets_finish(feat: torch.Tensor, mask: Optional[torch.Tensor], out: torch.Ten
     _stream_words(cursor, ticket, feat.device, "jets_finish", seed)
     f3 = lambda v: (C.c_float * 3)(*[float(x) for x in list(v)[:3]])
     mx, nr, sh = f3(maxes), f3(norms), f3(shifts)
-    check(_lib.lib().mpg_jets_finish(_p(feat), feat.stride(1), _p(mask), B, N, mx, nr, sh, _p(out), _p(mask_out),
-                                     int(row0) & 0xFFFFFFFFFFFFFFFF, total, int(key) & 0xFFFFFFFFFFFFFFFF,
-                                     C.c_void_p(cursor.data_ptr()), C.c_void_p(seed.data_ptr()), C.c_void_p(ticket.data_ptr()),
-                                     _stream()), "mpg_jets_finish")
+    words = (C.c_void_p(cursor.data_ptr()), C.c_void_p(seed.data_ptr()), C.c_void_p(ticket.data_ptr()), _stream())
+    front = (_p(feat), feat.stride(1), _p(mask), B, N, mx, nr, sh, _p(out), _p(mask_out), int(row0) & 0xFFFFFFFFFFFFFFFF, total,
+             int(key) & 0xFFFFFFFFFFFFFFFF)
+    if stride is None:
+        check(_lib.lib().mpg_jets_finish(*front, *words), "mpg_jets_finish")
+    else:
+        if not 1 <= int(stride) < 2**63:
+            raise ValueError(f"jets_finish: stride must be >= 1, got {stride!r}")
+        check(_lib.lib().mpg_jets_finish_stride(*front, int(stride), *words), "mpg_jets_finish_stride")
     return out
 
 
@@ -729,6 +735,56 @@ def ada_update(out: torch.Tensor, n_real: int, mid: float, target: float, step: 
                              f"{t.dtype} {tuple(t.shape)} on {t.device}")
     check(_lib.lib().mpg_ada_update(_p(out), n_real, float(mid), float(target), float(step), interval, _p(state), _p(aug_p), _p(r_out),
                                     _stream()), "mpg_ada_update")
+
+
+ADA_COUNT_MAX = 1 << 24      # a rank's sign count, and the ranks' sum, stay exact in fp32 up to here
+
+
+def _ada_words(what: str, device, state, aug_p, r_out):
+    for t, k, dt, name in ((state, 2, torch.int32, "state"), (aug_p, 1, torch.float32, "aug_p"), (r_out, 1, torch.float32, "r_out")):
+        if t.device != device or t.dtype != dt or not t.is_contiguous() or t.numel() != k:
+            raise ValueError(f"{what}: {name} must be a contiguous {dt} tensor of {k} element(s) on {device}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def _ada_slot(what: str, device, slot):
+    if slot.device != device or slot.dtype != torch.float32 or slot.numel() != 1:
+        raise ValueError(f"{what}: slot must be one float32 on {device}, got {slot.dtype} {tuple(slot.shape)} on {slot.device}")
+
+
+def ada_count(out: torch.Tensor, n_real: int, mid: float, slot: torch.Tensor):
+    """``mpg_ada_count``: the first half of ``ada_update`` for data-parallel ranks, ONE launch on the current stream --
+    ``slot[0] = float(count of sign(out[:n_real] - mid))``, a store.  ``slot``: one float32 on ``out``'s device (the tail of D's
+    flat gradient buffer: the gradient all-reduce adds the ranks' counts)."""
+    _chk(out, "out")
+    n_real = int(n_real)
+    if not out.is_contiguous() or not 1 <= n_real <= out.numel():
+        raise ValueError(f"ada_count: out must be contiguous with at least n_real = {n_real} >= 1 elements, got {tuple(out.shape)}")
+    if n_real > ADA_COUNT_MAX:
+        raise ValueError(f"ada_count: n_real = {n_real} > 2^24: the count would not be exact in the fp32 slot")
+    _ada_slot("ada_count", out.device, slot)
+    check(_lib.lib().mpg_ada_count(_p(out), n_real, float(mid), _p(slot), _stream()), "mpg_ada_count")
+
+
+def ada_settle(slot: torch.Tensor, n_real_total: int, target: float, step: float, interval: int, state: torch.Tensor,
+               aug_p: torch.Tensor, r_out: torch.Tensor):
+    """``mpg_ada_settle``: the second half of ``ada_update``, ONE launch of one thread behind the gradient all-reduce -- the rule
+    from ``state[0] += int(slot[0])`` onward with ``n_real_total`` (the real jets of all ranks) in the division.  A slot that is
+    not an integer within [-n_real_total, n_real_total] leaves ``state`` and ``aug_p`` untouched and ``r_out`` = NaN."""
+    _chk(slot, "slot")
+    n_real_total, interval = int(n_real_total), int(interval)
+    if n_real_total < 1 or interval < 1:
+        raise ValueError(f"ada_settle: n_real_total = {n_real_total} and interval = {interval} must be >= 1")
+    if n_real_total * interval > 2**31 - 1:
+        raise ValueError(f"ada_settle: n_real_total * interval = {n_real_total * interval} does not fit the int32 sign sum")
+    if not 0.0 <= float(target) <= 1.0:
+        raise ValueError(f"ada_settle: target must lie in [0, 1], got {target!r}")
+    if not float(step) >= 0.0:
+        raise ValueError(f"ada_settle: step must be >= 0, got {step!r}")
+    _ada_slot("ada_settle", slot.device, slot)
+    _ada_words("ada_settle", slot.device, state, aug_p, r_out)
+    check(_lib.lib().mpg_ada_settle(_p(slot), n_real_total, float(target), float(step), interval, _p(state), _p(aug_p), _p(r_out),
+                                    _stream()), "mpg_ada_settle")
 
 
 def augment_apply_reference(x: torch.Tensor, params: torch.Tensor) -> torch.Tensor:

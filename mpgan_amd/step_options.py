@@ -49,22 +49,40 @@ def _f32(v: float) -> float:
     return float(torch.tensor(float(v), dtype=torch.float32))
 
 
-def ada_rule(out, n_real: int, mid: float, target: float, step: float, interval: int, sign_sum: int, steps: int, p: float, r: float):
-    """``mpg_ada_update`` (include/mpgan_amd.h) in Python on a host tensor ``out``: (sign_sum, steps, p, r) after one D step.  The
-    counts are integers; the one division and the one sum are torch's fp32 operations on fp32 operands.  The CPU path of
-    ``TrainStep`` (host-logic tests with toy modules)."""
+def ada_count_rule(out, n_real: int, mid: float) -> int:
+    """``mpg_ada_count`` in Python on a host tensor ``out``: the count of sign(out[:n_real] - mid); a tie or a NaN counts on
+    neither side."""
+    o, mid = out.detach().reshape(-1)[:n_real].float(), torch.tensor(mid, dtype=torch.float32)
+    return int((o > mid).sum()) - int((o < mid).sum())
+
+
+def ada_settle_rule(s: float, n_real_total: int, target: float, step: float, interval: int, sign_sum: int, steps: int, p: float,
+                    r: float):
+    """``mpg_ada_settle`` in Python: (sign_sum, steps, p, r) after the D step whose sign count, summed over the ranks, is ``s``.
+    ``s`` that is not an integer within [-n_real_total, n_real_total] -- a broken collective -- moves nothing and gives r = NaN.
+    The one division and the one sum are torch's fp32 operations on fp32 operands."""
     f32 = lambda v: torch.tensor(v, dtype=torch.float32)
-    o, mid, target = out.detach().reshape(-1)[:n_real].float(), f32(mid), float(f32(target))
-    sign_sum += int((o > mid).sum()) - int((o < mid).sum())
+    s = float(s)
+    if not (abs(s) <= n_real_total and s == int(s)):      # (a NaN fails the first comparison)
+        return sign_sum, steps, p, float("nan")
+    target = float(f32(target))
+    sign_sum += int(s)
     steps += 1
     if steps != interval:
         return sign_sum, steps, p, r
-    r = float(f32(sign_sum) / f32(n_real * interval))
+    r = float(f32(sign_sum) / f32(n_real_total * interval))
     if r > target:
         p = float(f32(p) + f32(step))
     elif r < target:
         p = float(f32(p) - f32(step))
     return 0, 0, min(1.0, max(0.0, p)), r
+
+
+def ada_rule(out, n_real: int, mid: float, target: float, step: float, interval: int, sign_sum: int, steps: int, p: float, r: float):
+    """``mpg_ada_update`` (include/mpgan_amd.h) in Python on a host tensor ``out``: (sign_sum, steps, p, r) after one D step -- its
+    two halves, ``ada_count_rule`` and ``ada_settle_rule``, one behind the other.  The CPU path of ``TrainStep`` (host-logic
+    tests with toy modules)."""
+    return ada_settle_rule(ada_count_rule(out, n_real, mid), n_real, target, step, interval, sign_sum, steps, p, r)
 
 
 def effective_targets(y_real: torch.Tensor, y_fake: torch.Tensor, smoothing: bool):
@@ -215,26 +233,39 @@ class AdaController:
     """The adaptive augmentation probability (``Augment.adaptive_prob``), in D's file: one launch behind the D
     step's head (``update``) adds the signs of D(real) - mid to ``state`` = (sign sum, D steps counted) and, every ``interval`` D
     steps, moves ``p`` -- the augmenter's own probability word -- by ``step`` and leaves the interval's r in ``r``: all in device
-    memory, inside the capture."""
+    memory, inside the capture.
+    Data-parallel ranks (``split``) settle ONE p: ``update`` is then the count launch alone, which stores this rank's sign count
+    into ``slot`` -- the float at the tail of D's flat gradient buffer, so D's gradient all-reduce adds the ranks' counts -- and
+    ``settle``, first in the segment behind that all-reduce, runs the rule on the sum with ``n_total`` real jets per D step."""
     KEY = "mpgan_amd_ada"
 
-    def __init__(self, p: torch.Tensor, mid: float, target: float, interval: int, step: float):
+    def __init__(self, p: torch.Tensor, mid: float, target: float, interval: int, step: float, n_total: Optional[int] = None,
+                 slot: Optional[torch.Tensor] = None):
         self.mid, self.target, self.interval, self.step = mid, target, interval, step
         self.p, self.p0 = p, float(p)
         self.state = torch.zeros(2, device=p.device, dtype=torch.int32)
         self.r = torch.zeros(1, device=p.device)
+        self.split, self.slot, self.n_total = slot is not None, slot, n_total      # (the slot is transient: not carried, not saved)
         self.keep_out = False    # tests: keep the D step's last ``out`` tensor in ``last_out`` (no launch of its own)
         self.last_out = None
 
+    @staticmethod
+    def splits(augment, process_group, world_size: int, split: bool = False) -> bool:
+        """Does the controller ``augment`` asks for take the two-launch route?  With a process group of more than one rank, or
+        when forced (tests, the bench); one rank keeps the one launch."""
+        return bool(getattr(augment, "adaptive_prob", False)) and (bool(split) or (process_group is not None and world_size > 1))
+
     @classmethod
-    def from_args(cls, augment, p: torch.Tensor, loss: str, batch_size: int, world_size: int):
-        """The controller ``augment`` (an ``Augment`` or the reference's namespace) asks for, or None."""
+    def from_args(cls, augment, p: torch.Tensor, loss: str, batch_size: int, world_size: int, process_group=None,
+                  split: bool = False, slot: Optional[torch.Tensor] = None):
+        """The controller ``augment`` (an ``Augment`` or the reference's namespace) asks for, or None.  ``slot``: the tail of D's
+        flat gradient buffer on the split route (``splits``; a float of its own when none is given)."""
         if not getattr(augment, "adaptive_prob", False):
             return None
-        if world_size > 1:
-            raise ValueError(f"adaptive_prob with world_size = {world_size}: every rank would settle the probability from its own "
-                             "batches and the ranks would drift apart (the sign sum is not all-reduced); adaptive augmentation "
-                             "runs on one rank")
+        if world_size > 1 and process_group is None:
+            raise ValueError(f"adaptive_prob with world_size = {world_size} and no process group: every rank would settle the "
+                             "probability from its own batches and the ranks would drift apart (there is nothing to all-reduce "
+                             "the sign sum over); pass the ranks' process_group")
         target, interval, kimg = (getattr(augment, k, v) for k, v in ADA_DEFAULTS.items())
         if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
             raise ValueError(f"ada_interval must be an integer >= 1, got {interval!r}")
@@ -242,9 +273,21 @@ class AdaController:
             raise ValueError(f"ada_target must lie in [0, 1], got {target!r}")
         if not float(kimg) > 0.0:
             raise ValueError(f"ada_kimg must be > 0, got {kimg!r}")
+        n_total = batch_size * world_size      # the real jets of one D step, all ranks together
+        if n_total > ops.ADA_COUNT_MAX:
+            raise ValueError(f"adaptive_prob with batch_size * world_size = {n_total} > 2^24: the ranks' sign counts would not add "
+                             "exactly in fp32")
+        if n_total * interval > 2**31 - 1:
+            raise ValueError(f"adaptive_prob: batch_size * world_size * ada_interval = {n_total * interval} does not fit the int32 "
+                             "sign sum")
+        if cls.splits(augment, process_group, world_size, split):
+            slot = torch.zeros(1, device=p.device) if slot is None else slot
+        else:
+            slot = None
         # mid: the midpoint of the loss's two targets (sigmoid outputs against 1 / 0; raw scores either side of 0);
-        # step: p can cross [0, 1] in ada_kimg thousand real jets -- rounded to fp32 once, here
-        return cls(p, 0.5 if loss in ("og", "ls") else 0.0, _f32(target), interval, _f32(batch_size * interval / (1000.0 * float(kimg))))
+        # step: p can cross [0, 1] in ada_kimg thousand real jets (of all ranks) -- rounded to fp32 once, here
+        return cls(p, 0.5 if loss in ("og", "ls") else 0.0, _f32(target), interval, _f32(n_total * interval / (1000.0 * float(kimg))),
+                   n_total, slot)
 
     def read(self) -> dict:
         """{p, r, sign_sum, steps}; synchronises.  p and r are fp32 values held exactly by the Python floats."""
@@ -266,12 +309,29 @@ class AdaController:
         in stream order reads the new probability.  CPU (host-logic tests with toy modules): ``ada_rule``."""
         if self.keep_out:
             self.last_out = out
+        if self.split:      # (the count alone: ``settle`` follows behind D's gradient all-reduce)
+            if self.p.is_cuda:
+                ops.ada_count(out, n_real, self.mid, self.slot)
+            else:
+                self.slot.fill_(float(ada_count_rule(out, n_real, self.mid)))
+            return
         if self.p.is_cuda:
             ops.ada_update(out, n_real, self.mid, self.target, self.step, self.interval, self.state, self.p, self.r)
             return
         now = self.read()
         sign_sum, steps, p, r = ada_rule(out, n_real, self.mid, self.target, self.step, self.interval, now["sign_sum"], now["steps"],
                                          now["p"], now["r"])
+        self.write({"p": p, "r": r, "sign_sum": sign_sum, "steps": steps})
+
+    def settle(self):
+        """The split route's second launch, first in the segment behind D's gradient all-reduce: the slot now holds the sign
+        count of all ranks.  Every rank computes the same p from it.  CPU: ``ada_settle_rule``."""
+        if self.p.is_cuda:
+            ops.ada_settle(self.slot, self.n_total, self.target, self.step, self.interval, self.state, self.p, self.r)
+            return
+        now = self.read()
+        sign_sum, steps, p, r = ada_settle_rule(float(self.slot), self.n_total, self.target, self.step, self.interval, now["sign_sum"],
+                                                now["steps"], now["p"], now["r"])
         self.write({"p": p, "r": r, "sign_sum": sign_sum, "steps": steps})
 
     def tensors(self):    # (the warm-up's D steps move neither the probability nor the open interval)

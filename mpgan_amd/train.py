@@ -17,7 +17,9 @@ device inside the iteration (``ops.augment``), from the seed that keys the noise
 Label smoothing / label noise (``--label-smoothing`` / ``--label-noise``, train.py:341-363; ``TrainStep(label_smoothing=...,
 label_noise=...)``) are per-jet targets drawn on the device by one launch in front of D's head (``ops.label_targets``).
 The augmentation probability can follow the discriminator (``Augment(adaptive_prob=True)``, the reference's unimplemented
-``--adaptive-prob``): ADA's rule on D's outputs for the real jets, one launch behind D's head (``ops.ada_update``).
+``--adaptive-prob``): ADA's rule on D's outputs for the real jets, one launch behind D's head (``ops.ada_update``); under a
+process group the ranks settle one probability from the sign count of all their jets, which rides in D's gradient all-reduce
+(``ops.ada_count`` behind the head, ``ops.ada_settle`` behind the all-reduce).
 The training data can live on the device as well (``TrainStep(loader=data.DeviceJetLoader(...))``): the batch is then gathered by
 one launch at the top of the iteration, inside the capture, in the order of a keyed shuffle.
 An averaged generator (``TrainStep(ema=Ema(...))``; Yazici et al. 2019, StyleGAN's ``G_ema``) is kept by G's optimizer launch
@@ -117,10 +119,11 @@ class FlatParams:
 
     ``ema`` (a ``step_options.Ema``; ``batch_size``: the jets one step consumes, which ``Ema(kimg=...)`` needs): the launch also
     folds the new parameters into their exponential moving average ``self.ema`` (``mpg_*_ema``); ``self.ema_state`` holds its
-    step word and the launch's ticket."""
+    step word and the launch's ticket.  ``tail``: that many floats more at the end of the gradient buffer (``self.tail``), which
+    travel in its all-reduce and belong to no parameter."""
 
     def __init__(self, module: nn.Module, optimizer: str = "rmsprop", betas=(0.9, 0.999), weight_decay: float = 5e-4,
-                 ema: Optional[Ema] = None, batch_size: Optional[int] = None):
+                 ema: Optional[Ema] = None, batch_size: Optional[int] = None, tail: int = 0):
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         # Only what is TRAINED goes into the flat buffers: frozen parameters (spectral norm's power-iteration vectors,
@@ -138,7 +141,12 @@ class FlatParams:
         n = sum(p.numel() for p in ps)
         dev = ps[0].device
         self.flat = torch.empty(n, device=dev, dtype=torch.float32)
-        self.grad = torch.zeros(n, device=dev, dtype=torch.float32)
+        # ``tail`` floats behind the n gradients ride in the same buffer -- and so in the network's one gradient all-reduce
+        # (``grad_all``: what TrainStep reduces) -- without being gradients: the p.grad views and every optimizer launch cover the
+        # first n only (the adaptive augmentation's sign count: step_options.AdaController)
+        self.grad_all = torch.zeros(n + int(tail), device=dev, dtype=torch.float32)
+        self.grad = self.grad_all[:n] if tail else self.grad_all
+        self.tail = self.grad_all[n:] if tail else None
         self.sq = torch.zeros(n, device=dev, dtype=torch.float32)       # square_avg / exp_avg_sq
         self.aux = torch.zeros(n, device=dev, dtype=torch.float32) if optimizer != "rmsprop" else None  # exp_avg / acc_delta
         # optimiser steps taken.  Adam needs the count in its arithmetic, so it lives in device memory (a replayed
@@ -402,7 +410,7 @@ class TrainStep:
                  optimizer: str = "rmsprop", betas=(0.9, 0.999), gp_lambda: float = 0.0,
                  graph_collectives: Optional[bool] = None, augment=None, loader=None, num_critic: int = 1, num_gen: int = 1,
                  track_epoch_losses: bool = False, label_smoothing: bool = False, label_noise: float = 0.0,
-                 ema: Optional[Ema] = None):
+                 ema: Optional[Ema] = None, _ada_split: bool = False):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
         self.dev = dev = next(G.parameters()).device
@@ -458,7 +466,10 @@ class TrainStep:
         # (Ema(kimg=...): the half-life counts the jets of all ranks)
         self.fG = FlatParams(G, optimizer, betas, ema=ema, batch_size=batch_size * world_size)
         self._ema_twin = None        # (``ema_generator`` builds it on first use)
-        self.fD = FlatParams(D, optimizer, betas)
+        # (adaptive augmentation over ranks: the sign count's slot at the tail of D's gradient buffer, see ``AdaController``)
+        ada_split = (augment is not None and AdaController.splits(augment, process_group, world_size, _ada_split)
+                     and ops.augment_flags(augment.aug_r90, augment.aug_f, augment.aug_t, augment.aug_s) != 0)
+        self.fD = FlatParams(D, optimizer, betas, tail=1 if ada_split else 0)
         self._schedule = Schedule()      # (the schedule's batch index: saved with G's optimizer state, see ``batch_ndx``)
         self._seed = None
         if gpu:
@@ -540,7 +551,8 @@ class TrainStep:
             self.aug = Augmenter.from_args(augment, self.aug_p, batch_size)
         if self.aug is not None:
             self.aug_params = self.aug.params
-            self._ada = AdaController.from_args(augment, self.aug_p, loss, batch_size, world_size)
+            self._ada = AdaController.from_args(augment, self.aug_p, loss, batch_size, world_size, process_group, _ada_split,
+                                                self.fD.tail)
         self.ada_state, self.ada_r = (None, None) if self._ada is None else (self._ada.state, self._ada.r)    # (the controller's words)
         # the generator's noise and its jets' masks drawn by one launch (MPG_NOISE_MASK=0: mpg_normal, then mpg_rank_mask)
         self.noise_mask = gpu and on["MPG_NOISE_MASK"]
@@ -854,7 +866,12 @@ class TrainStep:
         if packs:
             ops.refresh_many(packs)
 
+    def _settle_ada(self):   # first behind D's gradient all-reduce: the ranks' sign counts have been added (``AdaController.settle``)
+        if self._ada is not None and self._ada.split:
+            self._ada.settle()
+
     def _seg_D_end(self):  # D_optimizer.step() (train.py:461) of a batch on which the generator does not train
+        self._settle_ada()
         # the seed moves on HERE, as it does in G's optimizer launch otherwise (_seg_end): the next critic step would redraw this
         # one's generator noise, dropout masks and augmentation maps without it
         self._close_batch("D")
@@ -865,6 +882,7 @@ class TrainStep:
             # the data loader yields the batch all the same, and train_G takes its labels (train.py:832-835, :872)
             self._open_batch()
         else:
+            self._settle_ada()     # (in front of train_G's augmentation, which reads the new p)
             # optimizer.zero_grad() of the next train_D (train.py:419) rides in this launch: the buffer is cleared behind its last use
             self.fD.step(self.lr_disc, gscale=1.0 / self.world, zero_grad=True)
             self._clean["D"] = True
@@ -906,7 +924,8 @@ class TrainStep:
         self._clean = {"D": True, "G": True}
 
     def _allreduce(self, flat: FlatParams):
-        mdist.allreduce_sum_(flat.grad, self.pg, self.world)  # sum; 1/world is folded into the optimiser step
+        # sum; 1/world is folded into the optimiser step.  (grad_all: the buffer with its tail -- D's carries the sign count)
+        mdist.allreduce_sum_(flat.grad_all, self.pg, self.world)
 
     # -- which of train_D / train_G a batch runs, and the segments of each kind of batch --------------
     KINDS = {"DG": ("D", "G"), "D": ("D",), "G": ("G",)}

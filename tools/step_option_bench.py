@@ -8,8 +8,10 @@ same with the option on -- and, where the option adds one launch to the D segmen
 
 labels   baseline: the default step.  Option: ``label_smoothing=True, label_noise=0.1`` (+ ``mpg_label_targets``, and the head
          reads its targets from memory).  Rows: a default_step, b labels_step, c label_launch.
-ada      baseline: the four augmentations at p = 0.5.  Option: the same with ``adaptive_prob=True`` (+ ``mpg_ada_update`` behind
-         the head).  Rows: a fixed_p_step, b adaptive_step, c ada_launch.
+ada      three steps: the four augmentations at p = 0.5 (a fixed_p_step), the same with ``adaptive_prob=True`` on the one-launch
+         route (b adaptive_step: + ``mpg_ada_update`` behind the head) and on the two-launch route that data-parallel ranks take,
+         forced on this one rank (d split_step: + ``mpg_ada_count`` behind the head and ``mpg_ada_settle`` in front of D's
+         optimizer launch, one float more in D's gradient buffer).  Lone launches: c ada_launch, e count_launch, f settle_launch.
 critic   baseline: the default step.  Option: ``num_critic=5`` (--num-critic).  Rows: a default_step, b d_only_replay (a batch
          on which only D trains), c dg_replay (both train: the launches of a), d mean_per_batch (over two full cycles).
 sn       three steps: a default_step (for scale), and spectral norm in G and D with ``ops.OPTIONS["sn_fused"]`` off (b
@@ -22,7 +24,8 @@ Every ``step()`` and every lone launch sits between two HIP events of its own --
 costs cancels between them.  A repetition is --batches steps of each kind (critic: two full cycles of the schedule) taken
 alternately, then as many lone launches; the rows are the means within a repetition, reported as median / min / max over --reps
 repetitions behind a warm-up that captures every graph.  No speed claim is made.  The last line states what the option is held to.
-labels, ada: (b) - (a) is at most the run-to-run spread of (a) (max - min of its repetitions) plus (c).  critic: (c) within
+labels, ada: (b) - (a) is at most the run-to-run spread of (a) (max - min of its repetitions) plus (c); ada also: (d) - (b) is at
+most the spread of (b) plus (f) -- the baseline of the split route is the unchanged one-launch route of the same process.  critic: (c) within
 the spread of (a), and (b) <= (a).  ema: (b) - (a) is at most the run-to-run spread of (a).
 """
 import argparse
@@ -119,10 +122,6 @@ OPTIONS = {
                    rows=("a default_step", "b labels_step", "c label_launch"),
                    fields=lambda a, opt: {"label_smoothing": SMOOTHING, "label_noise": NOISE},
                    condition=_launch_condition("labels", "default", "label"), tail=lambda opt: {"label_extra": float(opt.label_extra)}),
-    "ada": dict(base=lambda a: dict(augment=_augment()), opt=lambda a: dict(augment=_augment(adaptive_prob=True)), launch=_ada_launch,
-                rows=("a fixed_p_step", "b adaptive_step", "c ada_launch"),
-                fields=lambda a, opt: {"aug_prob": P0, "ada_interval": opt._ada.interval, "ada_step": opt._ada.step},
-                condition=_launch_condition("adaptive", "fixed", "ada"), tail=lambda opt: {"ada": opt.ada}),
     "critic": dict(base=lambda a: {}, opt=lambda a: dict(num_critic=a.num_critic), launch=None,
                    rows=("a default_step", "b d_only_replay", "c dg_replay", "d mean_per_batch"),
                    fields=lambda a, opt: {"num_critic": a.num_critic}, condition=_critic_condition, tail=lambda opt: {}),
@@ -130,6 +129,51 @@ OPTIONS = {
                 fields=lambda a, opt: {"ema_kimg": 10, "ema_beta": opt.fG.ema_carried.beta}, condition=_ema_condition,
                 tail=lambda opt: {"ema_t": opt.fG.ema_carried.t}),
 }
+
+
+def ada_bench(args, emit):
+    """--option ada: three captured steps in one process -- fixed p, adaptive on the one-launch route, adaptive on the split route
+    (``_ada_split=True``: what a rank of several runs, without the all-reduce) -- alternated, every ``step()`` between two HIP
+    events; then the three lone launches."""
+    rows = ("a fixed_p_step", "b adaptive_step", "d split_step", "c ada_launch", "e count_launch", "f settle_launch")
+    torch.manual_seed(0)
+    steps = [build(augment=_augment()), build(augment=_augment(adaptive_prob=True)),
+             build(augment=_augment(adaptive_prob=True), _ada_split=True)]
+    one, split = steps[1], steps[2]
+    assert not one._ada.split and split._ada.split and split.fD.grad_all.numel() == split.fD.n + 1
+    a = one._ada
+    out = torch.rand(2 * B, device="cuda")
+    words = (torch.zeros(2, dtype=torch.int32, device="cuda"), torch.full((1,), P0, device="cuda"), torch.zeros(1, device="cuda"))
+    slot = torch.zeros(1, device="cuda")
+    launches = [_ada_launch(one), lambda: ops.ada_count(out, B, a.mid, slot),
+                lambda: ops.ada_settle(slot, B, a.target, a.step, a.interval, *words)]
+    for _ in range(3):   # warm-up: captures every graph
+        for fn in (*(ts.step for ts in steps), *launches):
+            fn()
+    torch.cuda.synchronize()
+    us = {r: [] for r in rows}
+    for _ in range(args.reps):
+        t = {r: [] for r in rows}
+        for _ in range(args.batches):        # (alternated: the rows share whatever the box does meanwhile)
+            for r, ts in zip(rows[:3], steps):
+                t[r].append(timed(ts.step))
+        for r, fn in zip(rows[3:], launches):
+            t[r] = [timed(fn) for _ in range(args.batches)]
+        for r in rows:
+            us[r].append(float(np.mean(t[r])))
+    med = {}
+    for name, v in us.items():
+        med[name] = float(np.median(v))
+        emit({"model": "mpgan", "B": B, "N": N, "aug_prob": P0, "ada_interval": a.interval, "ada_step": a.step, "row": name,
+              "reps": args.reps, "batches_per_rep": args.batches, "median_us": med[name], "min_us": float(np.min(v)),
+              "max_us": float(np.max(v))})
+    emit({"model": "mpgan", "B": B, **_launch_condition("adaptive", "fixed", "ada")(med, us, (rows[0], rows[1], rows[3])),
+          "D_loss": float(one.D_loss), "G_loss": float(one.G_loss), "ada": one.ada})
+    diff, spread = med[rows[2]] - med[rows[1]], float(np.max(us[rows[1]]) - np.min(us[rows[1]]))
+    emit({"model": "mpgan", "B": B, "row": "condition_split", "split_minus_adaptive_us": diff, "spread_adaptive_us": spread,
+          "settle_launch_us": med[rows[5]], "count_launch_us": med[rows[4]],
+          "within_spread_plus_settle": bool(diff <= spread + med[rows[5]]), "D_loss": float(split.D_loss),
+          "G_loss": float(split.G_loss), "ada": split.ada})
 
 
 def sn_bench(args, emit):
@@ -172,7 +216,7 @@ def sn_bench(args, emit):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--option", choices=sorted([*OPTIONS, "sn"]), required=True)
+    ap.add_argument("--option", choices=sorted([*OPTIONS, "ada", "sn"]), required=True)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--batches", type=int, default=10, help="steps of each kind per repetition (critic: two cycles of the schedule)")
     ap.add_argument("--num-critic", type=int, default=5)
@@ -183,6 +227,8 @@ def main():
     emit = jsonl_sink(args.out)
     if args.option == "sn":
         return sn_bench(args, emit)
+    if args.option == "ada":
+        return ada_bench(args, emit)
     o = OPTIONS[args.option]
     critic = args.option == "critic"
     batches = 2 * args.num_critic if critic else args.batches
