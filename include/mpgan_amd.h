@@ -607,6 +607,58 @@ int mpg_adadelta_ema(float* p, float* g, float* v, float* u, uint64_t n, float l
                      float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, const MpgEma* ema, void* stream);
 int mpg_ema_update_host(float* e, const float* p_new, uint64_t n, uint32_t t, float beta, int start, int warmup);
 
+/* The optimizer-step control: a learning-rate schedule and gradient clipping by the global L2 norm (torch.nn.utils.
+ * clip_grad_norm_) for one network, as ONE launch in front of its optimizer launch -- inside a captured hipGraph, where lr and
+ * gscale passed by value would be constants.  The reference has neither option: this statement is the specification.
+ * Device state: state uint32[2] = {t, ticket} -- t counts the controlled steps this optimizer has taken, the ticket is the launch's
+ * arrival counter and reads 0 between launches; base float[1], the base learning rate; out float[4] = {lr_eff, s, norm, factor}.
+ * mpg_step_control computes, for the step about to be taken, with t as it stood before the launch:
+ *   factor: nknots == 0: 1.  Otherwise over the knots (knot_step[k], knot_f[k]), k < nknots <= MPG_LR_KNOTS, steps strictly
+ *           increasing and <= 2^24, factors finite and >= 0:
+ *             t <= knot_step[0]: knot_f[0];  t >= knot_step[last]: knot_f[last];  else on the segment knot_step[k] <= t < knot_step[k+1]:
+ *             w = (float)(t - knot_step[k]) / (float)(knot_step[k+1] - knot_step[k])       (both conversions exact, ONE fp32 division)
+ *             factor = knot_f[k] + w * (knot_f[k+1] - knot_f[k])                            (THREE fp32 operations)
+ *   lr_eff = base * factor
+ *   norm   = (float) sqrt(sum_i ((double)(gscale * g[i]))^2) over the n gradients: the product in fp32, squares and sums in fp64
+ *            in a fixed order that depends on n alone -- min(256, ceil(n / 256)) workgroups of 256 threads, every thread its strided
+ *            elements in index order, every workgroup a fixed tree, the workgroup that arrives last on the ticket the partials in
+ *            workgroup order: two launches on one buffer give the same bits.  Computed when max_norm clips or want_norm != 0;
+ *            otherwise 0 is written, the launch is one workgroup and reads no gradient.
+ *   gmul   = max_norm clips ? min(1, max_norm / (norm + 1e-6f)) : 1      (max_norm <= 0 or +inf: no clipping; a NaN quotient stays)
+ *   s      = gscale * gmul
+ * then t <- t + 1 (stopping at 2^32 - 1) and ticket <- 0, by the workgroup that arrived last.  Every fp32 operation rounds to
+ * nearest even on its own; nothing is contracted.  Non-finite gradients get no special treatment.
+ * partials: 256 doubles of scratch in device memory, the caller's, allocated once.
+ * A NULL block, state, base, out or partials; nknots outside [0, MPG_LR_KNOTS]; knot steps unordered or above 2^24; a factor
+ * negative or not finite; a NaN max_norm or gscale; a norm to compute with g NULL or n == 0: -1.
+ * mpg_step_control_host: the same rule from the same body compiled for the host, on host memory, in the launch's order of
+ * summation.  No HIP call; the same refusals.
+ * mpg_*_ctl: the optimizer launches with lr = out[0] and gscale = out[1], read from device memory at the top of the kernel (the
+ * arguments lr and gscale are not looked at); the per-element arithmetic is the plain launch's.  ema: NULL, or the averaged form's
+ * block.  A NULL ctl or out, n == 0, a bad ema block: -1. */
+#define MPG_LR_KNOTS 8
+typedef struct MpgStepCtl {
+    uint32_t* state;     /* t, ticket */
+    float* base;
+    float* out;          /* lr_eff, s, norm, factor */
+    double* partials;    /* 256 doubles */
+    int nknots;
+    uint32_t knot_step[MPG_LR_KNOTS];
+    float knot_f[MPG_LR_KNOTS];
+    float max_norm;
+    int want_norm;
+} MpgStepCtl;
+int mpg_step_control(const float* g, uint64_t n, float gscale, const MpgStepCtl* ctl, void* stream);
+int mpg_step_control_host(const float* g, uint64_t n, float gscale, const MpgStepCtl* ctl);
+int mpg_rmsprop_ctl(float* p, float* g, float* v, uint64_t n, float lr, float alpha, float eps, float gscale, int zero_grad,
+                    uint64_t* counter, uint64_t counter_add, const MpgStepCtl* ctl, const MpgEma* ema, void* stream);
+int mpg_adam_ctl(float* p, float* g, float* m, float* v, float* step, uint64_t n, float lr, float beta1,
+                 float beta2, float eps, float weight_decay, float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add,
+                 const MpgStepCtl* ctl, const MpgEma* ema, void* stream);
+int mpg_adadelta_ctl(float* p, float* g, float* v, float* u, uint64_t n, float lr, float rho, float eps,
+                     float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, const MpgStepCtl* ctl, const MpgEma* ema,
+                     void* stream);
+
 /* ---- evaluation metrics --------------------------------------------------------------------------
  * mpg_jet_obs: per-jet observables of the metrics the reference's evaluate (train.py:543-606) draws from jetnet / energyflow:
  * jetnet.utils.jet_features (for w1m) and the EFPs of jetnet.evaluation.w1efp (energyflow ("n==",4), ("d==",4), ("p==",1)).

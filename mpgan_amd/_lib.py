@@ -234,6 +234,14 @@ class MpgEma(C.Structure):
     _fields_ = [("ema", _fp), ("state", _fp), ("beta", C.c_float), ("start", C.c_int), ("warmup", C.c_int)]
 
 
+LR_KNOTS = 8   # MPG_LR_KNOTS of include/mpgan_amd.h
+
+
+class MpgStepCtl(C.Structure):
+    _fields_ = [("state", _fp), ("base", _fp), ("out", _fp), ("partials", _fp), ("nknots", C.c_int),
+                ("knot_step", C.c_uint32 * LR_KNOTS), ("knot_f", C.c_float * LR_KNOTS), ("max_norm", C.c_float), ("want_norm", C.c_int)]
+
+
 MPG_FN_NA = -100  # mpg_edge_fwd_fn: "not one of my shapes" (include/mpgan_amd.h)
 # what mpg_chain_route answers (MPG_CHAIN_ROUTE_* of include/mpgan_amd.h)
 CHAIN_ROUTE_CHAIN2, CHAIN_ROUTE_STRAIGHT, CHAIN_ROUTE_LOOPS = 1, 2, 3
@@ -299,6 +307,14 @@ SIGNATURES = {
     "mpg_adadelta_ema": (C.c_int, [_fp, _fp, _fp, _fp, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _fp, C.c_uint64,
                                    C.POINTER(MpgEma), C.c_void_p]),
     "mpg_ema_update_host": (C.c_int, [_fp, _fp, C.c_uint64, C.c_uint32, C.c_float, C.c_int, C.c_int]),
+    "mpg_step_control": (C.c_int, [_fp, C.c_uint64, C.c_float, C.POINTER(MpgStepCtl), C.c_void_p]),
+    "mpg_step_control_host": (C.c_int, [_fp, C.c_uint64, C.c_float, C.POINTER(MpgStepCtl)]),
+    "mpg_rmsprop_ctl": (C.c_int, [_fp, _fp, _fp, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _fp, C.c_uint64,
+                                  C.POINTER(MpgStepCtl), C.POINTER(MpgEma), C.c_void_p]),
+    "mpg_adam_ctl": (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                               C.c_float, C.c_int, _fp, C.c_uint64, C.POINTER(MpgStepCtl), C.POINTER(MpgEma), C.c_void_p]),
+    "mpg_adadelta_ctl": (C.c_int, [_fp, _fp, _fp, _fp, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, _fp, C.c_uint64,
+                                   C.POINTER(MpgStepCtl), C.POINTER(MpgEma), C.c_void_p]),
     "mpg_bridge_fwd": (C.c_int, [C.POINTER(MpgBridge), C.c_void_p]),
     "mpg_bridge_bwd": (C.c_int, [C.POINTER(MpgBridgeBwd), C.c_void_p]),
     "mpg_normal": (C.c_int, [_fp, C.c_uint64, _fp, C.c_uint32, C.c_float, C.c_float, C.c_void_p]),

@@ -81,10 +81,22 @@ MPG_DEV void ema_end(const MpgEma& a, uint32_t t) {
     }
 }
 
-template <bool EMA>
+// The controlled launches (mpg_*_ctl): lr and gscale are what mpg_step_control (csrc/step_control.hip) left in out[0] / out[1],
+// read once, here; the arguments of the same names are not looked at.  A third template parameter: the instantiations without it
+// read and write what they always did.
+template <bool CTL>
+MPG_DEV void ctl_read(const float* __restrict__ ctl_out, float& lr, float& gscale) {
+    if constexpr (CTL) {
+        lr = ctl_out[0];
+        gscale = ctl_out[1];
+    }
+}
+
+template <bool EMA, bool CTL>
 __global__ void rmsprop_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ v, size_t n,
                                float lr, float alpha, float eps, float gscale, int zero_grad, uint64_t* __restrict__ counter, uint64_t counter_add,
-                               MpgEma ema) {
+                               MpgEma ema, const float* __restrict__ ctl_out) {
+    ctl_read<CTL>(ctl_out, lr, gscale);
     if (counter != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *counter += counter_add;
     uint32_t t = 0;
     const EmaCoef ec = ema_begin<EMA>(ema, t);
@@ -102,10 +114,12 @@ __global__ void rmsprop_kernel(float* __restrict__ p, float* __restrict__ g, flo
     ema_end<EMA>(ema, t);
 }
 
-template <bool EMA>
+template <bool EMA, bool CTL>
 __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             const float* __restrict__ step, size_t n, float lr, float b1, float b2, float eps, float wd,
-                            float gscale, int zero_grad, uint64_t* __restrict__ counter, uint64_t counter_add, MpgEma ema) {
+                            float gscale, int zero_grad, uint64_t* __restrict__ counter, uint64_t counter_add, MpgEma ema,
+                            const float* __restrict__ ctl_out) {
+    ctl_read<CTL>(ctl_out, lr, gscale);
     if (counter != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *counter += counter_add;
     uint32_t te = 0;
     const EmaCoef ec = ema_begin<EMA>(ema, te);
@@ -130,10 +144,11 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
 }
 __global__ void step_inc_kernel(float* step) { *step += 1.f; }
 
-template <bool EMA>
+template <bool EMA, bool CTL>
 __global__ void adadelta_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ v, float* __restrict__ u,
                                 size_t n, float lr, float rho, float eps, float gscale, int zero_grad, uint64_t* __restrict__ counter, uint64_t counter_add,
-                                MpgEma ema) {
+                                MpgEma ema, const float* __restrict__ ctl_out) {
+    ctl_read<CTL>(ctl_out, lr, gscale);
     if (counter != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *counter += counter_add;
     uint32_t t = 0;
     const EmaCoef ec = ema_begin<EMA>(ema, t);
@@ -215,29 +230,35 @@ bool ema_args_ok(const MpgEma* a, uint64_t n) {
     return a->beta >= 0.f && a->beta < 1.f && a->start >= 0;      // (a NaN fails both comparisons)
 }
 
-template <bool EMA>
+template <bool EMA, bool CTL = false>
 int rmsprop_launch(float* p, float* g, float* v, uint64_t n, float lr, float alpha, float eps, float gscale, int zero_grad,
-                   uint64_t* counter, uint64_t counter_add, const MpgEma& ema, void* stream) {
-    hipLaunchKernelGGL(rmsprop_kernel<EMA>, dim3(nblocks_for<EMA>(n)), dim3(256), 0, (hipStream_t)stream, p, g, v, (size_t)n, lr, alpha,
-                       eps, gscale, zero_grad, counter, counter_add, ema);
+                   uint64_t* counter, uint64_t counter_add, const MpgEma& ema, void* stream, const float* ctl_out = nullptr) {
+    hipLaunchKernelGGL((rmsprop_kernel<EMA, CTL>), dim3(nblocks_for<EMA>(n)), dim3(256), 0, (hipStream_t)stream, p, g, v, (size_t)n, lr,
+                       alpha, eps, gscale, zero_grad, counter, counter_add, ema, ctl_out);
     return (int)hipGetLastError();
 }
 
-template <bool EMA>
+template <bool EMA, bool CTL = false>
 int adam_launch(float* p, float* g, float* m, float* v, float* step, uint64_t n, float lr, float beta1, float beta2, float eps,
-                float weight_decay, float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, const MpgEma& ema, void* stream) {
-    hipLaunchKernelGGL(adam_kernel<EMA>, dim3(nblocks_for<EMA>(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, step, (size_t)n, lr,
-                       beta1, beta2, eps, weight_decay, gscale, zero_grad, counter, counter_add, ema);
+                float weight_decay, float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, const MpgEma& ema, void* stream,
+                const float* ctl_out = nullptr) {
+    hipLaunchKernelGGL((adam_kernel<EMA, CTL>), dim3(nblocks_for<EMA>(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, step, (size_t)n,
+                       lr, beta1, beta2, eps, weight_decay, gscale, zero_grad, counter, counter_add, ema, ctl_out);
     hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
     return (int)hipGetLastError();
 }
 
-template <bool EMA>
+template <bool EMA, bool CTL = false>
 int adadelta_launch(float* p, float* g, float* v, float* u, uint64_t n, float lr, float rho, float eps, float gscale, int zero_grad,
-                    uint64_t* counter, uint64_t counter_add, const MpgEma& ema, void* stream) {
-    hipLaunchKernelGGL(adadelta_kernel<EMA>, dim3(nblocks_for<EMA>(n)), dim3(256), 0, (hipStream_t)stream, p, g, v, u, (size_t)n, lr, rho,
-                       eps, gscale, zero_grad, counter, counter_add, ema);
+                    uint64_t* counter, uint64_t counter_add, const MpgEma& ema, void* stream, const float* ctl_out = nullptr) {
+    hipLaunchKernelGGL((adadelta_kernel<EMA, CTL>), dim3(nblocks_for<EMA>(n)), dim3(256), 0, (hipStream_t)stream, p, g, v, u, (size_t)n,
+                       lr, rho, eps, gscale, zero_grad, counter, counter_add, ema, ctl_out);
     return (int)hipGetLastError();
+}
+
+// what a controlled entry point needs of its blocks: the words mpg_step_control wrote; a NULL ema is the launch without the average
+bool ctl_args_ok(const MpgStepCtl* ctl, const MpgEma* ema, uint64_t n) {
+    return ctl != nullptr && ctl->out != nullptr && n != 0 && (ema == nullptr || ema_args_ok(ema, n));
 }
 }  // namespace
 
@@ -280,6 +301,36 @@ extern "C" int mpg_adadelta_ema(float* p, float* g, float* v, float* u, uint64_t
                                 float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add, const MpgEma* ema, void* stream) {
     if (!ema_args_ok(ema, n)) return -1;
     return adadelta_launch<true>(p, g, v, u, n, lr, rho, eps, gscale, zero_grad, counter, counter_add, *ema, stream);
+}
+
+extern "C" int mpg_rmsprop_ctl(float* p, float* g, float* v, uint64_t n, float lr, float alpha, float eps, float gscale, int zero_grad,
+                               uint64_t* counter, uint64_t counter_add, const MpgStepCtl* ctl, const MpgEma* ema, void* stream) {
+    if (!ctl_args_ok(ctl, ema, n)) return -1;
+    if (ema != nullptr)
+        return rmsprop_launch<true, true>(p, g, v, n, lr, alpha, eps, gscale, zero_grad, counter, counter_add, *ema, stream, ctl->out);
+    return rmsprop_launch<false, true>(p, g, v, n, lr, alpha, eps, gscale, zero_grad, counter, counter_add, MpgEma{}, stream, ctl->out);
+}
+
+extern "C" int mpg_adam_ctl(float* p, float* g, float* m, float* v, float* step, uint64_t n, float lr, float beta1, float beta2, float eps,
+                            float weight_decay, float gscale, int zero_grad, uint64_t* counter, uint64_t counter_add,
+                            const MpgStepCtl* ctl, const MpgEma* ema, void* stream) {
+    if (!ctl_args_ok(ctl, ema, n) || step == nullptr) return -1;
+    if (ema != nullptr)
+        return adam_launch<true, true>(p, g, m, v, step, n, lr, beta1, beta2, eps, weight_decay, gscale, zero_grad, counter, counter_add,
+                                       *ema, stream, ctl->out);
+    return adam_launch<false, true>(p, g, m, v, step, n, lr, beta1, beta2, eps, weight_decay, gscale, zero_grad, counter, counter_add,
+                                    MpgEma{}, stream, ctl->out);
+}
+
+extern "C" int mpg_adadelta_ctl(float* p, float* g, float* v, float* u, uint64_t n, float lr, float rho, float eps, float gscale,
+                                int zero_grad, uint64_t* counter, uint64_t counter_add, const MpgStepCtl* ctl, const MpgEma* ema,
+                                void* stream) {
+    if (!ctl_args_ok(ctl, ema, n)) return -1;
+    if (ema != nullptr)
+        return adadelta_launch<true, true>(p, g, v, u, n, lr, rho, eps, gscale, zero_grad, counter, counter_add, *ema, stream,
+                                           ctl->out);
+    return adadelta_launch<false, true>(p, g, v, u, n, lr, rho, eps, gscale, zero_grad, counter, counter_add, MpgEma{}, stream,
+                                        ctl->out);
 }
 
 extern "C" int mpg_ema_update_host(float* e, const float* p_new, uint64_t n, uint32_t t, float beta, int start, int warmup) {

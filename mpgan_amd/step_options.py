@@ -2,7 +2,8 @@
 
 Each option owns its configuration, its device words and its one launch with the CPU statement beside it (the host-logic tests run
 toy modules on the CPU): ``Augmenter`` (``--aug-*``), ``AdaController`` (``Augment.adaptive_prob``), ``LabelDraw``
-(``--label-smoothing`` / ``--label-noise``).  ``train`` re-exports the public names.
+(``--label-smoothing`` / ``--label-noise``), ``StepControl`` (``LrSchedule`` / ``GradClip``: the learning rate and the gradient scale
+of an optimizer launch).  ``train`` re-exports the public names.
 """
 from __future__ import annotations
 
@@ -417,3 +418,190 @@ class LabelDraw:
         self.targets.copy_(t)
         self.extra.copy_(extra.reshape(1))
         self.drawn.copy_(torch.cat([y_real, y_fake]))
+
+
+# -- the optimizer-step control: learning-rate schedule and gradient clipping on the device ------------------------------------
+LR_KNOTS = 8                 # MPG_LR_KNOTS of include/mpgan_amd.h
+LR_KNOT_STEP_MAX = 1 << 24   # (knot steps convert to fp32 exactly up to here)
+
+
+class LrSchedule:
+    """The learning-rate schedule of ``TrainStep(lr_schedule=...)``: up to 8 knots ``(step, factor)``, the factor multiplying the
+    base learning rate; constant before the first and behind the last knot, linear in between (include/mpgan_amd.h states the
+    rule).  ``step`` counts that optimizer's own steps -- D steps for D, G steps for G.  Steps: integers,
+    strictly increasing, in [0, 2^24]; factors: finite and >= 0, held as fp32.  No knots: the factor is 1.  Cosine or exponential
+    shapes are approximated by knots: the rule stays one division and three fp32 operations with a bit-exact host twin."""
+
+    def __init__(self, knots=()):
+        knots = list(knots)
+        if len(knots) > LR_KNOTS:
+            raise ValueError(f"LrSchedule: at most {LR_KNOTS} knots, got {len(knots)}")
+        out, last = [], -1
+        for kn in knots:
+            try:
+                step, f = kn
+            except (TypeError, ValueError):
+                raise ValueError(f"LrSchedule: a knot is a (step, factor) pair, got {kn!r}") from None
+            if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step <= LR_KNOT_STEP_MAX:
+                raise ValueError(f"LrSchedule: a knot's step must be an integer in [0, 2^24], got {step!r}")
+            if step <= last:
+                raise ValueError(f"LrSchedule: knot steps must be strictly increasing, got {step!r} behind {last!r}")
+            if isinstance(f, bool) or not (0.0 <= float(f) < float("inf")):      # (a NaN fails both comparisons)
+                raise ValueError(f"LrSchedule: a knot's factor must be finite and >= 0, got {f!r}")
+            if not _f32(f) < float("inf"):
+                raise ValueError(f"LrSchedule: a knot's factor must be finite in fp32, got {f!r}")
+            out.append((step, _f32(f)))
+            last = step
+        self.knots = tuple(out)
+
+    @classmethod
+    def warmup(cls, steps: int):
+        """A linear ramp from 0 to 1 over the first ``steps`` steps, 1 from then on."""
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"LrSchedule.warmup: steps must be an integer >= 1, got {steps!r}")
+        return cls([(0, 0.0), (steps, 1.0)])
+
+    @classmethod
+    def warmup_decay(cls, warmup: int, hold_until: int, end: int, final: float = 0.0):
+        """A linear ramp from 0 to 1 over ``warmup`` steps (0: none), 1 until step ``hold_until``, a linear decay to ``final`` at step
+        ``end``, ``final`` from then on."""
+        for name, v in (("warmup", warmup), ("hold_until", hold_until), ("end", end)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"LrSchedule.warmup_decay: {name} must be an integer >= 0, got {v!r}")
+        if not warmup <= hold_until < end:
+            raise ValueError(f"LrSchedule.warmup_decay: needs warmup <= hold_until < end, got {warmup!r}, {hold_until!r}, {end!r}")
+        knots = [(0, 0.0), (warmup, 1.0)] if warmup else [(0, 1.0)]
+        if hold_until > warmup:
+            knots.append((hold_until, 1.0))
+        return cls(knots + [(end, final)])
+
+    def factor(self, t: int) -> float:
+        """The factor at step ``t`` as the kernel computes it (fp32 operations, one rounding each), held by a Python float."""
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+        ks = self.knots
+        if not ks:
+            return 1.0
+        if t <= ks[0][0]:
+            return ks[0][1]
+        if t >= ks[-1][0]:
+            return ks[-1][1]
+        k = max(i for i in range(len(ks) - 1) if ks[i][0] <= t)
+        w = f32(float(t - ks[k][0])) / f32(float(ks[k + 1][0] - ks[k][0]))
+        return float(f32(ks[k][1]) + w * (f32(ks[k + 1][1]) - f32(ks[k][1])))
+
+    def __repr__(self):
+        return f"LrSchedule({list(self.knots)})"
+
+
+class GradClip:
+    """Gradient clipping of ``TrainStep(grad_clip=...)``: ``torch.nn.utils.clip_grad_norm_`` with the L2 norm over all of a
+    network's gradients (averaged over the data-parallel ranks), as a factor on the optimizer launch's ``gscale``.
+    ``max_norm > 0`` clips; ``GradClip(None)`` clips nothing and turns the norm's read-out on (``TrainStep.step_control``)."""
+
+    def __init__(self, max_norm: Optional[float] = None):
+        if max_norm is not None and (isinstance(max_norm, bool) or not 0.0 < float(max_norm) < float("inf")):
+            raise ValueError(f"GradClip: max_norm must be finite and > 0 (or None for the norm's read-out alone), got {max_norm!r}")
+        self.max_norm = None if max_norm is None else _f32(max_norm)
+        if self.max_norm is not None and not 0.0 < self.max_norm < float("inf"):
+            raise ValueError(f"GradClip: max_norm must be finite and > 0 in fp32, got {max_norm!r}")
+
+    def __repr__(self):
+        return f"GradClip({self.max_norm})"
+
+
+class StepControl(DeviceWords):
+    """One optimizer's step control (``mpg_step_control``; include/mpgan_amd.h states the rule), in that optimizer's file: the
+    words an iteration moves are ``state`` = (t, ticket), ``base`` -- the base learning rate, which ``set_base`` writes -- and
+    ``out`` = (lr_eff, s, norm, factor), which the ``mpg_*_ctl`` optimizer launch reads.  The file carries
+    ``{t, base, knots, max_norm}``; the knots and ``max_norm`` are the step's own, as built, and the saved ones a record.  A file
+    without the key -- the reference's -- resumes the schedule where its optimizer stands: t = the loaded step count
+    (``loaded_steps``, which ``FlatParams.load_state_dict`` sets first)."""
+    KEY = "mpgan_amd_step_ctl"
+
+    def __init__(self, base: float, schedule: Optional[LrSchedule] = None, clip: Optional[GradClip] = None, device="cpu"):
+        from . import _lib
+        if schedule is not None and not isinstance(schedule, LrSchedule):
+            raise TypeError(f"lr_schedule must be a step_options.LrSchedule, got {type(schedule).__name__}")
+        if clip is not None and not isinstance(clip, GradClip):
+            raise TypeError(f"grad_clip must be a step_options.GradClip, got {type(clip).__name__}")
+        if isinstance(base, bool) or not 0.0 <= float(base) < float("inf"):
+            raise ValueError(f"the base learning rate must be finite and >= 0, got {base!r}")
+        dev = torch.device(device)
+        self.state = torch.zeros(2, device=dev, dtype=torch.uint32)
+        self.base = torch.full((1,), float(base), device=dev)
+        self.out = torch.zeros(4, device=dev)
+        self.out[0], self.out[3] = float(base), 1.0       # (what a read before the first step shows)
+        self.partials = torch.zeros(256, device=dev, dtype=torch.float64)     # scratch of the launch: not carried
+        super().__init__([self.state, self.base, self.out])
+        self.knots = () if schedule is None else schedule.knots
+        self.max_norm = None if clip is None else clip.max_norm
+        self.want_norm = clip is not None
+        self.loaded_steps = 0
+        b = _lib.MpgStepCtl()
+        b.state, b.base, b.out, b.partials = (t.data_ptr() for t in (self.state, self.base, self.out, self.partials))
+        b.nknots = len(self.knots)
+        for k, (step, f) in enumerate(self.knots):
+            b.knot_step[k], b.knot_f[k] = step, f
+        b.max_norm = 0.0 if self.max_norm is None else self.max_norm
+        b.want_norm = int(self.want_norm)
+        self.block = b
+
+    def launch(self, grad: torch.Tensor, gscale: float):
+        """The launch in front of the optimizer launch, on the current stream; ``grad``: the network's n gradients.  Host tensors:
+        ``mpg_step_control_host``, the same body."""
+        import ctypes as C
+        from . import _lib
+        g = C.c_void_p(grad.data_ptr())
+        if self.state.is_cuda:
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(_lib.lib().mpg_step_control(g, grad.numel(), gscale, C.byref(self.block), st), "mpg_step_control")
+        else:
+            _lib.check(_lib.lib().mpg_step_control_host(g, grad.numel(), gscale, C.byref(self.block)), "mpg_step_control_host")
+
+    @property
+    def t(self) -> int:
+        """Controlled steps taken so far (reads the word: synchronises)."""
+        return int(self.state[0].item())
+
+    def set_t(self, t: int):
+        if not 0 <= int(t) <= 0xFFFFFFFF:
+            raise ValueError(f"saved step-control state counts {t} steps: not a 32-bit count")
+        self.state.copy_(torch.tensor([int(t), 0], dtype=torch.int64).to(torch.uint32))
+
+    def set_base(self, lr: float):
+        """The base learning rate from the next step on, written on the current stream: a captured graph reads it from device
+        memory."""
+        if isinstance(lr, bool) or not 0.0 <= float(lr) < float("inf"):
+            raise ValueError(f"the base learning rate must be finite and >= 0, got {lr!r}")
+        self.base.fill_(float(lr))
+
+    def gmul(self, norm: float) -> float:
+        """The clipping factor the rule makes of an fp32 ``norm`` (fp32 operations, one rounding each)."""
+        if self.max_norm is None:
+            return 1.0
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+        q = f32(self.max_norm) / (f32(norm) + f32(1e-6))
+        return 1.0 if float(q) > 1.0 else float(q)
+
+    def next_lr(self) -> float:
+        """The learning rate of the step about to be taken, base * factor(t) in fp32 -- where a ``torch.optim.lr_scheduler`` leaves
+        ``param_groups[0]["lr"]`` between steps.  Synchronises."""
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+        return float(f32(float(self.base)) * f32(LrSchedule(self.knots).factor(self.t)))
+
+    def read(self) -> dict:
+        """{t, lr, factor, norm, clip}: the steps taken, and the last step's effective learning rate, schedule factor, gradient
+        norm (0 when none is computed) and clipping factor.  Synchronises."""
+        lr_eff, _, norm, factor = self.out.tolist()
+        return {"t": self.t, "lr": lr_eff, "factor": factor, "norm": norm, "clip": self.gmul(norm)}
+
+    def save(self, group):
+        group[self.KEY] = {"t": self.t, "base": float(self.base), "knots": [list(k) for k in self.knots], "max_norm": self.max_norm}
+
+    def load(self, group):
+        ent = group.get(self.KEY)
+        if ent is None:
+            self.set_t(self.loaded_steps)
+            return
+        self.set_t(int(ent["t"]))
+        self.set_base(float(ent["base"]))

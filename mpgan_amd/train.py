@@ -24,6 +24,9 @@ The training data can live on the device as well (``TrainStep(loader=data.Device
 one launch at the top of the iteration, inside the capture, in the order of a keyed shuffle.
 An averaged generator (``TrainStep(ema=Ema(...))``; Yazici et al. 2019, StyleGAN's ``G_ema``) is kept by G's optimizer launch
 itself -- two more memory streams in its loop -- and handed out as a module by ``ema_generator()``.
+Learning-rate schedules and gradient clipping (``TrainStep(lr_schedule=LrSchedule(...), grad_clip=GradClip(...))``) are settled on the
+device by one launch in front of each optimizer launch (``mpg_step_control``), which then reads its rate and its gradient scale from
+device memory: neither is a constant of the captured graphs.
 
 Two pieces of work the reference does and throws away are not done (results-neutral, SURVEY.md
 section 3.1): the D step does not back-propagate into G (its gradients are zeroed before use,
@@ -45,8 +48,8 @@ from torch import nn
 
 from . import _lib, ops, dist as mdist
 from .mpgan import MPGenerator, MPDiscriminator
-from .step_options import (ADA_DEFAULTS, AUG_SITES, AdaController, Augment, Augmenter, DeviceWords, Ema, EmaState, LabelDraw,  # noqa: F401
-                           Schedule, SeedState, ada_rule, effective_targets)
+from .step_options import (ADA_DEFAULTS, AUG_SITES, AdaController, Augment, Augmenter, DeviceWords, Ema, EmaState, GradClip,  # noqa: F401
+                           LabelDraw, LrSchedule, Schedule, SeedState, StepControl, ada_rule, effective_targets)
 
 LR = {  # setup_training.py:848-872 (lr_disc, lr_gen) per jet type for model = mpgan
     "g": (3e-5, 1e-5), "t": (6e-5, 2e-5), "q": (1.5e-5, 0.5e-5),
@@ -120,10 +123,13 @@ class FlatParams:
     ``ema`` (a ``step_options.Ema``; ``batch_size``: the jets one step consumes, which ``Ema(kimg=...)`` needs): the launch also
     folds the new parameters into their exponential moving average ``self.ema`` (``mpg_*_ema``); ``self.ema_state`` holds its
     step word and the launch's ticket.  ``tail``: that many floats more at the end of the gradient buffer (``self.tail``), which
-    travel in its all-reduce and belong to no parameter."""
+    travel in its all-reduce and belong to no parameter.  ``control`` (a ``step_options.StepControl`` on the parameters' device):
+    ``step`` issues ``mpg_step_control`` and then the ``mpg_*_ctl`` optimizer launch, which takes the learning rate and the gradient
+    scale from the control's device words instead of its arguments."""
 
     def __init__(self, module: nn.Module, optimizer: str = "rmsprop", betas=(0.9, 0.999), weight_decay: float = 5e-4,
-                 ema: Optional[Ema] = None, batch_size: Optional[int] = None, tail: int = 0):
+                 ema: Optional[Ema] = None, batch_size: Optional[int] = None, tail: int = 0,
+                 control: Optional[StepControl] = None):
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
         # Only what is TRAINED goes into the flat buffers: frozen parameters (spectral norm's power-iteration vectors,
@@ -174,6 +180,12 @@ class FlatParams:
             self._ema_block = _lib.MpgEma(C.c_void_p(self.ema.data_ptr()), C.c_void_p(self.ema_state.data_ptr()), beta, ema.start,
                                           int(ema.warmup))
             self.ema_carried = EmaState(self.flat, self.ema, self.ema_state, beta, ema.start, ema.warmup)
+        if control is not None:
+            if not isinstance(control, StepControl):
+                raise TypeError(f"control must be a step_options.StepControl, got {type(control).__name__}")
+            if control.state.device != dev:
+                raise ValueError(f"control lives on {control.state.device}, the parameters on {dev}")
+        self.control = control
 
     def zero_grad(self):
         self.grad.zero_()
@@ -183,7 +195,10 @@ class FlatParams:
         """One optimiser step over the flat buffer; ``gscale`` multiplies the gradient first; ``zero_grad``: the gradient
         buffer is cleared by the same launch, behind its last use; ``advance_seed``: the device's dropout / noise seed
         (``ops.seed_tensor``) is moved on by ``ops.SEED_STEP`` in the same launch -- ``ops.bump_seed`` of the next iteration
-        without a kernel of its own."""
+        without a kernel of its own.  With a ``control`` the launch in front settles the learning rate and the gradient scale on
+        the device (schedule and clipping; ``gscale`` goes into it) and ``lr`` is not looked at: ``control.set_base`` moves it."""
+        if self.control is not None:
+            return self._controlled_step(gscale, zero_grad, advance_seed)
         self.lr = lr
         vp = lambda t: C.c_void_p(t.data_ptr())
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -202,6 +217,28 @@ class FlatParams:
             args = (vp(self.flat), vp(self.grad), vp(self.sq), vp(self.aux), self.n, lr, 0.9, 1e-6, gscale, z, cnt, add)
         _lib.check(getattr(L, name)(*args, *tail), name)
         if not (self.flat.is_cuda and torch.cuda.is_current_stream_capturing()):  # a capture records the launch, it does not run it
+            self._host_steps += 1
+
+    def _controlled_step(self, gscale: float, zero_grad: bool, advance_seed):
+        """``mpg_step_control`` over the gradient as it stands, then the ``mpg_*_ctl`` entry point: the plain one's arguments (lr
+        and gscale unused) with the control's block and the nullable averaged-generator block in front of the stream."""
+        ctl = self.control
+        ctl.launch(self.grad, gscale)
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        z = int(zero_grad)
+        cnt, add = (None, 0) if advance_seed is None else (vp(advance_seed), ops.SEED_STEP)
+        name = "mpg_" + self.optimizer + "_ctl"
+        tail = (C.byref(ctl.block), None if self._ema_block is None else C.byref(self._ema_block), st)
+        if self.optimizer == "rmsprop":
+            args = (vp(self.flat), vp(self.grad), vp(self.sq), self.n, 0.0, 0.99, 1e-8, gscale, z, cnt, add)
+        elif self.optimizer == "adam":
+            args = (vp(self.flat), vp(self.grad), vp(self.aux), vp(self.sq), vp(self.step_count), self.n,
+                    0.0, self.betas[0], self.betas[1], 1e-8, self.weight_decay, gscale, z, cnt, add)
+        else:
+            args = (vp(self.flat), vp(self.grad), vp(self.sq), vp(self.aux), self.n, 0.0, 0.9, 1e-6, gscale, z, cnt, add)
+        _lib.check(getattr(_lib.lib(), name)(*args, *tail), name)
+        if not torch.cuda.is_current_stream_capturing():
             self._host_steps += 1
 
     def note_step(self):
@@ -238,6 +275,8 @@ class FlatParams:
         a module without frozen parameters.  ``filtered=False``: built over ALL of ``module.parameters()``, frozen ones
         included without state (what the reference's other branch gives a spectral-norm discriminator)."""
         lr = self.lr if lr is None else lr
+        if self.control is not None:     # (the effective rate, where a torch.optim.lr_scheduler would leave it)
+            lr = self.control.next_lr()
         sd = self._torch_optimizer(1e-2 if lr is None else lr).state_dict()
         k_sq, k_aux = self._STATE_KEYS[self.optimizer]
         steps = torch.tensor(self.steps, dtype=torch.float32)
@@ -292,6 +331,8 @@ class FlatParams:
         self.step_count.fill_(steps)
         self._host_steps = int(steps)
         self.lr = groups[0].get("lr", self.lr)
+        if self.control is not None:     # (a file without the control's key resumes the schedule at the optimizer's step count)
+            self.control.loaded_steps = int(steps)
         for c in self.carried:
             c.load(groups[0])
         return self.lr
@@ -402,7 +443,12 @@ class TrainStep:
     form, ``og`` + smoothing refused as the reference's BCELoss refuses it, ``w`` / ``hinge`` untouched by either.
     ``ema`` (``step_options.Ema``): an exponential moving average of G's weights, folded by G's optimizer launch (so it moves on
     the batches that train G and on no other; identical on every rank, as the weights are); ``ema_generator()`` hands it out as
-    a module, ``fG.ema`` / ``fG.ema_state`` are its buffers."""
+    a module, ``fG.ema`` / ``fG.ema_state`` are its buffers.
+    ``lr_schedule`` (``step_options.LrSchedule``) / ``grad_clip`` (``step_options.GradClip``): a learning-rate schedule over each
+    optimizer's own steps and clipping of each network's (rank-averaged) gradient by its global L2 norm, settled on the device by
+    one launch in front of each optimizer launch (``mpg_step_control``), inside the capture; each takes one object for both
+    networks or a ``(disc, gen)`` pair whose entries may be None.  ``set_lr`` moves the base rates without a recapture;
+    ``step_control`` reads step counts, rates, factors and gradient norms back."""
 
     def __init__(self, G: nn.Module, D: nn.Module, batch_size: int, num_particles: int, latent: int = 32,
                  lr_disc: float = 3e-5, lr_gen: float = 1e-5, noise_std: float = 0.2, use_graphs: bool = True,
@@ -410,7 +456,7 @@ class TrainStep:
                  optimizer: str = "rmsprop", betas=(0.9, 0.999), gp_lambda: float = 0.0,
                  graph_collectives: Optional[bool] = None, augment=None, loader=None, num_critic: int = 1, num_gen: int = 1,
                  track_epoch_losses: bool = False, label_smoothing: bool = False, label_noise: float = 0.0,
-                 ema: Optional[Ema] = None, _ada_split: bool = False):
+                 ema: Optional[Ema] = None, lr_schedule=None, grad_clip=None, _ada_split: bool = False):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
         self.dev = dev = next(G.parameters()).device
@@ -464,12 +510,24 @@ class TrainStep:
         if ema is not None and not isinstance(ema, Ema):
             raise TypeError(f"ema must be a step_options.Ema, got {type(ema).__name__}")
         # (Ema(kimg=...): the half-life counts the jets of all ranks)
-        self.fG = FlatParams(G, optimizer, betas, ema=ema, batch_size=batch_size * world_size)
+        # the step controls (``StepControl``): one per network that has a schedule or a clip; None: that optimizer's launch as it was
+        def _pair(v, name, cls):
+            pair = tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+            if len(pair) != 2 or not all(x is None or isinstance(x, cls) for x in pair):
+                raise TypeError(f"{name} must be a step_options.{cls.__name__}, None or a (disc, gen) pair of those, got {v!r}")
+            return pair
+        scheds, clips = _pair(lr_schedule, "lr_schedule", LrSchedule), _pair(grad_clip, "grad_clip", GradClip)
+        if not gpu and any(x is not None for x in scheds + clips):
+            raise ValueError("lr_schedule / grad_clip: the step control is a launch in front of the fused optimizer launch; the "
+                             "step's networks are not on a GPU")
+        ctl_D, ctl_G = (None if s is None and c is None else StepControl(lr, s, c, dev)
+                        for lr, s, c in zip((lr_disc, lr_gen), scheds, clips))
+        self.fG = FlatParams(G, optimizer, betas, ema=ema, batch_size=batch_size * world_size, control=ctl_G)
         self._ema_twin = None        # (``ema_generator`` builds it on first use)
         # (adaptive augmentation over ranks: the sign count's slot at the tail of D's gradient buffer, see ``AdaController``)
         ada_split = (augment is not None and AdaController.splits(augment, process_group, world_size, _ada_split)
                      and ops.augment_flags(augment.aug_r90, augment.aug_f, augment.aug_t, augment.aug_s) != 0)
-        self.fD = FlatParams(D, optimizer, betas, tail=1 if ada_split else 0)
+        self.fD = FlatParams(D, optimizer, betas, tail=1 if ada_split else 0, control=ctl_D)
         self._schedule = Schedule()      # (the schedule's batch index: saved with G's optimizer state, see ``batch_ndx``)
         self._seed = None
         if gpu:
@@ -569,6 +627,9 @@ class TrainStep:
             self.fG.carried.append(DeviceWords(self.epoch_sums.values()))
         if self.fG.ema_carried is not None:      # (the average and its words: the warm-up of ``capture`` puts both back)
             self.fG.carried.append(self.fG.ema_carried)
+        for f in (self.fD, self.fG):             # (the controls' words: t, base, out)
+            if f.control is not None:
+                f.carried.append(f.control)
         # a device-resident data set (data.DeviceJetLoader): its feed launch is the first thing of every iteration
         self.loader = None
         if loader is not None:
@@ -626,6 +687,32 @@ class TrainStep:
         if self.aug_p is None:
             raise RuntimeError("TrainStep was built without augmentation")
         self.aug_p.fill_(float(p))
+
+    def set_lr(self, lr_disc: Optional[float] = None, lr_gen: Optional[float] = None):
+        """The base learning rates from the next step on (None: as it is).  On a network built with ``lr_schedule=`` / ``grad_clip=``
+        the value is written to device memory on the current stream and a captured graph follows it: no recapture.  On a network
+        without, the rate is an argument of the optimizer launch and a constant of a captured graph: allowed until the first
+        capture, an error after it."""
+        for name, lr, flat in (("lr_disc", lr_disc, self.fD), ("lr_gen", lr_gen, self.fG)):
+            if lr is None:
+                continue
+            if flat.control is not None:
+                flat.control.set_base(lr)
+            elif self._graphs is not None or self._alone_graphs:
+                raise RuntimeError(f"set_lr({name}=...): the iteration has been captured with this learning rate as a constant of "
+                                   "its graphs; build the step with lr_schedule= (LrSchedule([]) keeps the rate as it is) or "
+                                   "grad_clip= to move it afterwards")
+            setattr(self, name, float(lr))
+
+    @property
+    def step_control(self) -> dict:
+        """{"D": {...}, "G": {...}}: per network ``t`` (controlled optimizer steps taken) and the last step's ``lr`` (effective),
+        ``factor`` (the schedule's), ``norm`` (of the rank-averaged gradient, 0 when none is computed) and ``clip`` (the factor the
+        clipping put on the gradient); None for a network without control.  Synchronises -- read it once per epoch, beside the
+        loss log, not per iteration."""
+        if self.fD.control is None and self.fG.control is None:
+            raise RuntimeError("TrainStep was built without lr_schedule / grad_clip")
+        return {k: None if f.control is None else f.control.read() for k, f in (("D", self.fD), ("G", self.fG))}
 
     @property
     def ada(self) -> dict:

@@ -16,6 +16,10 @@ AUG = train.Augment(aug_r90=True, aug_f=True, aug_t=True, aug_s=True, aug_prob=0
 SN = bool(os.environ.get("OPC_SN"))
 # (OPC_EMA=1: the averaged generator, folded by G's optimizer launch -- the default step's counts, launch for launch)
 EMA = train.Ema(kimg=10) if os.environ.get("OPC_EMA") else None
+# (OPC_CTL=1: a learning-rate schedule and a gradient clip on both networks -- the default step's library launches plus the two
+# mpg_step_control launches, 43 + 2, and its ATen launches unchanged at 87)
+CTL = dict(lr_schedule=train.LrSchedule.warmup_decay(100, 5000, 6000, 0.1), grad_clip=train.GradClip(1.0)) if os.environ.get("OPC_CTL") \
+    else {}
 
 
 def count(title):
@@ -24,7 +28,7 @@ def count(title):
         G, D = train.default_gapt(30, device=dev)
     else:
         G, D = train.default_mpgan(30, device=dev, spectral_norm_gen=SN, spectral_norm_disc=SN)
-    ts = train.TrainStep(G, D, BATCH, 30, latent=64 if os.environ.get("OPC_GAPT") else 32, use_graphs=False, augment=AUG, ema=EMA)
+    ts = train.TrainStep(G, D, BATCH, 30, latent=64 if os.environ.get("OPC_GAPT") else 32, use_graphs=False, augment=AUG, ema=EMA, **CTL)
     data, labels = synthetic_jets(BATCH, 30, seed=1, dist="gluon")
     ts.set_batch(data.to(dev), labels.to(dev))
     for _ in range(3): ts.step()

@@ -1,7 +1,7 @@
 """What one option of the captured training iteration costs next to the step without it, on one GPU.  One JSON object per line on
 stdout and in --out.
 
-    python tools/step_option_bench.py --option {labels,ada,critic,sn,ema} [--reps 10] [--out profiles/<option>_bench.jsonl]
+    python tools/step_option_bench.py --option {labels,ada,critic,sn,ema,ctl} [--reps 10] [--out profiles/<option>_bench.jsonl]
 
 MPGAN at N = 30, B = 256, the captured iteration, one process.  Two steps over the same weights and batch -- a baseline and the
 same with the option on -- and, where the option adds one launch to the D segment, that launch on its own outside any graph:
@@ -20,13 +20,19 @@ sn       three steps: a default_step (for scale), and spectral norm in G and D w
 ema      baseline: the default step.  Option: ``ema=Ema(kimg=10)`` -- G's optimizer launch also folds the averaged generator; no
          launch is added, so there is no lone launch to time.  Rows: a default_step, b ema_step.
 
+ctl      baseline: the default step.  Option: ``lr_schedule=LrSchedule.warmup_decay(100, 5000, 6000, 0.1), grad_clip=GradClip(1.0)``
+         on both networks (+ ``mpg_step_control`` in front of each optimizer launch, which reads its rate and its gradient scale
+         from memory).  Rows: a default_step, b ctl_step, c ctl_launch_D, d ctl_launch_G (each network's launch alone, over a
+         gradient of that network's size).
+
 Every ``step()`` and every lone launch sits between two HIP events of its own -- in all rows alike, so that what an event pair
 costs cancels between them.  A repetition is --batches steps of each kind (critic: two full cycles of the schedule) taken
 alternately, then as many lone launches; the rows are the means within a repetition, reported as median / min / max over --reps
 repetitions behind a warm-up that captures every graph.  No speed claim is made.  The last line states what the option is held to.
 labels, ada: (b) - (a) is at most the run-to-run spread of (a) (max - min of its repetitions) plus (c); ada also: (d) - (b) is at
 most the spread of (b) plus (f) -- the baseline of the split route is the unchanged one-launch route of the same process.  critic: (c) within
-the spread of (a), and (b) <= (a).  ema: (b) - (a) is at most the run-to-run spread of (a).
+the spread of (a), and (b) <= (a).  ema: (b) - (a) is at most the run-to-run spread of (a).  ctl: (b) - (a) is at most the spread of
+(a) plus (c) plus (d).
 """
 import argparse
 import json
@@ -176,6 +182,45 @@ def ada_bench(args, emit):
           "G_loss": float(split.G_loss), "ada": split.ada})
 
 
+def ctl_bench(args, emit):
+    """--option ctl: the default step and the step with a schedule and a clip on both networks, alternated, every ``step()`` between
+    two HIP events; then each network's ``mpg_step_control`` launch alone, over a gradient of that network's size."""
+    from mpgan_amd.step_options import GradClip, LrSchedule, StepControl
+    rows = ("a default_step", "b ctl_step", "c ctl_launch_D", "d ctl_launch_G")
+    sched, clip = LrSchedule.warmup_decay(100, 5000, 6000, 0.1), GradClip(1.0)
+    torch.manual_seed(0)
+    base, opt = build(), build(lr_schedule=sched, grad_clip=clip)
+    launches = []
+    for flat, lr in ((opt.fD, opt.lr_disc), (opt.fG, opt.lr_gen)):
+        ctl, g = StepControl(lr, sched, clip, "cuda"), torch.randn(flat.n, device="cuda")
+        launches.append(lambda ctl=ctl, g=g: ctl.launch(g, 1.0))
+    for _ in range(3):   # warm-up: captures every graph
+        for fn in (base.step, opt.step, *launches):
+            fn()
+    torch.cuda.synchronize()
+    us = {r: [] for r in rows}
+    for _ in range(args.reps):
+        t = {r: [] for r in rows}
+        for _ in range(args.batches):        # (alternated: the rows share whatever the box does meanwhile)
+            t[rows[0]].append(timed(base.step))
+            t[rows[1]].append(timed(opt.step))
+        for r, fn in zip(rows[2:], launches):
+            t[r] = [timed(fn) for _ in range(args.batches)]
+        for r in rows:
+            us[r].append(float(np.mean(t[r])))
+    med = {}
+    for name, v in us.items():
+        med[name] = float(np.median(v))
+        emit({"model": "mpgan", "B": B, "N": N, "lr_knots": [list(k) for k in sched.knots], "max_norm": clip.max_norm, "n_D": opt.fD.n,
+              "n_G": opt.fG.n, "row": name, "reps": args.reps, "batches_per_rep": args.batches, "median_us": med[name],
+              "min_us": float(np.min(v)), "max_us": float(np.max(v))})
+    diff, spread = med[rows[1]] - med[rows[0]], float(np.max(us[rows[0]]) - np.min(us[rows[0]]))
+    emit({"model": "mpgan", "B": B, "row": "condition", "ctl_minus_default_us": diff, "spread_default_us": spread,
+          "ctl_launch_D_us": med[rows[2]], "ctl_launch_G_us": med[rows[3]],
+          "within_spread_plus_launches": bool(diff <= spread + med[rows[2]] + med[rows[3]]), "D_loss": float(opt.D_loss),
+          "G_loss": float(opt.G_loss), "step_control": opt.step_control})
+
+
 def sn_bench(args, emit):
     """--option sn: three captured steps in one process -- the default step (for scale), and spectral norm in G and D built under
     ``ops.OPTIONS["sn_fused"]`` off (a launch per wrapped layer, MPLayer._forward_edges) and on (one grouped launch per network
@@ -216,7 +261,7 @@ def sn_bench(args, emit):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--option", choices=sorted([*OPTIONS, "ada", "sn"]), required=True)
+    ap.add_argument("--option", choices=sorted([*OPTIONS, "ada", "sn", "ctl"]), required=True)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--batches", type=int, default=10, help="steps of each kind per repetition (critic: two cycles of the schedule)")
     ap.add_argument("--num-critic", type=int, default=5)
@@ -229,6 +274,8 @@ def main():
         return sn_bench(args, emit)
     if args.option == "ada":
         return ada_bench(args, emit)
+    if args.option == "ctl":
+        return ctl_bench(args, emit)
     o = OPTIONS[args.option]
     critic = args.option == "critic"
     batches = 2 * args.num_critic if critic else args.batches
