@@ -361,6 +361,34 @@ typedef struct MpgKnnEdgeBwd {
 } MpgKnnEdgeBwd;
 int mpg_knn_edge_bwd(const MpgKnnEdgeBwd* p, void* stream);
 
+/* mpg_knn_edge_jvp: the second-order half of the same span -- what a twice-differentiable edge aggregation (the gradient penalty,
+ * train.py:286-324) needs beside mpg_knn_edge_fwd / _bwd -- on the same rows, tiles and parked gates (E1 / E2 > 0 where kept,
+ * sign3, the regenerated keep words).  Two modes:
+ *   dot (ta == NULL)   E3_row = gate3 (W3 E2_row + b3) from the parked E2;  rowdot[row] = <E3_row, dagg_i>;
+ *                      dmask[b,j] = agg_scale * sum of rowdot over the rows that list sender j, in ascending receiver order:
+ *                      the gradient of sum_i <agg_i, dagg_i> with respect to mask_j.
+ *   jvp (ta != NULL)   T1 = gate1 (ta_i + tc_j), T2 = gate2 W2 T1, T3 = gate3 W3 T2 (tangent rows split hi + lo in fp16 in a
+ *                      power-of-two unit of their own row, three terms);  T1 [B*N*k, 96] and T2 [B*N*k, 160] leave row-major in
+ *                      fp32 (dropout scale included) when non-NULL;  aggt[b,i,:] = agg_scale * sum_r (mask_j T3 + mu_j E3) in
+ *                      ascending r when non-NULL (mu NULL: no E3 term);  rowdot[row] = <T3_row, dagg_i> and dmask as above
+ *                      when non-NULL (both or none).
+ * A row takes part when mask_j != 0 or mu_j != 0; a tile without such a row is skipped, its rows written as zeros.
+ * Errors as mpg_knn_edge_fwd: -1 sizes, -2 a required pointer is NULL, -3 E1 / E2 / sign3 (or rowdot / dmask, or ta / tc) not
+ * all-or-none, -4 alpha outside [0, 1], -5 a row stride below its width or not a multiple of 4, -6 RW * k * 784 bytes of LDS
+ * above 160 KiB, -7 B * N * N beyond the 32-bit dropout key.  No atomics; nothing depends on which wave finishes first. */
+typedef struct MpgKnnEdgeJvp {
+    const unsigned int* nbr; const float* mask; const float* mu;   /* mask, mu: [B*N] or NULL                        */
+    const float* dagg; int ld_dagg;                                 /* [B*N, >= 192]                                  */
+    const float* ta; const float* tc; int ld_t;                     /* [B*N, >= 96] each: u W1a^T, u W1b^T (no bias)  */
+    const void* W2img; const void* W3img; const float* b3;          /* as MpgKnnEdgeFwd                               */
+    const float* E1; const float* E2; const unsigned short* sign3;  /* from mpg_knn_edge_fwd                          */
+    float* T1; float* T2; float* aggt; float* rowdot; float* dmask;
+    int B, N, k, RW;
+    float alpha, agg_scale;
+    const uint64_t* seed; uint32_t tag_base, thr; float dscale;
+} MpgKnnEdgeJvp;
+int mpg_knn_edge_jvp(const MpgKnnEdgeJvp* p, void* stream);
+
 /* ---- attention core of GAPT's MAB ---------------------------------------------------------------
  * mpg_attn_fwd / mpg_attn_bwd: per (jet b, head h), d = E / H:
  *     P = softmax_s( q_h k_h^T / sqrt(d)  with keys s where ignore[b,s] != 0 at -inf ),   o_h = P v_h

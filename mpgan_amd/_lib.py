@@ -111,6 +111,20 @@ class MpgKnnEdgeBwd(C.Structure):
     ]
 
 
+class MpgKnnEdgeJvp(C.Structure):
+    _fields_ = [
+        ("nbr", _fp), ("mask", _fp), ("mu", _fp),
+        ("dagg", _fp), ("ld_dagg", C.c_int),
+        ("ta", _fp), ("tc", _fp), ("ld_t", C.c_int),
+        ("W2img", _fp), ("W3img", _fp), ("b3", _fp),
+        ("E1", _fp), ("E2", _fp), ("sign3", _fp),
+        ("T1", _fp), ("T2", _fp), ("aggt", _fp), ("rowdot", _fp), ("dmask", _fp),
+        ("B", C.c_int), ("N", C.c_int), ("k", C.c_int), ("RW", C.c_int),
+        ("alpha", C.c_float), ("agg_scale", C.c_float),
+        ("seed", _fp), ("tag_base", C.c_uint32), ("thr", C.c_uint32), ("dscale", C.c_float),
+    ]
+
+
 class MpgReduceJob(C.Structure):
     _fields_ = [
         ("part", _fp), ("S", C.c_int), ("N", C.c_int), ("K", C.c_int), ("has_bias", C.c_int),
@@ -280,6 +294,7 @@ SIGNATURES = {
     "mpg_mab_chain_fwd": (C.c_int, [C.POINTER(MpgMabChain), C.c_void_p]),
     "mpg_knn_edge_fwd": (C.c_int, [C.POINTER(MpgKnnEdgeFwd), C.c_void_p]),
     "mpg_knn_edge_bwd": (C.c_int, [C.POINTER(MpgKnnEdgeBwd), C.c_void_p]),
+    "mpg_knn_edge_jvp": (C.c_int, [C.POINTER(MpgKnnEdgeJvp), C.c_void_p]),
     "mpg_knn_sets": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_void_p]),
     "mpg_rank_mask": (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_void_p]),
     "mpg_jet_order": (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_void_p]),

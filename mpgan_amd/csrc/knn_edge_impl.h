@@ -120,4 +120,23 @@ MPG_DEV void knn_layer(const KnnImg& img, int nfrag, const V* bh, const V* bl, I
     });
 }
 
+// ---- what the kernels that take a GRADIENT or TANGENT row as the B operand share (knn_edge_bwd.hip, knn_edge_jvp.hip)
+// power-of-two unit of a row whose largest magnitude is `mx`: mx * unit in [2^10, 2^11) -- inside fp16's range with 22
+// significand bits for the hi + lo pair --, 1 for a row of zeros; `inv` = 1 / unit, exact
+MPG_DEV void knn_unit(float mx, float& unit, float& inv) {
+    const int ex = (int)((__builtin_bit_cast(uint32_t, mx) >> 23) & 0xffu);
+    int f = ex == 0 ? 127 : 264 - ex;
+    f = max(30, min(224, f));
+    unit = __builtin_bit_cast(float, (uint32_t)f << 23);
+    inv = __builtin_bit_cast(float, (uint32_t)(254 - f) << 23);
+}
+
+MPG_DEV float knn_row_max(float mx) { return fmaxf(mx, __shfl_xor(mx, 32)); }   // (with the row's other lane half)
+
+// four consecutive floats of a dagg row: one 16-byte load where the rows are 16-byte aligned (`vec`, uniform), else four loads
+MPG_DEV void knn_ld4(const float* q, bool vec, float* o) {
+    if (vec) { const float4 d4 = ld4(q); o[0] = d4.x; o[1] = d4.y; o[2] = d4.z; o[3] = d4.w; }
+    else { o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[3]; }
+}
+
 }  // namespace

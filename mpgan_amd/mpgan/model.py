@@ -314,6 +314,8 @@ class MPLayer(nn.Module):
         assert not (use_mask and mask is None), "need ``mask`` tensor if using ``use_mask`` option"
         assert not (self.clabels and labels is None), "need ``labels`` tensor if using ``clabels`` option"
         assert not (self.mask_fne_np and num_jet_particles is None), "need ``num_jet_particles`` tensor if using ``mask_fne_np`` option"
+        if x.is_cuda and ops.double_backward_on(x.device) and self.gp_rows_ok(x.shape[0], x.shape[1], True):
+            return self._forward_rows(x, use_mask, mask)
         if (not self.fused or (x.is_cuda and ops.double_backward_on(x.device))
                 or (self.spectral_norm and not ops.OPTIONS["sn_fused"])):
             return self._forward_edges(x, use_mask, mask, labels, num_jet_particles)
@@ -352,6 +354,33 @@ class MPLayer(nn.Module):
             V1, fn[0].bias, V2, fn[1].bias, V3, fn[2].bias, es, xfn,
             ops.MPLayerSettings(self.sum, self.fe.leaky_relu_alpha, self.fe.dropout_p, self.training, packed, nbr, self.num_knn,
                                 self.n_es, handoff, not torch.is_grad_enabled(), not self.spectral_norm))
+
+    def gp_rows_ok(self, B: int, N: int, double_backward: bool, options: dict = None) -> bool:
+        """``ops.gp_rows_route`` with this layer's facts: would a call on B jets of N particles inside ``ops.double_backward_route``
+        take the twice-differentiable row kernels (``_forward_rows``)?  Host only."""
+        return ops.gp_rows_route(B, N, N if self.fully_connected else self.num_knn, fused=self.fused, n_es=self.n_es,
+                                 diff_cols=self._diff_cols, spectral_norm=self.spectral_norm,
+                                 batch_norm=self.fe.batch_norm or self.fn.batch_norm, double_backward=double_backward, options=options)
+
+    def _forward_rows(self, x: Tensor, use_mask: bool, mask: Tensor) -> Tensor:
+        """The twice-differentiable route on the row kernels (``ops.EdgeRowsFn``): the edge aggregation as one op over explicit edge
+        rows -- a fully connected layer is k = N with every sender listed, a k-NN layer takes its ``ops.knn_sets`` words, constants as
+        on the other routes --, the node network in its ``_forward_dd`` form.  The edge dropout's tags come from ``ops.next_tag``
+        and its seed is the device seed, like every fused call's.  The penalty differentiates with respect to the input alone
+        (train.py:304-311), so that first derivative (``create_graph=True``) leaves the parameter gradients out; the penalty's
+        backward has them, of both orders."""
+        B, N, _ = x.shape
+        fe, nbr = self.fe.net, None
+        if not self.fully_connected:
+            if self.num_knn + int(not self.self_loops) > N:
+                raise ValueError(f"num_knn = {self.num_knn} neighbours (self_loops = {self.self_loops}) out of {N} nodes")
+            with torch.no_grad():
+                nbr = ops.knn_sets(x, mask if use_mask else None, self.num_knn, self.self_loops)
+        agg = ops.EdgeRowsFn.apply(x, mask if use_mask else None, fe[0].weight, fe[0].bias, fe[1].weight, fe[1].bias, fe[2].weight,
+                                   fe[2].bias, ops.EdgeRowsSettings(self.sum, self.fe.leaky_relu_alpha, self.fe.dropout_p, self.training,
+                                                                    self._packed(), nbr, self.num_knn, None, False))
+        h = torch.cat((agg, x), dim=2).reshape(B * N, -1)
+        return self.fn(h.contiguous()).reshape(B, N, self.output_node_size)
 
     def _folded_w1(self, W1: Tensor) -> Tensor:
         """fe.net.0.weight with the coordinate-difference columns folded into the node columns: the reference appends

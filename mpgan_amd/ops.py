@@ -2,7 +2,8 @@
 
 Everything here hands raw device pointers + sizes to libmpgan_amd.so on torch's current HIP
 stream; torch is used for memory, autograd bookkeeping and a few tiny reductions only.  There is
-no CPU path: tensors must live on a gfx950 device.
+no CPU path: tensors must live on a gfx950 device.  (One exception, for checking a derivative rule in fp64 without a GPU:
+``EdgeRowsFn`` / ``EdgeRowsVJPFn`` evaluate CPU tensors with the same formulas in plain torch.)
 """
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import MpgGemm, MpgEdgeFwd, MpgEdgeBwd, MpgEdgeDw, MpgKnnEdgeFwd, MpgKnnEdgeBwd, MpgPackJob, MpgChain, MpgReduceJob, check
+from ._lib import MpgGemm, MpgEdgeFwd, MpgEdgeBwd, MpgEdgeDw, MpgKnnEdgeFwd, MpgKnnEdgeBwd, MpgKnnEdgeJvp, MpgPackJob, MpgChain, MpgReduceJob, check
 
 H1, H2, H3 = 96, 160, 192
 # Exact power-of-two operand scales of the forward products (csrc/edge_common.h): fp16 hi/lo pairs keep their 22 bits
@@ -58,6 +59,10 @@ OPTIONS = {
     # B * N * k rows of the neighbour sets) instead of the dense kernels with the neighbour bit as a factor over all N * N pairs;
     # see ``knn_sparse_route`` for what it covers.  Off unless asked for: MPG_KNN_SPARSE=1.
     "knn_sparse": os.environ.get("MPG_KNN_SPARSE", "0") not in ("", "0"),
+    # the gradient penalty's edge aggregation on the row kernels (``EdgeRowsFn``: mpg_knn_edge_fwd / _bwd / _jvp, twice differentiable)
+    # instead of the materialised edge matrix of MPLayer._forward_edges, for the layers ``gp_rows_route`` covers.  Off unless asked
+    # for: MPG_GP_ROWS=1, or TrainStep(gp_rows=True).
+    "gp_rows": os.environ.get("MPG_GP_ROWS", "0") not in ("", "0"),
 }
 NUM_CUS = 256
 # Forward products (they decide LeakyReLU signs) are split as fp16 hi/lo with the operand scales below (~2^-21 per
@@ -1368,6 +1373,335 @@ def _knn_backward(ctx, call, ks, gy2, fng, tg, dx):
             wb.flush()
     if dx is not None:
         run_chain(_dx_chain(call, fng.dh0, dx, dadc))
+
+
+# ---- the edge aggregation as a twice-differentiable op on the row kernels (the gradient penalty, train.py:286-324)
+# One MPLayer's  agg_i = s sum_j m_j E3_ij  (DESIGN.md section 4 has the rule):
+#   EdgeRowsFn      forward: agg (``mpg_knn_edge_fwd`` over explicit edge rows -- a fully connected layer is k = N with all-ones neighbour
+#                   words --, E1 / E2 / sign3 parked); backward: ``EdgeRowsVJPFn.apply``, so the first derivative is itself a node.
+#   EdgeRowsVJPFn   forward: x_bar, m_bar and the parameter gradients for a cotangent a_bar (``mpg_knn_edge_bwd``, the dot mode of
+#                   ``mpg_knn_edge_jvp``, the weight-gradient GEMMs); backward (once differentiable): the gradients of
+#                   Phi = <u, x_bar> + <mu, m_bar> (the jvp mode of ``mpg_knn_edge_jvp``; ``mpg_knn_edge_bwd`` with mu as the mask).
+# The gates (dropout keep-and-scale times LeakyReLU') are constants of the call, as they are almost everywhere.  CPU tensors take
+# the same formulas in plain torch, in the tensors' dtype, with explicit keep masks: the rule can be checked in fp64 without a GPU.
+GP_ROWS_PARK_ROW_BYTES = KNN_PARK_ROW_BYTES + (H1 + H2) * 4 + 2 * KNN_GRAD_ROW_BYTES   # E1 E2 sign3 | T1 T2 | two sets of dZ1..3
+# a sender whose mask is exactly 0 is no sender to the row kernels (its rows are neither computed nor parked), but m_bar_j =
+# s sum_i <E3_ij, a_bar_i> does not vanish with m_j: where the mask takes a gradient its exact zeros enter the kernels as this factor
+ROWS_MASK_FLOOR = 2.0 ** -64
+EdgeRowsSettings = namedtuple("EdgeRowsSettings", "sum_agg alpha p_drop training packed nbr k keeps param_grads",
+                              defaults=(0.0, True, None, None, 0, None, True))
+
+
+class PackedEdgeRows(_PackedSet):
+    """The weight images ``EdgeRowsFn`` needs, for callers without an MPLayer's ``PackedMPLayer`` (which has them under the same names)."""
+
+    def __init__(self, params, F, dscale, f16):
+        W1, W2, W3 = params
+        self.F, self.dscale, self.f16 = F, float(dscale), bool(f16)
+        super().__init__(params, {
+            "W2": (W2, H2, H1, 0, dscale * SC_W2, f16, 0, 0), "W3": (W3, H3, H2, 0, dscale * SC_W3, f16, 0, 0),
+            "W3T": (W3, H2, H3, 1, dscale * SC_W3, True, 0, 0), "W2T": (W2, H1, H2, 1, dscale * SC_W2, True, 0, 0),
+            "W1S": (W1, 2 * H1, F, 0, SC_WN, f16, H1, F),
+        })
+
+
+def gp_rows_route(B, N, k, *, fused=True, n_es=0, diff_cols=0, spectral_norm=False, batch_norm=False, double_backward=False,
+                  options=None):
+    """Does an MPLayer call inside ``double_backward_route`` take ``EdgeRowsFn`` instead of the materialised edge matrix?  Only with
+    the option on (``OPTIONS["gp_rows"]``), for a layer of the fused widths (``fused``) without edge scalars, difference columns,
+    spectral norm or batch norm, N <= ``KNN_MAX_N`` and rows that ``knn_plan`` accepts; ``k`` = N for a fully connected layer.  Host only."""
+    opt = OPTIONS if options is None else options
+    if not (opt.get("gp_rows") and double_backward and fused and n_es == 0 and not diff_cols and not spectral_norm and not batch_norm):
+        return False
+    if not (0 < k <= N <= KNN_MAX_N):
+        return False
+    try:
+        knn_plan(B, N, k, True)
+    except (ValueError, RuntimeError):
+        return False
+    return True
+
+
+class _RowsState:
+    """What one ``EdgeRowsFn`` call keeps for its two derivatives beside its saved inputs (constants of the call)."""
+    __slots__ = ("cpu", "B", "N", "F", "k", "kp", "nbr", "agg_scale", "alpha", "thr", "dscale", "tag", "pk", "seed_t", "m1",
+                 "E1", "E2", "E3", "sign3", "G", "w", "adj", "param_grads")
+
+
+def _rows_gates_cpu(x, W1, b1, W2, b2, W3, b3, alpha, keeps):
+    F = x.shape[-1]
+    a, c = x @ W1[:, :F].t() + b1, x @ W1[:, F:2 * F].t()
+    one = lambda Z, K: torch.where(Z > 0, torch.ones_like(Z), torch.full_like(Z, alpha)) * (1 if K is None else K)
+    K1, K2, K3 = keeps if keeps is not None else (None, None, None)
+    Z1 = a.unsqueeze(2) + c.unsqueeze(1)              # [B, i, j, H1]
+    G1 = one(Z1, K1); E1 = G1 * Z1
+    Z2 = E1 @ W2.t() + b2
+    G2 = one(Z2, K2); E2 = G2 * Z2
+    Z3 = E2 @ W3.t() + b3
+    G3 = one(Z3, K3); E3 = G3 * Z3
+    return (G1, G2, G3), (E1, E2, E3)
+
+
+def _rows_chain_cpu(st, W2, W3, wt, abar):
+    # the first-order chain with the per-edge weight ``wt`` [B, i, j, 1] in the mask's place: (dZ1, dZ2, dZ3)
+    G1, G2, G3 = st.G
+    dZ3 = G3 * (st.agg_scale * wt * abar.unsqueeze(2))
+    dZ2 = G2 * (dZ3 @ W3)
+    dZ1 = G1 * (dZ2 @ W2)
+    return dZ1, dZ2, dZ3
+
+
+def _outer(dz, e):
+    return torch.einsum("bijo,bijk->ok", dz, e)
+
+
+def _rows_words(B, N, dev):
+    return torch.full((B * N, (N + 31) // 32), -1, device=dev, dtype=torch.int32)   # every sender: the fully connected layer
+
+
+def _rows_bwd_launch(st, mask1, abar2, need_w):
+    # ``mpg_knn_edge_bwd`` of the call behind ``st`` with ``mask1`` as the senders' weights: (dZ1, dZ2, dZ3, da | dc)
+    V, dev = st.B * st.N, abar2.device
+    dZ1 = torch.empty((V * st.k, H1), device=dev, dtype=torch.float32)
+    dZ2 = torch.empty((V * st.k, H2), device=dev, dtype=torch.float32) if need_w else None
+    dZ3 = torch.empty((V * st.k, H3), device=dev, dtype=torch.float32) if need_w else None
+    dadc = torch.empty((V, 2 * H1), device=dev, dtype=torch.float32)
+    e = MpgKnnEdgeBwd()
+    e.mask, e.nbr, e.W3Timg, e.W2Timg = _p(mask1), _p(st.nbr), st.pk.ptr("W3T"), st.pk.ptr("W2T")
+    e.dagg, e.ld_dagg = _p(abar2), abar2.stride(0)
+    e.B, e.N, e.k, e.RW, e.alpha, e.agg_scale = st.B, st.N, st.k, st.kp.RW, st.alpha, st.agg_scale
+    e.seed, e.tag_base, e.thr, e.dscale = _p(st.seed_t), st.tag, st.thr, st.dscale
+    e.E1, e.E2, e.sign3 = _p(st.E1), _p(st.E2), _p(st.sign3)
+    e.dZ1, e.dZ2, e.dZ3, e.dadc = _p(dZ1), _p(dZ2), _p(dZ3), _p(dadc)
+    check(_lib.lib().mpg_knn_edge_bwd(C.byref(e), _stream()), "mpg_knn_edge_bwd")
+    return dZ1, dZ2, dZ3, dadc
+
+
+def _rows_jvp_desc(st, abar2, b3):
+    e = MpgKnnEdgeJvp()
+    e.nbr, e.mask, e.dagg, e.ld_dagg = _p(st.nbr), _p(st.m1), _p(abar2), abar2.stride(0)
+    e.W2img, e.W3img, e.b3 = st.pk.ptr("W2"), st.pk.ptr("W3"), _p(b3)
+    e.E1, e.E2, e.sign3 = _p(st.E1), _p(st.E2), _p(st.sign3)
+    e.B, e.N, e.k, e.RW, e.alpha, e.agg_scale = st.B, st.N, st.k, st.kp.RW, st.alpha, st.agg_scale
+    e.seed, e.tag_base, e.thr, e.dscale = _p(st.seed_t), st.tag, st.thr, st.dscale
+    return e
+
+
+def _rows_dx(W1, F, dadc):
+    # W1a^T da + W1b^T dc  [V, F]
+    dx = linear_bwd_data(dadc[:, :H1], W1, w_col0=0, w_cols=F)
+    return linear_bwd_data(dadc[:, H1:], W1, w_col0=F, w_cols=F, out=dx, accumulate=True)
+
+
+class EdgeRowsFn(torch.autograd.Function):
+    """agg [B, N, 192] = s sum_j m_j fe([x_i ; x_j]) of one MPLayer (mpgan/model.py:256-267), twice differentiable: see above.
+    ``mask``: [B, N] / [B, N, 1] real-valued sender weights or None; ``settings``: an ``EdgeRowsSettings`` -- ``packed`` a
+    ``PackedMPLayer`` / ``PackedEdgeRows`` for the call's dropout scale (built for the call when None), ``nbr`` the neighbour words of
+    ``knn_sets`` with ``k`` neighbours (None: fully connected); on the CPU ``nbr`` is a 0/1 adjacency [B, N, N] and ``keeps`` the three
+    keep-and-scale masks [B, N, N, 96 / 160 / 192] (None: no dropout).  ``param_grads`` False: a first derivative taken with
+    ``create_graph=True`` leaves the parameter gradients out (None) -- the penalty differentiates with respect to the input alone
+    there (train.py:304-311), and four GEMMs over all edge rows would be formed for nobody; a plain backward through the op (the
+    penalty's own backward reaches it again: D's pooled output and the next layer's input depend on agg) always has them."""
+
+    @staticmethod
+    def forward(ctx, x, mask, W1, b1, W2, b2, W3, b3, settings):
+        s = settings
+        B, N, F = x.shape
+        st = _RowsState()
+        st.cpu, st.B, st.N, st.F, st.alpha, st.param_grads = not x.is_cuda, B, N, F, float(s.alpha), bool(s.param_grads)
+        st.k = int(s.k) if s.nbr is not None else N
+        st.agg_scale = 1.0 if s.sum_agg else 1.0 / st.k
+        ctx.st, ctx.mask_shape = st, None if mask is None else tuple(mask.shape)
+        ctx.save_for_backward(x, mask, W1, b1, W2, b2, W3, b3)
+        if st.cpu:
+            st.G, E = _rows_gates_cpu(x, W1, b1, W2, b2, W3, b3, st.alpha, s.keeps)
+            st.E1, st.E2, st.E3 = E
+            st.adj = torch.ones((B, N, N, 1), dtype=x.dtype) if s.nbr is None else s.nbr.to(x.dtype).reshape(B, N, N, 1)
+            st.w = st.adj if mask is None else st.adj * mask.reshape(B, 1, N, 1)
+            return st.agg_scale * (st.w * st.E3).sum(2)
+        _chk(x, "x")
+        V, dev = B * N, x.device
+        st.kp = knn_plan(B, N, st.k, True)   # (raises before any allocation or launch)
+        st.thr, st.dscale = drop_params(s.p_drop) if s.training else (0, 1.0)
+        st.seed_t, st.tag = seed_tensor(dev), next_tag(dev, "edge_rows", st.thr)
+        pk = s.packed
+        if pk is None or pk.dscale != st.dscale or pk.f16 != FWD_F16:
+            pk = PackedEdgeRows((W1, W2, W3), F, st.dscale, FWD_F16)
+        st.pk = pk.ensure()
+        st.nbr = s.nbr if s.nbr is not None else _rows_words(B, N, dev)
+        x2 = _unit_cols(x.reshape(V, F))
+        st.m1 = None
+        if mask is not None:
+            st.m1 = mask.detach().reshape(V).contiguous()
+            if ctx.needs_input_grad[1]:
+                st.m1 = torch.where(st.m1 == 0, torch.full_like(st.m1, ROWS_MASK_FLOOR), st.m1)
+        ac = torch.empty((V, 2 * H1), device=dev, dtype=torch.float32)
+        run_chain(_ac_chain(st.pk, b1, x2, ac, MPLayerCfg(B, N, F, st.agg_scale, st.alpha, st.thr, st.dscale, st.tag, 1, FWD_F16, 0)))
+        st.E1 = torch.empty((V * st.k, H1), device=dev, dtype=torch.float32)
+        st.E2 = torch.empty((V * st.k, H2), device=dev, dtype=torch.float32)
+        st.sign3 = torch.empty((V * st.k, 6, 2), device=dev, dtype=torch.int16)
+        agg = torch.empty((V, H3), device=dev, dtype=torch.float32)
+        e = MpgKnnEdgeFwd()
+        e.a, e.c, e.ld_ac, e.mask, e.nbr = _p(ac), _p(ac, H1), 2 * H1, _p(st.m1), _p(st.nbr)
+        e.W2img, e.W3img, e.b2, e.b3, e.agg = st.pk.ptr("W2"), st.pk.ptr("W3"), _p(b2), _p(b3), _p(agg)
+        e.B, e.N, e.k, e.RW, e.alpha, e.agg_scale = B, N, st.k, st.kp.RW, st.alpha, st.agg_scale
+        e.seed, e.tag_base, e.thr, e.dscale = _p(st.seed_t), st.tag, st.thr, st.dscale
+        e.E1, e.E2, e.sign3 = _p(st.E1), _p(st.E2), _p(st.sign3)
+        check(_lib.lib().mpg_knn_edge_fwd(C.byref(e), _stream()), "mpg_knn_edge_fwd")
+        return agg.reshape(B, N, H3)
+
+    @staticmethod
+    def backward(ctx, abar):
+        x, mask, W1, b1, W2, b2, W3, b3 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        again = torch.is_grad_enabled()     # (create_graph=True: this derivative will be differentiated itself)
+        flags = (need[0], mask is not None and need[1], any(need[2:8]) and (ctx.st.param_grads or not again), again)
+        out = EdgeRowsVJPFn.apply(abar, x, mask, W1, b1, W2, b2, W3, b3, ctx.st, flags, ctx.mask_shape)
+        return (*out, None)
+
+
+class EdgeRowsVJPFn(torch.autograd.Function):
+    """The first derivative of ``EdgeRowsFn`` as a function of (a_bar, x, mask, parameters): (x_bar, m_bar, W1_bar, b1_bar, ...,
+    b3_bar).  Its own backward takes cotangents ``u`` on x_bar and ``mu`` on m_bar -- one on a parameter gradient raises -- and is
+    once differentiable: a third derivative declines loudly."""
+
+    @staticmethod
+    def forward(ctx, abar, x, mask, W1, b1, W2, b2, W3, b3, st, flags, mask_shape):
+        need_x, need_m, need_w, again = flags
+        ctx.st, ctx.flags, ctx.mask_shape = st, flags, mask_shape
+        ctx.set_materialize_grads(False)
+        B, N, F = st.B, st.N, st.F
+        if st.cpu:
+            ctx.save_for_backward(abar, x, mask, W1, W2, W3)
+            dZ1, dZ2, dZ3 = _rows_chain_cpu(st, W2, W3, st.w, abar)
+            da, dc = dZ1.sum(2), dZ1.sum(1)
+            xbar = da @ W1[:, :F] + dc @ W1[:, F:2 * F]
+            mbar = None
+            if need_m:
+                mbar = (st.agg_scale * (st.adj * st.E3 * abar.unsqueeze(2)).sum((1, 3))).reshape(mask_shape)
+            pg = (None,) * 6
+            if need_w:
+                pg = (torch.cat((da.reshape(-1, H1).t() @ x.reshape(-1, F), dc.reshape(-1, H1).t() @ x.reshape(-1, F)), 1),
+                      da.sum((0, 1)), _outer(dZ2, st.E1), dZ2.sum((0, 1, 2)), _outer(dZ3, st.E2), dZ3.sum((0, 1, 2)))
+            ctx.dz = (dZ1, dZ2, dZ3)
+            return (xbar, mbar, *pg)
+        V = B * N
+        abar2 = abar.reshape(V, H3).contiguous()
+        x2 = _unit_cols(x.reshape(V, F))
+        dZ1, dZ2, dZ3, dadc = _rows_bwd_launch(st, st.m1, abar2, need_w or again)
+        ctx.save_for_backward(abar2, x2, W1, b3)
+        ctx.dz = (dZ1, dZ2, dZ3, dadc) if again else None
+        xbar = _rows_dx(W1, F, dadc).reshape(B, N, F) if need_x else None
+        mbar = None
+        if need_m:
+            rowdot = torch.empty((V * st.k,), device=x.device, dtype=torch.float32)
+            mbar = torch.empty((V,), device=x.device, dtype=torch.float32)
+            e = _rows_jvp_desc(st, abar2, b3)
+            e.rowdot, e.dmask = _p(rowdot), _p(mbar)
+            check(_lib.lib().mpg_knn_edge_jvp(C.byref(e), _stream()), "mpg_knn_edge_jvp")
+            mbar = mbar.reshape(mask_shape)
+        pg = (None,) * 6
+        if need_w:
+            dev = x.device
+            g1 = torch.empty_like(W1); gb1 = torch.empty_like(b1)
+            g2 = torch.empty_like(W2); gb2 = torch.empty_like(b2)
+            g3 = torch.empty_like(W3); gb3 = torch.empty_like(b3)
+            wb = WgradBatch()
+            wb.add(dadc[:, :H1], x2, out=g1, out_col0=0, bias_out=gb1)
+            wb.add(dadc[:, H1:], x2, out=g1, out_col0=F)
+            wb.add(dZ2, st.E1, out=g2, bias_out=gb2)
+            wb.add(dZ3, st.E2, out=g3, bias_out=gb3)
+            wb.flush()
+            pg = (g1, gb1, g2, gb2, g3, gb3)
+        return (xbar, mbar, *pg)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, u, mu, *gparams):
+        if any(g is not None for g in gparams):
+            raise RuntimeError("EdgeRowsVJPFn: a cotangent arrived on a parameter-gradient output; the second-order rule covers the "
+                               "input gradient and the mask gradient only")
+        st = ctx.st
+        B, N, F = st.B, st.N, st.F
+        _, n_x, n_m, n_W1, n_b1, n_W2, n_b2, n_W3, n_b3 = ctx.needs_input_grad[:9]
+        if st.cpu:
+            abar, x, mask, W1, W2, W3 = ctx.saved_tensors
+            dZ1, dZ2, dZ3 = ctx.dz
+            G1, G2, G3 = st.G
+            if u is None:
+                u = torch.zeros_like(x)
+            P = (u @ W1[:, :F].t()).unsqueeze(2) + (u @ W1[:, F:2 * F].t()).unsqueeze(1)
+            T1 = G1 * P
+            T2 = G2 * (T1 @ W2.t())
+            T3 = G3 * (T2 @ W3.t())
+            g_abar = st.w * T3
+            g_m = None
+            if mask is not None:
+                g_m = (st.agg_scale * (st.adj * T3 * abar.unsqueeze(2)).sum((1, 3))).reshape(ctx.mask_shape)
+            da, dc = dZ1.sum(2).reshape(-1, H1), dZ1.sum(1).reshape(-1, H1)
+            u2, x2 = u.reshape(-1, F), x.reshape(-1, F)
+            g_W1 = torch.cat((da.t() @ u2, dc.t() @ u2), 1)
+            g_W2, g_W3 = _outer(dZ2, T1), _outer(dZ3, T2)
+            g_x = g_b1 = g_b2 = g_b3 = None
+            if mu is not None:
+                wmu = st.adj * mu.reshape(B, 1, N, 1)
+                g_abar = g_abar + wmu * st.E3
+                tZ1, tZ2, tZ3 = _rows_chain_cpu(st, W2, W3, wmu, abar)
+                ta, tc = tZ1.sum(2), tZ1.sum(1)
+                g_x = ta @ W1[:, :F] + tc @ W1[:, F:2 * F]
+                g_W1 = g_W1 + torch.cat((ta.reshape(-1, H1).t() @ x2, tc.reshape(-1, H1).t() @ x2), 1)
+                g_W2, g_W3 = g_W2 + _outer(tZ2, st.E1), g_W3 + _outer(tZ3, st.E2)
+                g_b1, g_b2, g_b3 = ta.sum((0, 1)), tZ2.sum((0, 1, 2)), tZ3.sum((0, 1, 2))
+            g_abar = st.agg_scale * g_abar.sum(2)
+            return (g_abar, g_x, g_m, g_W1, g_b1, g_W2, g_b2, g_W3, g_b3, None, None, None)
+        abar2, x2, W1, b3 = ctx.saved_tensors
+        if ctx.dz is None:
+            raise RuntimeError("EdgeRowsVJPFn: the first derivative was taken without create_graph=True; there is nothing to differentiate again")
+        dZ1, dZ2, dZ3, dadc = ctx.dz
+        V, dev = B * N, abar2.device
+        need_w = n_W1 or n_W2 or n_W3 or n_b1 or n_b2 or n_b3
+        u2 = torch.zeros((V, F), device=dev, dtype=torch.float32) if u is None else _unit_cols(u.reshape(V, F).float())
+        # the tangent projections, without bias; bf16 hi + lo operands: a cotangent has no fixed magnitude
+        ta = linear_fwd(u2, W1, None, w_col0=0, w_cols=F, f16=False)
+        tc = linear_fwd(u2, W1, None, w_col0=F, w_cols=F, f16=False)
+        rows = V * st.k
+        T1 = torch.empty((rows, H1), device=dev, dtype=torch.float32) if need_w else None
+        T2 = torch.empty((rows, H2), device=dev, dtype=torch.float32) if need_w else None
+        g_abar = torch.empty((V, H3), device=dev, dtype=torch.float32)
+        want_m = st.m1 is not None and n_m
+        rowdot = torch.empty((rows,), device=dev, dtype=torch.float32) if want_m else None
+        g_m = torch.empty((V,), device=dev, dtype=torch.float32) if want_m else None
+        mu1 = None if mu is None else mu.reshape(V).contiguous().float()
+        e = _rows_jvp_desc(st, abar2, b3)
+        e.mu, e.ta, e.tc, e.ld_t = _p(mu1), _p(ta), _p(tc), ta.stride(0)
+        e.T1, e.T2, e.aggt, e.rowdot, e.dmask = _p(T1), _p(T2), _p(g_abar), _p(rowdot), _p(g_m)
+        check(_lib.lib().mpg_knn_edge_jvp(C.byref(e), _stream()), "mpg_knn_edge_jvp")
+        g_x = tdz = None
+        if mu1 is not None:   # the first-order chain once more, mu in the mask's place (it may be negative: the kernel tests != 0)
+            tdz = _rows_bwd_launch(st, mu1, abar2, need_w)
+            if n_x:
+                g_x = _rows_dx(W1, F, tdz[3]).reshape(B, N, F)
+        pg = (None,) * 6
+        if need_w:
+            W2s, W3s = st.pk.params[1], st.pk.params[2]
+            g1 = torch.empty_like(W1); g2 = torch.empty_like(W2s); g3 = torch.empty_like(W3s)
+            gb = [None, None, None]
+            wb = WgradBatch()
+            wb.add(dadc[:, :H1], u2, out=g1, out_col0=0)
+            wb.add(dadc[:, H1:], u2, out=g1, out_col0=F)
+            wb.add(dZ2, T1, out=g2)
+            wb.add(dZ3, T2, out=g3)
+            if tdz is not None:
+                tZ1, tZ2, tZ3, tdadc = tdz
+                gb = [torch.zeros((h,), device=dev, dtype=torch.float32) for h in (H1, H2, H3)]   # (their jobs add: the tangent stream has no bias)
+                wb.add(tdadc[:, :H1], x2, out=g1, out_col0=0, bias_out=gb[0], accumulate=True)
+                wb.add(tdadc[:, H1:], x2, out=g1, out_col0=F, accumulate=True)
+                wb.add(tZ2, st.E1, out=g2, bias_out=gb[1], accumulate=True)
+                wb.add(tZ3, st.E2, out=g3, bias_out=gb[2], accumulate=True)
+            wb.flush()
+            pg = (g1, gb[0], g2, gb[1], g3, gb[2])
+        g_m = None if g_m is None else g_m.reshape(ctx.mask_shape)
+        return (g_abar.reshape(B, N, H3), g_x, g_m, *pg, None, None, None)
 
 
 # ---- forward

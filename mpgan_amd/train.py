@@ -456,7 +456,8 @@ class TrainStep:
                  optimizer: str = "rmsprop", betas=(0.9, 0.999), gp_lambda: float = 0.0,
                  graph_collectives: Optional[bool] = None, augment=None, loader=None, num_critic: int = 1, num_gen: int = 1,
                  track_epoch_losses: bool = False, label_smoothing: bool = False, label_noise: float = 0.0,
-                 ema: Optional[Ema] = None, lr_schedule=None, grad_clip=None, _ada_split: bool = False):
+                 ema: Optional[Ema] = None, lr_schedule=None, grad_clip=None, gp_rows: Optional[bool] = None,
+                 _ada_split: bool = False):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
         self.dev = dev = next(G.parameters()).device
@@ -489,6 +490,9 @@ class TrainStep:
         # (tests, measurements: the three graphs of a multi-rank iteration without a process group)
         self.split_graphs = bool(_switch("MPG_SPLIT_GRAPHS", ""))
         self.gp_lambda = float(gp_lambda)
+        # the penalty's MPLayers on the twice-differentiable row kernels where ``ops.gp_rows_route`` covers them (None: as
+        # ``ops.OPTIONS["gp_rows"]`` / MPG_GP_ROWS says as the step is built)
+        self.gp_rows = bool(ops.OPTIONS["gp_rows"]) if gp_rows is None else bool(gp_rows)
         self.GP = torch.zeros((), device=dev)   # last penalty value (the reference's losses["gp"])
         self.fixed_alpha = None   # tests: the interpolation weights [B, 1, 1] instead of fresh uniform samples
         self.G, self.D = G, D
@@ -593,6 +597,11 @@ class TrainStep:
         # that they start on CUs the one-round data-gradient launches leave idle and their launch boundaries stop
         # serialising with the data path.  MPG_WGRAD_SIDE=0 switches it off.
         self.wgrad_side = gpu and on["MPG_WGRAD_SIDE"]
+        # (not beside the penalty on the rows route: there D's edge-network parameters get gradients from two sides in one backward --
+        #  added into .grad by the fused layers' launches on that second stream, and handed to autograd by the twice-differentiable
+        #  op, whose accumulation runs on the main stream.  On one stream the two are ordered, in eager execution and in a replay alike)
+        if self.gp_lambda and self.gp_rows:
+            self.wgrad_side = False
         self._wside = None
         # The generator-ahead branch is forked at the top of the D segment (MPG_GEN_AHEAD_LATE=0: beside the D step's own
         # generator call), or -- default -- behind the D step's last data-gradient launch, beside the weight-gradient tail
@@ -911,9 +920,13 @@ class TrainStep:
         B = real.shape[0]
         alpha = self.fixed_alpha if self.fixed_alpha is not None else torch.rand(B, 1, 1, device=real.device)
         x = (alpha * real + (1 - alpha) * fake.detach()).requires_grad_(True)
-        with ops.double_backward_route(self.dev):
-            prob = self.D(x)
-            grads = torch.autograd.grad(prob, x, torch.ones_like(prob), create_graph=True, retain_graph=True)[0]
+        prev, ops.OPTIONS["gp_rows"] = ops.OPTIONS["gp_rows"], self.gp_rows
+        try:
+            with ops.double_backward_route(self.dev):
+                prob = self.D(x)
+                grads = torch.autograd.grad(prob, x, torch.ones_like(prob), create_graph=True, retain_graph=True)[0]
+        finally:
+            ops.OPTIONS["gp_rows"] = prev
         norm = torch.sqrt((grads.reshape(B, -1) ** 2).sum(1) + 1e-12)
         return self.gp_lambda * ((norm - 1) ** 2).mean()
 

@@ -1,7 +1,7 @@
 """What one option of the captured training iteration costs next to the step without it, on one GPU.  One JSON object per line on
 stdout and in --out.
 
-    python tools/step_option_bench.py --option {labels,ada,critic,sn,ema,ctl} [--reps 10] [--out profiles/<option>_bench.jsonl]
+    python tools/step_option_bench.py --option {labels,ada,critic,sn,ema,ctl,gp} [--reps 10] [--out profiles/<option>_bench.jsonl]
 
 MPGAN at N = 30, B = 256, the captured iteration, one process.  Two steps over the same weights and batch -- a baseline and the
 same with the option on -- and, where the option adds one launch to the D segment, that launch on its own outside any graph:
@@ -24,6 +24,11 @@ ctl      baseline: the default step.  Option: ``lr_schedule=LrSchedule.warmup_de
          on both networks (+ ``mpg_step_control`` in front of each optimizer launch, which reads its rate and its gradient scale
          from memory).  Rows: a default_step, b ctl_step, c ctl_launch_D, d ctl_launch_G (each network's launch alone, over a
          gradient of that network's size).
+
+gp       two steps with ``loss="w", gp_lambda=10``: the penalty's D(x) on the materialised edge matrix (a gp_step_edges: the
+         route ``ops.double_backward_route`` has always taken) and on the twice-differentiable row kernels (b gp_step_rows:
+         ``gp_rows=True``), at N = 30, B = 256 and again at N = 150, B = 16.  Held to, per shape: the median of (b) is not above the
+         median of (a), measured in the same run.
 
 Every ``step()`` and every lone launch sits between two HIP events of its own -- in all rows alike, so that what an event pair
 costs cancels between them.  A repetition is --batches steps of each kind (critic: two full cycles of the schedule) taken
@@ -259,9 +264,48 @@ def sn_bench(args, emit):
           **{f"{k}_loss_{r[2:]}": float(getattr(ts, k + "_loss")) for r, ts in zip(rows[1:], steps[1:]) for k in ("D", "G")}})
 
 
+def gp_bench(args, emit):
+    """--option gp: the captured --gp iteration with the penalty on the existing route and on the rows route, alternated in one
+    process, every ``step()`` between two HIP events; at the headline shape and at N = 150, B = 16."""
+    rows = ("a gp_step_edges", "b gp_step_rows")
+    for n, b in ((N, B), (150, 16)):
+        torch.manual_seed(0)
+        steps = []
+        for gp_rows in (False, True):
+            G, D = train.default_mpgan(n, loss="w")
+            lrs = train.LR["g"]
+            ts = train.TrainStep(G, D, b, n, lr_disc=lrs[0], lr_gen=lrs[1], use_graphs=True, loss="w", gp_lambda=10.0, gp_rows=gp_rows)
+            x, labels = mdata.synthetic_jets(b, n, seed=1)
+            ts.set_batch(x.cuda(), labels.cuda())
+            for _ in range(3):   # warm-up: captures the graph
+                ts.step()
+            torch.cuda.synchronize()
+            steps.append(ts)
+        assert all(l.gp_rows_ok(b, n, True, dict(ops.OPTIONS, gp_rows=True)) for l in steps[1].D.mp_layers)
+        us = {r: [] for r in rows}
+        for _ in range(args.reps):
+            t = {r: [] for r in rows}
+            for _ in range(args.batches):        # (alternated: the rows share whatever the box does meanwhile)
+                for r, ts in zip(rows, steps):
+                    t[r].append(timed(ts.step))
+            for r in rows:
+                us[r].append(float(np.mean(t[r])))
+        med = {}
+        for name, v in us.items():
+            med[name] = float(np.median(v))
+            emit({"model": "mpgan", "B": b, "N": n, "loss": "w", "gp_lambda": 10.0, "gp_rows": name == rows[1], "row": name,
+                  "reps": args.reps, "batches_per_rep": args.batches, "median_us": med[name], "min_us": float(np.min(v)),
+                  "max_us": float(np.max(v)), "jets_per_s": b / (med[name] * 1e-6)})
+        emit({"model": "mpgan", "B": b, "N": n, "row": "condition", "rows_minus_edges_us": med[rows[1]] - med[rows[0]],
+              "rows_le_edges": bool(med[rows[1]] <= med[rows[0]]),
+              **{f"{k}_{r[2:]}": float(getattr(ts, k)) for r, ts in zip(rows, steps) for k in ("D_loss", "GP")}})
+        del steps
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--option", choices=sorted([*OPTIONS, "ada", "sn", "ctl"]), required=True)
+    ap.add_argument("--option", choices=sorted([*OPTIONS, "ada", "sn", "ctl", "gp"]), required=True)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--batches", type=int, default=10, help="steps of each kind per repetition (critic: two cycles of the schedule)")
     ap.add_argument("--num-critic", type=int, default=5)
@@ -276,6 +320,8 @@ def main():
         return ada_bench(args, emit)
     if args.option == "ctl":
         return ctl_bench(args, emit)
+    if args.option == "gp":
+        return gp_bench(args, emit)
     o = OPTIONS[args.option]
     critic = args.option == "critic"
     batches = 2 * args.num_critic if critic else args.batches
