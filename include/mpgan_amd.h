@@ -410,6 +410,28 @@ typedef struct MpgAttn {
 int mpg_attn_fwd(const MpgAttn* p, void* stream);
 int mpg_attn_bwd(const MpgAttn* p, void* stream);
 
+/* mpg_attn_dd: the second-order half -- what a twice-differentiable attention core (the gradient penalty through GAPT's MAB) needs
+ * beyond the two calls above.  With dq, dk, dv = mpg_attn_bwd(q, k, v, d_o) and cotangents uq, uk, uv on them, it writes the
+ * gradients of  Phi = <uq, dq> + <uk, dk> + <uv, dv>  with respect to q, k, v and d_o (c = 1 / sqrt(d), rowsum over keys):
+ *     A = d_o v^T,  a = rowsum(P*A),  dS = P*(A - a);    Sd = c (uq k^T + q uk^T),  r = rowsum(P*Sd),  Pd = P*(Sd - r)
+ *     M = Sd*(A - a) - r*A + d_o uv^T,   D2 = P*(M - rowsum(P*M))
+ *     gq = c (D2 k + dS uk)    gk = c (D2^T q + dS^T uq)    gv = Pd^T d_o    gdo = Pd v + P uv
+ * Operands as in MpgAttn (heads side by side, any row stride >= H * d, unit column stride); P as mpg_attn_fwd wrote it for the same
+ * B, L, S, H, d (the layout is taken from the predicate the other two entry points use).  uq / uk / uv may be NULL (= zero) and any
+ * output may be NULL (= not wanted): the work behind them is skipped, not only the store.  Ignored keys contribute exactly zero, a
+ * jet without a real key gets exact zeros in all four outputs.  Covers d in {8, 16, 32} and 1 <= L, S <= 160; no L x S tile is
+ * written anywhere; every sum runs in a fixed order (no atomics: two launches give the same bits).
+ * Errors, before anything is launched: -1 sizes outside the above, -2 q / k / v / d_o / P is NULL, -5 a row stride below H * d. */
+typedef struct MpgAttnDD {
+    const float* q; const float* k; const float* v; const float* d_o; int ldq, ldk, ldv, ldo;
+    const float* uq; const float* uk; const float* uv; int lduq, lduk, lduv;
+    const float* ignore;
+    const float* P;
+    float* gq; float* gk; float* gv; float* gdo; int ldgq, ldgk, ldgv, ldgdo;
+    int B, L, S, H, d;
+} MpgAttnDD;
+int mpg_attn_dd(const MpgAttnDD* p, void* stream);
+
 /* ---- the per-jet pieces around the message-passing layers ----------------------------------------
  * mpg_rank_mask: MPGenerator._get_mask, mask_c branch (mpgan/model.py:689-699; GAPT_G :255-258): with
  * n_b = int(labels[b] * N), mask[b, i] = 1 for the n_b particles of jet b with the smallest first feature

@@ -175,6 +175,17 @@ class MpgAttn(C.Structure):
     ]
 
 
+class MpgAttnDD(C.Structure):
+    _fields_ = [
+        ("q", _fp), ("k", _fp), ("v", _fp), ("d_o", _fp), ("ldq", C.c_int), ("ldk", C.c_int), ("ldv", C.c_int), ("ldo", C.c_int),
+        ("uq", _fp), ("uk", _fp), ("uv", _fp), ("lduq", C.c_int), ("lduk", C.c_int), ("lduv", C.c_int),
+        ("ignore", _fp), ("P", _fp),
+        ("gq", _fp), ("gk", _fp), ("gv", _fp), ("gdo", _fp),
+        ("ldgq", C.c_int), ("ldgk", C.c_int), ("ldgv", C.c_int), ("ldgdo", C.c_int),
+        ("B", C.c_int), ("L", C.c_int), ("S", C.c_int), ("H", C.c_int), ("d", C.c_int),
+    ]
+
+
 class MpgDiscHead(C.Structure):
     _fields_ = [
         ("y", _fp), ("ldy", C.c_int), ("mask", _fp), ("w", _fp), ("bias", _fp),
@@ -289,6 +300,7 @@ SIGNATURES = {
     "mpg_edge_dw": (C.c_int, [C.POINTER(MpgEdgeDw), C.c_void_p]),
     "mpg_attn_fwd": (C.c_int, [C.POINTER(MpgAttn), C.c_void_p]),
     "mpg_attn_bwd": (C.c_int, [C.POINTER(MpgAttn), C.c_void_p]),
+    "mpg_attn_dd": (C.c_int, [C.POINTER(MpgAttnDD), C.c_void_p]),
     "mpg_mab_fwd": (C.c_int, [C.POINTER(MpgMab), C.c_void_p]),
     "mpg_mab_bwd": (C.c_int, [C.POINTER(MpgMab), C.c_void_p]),
     "mpg_mab_chain_fwd": (C.c_int, [C.POINTER(MpgMabChain), C.c_void_p]),

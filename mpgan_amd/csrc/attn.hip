@@ -10,6 +10,7 @@
 // live in registers (fully unrolled), P is written once, transposed ([S][L]: lanes contiguous).  The backward
 // keeps dS and P in LDS between its query-major half (dQ) and its key-major half (dK, dV).
 // Anything larger takes the generic kernels below (one workgroup per (jet, head), scores through memory).
+// mpg_attn_dd (behind them) is the second derivative the gradient penalty needs, for either layout of P.
 #include "common.h"
 #include "../../include/mpgan_amd.h"
 
@@ -302,11 +303,179 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const MpgAttn p) {
         for (int c = 0; c < d; ++c) { ko[c] = dk[c] * scale; vo[c] = dv[c]; }
     }
 }
-// The fast path is chosen by shape alone (forward and backward must agree on the layout of P); its float4 row
-// accesses then REQUIRE 16-byte aligned bases and strides -- anything else is an error, not a silent fallback.
-static bool attn_fast_shape(const MpgAttn* p) {
-    return p->S <= AT_S && p->L <= AT_L && (p->d == 8 || p->d == 16 || p->d == 32);
+// ---- second order: the gradients of Phi = <uq, dq> + <uk, dk> + <uv, dv> with respect to q, k, v and dO (DESIGN.md section 4,
+// "Gradient penalty on the attention core").  One workgroup per (jet, head), a thread per query and then a thread per key; all seven
+// operands of the pair sit in LDS.  No L x S tile is kept anywhere: a thread forms the four dot products of an element
+//     A = G_l . v_s      Sd = c (uq_l . k_s + q_l . uk_s)      W = G_l . uv_s
+// where it needs them (twice query-major, once key-major) and reads P as the forward left it.  With a = sum_s P A, r = sum_s P Sd:
+//     dS = P (A - a)    Pd = P (Sd - r)    M = Sd (A - a) - r A + W    D2 = P (M - m),   m = sum_s P M = sum_s P Sd A - 2 a r + sum_s P W
+// so ONE query-major pass gives the three row scalars.  Every sum runs in index order inside one thread: no atomics, the same bits
+// from every launch.  An ignored key is skipped (its P is an exact 0: it contributes exactly nothing, its own gk / gv rows are
+// zeros); a jet without a real key gets zeros everywhere.
+template <int D>
+MPG_DEV float dot_row(const float (&x)[D], const float* row) {
+    float acc = 0.f;
+#pragma unroll
+    for (int c = 0; c < D; c += 4) {
+        const float4 t = *reinterpret_cast<const float4*>(row + c);
+        acc += x[c] * t.x; acc += x[c + 1] * t.y; acc += x[c + 2] * t.z; acc += x[c + 3] * t.w;
+    }
+    return acc;
 }
+template <int D>
+MPG_DEV void axpy_row(float (&y)[D], float a, const float* row) {
+#pragma unroll
+    for (int c = 0; c < D; c += 4) {
+        const float4 t = *reinterpret_cast<const float4*>(row + c);
+        y[c] += a * t.x; y[c + 1] += a * t.y; y[c + 2] += a * t.z; y[c + 3] += a * t.w;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_dd_kernel(const MpgAttnDD p, const int p_sl) {   // p_sl: P is [S][L] (else [L][S])
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int pair = blockIdx.x, b = pair / p.H, hd = pair % p.H;
+    const int L = p.L, S = p.S;
+    const bool hq = p.uq != nullptr, hk = p.uk != nullptr, hv = p.uv != nullptr;
+    float* qs = sm;               // [L][D]
+    float* gs = qs + L * D;       // [L][D]  dO
+    float* uqs = gs + L * D;      // [L][D]
+    float* ks = uqs + L * D;      // [S][D]
+    float* vs = ks + S * D;
+    float* uks = vs + S * D;
+    float* uvs = uks + S * D;
+    float* ar = uvs + S * D;      // [L] each: a, r, m
+    float* rr = ar + L;
+    float* mr = rr + L;
+    float* ig = mr + L;           // [S]
+    for (int t = threadIdx.x; t < L * D; t += blockDim.x) {
+        const size_t row = (size_t)(b * L + t / D);
+        const int c = hd * D + t % D;
+        qs[t] = p.q[row * p.ldq + c];
+        gs[t] = p.d_o[row * p.ldo + c];
+        if (hq) uqs[t] = p.uq[row * p.lduq + c];
+    }
+    for (int t = threadIdx.x; t < S * D; t += blockDim.x) {
+        const size_t row = (size_t)(b * S + t / D);
+        const int c = hd * D + t % D;
+        ks[t] = p.k[row * p.ldk + c];
+        vs[t] = p.v[row * p.ldv + c];
+        if (hk) uks[t] = p.uk[row * p.lduk + c];
+        if (hv) uvs[t] = p.uv[row * p.lduv + c];
+    }
+    for (int s = threadIdx.x; s < S; s += blockDim.x) ig[s] = (p.ignore != nullptr && p.ignore[b * S + s] != 0.f) ? 1.f : 0.f;
+    __syncthreads();
+    const float scale = rsqrtf((float)D);
+    const float* Pb = p.P + (size_t)pair * L * S;
+    const int pl = p_sl ? 1 : S, ps = p_sl ? L : 1;   // strides of P in l and in s
+    const bool want_q = p.gq != nullptr, want_o = p.gdo != nullptr, want_k = p.gk != nullptr, want_v = p.gv != nullptr;
+
+    for (int l = threadIdx.x; l < L; l += blockDim.x) {   // ---- query-major: the row scalars, then gq and gdo
+        float q[D], g[D], uq[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) { q[c] = qs[l * D + c]; g[c] = gs[l * D + c]; uq[c] = hq ? uqs[l * D + c] : 0.f; }
+        const float* Pl = Pb + (size_t)l * pl;
+        float a = 0.f, r = 0.f, t = 0.f, w = 0.f;
+        for (int s = 0; s < S; ++s) {
+            if (ig[s] != 0.f) continue;   // (workgroup-uniform)
+            const float pr = Pl[s * ps];
+            const float A = dot_row<D>(g, vs + s * D);
+            float sd = 0.f;
+            if (hq) sd += dot_row<D>(uq, ks + s * D);
+            if (hk) sd += dot_row<D>(q, uks + s * D);
+            sd *= scale;
+            a += pr * A; r += pr * sd; t += pr * sd * A;
+            if (hv) w += pr * dot_row<D>(g, uvs + s * D);
+        }
+        const float m = t - 2.f * a * r + w;
+        ar[l] = a; rr[l] = r; mr[l] = m;
+        if (!want_q && !want_o) continue;
+        float gq[D], go[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) { gq[c] = 0.f; go[c] = 0.f; }
+        for (int s = 0; s < S; ++s) {
+            if (ig[s] != 0.f) continue;
+            const float pr = Pl[s * ps];
+            const float A = dot_row<D>(g, vs + s * D);
+            float sd = 0.f;
+            if (hq) sd += dot_row<D>(uq, ks + s * D);
+            if (hk) sd += dot_row<D>(q, uks + s * D);
+            sd *= scale;
+            if (want_q) {
+                const float W = hv ? dot_row<D>(g, uvs + s * D) : 0.f;
+                const float d2 = pr * (sd * (A - a) - r * A + W - m);
+                axpy_row<D>(gq, d2, ks + s * D);
+                if (hk) axpy_row<D>(gq, pr * (A - a), uks + s * D);
+            }
+            if (want_o) {
+                axpy_row<D>(go, pr * (sd - r), vs + s * D);
+                if (hv) axpy_row<D>(go, pr, uvs + s * D);
+            }
+        }
+        const size_t row = (size_t)(b * L + l);
+        if (want_q) {
+            float* o = p.gq + row * p.ldgq + hd * D;
+#pragma unroll
+            for (int c = 0; c < D; ++c) o[c] = gq[c] * scale;
+        }
+        if (want_o) {
+            float* o = p.gdo + row * p.ldgdo + hd * D;
+#pragma unroll
+            for (int c = 0; c < D; ++c) o[c] = go[c];
+        }
+    }
+    if (!want_k && !want_v) return;
+    __syncthreads();
+    for (int s = threadIdx.x; s < S; s += blockDim.x) {   // ---- key-major: gk and gv
+        float gk[D], gv[D];
+#pragma unroll
+        for (int c = 0; c < D; ++c) { gk[c] = 0.f; gv[c] = 0.f; }
+        if (ig[s] == 0.f) {
+            float k[D], v[D], uk[D], uv[D];
+#pragma unroll
+            for (int c = 0; c < D; ++c) {
+                k[c] = ks[s * D + c]; v[c] = vs[s * D + c];
+                uk[c] = hk ? uks[s * D + c] : 0.f; uv[c] = hv ? uvs[s * D + c] : 0.f;
+            }
+            const float* Ps = Pb + (size_t)s * ps;
+            for (int l = 0; l < L; ++l) {
+                const float pr = Ps[l * pl];
+                const float a = ar[l], r = rr[l], m = mr[l];
+                const float A = dot_row<D>(v, gs + l * D);
+                float sd = 0.f;
+                if (hq) sd += dot_row<D>(k, uqs + l * D);
+                if (hk) sd += dot_row<D>(uk, qs + l * D);
+                sd *= scale;
+                if (want_k) {
+                    const float W = hv ? dot_row<D>(uv, gs + l * D) : 0.f;
+                    const float d2 = pr * (sd * (A - a) - r * A + W - m);
+                    axpy_row<D>(gk, d2, qs + l * D);
+                    if (hq) axpy_row<D>(gk, pr * (A - a), uqs + l * D);
+                }
+                if (want_v) axpy_row<D>(gv, pr * (sd - r), gs + l * D);
+            }
+        }
+        const size_t row = (size_t)(b * S + s);
+        if (want_k) {
+            float* o = p.gk + row * p.ldgk + hd * D;
+#pragma unroll
+            for (int c = 0; c < D; ++c) o[c] = gk[c] * scale;
+        }
+        if (want_v) {
+            float* o = p.gv + row * p.ldgv + hd * D;
+#pragma unroll
+            for (int c = 0; c < D; ++c) o[c] = gv[c];
+        }
+    }
+}
+
+// The fast path is chosen by shape alone (forward, backward and the second-order kernel must agree on the layout of P: [S][L] where
+// this says yes, [L][S] elsewhere); its float4 row accesses then REQUIRE 16-byte aligned bases and strides -- anything else is an
+// error, not a silent fallback.
+static bool attn_fast_shape(int L, int S, int d) {
+    return S <= AT_S && L <= AT_L && (d == 8 || d == 16 || d == 32);
+}
+static bool attn_fast_shape(const MpgAttn* p) { return attn_fast_shape(p->L, p->S, p->d); }
 static bool attn_aligned(const MpgAttn* p, bool bwd) {
     auto al = [](const void* q, int ld) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0 && ld % 4 == 0; };
     bool ok = al(p->q, p->ldq) && al(p->k, p->ldk) && al(p->v, p->ldv);
@@ -362,4 +531,25 @@ extern "C" int mpg_attn_bwd(const MpgAttn* p, void* stream) {
     const size_t lds = ((size_t)2 * p->S * p->d + 2 * p->L * p->d + (size_t)p->L * p->S) * 4;
     if (lds > 160 * 1024) return -2;
     return mpg_go<attn_bwd_kernel>(dim3(p->B * p->H), dim3(64), (int)lds, (hipStream_t)stream, *p);
+}
+
+extern "C" int mpg_attn_dd(const MpgAttnDD* p, void* stream) {
+    constexpr int DD_MAX = 160;   // tokens on either side: every block GAPT builds at N = 30 and N = 150
+    if (!(p->d == 8 || p->d == 16 || p->d == 32) || p->B <= 0 || p->H <= 0 || p->L < 1 || p->L > DD_MAX || p->S < 1 || p->S > DD_MAX) return -1;
+    if (p->q == nullptr || p->k == nullptr || p->v == nullptr || p->d_o == nullptr || p->P == nullptr) return -2;
+    const int E = p->H * p->d;
+    auto ld_ok = [E](const void* ptr, int ld) { return ptr == nullptr || ld >= E; };
+    if (!(ld_ok(p->q, p->ldq) && ld_ok(p->k, p->ldk) && ld_ok(p->v, p->ldv) && ld_ok(p->d_o, p->ldo) && ld_ok(p->uq, p->lduq) &&
+          ld_ok(p->uk, p->lduk) && ld_ok(p->uv, p->lduv) && ld_ok(p->gq, p->ldgq) && ld_ok(p->gk, p->ldgk) && ld_ok(p->gv, p->ldgv) &&
+          ld_ok(p->gdo, p->ldgdo)))
+        return -5;
+    if (p->gq == nullptr && p->gk == nullptr && p->gv == nullptr && p->gdo == nullptr) return 0;   // nothing wanted: nothing launched
+    const int p_sl = attn_fast_shape(p->L, p->S, p->d) ? 1 : 0;
+    const int longer = p->L > p->S ? p->L : p->S;
+    const dim3 grid(p->B * p->H), block(longer <= 64 ? 64 : (longer <= 128 ? 128 : 192));   // a thread per query, then per key
+    const size_t lds = ((size_t)(3 * p->L + 4 * p->S) * p->d + 3 * p->L + p->S) * 4;         // <= 145920 bytes
+    using Go = int (*)(dim3, dim3, int, hipStream_t, const MpgAttnDD&, const int&);
+    static constexpr Go GO[3] = {mpg_go<attn_dd_kernel<8>, MpgAttnDD, int>, mpg_go<attn_dd_kernel<16>, MpgAttnDD, int>,
+                                 mpg_go<attn_dd_kernel<32>, MpgAttnDD, int>};
+    return GO[p->d == 8 ? 0 : (p->d == 16 ? 1 : 2)](grid, block, (int)lds, (hipStream_t)stream, *p, p_sl);
 }

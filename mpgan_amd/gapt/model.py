@@ -102,6 +102,11 @@ class MAB(nn.Module):
         W, b = att.in_proj_weight, att.in_proj_bias
         mm = ops.MatMulFn.apply
         x2, y2 = x.reshape(B * L, E), y.reshape(B * S, E)
+        if ops.gp_attn_route(E, H, L, S, double_backward=True):
+            # the attention core on its own kernels, twice differentiable (``ops.AttnCoreFn``): nothing of size L x S x d is built
+            o = ops.AttnCoreFn.apply(mm(x2, W[:E], "nt") + b[:E], mm(y2, W[E:2 * E], "nt") + b[E:2 * E],
+                                     mm(y2, W[2 * E:], "nt") + b[2 * E:], ignore, B, L, S, H)
+            return self._after_attention_dd(x2, o, B, L, E)
         q = (mm(x2, W[:E], "nt") + b[:E]).reshape(B, L, H, d).permute(0, 2, 1, 3)            # [B, H, L, d]
         k = (mm(y2, W[E:2 * E], "nt") + b[E:2 * E]).reshape(B, S, H, d).permute(0, 2, 1, 3)
         v = (mm(y2, W[2 * E:], "nt") + b[2 * E:]).reshape(B, S, H, d).permute(0, 2, 1, 3)
@@ -114,6 +119,11 @@ class MAB(nn.Module):
         else:
             pr = torch.softmax(s, dim=-1)
         o = (pr.unsqueeze(-1) * v.unsqueeze(2)).sum(3).permute(0, 2, 1, 3).reshape(B * L, E)
+        return self._after_attention_dd(x2, o, B, L, E)
+
+    def _after_attention_dd(self, x2: Tensor, o: Tensor, B: int, L: int, E: int) -> Tensor:
+        """``_forward_dd`` behind the attention core: out-projection with the residual, LayerNorm, dropout, feed-forward."""
+        att, mm = self.attention, ops.MatMulFn.apply
         za = x2 + mm(o, att.out_proj.weight, "nt") + att.out_proj.bias
         if self.layer_norm:
             za = torch.nn.functional.layer_norm(za, (E,), self.norm1.weight, self.norm1.bias, self.norm1.eps)

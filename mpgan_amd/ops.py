@@ -63,6 +63,10 @@ OPTIONS = {
     # instead of the materialised edge matrix of MPLayer._forward_edges, for the layers ``gp_rows_route`` covers.  Off unless asked
     # for: MPG_GP_ROWS=1, or TrainStep(gp_rows=True).
     "gp_rows": os.environ.get("MPG_GP_ROWS", "0") not in ("", "0"),
+    # the gradient penalty's attention core (softmax(q k^T / sqrt(d)) v of every MAB) on the attention kernels (``AttnCoreFn``:
+    # mpg_attn_fwd / _bwd / _dd, twice differentiable) instead of the broadcast products of MAB._forward_dd, for the blocks
+    # ``gp_attn_route`` covers.  Off unless asked for: MPG_GP_ATTN=1, or TrainStep(gp_attn=True).
+    "gp_attn": os.environ.get("MPG_GP_ATTN", "0") not in ("", "0"),
 }
 NUM_CUS = 256
 # Forward products (they decide LeakyReLU signs) are split as fp16 hi/lo with the operand scales below (~2^-21 per
@@ -2391,6 +2395,169 @@ class FusedAttnFn(torch.autograd.Function):
         a.lddq, a.lddk, a.lddv = H * d, H * d, H * d
         check(_lib.lib().mpg_attn_bwd(C.byref(a), _stream()), "mpg_attn_bwd")
         return dq, dk, dv, None, None, None, None, None
+
+
+# ---- the attention core, twice differentiable (the gradient penalty through GAPT's MAB)
+#   AttnCoreFn      forward: ``mpg_attn_fwd``; backward: ``AttnCoreVJPFn``.
+#   AttnCoreVJPFn   forward: the first derivative (dq, dk, dv) as a function of (d_o, q, k, v) on ``mpg_attn_bwd``; backward (once
+#                   differentiable): the gradients of Phi = <uq, dq> + <uk, dk> + <uv, dv> on ``mpg_attn_dd``.
+# CPU tensors take the same formulas in plain torch, in the tensors' dtype.
+ATTN_DD_MAX_TOKENS = 160     # mpg_attn_dd: queries / keys of a (jet, head) pair
+ATTN_DD_HEAD_DIMS = (8, 16, 32)
+
+
+def gp_attn_route(E, H, L, S, *, double_backward, options=None) -> bool:
+    """Does a MAB call inside ``double_backward_route`` take ``AttnCoreFn`` for softmax(q k^T / sqrt(d)) v instead of the broadcast
+    products of ``MAB._forward_dd``?  Only with the option on (``OPTIONS["gp_attn"]``) and for the shapes ``mpg_attn_dd`` covers: heads
+    of 8, 16 or 32 features, 1 <= L, S <= ``ATTN_DD_MAX_TOKENS``.  Host only: sizes and the switch decide."""
+    opt = OPTIONS if options is None else options
+    if not (opt.get("gp_attn") and double_backward):
+        return False
+    return H > 0 and E % H == 0 and E // H in ATTN_DD_HEAD_DIMS and 1 <= L <= ATTN_DD_MAX_TOKENS and 1 <= S <= ATTN_DD_MAX_TOKENS
+
+
+def _attn_heads(t, B, T, H, d):
+    return t.reshape(B, T, H, d).permute(0, 2, 1, 3)          # [rows, E] -> [B, H, T, d]
+
+
+def _attn_rows(t, B, T, H, d):
+    return t.permute(0, 2, 1, 3).reshape(B * T, H * d)
+
+
+def _attn_probs_cpu(q, k, ignore, dims):
+    B, L, S, H, d = dims
+    s = _attn_heads(q, B, L, H, d) @ _attn_heads(k, B, S, H, d).transpose(2, 3) * (1.0 / d ** 0.5)
+    if ignore is None:
+        return torch.softmax(s, -1)
+    ig = ignore.reshape(B, 1, 1, S) != 0
+    dead = ig.all(dim=-1, keepdim=True)
+    return torch.softmax(s.masked_fill(ig & ~dead, float("-inf")), -1) * (~dead).to(s.dtype)
+
+
+def _attn_launch_rows(t, E):
+    # what the kernels take as a [rows, E] operand: unit column stride, a row stride of at least the width
+    return t if (t.stride(1) == 1 and t.stride(0) >= E) else t.contiguous()
+
+
+class AttnCoreFn(torch.autograd.Function):
+    """softmax(q k^T / sqrt(d) + key mask) v per (jet, head) as ``FusedAttnFn`` computes it -- q [B*L, E], k, v [B*S, E] (row-strided
+    views are fine), ignore [B*S] floats (1 = padded key) or None -- and twice differentiable: its backward is ``AttnCoreVJPFn``."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, ignore, B, L, S, H):
+        E = q.shape[1]
+        d = E // H
+        ctx.dims, ctx.ignore = (B, L, S, H, d), ignore
+        if not q.is_cuda:
+            P = _attn_probs_cpu(q, k, ignore, ctx.dims)
+            ctx.save_for_backward(q, k, v, P)
+            return _attn_rows(P @ _attn_heads(v, B, S, H, d), B, L, H, d)
+        _chk(q, "q")
+        ql, kl, vl = (_attn_launch_rows(t, E) for t in (q, k, v))
+        o = torch.empty((B * L, E), device=q.device, dtype=torch.float32)
+        P = torch.empty((B, H, L, S), device=q.device, dtype=torch.float32)   # (layout private to the kernels)
+        a = _attn_struct(ql, kl, vl, ignore, o, P, B, L, S, H, d)
+        check(_lib.lib().mpg_attn_fwd(C.byref(a), _stream()), "mpg_attn_fwd")
+        ctx.save_for_backward(q, k, v, P)     # (the inputs themselves: the second derivative flows back through them)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        q, k, v, P = ctx.saved_tensors
+        return (*AttnCoreVJPFn.apply(go, q, k, v, P, ctx.ignore, ctx.dims), None, None, None, None, None)
+
+
+class AttnCoreVJPFn(torch.autograd.Function):
+    """The first derivative of ``AttnCoreFn`` as a function of (d_o, q, k, v): (dq, dk, dv).  Its own backward takes cotangents uq,
+    uk, uv on them -- an absent one is zero -- and is once differentiable: a third derivative declines loudly."""
+
+    @staticmethod
+    def forward(ctx, go, q, k, v, P, ignore, dims):
+        B, L, S, H, d = dims
+        ctx.dims, ctx.ignore = dims, ignore
+        ctx.set_materialize_grads(False)
+        if not q.is_cuda:
+            ctx.save_for_backward(go, q, k, v, P)
+            c = 1.0 / d ** 0.5
+            G, qh, kh, vh = _attn_heads(go, B, L, H, d), _attn_heads(q, B, L, H, d), _attn_heads(k, B, S, H, d), _attn_heads(v, B, S, H, d)
+            A = G @ vh.transpose(2, 3)
+            dS = P * (A - (P * A).sum(-1, keepdim=True))
+            return (_attn_rows(c * (dS @ kh), B, L, H, d), _attn_rows(c * (dS.transpose(2, 3) @ qh), B, S, H, d),
+                    _attn_rows(P.transpose(2, 3) @ G, B, S, H, d))
+        E = H * d
+        go, q, k, v = (_attn_launch_rows(t.float(), E) for t in (go, q, k, v))
+        dq = torch.empty((B * L, E), device=q.device, dtype=torch.float32)
+        dk = torch.empty((B * S, E), device=q.device, dtype=torch.float32)
+        dv = torch.empty((B * S, E), device=q.device, dtype=torch.float32)
+        a = _attn_struct(q, k, v, ignore, go, P, B, L, S, H, d)
+        a.d_o = _p(go)
+        a.dq, a.dk, a.dv = _p(dq), _p(dk), _p(dv)
+        a.lddq, a.lddk, a.lddv = E, E, E
+        check(_lib.lib().mpg_attn_bwd(C.byref(a), _stream()), "mpg_attn_bwd")
+        ctx.save_for_backward(go, q, k, v, P)
+        return dq, dk, dv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, uq, uk, uv):
+        go, q, k, v, P = ctx.saved_tensors
+        B, L, S, H, d = ctx.dims
+        n_go, n_q, n_k, n_v = ctx.needs_input_grad[:4]
+        tail = (None, None, None)
+        if uq is None and uk is None and uv is None:
+            return (None, None, None, None, *tail)
+        if not q.is_cuda:
+            c = 1.0 / d ** 0.5
+            hl, hs = (lambda t: _attn_heads(t, B, L, H, d)), (lambda t: _attn_heads(t, B, S, H, d))
+            G, qh, kh, vh = hl(go), hl(q), hs(k), hs(v)
+            rowsum = lambda X: (P * X).sum(-1, keepdim=True)
+            A = G @ vh.transpose(2, 3)
+            Aa = A - rowsum(A)
+            dS = P * Aa
+            Sd = torch.zeros_like(P)
+            if uq is not None:
+                Sd = Sd + c * (hl(uq) @ kh.transpose(2, 3))
+            if uk is not None:
+                Sd = Sd + c * (qh @ hs(uk).transpose(2, 3))
+            r = rowsum(Sd)
+            Pd = P * (Sd - r)
+            M = Sd * Aa - r * A
+            if uv is not None:
+                M = M + G @ hs(uv).transpose(2, 3)
+            D2 = P * (M - rowsum(M))
+            g_q = c * (D2 @ kh)
+            if uk is not None:
+                g_q = g_q + c * (dS @ hs(uk))
+            g_k = c * (D2.transpose(2, 3) @ qh)
+            if uq is not None:
+                g_k = g_k + c * (dS.transpose(2, 3) @ hl(uq))
+            g_v = Pd.transpose(2, 3) @ G
+            g_go = Pd @ vh
+            if uv is not None:
+                g_go = g_go + P @ hs(uv)
+            return (_attn_rows(g_go, B, L, H, d), _attn_rows(g_q, B, L, H, d), _attn_rows(g_k, B, S, H, d),
+                    _attn_rows(g_v, B, S, H, d), *tail)
+        E, dev = H * d, q.device
+        e = _lib.MpgAttnDD()
+        e.q, e.k, e.v, e.d_o = _p(q), _p(k), _p(v), _p(go)
+        e.ldq, e.ldk, e.ldv, e.ldo = q.stride(0), k.stride(0), v.stride(0), go.stride(0)
+        keep = []
+        for name, u, rows in (("uq", uq, B * L), ("uk", uk, B * S), ("uv", uv, B * S)):
+            if u is not None:
+                u = _attn_launch_rows(u.float(), E)
+                if tuple(u.shape) != (rows, E):
+                    raise ValueError(f"AttnCoreVJPFn: cotangent {name} has shape {tuple(u.shape)}, expected {(rows, E)}")
+                keep.append(u)
+                setattr(e, name, _p(u)); setattr(e, "ld" + name, u.stride(0))
+        e.ignore, e.P = _p(ctx.ignore), _p(P)
+        out = []
+        for name, need, rows in (("gdo", n_go, B * L), ("gq", n_q, B * L), ("gk", n_k, B * S), ("gv", n_v, B * S)):
+            g = torch.empty((rows, E), device=dev, dtype=torch.float32) if need else None
+            setattr(e, name, _p(g)); setattr(e, "ld" + name, E)
+            out.append(g)
+        e.B, e.L, e.S, e.H, e.d = B, L, S, H, d
+        check(_lib.lib().mpg_attn_dd(C.byref(e), _stream()), "mpg_attn_dd")
+        return (*out, *tail)
 
 
 # ------------------------------------------------------------------------------------- one launch per MAB

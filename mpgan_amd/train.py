@@ -457,7 +457,7 @@ class TrainStep:
                  graph_collectives: Optional[bool] = None, augment=None, loader=None, num_critic: int = 1, num_gen: int = 1,
                  track_epoch_losses: bool = False, label_smoothing: bool = False, label_noise: float = 0.0,
                  ema: Optional[Ema] = None, lr_schedule=None, grad_clip=None, gp_rows: Optional[bool] = None,
-                 _ada_split: bool = False):
+                 gp_attn: Optional[bool] = None, _ada_split: bool = False):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
         self.dev = dev = next(G.parameters()).device
@@ -493,6 +493,10 @@ class TrainStep:
         # the penalty's MPLayers on the twice-differentiable row kernels where ``ops.gp_rows_route`` covers them (None: as
         # ``ops.OPTIONS["gp_rows"]`` / MPG_GP_ROWS says as the step is built)
         self.gp_rows = bool(ops.OPTIONS["gp_rows"]) if gp_rows is None else bool(gp_rows)
+        # ... and the penalty's attention cores on the twice-differentiable attention kernels where ``ops.gp_attn_route`` covers them
+        # (None: as ``ops.OPTIONS["gp_attn"]`` / MPG_GP_ATTN says as the step is built).  The core has no parameters: nothing it
+        # hands to autograd meets a gradient of the second stream, so ``wgrad_side`` stays as it is
+        self.gp_attn = bool(ops.OPTIONS["gp_attn"]) if gp_attn is None else bool(gp_attn)
         self.GP = torch.zeros((), device=dev)   # last penalty value (the reference's losses["gp"])
         self.fixed_alpha = None   # tests: the interpolation weights [B, 1, 1] instead of fresh uniform samples
         self.G, self.D = G, D
@@ -921,12 +925,13 @@ class TrainStep:
         alpha = self.fixed_alpha if self.fixed_alpha is not None else torch.rand(B, 1, 1, device=real.device)
         x = (alpha * real + (1 - alpha) * fake.detach()).requires_grad_(True)
         prev, ops.OPTIONS["gp_rows"] = ops.OPTIONS["gp_rows"], self.gp_rows
+        prev_attn, ops.OPTIONS["gp_attn"] = ops.OPTIONS["gp_attn"], self.gp_attn
         try:
             with ops.double_backward_route(self.dev):
                 prob = self.D(x)
                 grads = torch.autograd.grad(prob, x, torch.ones_like(prob), create_graph=True, retain_graph=True)[0]
         finally:
-            ops.OPTIONS["gp_rows"] = prev
+            ops.OPTIONS["gp_rows"], ops.OPTIONS["gp_attn"] = prev, prev_attn
         norm = torch.sqrt((grads.reshape(B, -1) ** 2).sum(1) + 1e-12)
         return self.gp_lambda * ((norm - 1) ** 2).mean()
 

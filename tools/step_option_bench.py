@@ -1,7 +1,7 @@
 """What one option of the captured training iteration costs next to the step without it, on one GPU.  One JSON object per line on
 stdout and in --out.
 
-    python tools/step_option_bench.py --option {labels,ada,critic,sn,ema,ctl,gp} [--reps 10] [--out profiles/<option>_bench.jsonl]
+    python tools/step_option_bench.py --option {labels,ada,critic,sn,ema,ctl,gp} [--model gapt] [--reps 10] [--out profiles/<option>_bench.jsonl]
 
 MPGAN at N = 30, B = 256, the captured iteration, one process.  Two steps over the same weights and batch -- a baseline and the
 same with the option on -- and, where the option adds one launch to the D segment, that launch on its own outside any graph:
@@ -29,6 +29,10 @@ gp       two steps with ``loss="w", gp_lambda=10``: the penalty's D(x) on the ma
          route ``ops.double_backward_route`` has always taken) and on the twice-differentiable row kernels (b gp_step_rows:
          ``gp_rows=True``), at N = 30, B = 256 and again at N = 150, B = 16.  Held to, per shape: the median of (b) is not above the
          median of (a), measured in the same run.
+         ``--model gapt``: the attention discriminator instead, the penalty's attention cores as broadcast products (a gp_step_dd:
+         ``MAB._forward_dd`` as it has always run) and on the twice-differentiable attention kernels (b gp_step_attn:
+         ``gp_attn=True``), at N = 30, B = 512 and at N = 150, B = 64.  Held to, per shape: the median of (b) is not above the
+         median of (a) by more than (a)'s own run-to-run spread (max - min of its repetitions).
 
 Every ``step()`` and every lone launch sits between two HIP events of its own -- in all rows alike, so that what an event pair
 costs cancels between them.  A repetition is --batches steps of each kind (critic: two full cycles of the schedule) taken
@@ -267,6 +271,8 @@ def sn_bench(args, emit):
 def gp_bench(args, emit):
     """--option gp: the captured --gp iteration with the penalty on the existing route and on the rows route, alternated in one
     process, every ``step()`` between two HIP events; at the headline shape and at N = 150, B = 16."""
+    if args.model == "gapt":
+        return gp_attn_bench(args, emit)
     rows = ("a gp_step_edges", "b gp_step_rows")
     for n, b in ((N, B), (150, 16)):
         torch.manual_seed(0)
@@ -303,14 +309,57 @@ def gp_bench(args, emit):
         torch.cuda.empty_cache()
 
 
+def gp_attn_bench(args, emit):
+    """--option gp --model gapt: the captured --gp iteration of GAPT with the penalty's attention cores on the existing route and on
+    the attention kernels, alternated in one process, every ``step()`` between two HIP events; at N = 30, B = 512 and N = 150, B = 64."""
+    rows = ("a gp_step_dd", "b gp_step_attn")
+    for n, b in ((30, 512), (150, 64)):
+        torch.manual_seed(0)
+        steps = []
+        for gp_attn in (False, True):
+            G, D = train.default_gapt(n)
+            lrs = train.LR_GAPT
+            ts = train.TrainStep(G, D, b, n, latent=64, lr_disc=lrs[0], lr_gen=lrs[1], use_graphs=True, loss="w", gp_lambda=10.0,
+                                 gp_attn=gp_attn)
+            x, labels = mdata.synthetic_jets(b, n, seed=1)
+            ts.set_batch(x.cuda(), labels.cuda())
+            for _ in range(3):   # warm-up: captures the graph
+                ts.step()
+            torch.cuda.synchronize()
+            steps.append(ts)
+        us = {r: [] for r in rows}
+        for _ in range(args.reps):
+            t = {r: [] for r in rows}
+            for _ in range(args.batches):        # (alternated: the rows share whatever the box does meanwhile)
+                for r, ts in zip(rows, steps):
+                    t[r].append(timed(ts.step))
+            for r in rows:
+                us[r].append(float(np.mean(t[r])))
+        med = {}
+        for name, v in us.items():
+            med[name] = float(np.median(v))
+            emit({"model": "gapt", "B": b, "N": n, "loss": "w", "gp_lambda": 10.0, "gp_attn": name == rows[1], "row": name,
+                  "reps": args.reps, "batches_per_rep": args.batches, "median_us": med[name], "min_us": float(np.min(v)),
+                  "max_us": float(np.max(v)), "jets_per_s": b / (med[name] * 1e-6)})
+        diff, spread = med[rows[1]] - med[rows[0]], float(np.max(us[rows[0]]) - np.min(us[rows[0]]))
+        emit({"model": "gapt", "B": b, "N": n, "row": "condition", "attn_minus_dd_us": diff, "spread_dd_us": spread,
+              "attn_within_spread_of_dd": bool(diff <= spread),
+              **{f"{k}_{r[2:]}": float(getattr(ts, k)) for r, ts in zip(rows, steps) for k in ("D_loss", "GP")}})
+        del steps
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--option", choices=sorted([*OPTIONS, "ada", "sn", "ctl", "gp"]), required=True)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--batches", type=int, default=10, help="steps of each kind per repetition (critic: two cycles of the schedule)")
     ap.add_argument("--num-critic", type=int, default=5)
+    ap.add_argument("--model", choices=["mpgan", "gapt"], default="mpgan", help="gapt: with --option gp only")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.model != "mpgan" and args.option != "gp":
+        raise SystemExit("--model gapt is measured by --option gp only")
     if not torch.cuda.is_available():
         raise SystemExit(f"{args.option}_bench: no GPU visible (timings are taken on the device or not at all)")
     emit = jsonl_sink(args.out)
