@@ -493,6 +493,46 @@ int mpg_disc_head_bwd(const MpgDiscHead* p, void* stream);
  * + mpg_disc_head_bwd).  Same results as the two calls. */
 int mpg_disc_head_loss(const MpgDiscHead* p, void* stream);
 
+/* mpg_disc_head_dd: what a twice-differentiable head (the gradient penalty through MPDiscriminator / GAPT_D) needs beside
+ * mpg_disc_head_fwd.  There the mask is real-valued and takes a gradient, which mpg_disc_head_bwd does not form.  Per jet, with
+ * d = 1 (sum), sum_i m_i + 1e-12 (mean, mask) or N (mean, no mask), kappa the keep-and-scale of the output dropout (regenerated
+ * from seed / tag / thr as the forward draws it), phi the sigmoid or the identity:
+ *     t_i = <w, y_i>,  S = sum_i m_i t_i,  s = S / d + b,  z = kappa s,  out = phi(z),  c = S / d (mean with mask) or 0
+ * mode 0, the first derivative for the cotangent g on out (g NULL = zero):  gh = g phi'(z) kappa
+ *     gy_i = gh m_i w / d      gm_i = gh (t_i - c) / d      gw = sum_b gh sum_i m_i y_i / d      gb = sum_b gh
+ * mode 1, the second derivative: with cotangents U_i on gy_i and mu_i on gm_i (either may be NULL = zero) and
+ *     Phi = sum_i <U_i, gy_i> + sum_i mu_i gm_i = gh R,   a_i = <w, U_i>,  Q = sum_i mu_i (mean with mask; 0 otherwise),
+ *     R = (sum_i m_i a_i + sum_i mu_i t_i - c Q) / d,     H = g kappa^2 phi''(z) R,     e_i = (mu_i - Q m_i / d) / d
+ * it writes the gradients of Phi:
+ *     gg = kappa phi'(z) R                          (with respect to g)
+ *     gy_i = (H m_i / d + gh e_i) w
+ *     gm_i = H (t_i - c) / d + gh ((a_i - Q (t_i - c) / d) / d - [mean with mask] R / d)
+ *     gw = sum_b ( sum_i (H m_i / d + gh e_i) y_i + (gh / d) sum_i m_i U_i )        gb = sum_b H
+ * Under the mean with a mask the differences t_i - c, a_i d - sum_j m_j a_j and mu_i d - Q m_i are formed as single sums of pairwise
+ * terms (sum_j m_j (t_i - t_j) + 1e-12 t_i, ...): a jet with one real particle, where they are 1e-12 of their terms, keeps its digits.
+ * One wave per jet, fp32; every sum over a jet's particles and over the features runs in index order, gw / gb across jets through
+ * per-jet rows `part` [B, F + 1] and a fixed-order reduction; no atomics: two launches give the same bits.  Any output may be NULL
+ * (= not wanted; `part` is needed for gw / gb) and the work behind it is skipped, as is the work behind a NULL U / mu.
+ * mask NULL: m_i = 1, gm must be NULL.  1 <= N <= 1024.
+ * Errors, before anything is launched: -1 sizes or mode, -2 a required pointer is NULL, -5 a row stride below F. */
+typedef struct MpgDiscHeadDD {
+    const float* y; int ldy;              /* [B, N, F], row (particle) stride ldy                  */
+    const float* mask;                    /* [B, N] or NULL                                        */
+    const float* w; const float* bias;    /* weight [F], bias [1] or NULL                          */
+    int B, N, F, mean, sigmoid;
+    const uint64_t* seed; uint32_t tag, thr; float dscale;
+    int mode;
+    const float* g;                       /* [B]: the cotangent on out                             */
+    const float* U; int ldu;              /* [B, N, F] or NULL (mode 1)                            */
+    const float* mu;                      /* [B, N] or NULL (mode 1)                               */
+    float* gy; int ld_gy;                 /* [B, N, F] or NULL                                     */
+    float* gm;                            /* [B, N] or NULL                                        */
+    float* gg;                            /* [B] or NULL (mode 1)                                  */
+    float* part;                          /* [B, F + 1] scratch for gw / gb                        */
+    float* gw; float* gb;                 /* [F], [1] or NULL                                      */
+} MpgDiscHeadDD;
+int mpg_disc_head_dd(const MpgDiscHeadDD* p, void* stream);
+
 /* mpg_bridge_fwd / mpg_bridge_bwd: the rows between a GAPT generator's last attention block and the discriminator's first
  * one as ONE launch each way (csrc/bridge.hip) -- gen's final_fc (gapt/model.py:248, :263: Linear K -> F, no activation) and
  * final tanh (:265), then disc's input_embedding (:300-302, :336-339: Linear F -> E, LeakyReLU, dropout), which otherwise run

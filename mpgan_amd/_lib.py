@@ -199,6 +199,17 @@ class MpgDiscHead(C.Structure):
     ]
 
 
+class MpgDiscHeadDD(C.Structure):
+    _fields_ = [
+        ("y", _fp), ("ldy", C.c_int), ("mask", _fp), ("w", _fp), ("bias", _fp),
+        ("B", C.c_int), ("N", C.c_int), ("F", C.c_int), ("mean", C.c_int), ("sigmoid", C.c_int),
+        ("seed", _fp), ("tag", C.c_uint32), ("thr", C.c_uint32), ("dscale", C.c_float),
+        ("mode", C.c_int),
+        ("g", _fp), ("U", _fp), ("ldu", C.c_int), ("mu", _fp),
+        ("gy", _fp), ("ld_gy", C.c_int), ("gm", _fp), ("gg", _fp), ("part", _fp), ("gw", _fp), ("gb", _fp),
+    ]
+
+
 class MpgBridge(C.Structure):
     _fields_ = [
         ("x", _fp), ("ldx", C.c_int), ("W1", _fp), ("b1", _fp), ("act1", C.c_int),
@@ -315,6 +326,7 @@ SIGNATURES = {
     "mpg_disc_head_fwd": (C.c_int, [C.POINTER(MpgDiscHead), C.c_void_p]),
     "mpg_disc_head_bwd": (C.c_int, [C.POINTER(MpgDiscHead), C.c_void_p]),
     "mpg_disc_head_loss": (C.c_int, [C.POINTER(MpgDiscHead), C.c_void_p]),
+    "mpg_disc_head_dd": (C.c_int, [C.POINTER(MpgDiscHeadDD), C.c_void_p]),
     "mpg_layernorm_fwd": (C.c_int, [_fp, C.c_int, _fp, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "mpg_layernorm_bwd": (C.c_int, [_fp, C.c_int, _fp, C.c_int, _fp, _fp, _fp, C.c_int, _fp, C.c_int, _fp, _fp, C.c_int,
                                     C.c_int, C.c_int, C.c_void_p]),

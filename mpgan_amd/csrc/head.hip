@@ -9,6 +9,8 @@
 //                        + Dropout) + the final sigmoid -- and, when a loss is named, the per-jet loss terms of
 //                        calc_D_loss / calc_G_loss (train.py:331-395, :465-476) with their gradient, so that the
 //                        backward starts from the last MPLayer's output without any autograd node in between
+//   mpg_disc_head_dd     the same head for the gradient penalty (a real-valued mask that takes a gradient): its first derivative
+//                        with the mask gradient (mode 0) and the second derivative (mode 1), fp32, fixed summation order
 #include "common.h"
 #include "../../include/mpgan_amd.h"
 
@@ -252,6 +254,126 @@ __global__ __launch_bounds__(256) void disc_head_reduce_kernel(const MpgDiscHead
     }
 }
 
+// ---- the twice-differentiable head (mpg_disc_head_dd; the rule is derived in DESIGN.md section 4): one wave per jet.
+// Pass 1, lane = particle: t_i = <w, y_i> and a_i = <w, U_i>, features in index order, parked in LDS with m_i and mu_i; then every
+// lane adds up the jet's five scalars itself, particles in index order (the same bits in every lane: nothing to broadcast), and
+// writes its particles' coefficients.  Pass 2, lane = feature: the rank-one rows gy_i = cy_i w and the jet's row of `part`
+// (its share of gw, particles in index order; gb in column F).
+__global__ __launch_bounds__(64) void disc_head_dd_kernel(const MpgDiscHeadDD p) {
+    extern __shared__ float dd[];
+    const int N = p.N, F = p.F, b = blockIdx.x, lane = threadIdx.x;
+    float* st = dd;            // t_i
+    float* sm = dd + N;        // m_i
+    float* sa = dd + 2 * N;    // a_i, then cu_i (the factor of U_i in gw)
+    float* su = dd + 3 * N;    // mu_i
+    float* sc = dd + 4 * N;    // cy_i (the factor of w in gy_i, of y_i in gw)
+    float* sq = dd + 5 * N;    // tau_i = t_i - c
+    float* sal = dd + 6 * N;   // a_i d - sum_j m_j a_j  (mean with a mask)
+    float* sbe = dd + 7 * N;   // mu_i d - Q m_i        (mean with a mask)
+    const float* yb = p.y + (size_t)b * N * p.ldy;
+    const float* Ub = (p.mode == 1 && p.U != nullptr) ? p.U + (size_t)b * N * p.ldu : nullptr;
+    const float* mub = (p.mode == 1 && p.mu != nullptr) ? p.mu + (size_t)b * N : nullptr;
+    for (int i = lane; i < N; i += 64) {
+        float t = 0.f, a = 0.f;
+        for (int f = 0; f < F; ++f) t += p.w[f] * yb[(size_t)i * p.ldy + f];
+        if (Ub != nullptr)
+            for (int f = 0; f < F; ++f) a += p.w[f] * Ub[(size_t)i * p.ldu + f];
+        st[i] = t; sa[i] = a;
+        sm[i] = p.mask != nullptr ? p.mask[(size_t)b * N + i] : 1.f;
+        su[i] = mub != nullptr ? mub[i] : 0.f;
+    }
+    __syncthreads();
+    float S = 0.f, M = 0.f, A = 0.f, Q = 0.f;
+    for (int i = 0; i < N; ++i) {
+        const float m = sm[i];
+        S += m * st[i]; M += m; A += m * sa[i]; Q += su[i];
+    }
+    const bool mm = p.mean && p.mask != nullptr;   // the divisor depends on the mask
+    const float inv_d = p.mean ? 1.f / (p.mask != nullptr ? M + 1e-12f : (float)N) : 1.f;
+    if (!mm) Q = 0.f;
+    // tau_i = t_i - c, and under the mean with a mask the two other differences of the rule, each as ONE sum of pairwise terms:
+    //   t_i - S / d        = (sum_j m_j (t_i - t_j) + 1e-12 t_i) / d
+    //   a_i d - sum m_j a_j = sum_j m_j (a_i - a_j) + 1e-12 a_i            mu_i d - Q m_i = sum_j (mu_i m_j - mu_j m_i) + 1e-12 mu_i
+    // (formed as t_i - S / d a jet with one real particle -- where the three are 1e-12 of their terms -- would keep no digit)
+    for (int i = lane; i < N; i += 64) {
+        float tau = st[i], al = 0.f, be = 0.f;
+        if (mm) {
+            const float ti = st[i], ai = sa[i], ui = su[i], mi = sm[i];
+            float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+            for (int j = 0; j < N; ++j) {
+                const float mj = sm[j];
+                // (the term of j = i is left out of s3: contracted into one fma, mu_i m_i - mu_i m_i is not the exact zero it is)
+                s1 += mj * (ti - st[j]); s2 += mj * (ai - sa[j]); s3 += j == i ? 0.f : ui * mj - su[j] * mi;
+            }
+            tau = (s1 + 1e-12f * ti) * inv_d; al = s2 + 1e-12f * ai; be = s3 + 1e-12f * ui;
+        }
+        sq[i] = tau; sal[i] = al; sbe[i] = be;
+    }
+    __syncthreads();
+    float kappa = 1.f;
+    if (p.thr) {
+        const uint64_t sd = *p.seed;
+        kappa = drop_keep_f((uint32_t)sd, (uint32_t)(sd >> 32), p.tag, (uint32_t)b, 0, p.thr) ? p.dscale : 0.f;
+    }
+    const float z = kappa * (S * inv_d + (p.bias != nullptr ? p.bias[0] : 0.f));
+    float d1 = 1.f, d2 = 0.f;   // phi'(z), phi''(z)
+    if (p.sigmoid) { const float o = 1.f / (1.f + expf(-z)); d1 = o * (1.f - o); d2 = d1 * (1.f - 2.f * o); }
+    const float g = p.g != nullptr ? p.g[b] : 0.f;
+    const float gh = g * d1 * kappa;
+    float R = 0.f, H = 0.f, Pt = 0.f;
+    if (p.mode == 1) {
+        for (int i = 0; i < N; ++i) Pt += su[i] * sq[i];   // sum_i mu_i (t_i - c)
+        R = (A + Pt) * inv_d;
+        H = g * kappa * kappa * d2 * R;
+        if (lane == 0 && p.gg != nullptr) p.gg[b] = kappa * d1 * R;
+    }
+    for (int i = lane; i < N; i += 64) {
+        const float m = sm[i], tau = sq[i];
+        float cy, cu = 0.f, gm;
+        if (p.mode == 0) {
+            cy = gh * m * inv_d;
+            gm = gh * tau * inv_d;
+        } else {
+            const float e = mm ? sbe[i] * inv_d * inv_d : su[i] * inv_d;
+            cy = H * m * inv_d + gh * e;
+            cu = gh * m * inv_d;
+            gm = H * tau * inv_d + gh * (mm ? ((sal[i] - Pt) * inv_d - Q * tau * inv_d) * inv_d : sa[i] * inv_d);
+        }
+        sc[i] = cy; sa[i] = cu;
+        if (p.gm != nullptr) p.gm[(size_t)b * N + i] = gm;
+    }
+    __syncthreads();
+    if (p.gy == nullptr && p.part == nullptr) return;
+    for (int f = lane; f < F; f += 64) {
+        const float wf = p.w[f];
+        float acc = 0.f;
+        for (int i = 0; i < N; ++i) {
+            const float cy = sc[i];
+            if (p.gy != nullptr) p.gy[((size_t)b * N + i) * p.ld_gy + f] = cy * wf;
+            if (p.part != nullptr) {
+                acc += cy * yb[(size_t)i * p.ldy + f];
+                if (Ub != nullptr) acc += sa[i] * Ub[(size_t)i * p.ldu + f];
+            }
+        }
+        if (p.part != nullptr) p.part[(size_t)b * (F + 1) + f] = acc;
+    }
+    if (lane == 0 && p.part != nullptr) p.part[(size_t)b * (F + 1) + F] = p.mode == 0 ? gh : H;
+}
+
+// gw[f] = sum_b part[b, f], gb = sum_b part[b, F]: one wave per output, four loads in flight per lane, a fixed order
+__global__ __launch_bounds__(256) void disc_head_dd_reduce_kernel(const float* __restrict__ part, int B, int F, float* __restrict__ gw,
+                                                                  float* __restrict__ gb) {
+    const int f = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (f > F) return;
+    float* dst = f < F ? (gw != nullptr ? gw + f : nullptr) : gb;
+    if (dst == nullptr) return;
+    auto term = [&](int b) { return b < B ? part[(size_t)b * (F + 1) + f] : 0.f; };
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    for (int b = lane; b < B; b += 256) { s0 += term(b); s1 += term(b + 64); s2 += term(b + 128); s3 += term(b + 192); }
+    const float s = wave_sum((s0 + s1) + (s2 + s3));
+    if (lane == 0) *dst = s;
+}
+
 // ---- k-nearest-neighbour sets (MPLayer._getA_knn, mpgan/model.py:319-381) as bit masks; one workgroup per jet
 __global__ __launch_bounds__(256) void knn_sets_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ mask, int N, int F,
                                                        int k, int first, unsigned int* __restrict__ nbr) {
@@ -430,6 +552,19 @@ extern "C" int mpg_disc_head_loss(const MpgDiscHead* p, void* stream) {
     hipLaunchKernelGGL(disc_head_fwd_kernel<true>, dim3((p->B + 3) / 4), dim3(256), 0, st, *p);
     if (p->loss_out != nullptr || p->dw != nullptr)
         hipLaunchKernelGGL(disc_head_reduce_kernel, dim3(1 + (p->dw != nullptr ? (p->F + 1 + 3) / 4 : 0)), dim3(256), 0, st, *p);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mpg_disc_head_dd(const MpgDiscHeadDD* p, void* stream) {
+    if (p->B <= 0 || p->N <= 0 || p->N > 1024 || p->F <= 0 || p->mode < 0 || p->mode > 1) return -1;
+    if (p->y == nullptr || p->w == nullptr || (p->thr != 0 && p->seed == nullptr) || (p->mode == 1 && p->g == nullptr)) return -2;
+    if ((p->gw != nullptr || p->gb != nullptr) && p->part == nullptr) return -2;
+    if (p->gm != nullptr && p->mask == nullptr) return -2;
+    if (p->ldy < p->F || (p->gy != nullptr && p->ld_gy < p->F) || (p->U != nullptr && p->ldu < p->F)) return -5;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(disc_head_dd_kernel, dim3(p->B), dim3(64), 8 * p->N * sizeof(float), st, *p);
+    if (p->gw != nullptr || p->gb != nullptr)
+        hipLaunchKernelGGL(disc_head_dd_reduce_kernel, dim3((p->F + 1 + 3) / 4), dim3(256), 0, st, p->part, p->B, p->F, p->gw, p->gb);
     return (int)hipGetLastError();
 }
 

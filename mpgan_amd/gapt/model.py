@@ -124,14 +124,16 @@ class MAB(nn.Module):
     def _after_attention_dd(self, x2: Tensor, o: Tensor, B: int, L: int, E: int) -> Tensor:
         """``_forward_dd`` behind the attention core: out-projection with the residual, LayerNorm, dropout, feed-forward."""
         att, mm = self.attention, ops.MatMulFn.apply
+        # (with ops.OPTIONS["gp_chain"] the block's two dropouts are keyed by the device seed like the LinearNets': ops.keyed_dropout)
+        drop = ops.keyed_dropout if ops.OPTIONS["gp_chain"] else torch.nn.functional.dropout
         za = x2 + mm(o, att.out_proj.weight, "nt") + att.out_proj.bias
         if self.layer_norm:
             za = torch.nn.functional.layer_norm(za, (E,), self.norm1.weight, self.norm1.bias, self.norm1.eps)
-        z = torch.nn.functional.dropout(za, self.dropout_p, self.training)
+        z = drop(za, self.dropout_p, self.training)
         zf = self.ff(z, resid=z)                                                             # (LinearNet takes its own dd form)
         if self.layer_norm:
             zf = torch.nn.functional.layer_norm(zf, (E,), self.norm2.weight, self.norm2.bias, self.norm2.eps)
-        return torch.nn.functional.dropout(zf, self.dropout_p, self.training).reshape(B, L, E)
+        return drop(zf, self.dropout_p, self.training).reshape(B, L, E)
 
     @staticmethod
     def _ignore_of(y_mask, B: int, S: int):
@@ -436,9 +438,13 @@ class GAPT_D(nn.Module):
 
     def forward(self, x: Tensor, labels: Tensor = None):
         pooled, _ = self.features(x, labels)
-        head = self.fused_head() if (pooled.is_cuda and not ops.double_backward_on(pooled.device)) else None
+        dd = pooled.is_cuda and ops.double_backward_on(pooled.device)
+        head = self.fused_head() if (pooled.is_cuda and (not dd or ops.gp_head_route(1, True))) else None
         if head is None:
             return torch.sigmoid(self.final_fc(pooled.squeeze()))  # .squeeze() as the reference (:344)
         w, b, mean, sigmoid, p = head
-        out = ops.DiscHeadFn.apply(pooled, None, w, b, mean, sigmoid, p, self.training)
+        if dd:   # (the N = 1, no-mask form, twice differentiable)
+            out = ops.DiscHeadDDFn.apply(pooled, None, w, b, ops.DiscHeadDDSettings(mean, sigmoid, p, self.training, None, False))
+        else:
+            out = ops.DiscHeadFn.apply(pooled, None, w, b, mean, sigmoid, p, self.training)
         return out.unsqueeze(1) if out.shape[0] > 1 else out   # shapes of the reference's .squeeze() path

@@ -143,12 +143,31 @@ class LinearNet(nn.Module):
                 bn.running_var.mul_(1 - mom).add_(var, alpha=mom * M / max(M - 1, 1))
         return y
 
-    def _forward_dd(self, x: Tensor, resid: Tensor = None) -> Tensor:
+    def gp_chain_ok(self, double_backward: bool, options: dict = None) -> bool:
+        """``ops.gp_chain_route`` with this net's facts: would a call inside ``ops.double_backward_route`` run as ``ops.LinearNetFn``?
+        Host only."""
+        if not self.plain:
+            return False
+        widths = [self.net[0].in_features] + [l.out_features for l in self.net]
+        return ops.gp_chain_route(widths, self.final_linear, self.batch_norm, self.spectral_norm, double_backward, options=options)
+
+    def _forward_dd(self, x: Tensor, resid: Tensor = None, x2: Tensor = None) -> Tensor:
         """The twice-differentiable form (``ops.double_backward_route``): Linear as ``ops.MatMulFn`` + bias, LeakyReLU and
         dropout as ATen's own (their derivative formulas are differentiable; dropout draws from torch's generator, as
-        the reference's does).  Batch norm has a first-order kernel only."""
+        the reference's does).  Batch norm has a first-order kernel only.  With ``ops.OPTIONS["gp_chain"]`` a net that
+        ``ops.gp_chain_route`` covers runs as ``ops.LinearNetFn`` instead: one chained launch per pass, its dropout keyed by the
+        device seed and ``ops.next_tag``, the input rows as the two parts (x | x2) when ``x2`` is given."""
         if self.batch_norm:
             raise NotImplementedError("LinearNet: batch norm has no double-backward route (the gradient penalty needs one)")
+        if self.gp_chain_ok(True):
+            shp = x.shape
+            y = ops.linear_net_dd(x.reshape(-1, shp[-1]), None if x2 is None else x2.reshape(-1, x2.shape[-1]),
+                                  [l.weight for l in self.net], [l.bias for l in self.net], final_linear=self.final_linear,
+                                  alpha=self.leaky_relu_alpha, p_drop=self.dropout_p, training=self.training,
+                                  resid=None if resid is None else resid.reshape(-1, resid.shape[-1]))
+            return y.reshape(*shp[:-1], y.shape[-1])
+        if x2 is not None:
+            x = torch.cat((x, x2), dim=-1)
         last = len(self.net) - 1
         shp = x.shape
         x = x.reshape(-1, shp[-1])
@@ -163,11 +182,14 @@ class LinearNet(nn.Module):
         x = x.reshape(*shp[:-1], x.shape[-1])
         return x if resid is None else x + resid
 
-    def forward(self, x: Tensor, resid: Tensor = None) -> Tensor:
+    def forward(self, x: Tensor, resid: Tensor = None, x2: Tensor = None) -> Tensor:
         """``resid`` (not in the reference signature): added to the output, inside the last layer's launch when that
-        layer has no activation -- MAB's ``x + ff(x)``."""
+        layer has no activation -- MAB's ``x + ff(x)``.  ``x2`` (neither): more input columns, held apart -- the net runs on
+        (x | x2); only the twice-differentiable op takes the two parts as they are, every other route concatenates."""
         if x.is_cuda and ops.double_backward_on(x.device):
-            return self._forward_dd(x, resid)
+            return self._forward_dd(x, resid, x2)
+        if x2 is not None:
+            x = torch.cat((x, x2), dim=-1)
         last = len(self.net) - 1
         eff = _spectral_group(self.net) if (self.spectral_norm and x.is_cuda and ops.OPTIONS["sn_fused"]) else None
         for k, lin in enumerate(self.net):
@@ -301,6 +323,8 @@ class MPLayer(nn.Module):
         if edge_mask is not None:
             E = E * edge_mask
         agg = E.sum(dim=2) if self.sum else E.mean(dim=2)
+        if not (self.clabels or self.mask_fne_np) and x.is_cuda and ops.double_backward_on(x.device) and self.fn.gp_chain_ok(True):
+            return self._fn_parts(agg, x)
         h = torch.cat((agg, x), dim=2).reshape(B * N, -1)
         if self.clabels:
             h = torch.cat((h, labels[:, :self.clabels].repeat(N, 1)), dim=1)
@@ -379,8 +403,15 @@ class MPLayer(nn.Module):
         agg = ops.EdgeRowsFn.apply(x, mask if use_mask else None, fe[0].weight, fe[0].bias, fe[1].weight, fe[1].bias, fe[2].weight,
                                    fe[2].bias, ops.EdgeRowsSettings(self.sum, self.fe.leaky_relu_alpha, self.fe.dropout_p, self.training,
                                                                     self._packed(), nbr, self.num_knn, None, False))
+        if self.fn.gp_chain_ok(True):
+            return self._fn_parts(agg, x)
         h = torch.cat((agg, x), dim=2).reshape(B * N, -1)
         return self.fn(h.contiguous()).reshape(B, N, self.output_node_size)
+
+    def _fn_parts(self, agg: Tensor, x: Tensor) -> Tensor:
+        """The node network on (agg | x) held apart (``ops.LinearNetFn``'s two-part input): no ``torch.cat`` and none of its derivatives."""
+        B, N, _ = x.shape
+        return self.fn(agg.reshape(B * N, -1), x2=x.reshape(B * N, -1)).reshape(B, N, self.output_node_size)
 
     def _folded_w1(self, W1: Tensor) -> Tensor:
         """fe.net.0.weight with the coordinate-difference columns folded into the node columns: the reference appends
@@ -661,11 +692,14 @@ class MPDiscriminator(MPNet):
         return x, mask
 
     def forward(self, x: Tensor, labels: Tensor = None) -> Tensor:
-        head = self.fused_head() if (x.is_cuda and not ops.double_backward_on(x.device)) else None
+        dd = x.is_cuda and ops.double_backward_on(x.device)
+        head = self.fused_head() if (x.is_cuda and (not dd or ops.gp_head_route(x.shape[1], True))) else None
         if head is None:
             return super().forward(x, labels)
         y, mask = self.features(x, labels)
         w, b, mean, sigmoid, p = head
+        if dd:   # (the mask is real-valued here and takes a gradient: ops.DiscHeadDDFn)
+            return ops.DiscHeadDDFn.apply(y, mask, w, b, ops.DiscHeadDDSettings(mean, sigmoid, p, self.training, None, False)).unsqueeze(1)
         return ops.DiscHeadFn.apply(y, mask, w, b, mean, sigmoid, p, self.training).unsqueeze(1)
 
     def _post_mp(self, x, labels, use_mask, mask, num_jet_particles):

@@ -3,7 +3,8 @@
 Everything here hands raw device pointers + sizes to libmpgan_amd.so on torch's current HIP
 stream; torch is used for memory, autograd bookkeeping and a few tiny reductions only.  There is
 no CPU path: tensors must live on a gfx950 device.  (One exception, for checking a derivative rule in fp64 without a GPU:
-``EdgeRowsFn`` / ``EdgeRowsVJPFn`` evaluate CPU tensors with the same formulas in plain torch.)
+``EdgeRowsFn`` / ``EdgeRowsVJPFn``, ``AttnCoreFn``, ``LinearNetFn`` and ``DiscHeadDDFn`` evaluate CPU tensors with the same formulas in
+plain torch.)
 """
 from __future__ import annotations
 
@@ -67,6 +68,12 @@ OPTIONS = {
     # mpg_attn_fwd / _bwd / _dd, twice differentiable) instead of the broadcast products of MAB._forward_dd, for the blocks
     # ``gp_attn_route`` covers.  Off unless asked for: MPG_GP_ATTN=1, or TrainStep(gp_attn=True).
     "gp_attn": os.environ.get("MPG_GP_ATTN", "0") not in ("", "0"),
+    # the gradient penalty's LinearNets as one twice-differentiable op each (``LinearNetFn``: mpg_chain for the forward, the
+    # input-gradient chain and the tangent chain, one grouped launch for all weight gradients, keyed dropout) instead of the
+    # MatMulFn / bias / leaky_relu / dropout composites of LinearNet._forward_dd, for the nets ``gp_chain_route`` covers, and the
+    # discriminator's pooling + fnd_layer + sigmoid on ``DiscHeadDDFn`` (mpg_disc_head_fwd / _dd).  Off unless asked for:
+    # MPG_GP_CHAIN=1, or TrainStep(gp_chain=True).
+    "gp_chain": os.environ.get("MPG_GP_CHAIN", "0") not in ("", "0"),
 }
 NUM_CUS = 256
 # Forward products (they decide LeakyReLU signs) are split as fp16 hi/lo with the operand scales below (~2^-21 per
@@ -2283,6 +2290,279 @@ def double_backward_on(device) -> bool:
     return dev_state(device).double_backward
 
 
+# ---- LinearNet as one twice-differentiable op (the gradient penalty; OPTIONS["gp_chain"]) ----------------------------------------
+# On rows X_0 = (A | A2), with K_l the dropout keep-and-scale of layer l and G_l = K_l lrelu'(Z_l) (lrelu' = 1 on a layer without
+# activation), constant almost everywhere:
+#   forward       Z_l = X_{l-1} W_l^T + b_l ,  X_l = K_l lrelu(Z_l) = G_l Z_l                          l = 1..L   (+ resid on X_L)
+#   first order   dZ_L = G_L Y_bar ,  dZ_{l-1} = G_{l-1} (dZ_l W_l) ,  x_bar = dZ_1 W_1 ,  W_bar_l = dZ_l^T X_{l-1} ,  b_bar_l = colsum dZ_l
+#   second order  (u on x_bar, Phi = <u, x_bar>)   T_0 = u ,  T_l = G_l (T_{l-1} W_l^T)
+#                 dPhi/dY_bar = T_L ,  dPhi/dW_l = dZ_l^T T_{l-1} ,  dPhi/dX_0 = 0 ,  dPhi/db_l = 0
+# All three passes are mpg_chain launches on bf16 hi/lo images (three terms: cotangents and tangents of any magnitude pass): the
+# forward chain with per-layer outputs; the input-gradient chain with gateH = X_{l-1} and per-layer out = dZ_l; the tangent chain in
+# the forward form with act = 0, no bias and gateH = X_l.  mpg_chain's gate on its INPUT is the dropout keep alone (in_thr): where the
+# op's last layer has an activation (a net without final_linear, the leading ops of a net of more than three layers) dZ_L comes
+# from one mpg_gate launch in front of the chain -- the one field the chain lacks (an input gateH).  All W_bar / dPhi/dW of an op
+# come from one grouped split-K launch (``WgradBatch``).  The masks are regenerated from (tag, thr) in the gates, never stored;
+# ``dropout_mask(rows, width, tag + 1 + l, thr)`` is layer l's (0-based; ``tag`` = the op's ``next_tag``).
+CHAIN_OP_LAYERS = 3
+LinearNetSettings = namedtuple("LinearNetSettings", "acts alpha p_drop training keeps param_grads", defaults=(0.2, 0.0, True, None, True))
+
+
+class PackedLinearNet(_PackedSet):
+    """The images one ``LinearNetFn`` call needs: W_l as the forward and tangent chains apply it and its transpose for the
+    input-gradient chain, bf16 hi/lo, one ``mpg_pack_many`` launch."""
+
+    def __init__(self, weights):
+        spec = {}
+        for l, W in enumerate(weights):
+            n, k = W.shape
+            spec[f"W{l}"] = (W, n, k, 0, 1.0, False, 0, 0)
+            spec[f"W{l}T"] = (W, k, n, 1, 1.0, False, 0, 0)
+        super().__init__(tuple(weights), spec)
+
+
+def _chain_sizes_ok(widths) -> bool:
+    # would mpg_chain take layers of these widths (K = widths[l], N = widths[l + 1])?  Sizes only: no pointer is dereferenced
+    c = MpgChain()
+    c.A, c.lda, c.K1, c.a_slabs = C.c_void_p(16), widths[0], widths[0], 1
+    c.M, c.nlayers, c.alpha = 32, len(widths) - 1, 0.2
+    for l in range(len(widths) - 1):
+        c.L[l].K, c.L[l].N = widths[l], widths[l + 1]
+    return chain_route(c) > 0
+
+
+def gp_chain_pieces(nlayers: int):
+    """The layer ranges [i0, i1) of the consecutive ops a net of ``nlayers`` layers runs as (``CHAIN_OP_LAYERS`` each at most)."""
+    return [(i0, min(i0 + CHAIN_OP_LAYERS, nlayers)) for i0 in range(0, nlayers, CHAIN_OP_LAYERS)]
+
+
+def gp_chain_route(widths, final_linear, batch_norm, spectral_norm, double_backward, options=None) -> bool:
+    """Does a LinearNet call inside ``double_backward_route`` take ``LinearNetFn`` instead of the composites of
+    ``LinearNet._forward_dd``?  Only with the option on (``OPTIONS["gp_chain"]``), for a plain net (no batch norm, no spectral norm)
+    every piece of which ``mpg_chain_route`` accepts in the forward and in the input-gradient direction (``widths``: input width,
+    then every layer's output width).  ``final_linear`` does not restrict anything: a last layer with an activation costs one
+    ``mpg_gate`` launch.  Host only."""
+    opt = OPTIONS if options is None else options
+    if not (opt.get("gp_chain") and double_backward) or batch_norm or spectral_norm or len(widths) < 2 or min(widths) < 1:
+        return False
+    widths = [int(v) for v in widths]
+    for i0, i1 in gp_chain_pieces(len(widths) - 1):
+        w = widths[i0:i1 + 1]
+        if not (_chain_sizes_ok(w) and _chain_sizes_ok(w[::-1])):
+            return False
+    return True
+
+
+class _NetState:
+    """What one ``LinearNetFn`` call keeps for its two derivatives beside its saved inputs."""
+    __slots__ = ("cpu", "M", "K1", "L", "widths", "acts", "alpha", "thr", "dscale", "tag", "seed_t", "pk", "X", "G", "param_grads",
+                 "has_bias", "has_resid")
+
+
+def _net_gate(st, l, Y):
+    # the ``gate`` entry of a chain layer that multiplies by G_l (0-based l), or None where G_l = 1.  ``st.X`` holds the outputs of
+    # every layer but the last, whose output ``Y`` is the op's own (saved as an output, not on the state: no reference cycle)
+    X = Y if l == st.L - 1 else st.X[l]
+    return (X, st.acts[l], st.tag + 1 + l, st.thr, st.dscale) if (st.acts[l] or st.thr) else None
+
+
+class LinearNetFn(torch.autograd.Function):
+    """Up to three layers of a plain LinearNet on rows (A | A2) [M, K1 + K2], twice differentiable: see above.  ``resid`` [M, N_L] or
+    None is added to the output (only behind a last layer without activation); ``settings``: a ``LinearNetSettings`` -- ``acts`` one
+    flag per layer, ``keeps`` the keep-and-scale masks of a CPU call (None: no dropout), ``param_grads`` False: a first derivative
+    taken with ``create_graph=True`` forms no parameter gradients (the penalty differentiates with respect to the input alone).
+    ``params``: W_1, b_1, ..., W_L, b_L (a bias may be None).  CPU tensors take the same formulas in plain torch, in their dtype."""
+
+    @staticmethod
+    def forward(ctx, A, A2, resid, settings, *params):
+        s = settings
+        Ws, bs = params[0::2], params[1::2]
+        L = len(Ws)
+        if not (1 <= L <= CHAIN_OP_LAYERS and len(s.acts) == L and len(bs) == L):
+            raise ValueError(f"LinearNetFn: 1..{CHAIN_OP_LAYERS} layers with a flag and a bias slot each, got {L}")
+        if resid is not None and s.acts[-1]:
+            raise NotImplementedError("LinearNetFn: a residual needs a last layer without activation")
+        st = _NetState()
+        st.cpu, st.M, st.K1, st.L = not A.is_cuda, A.shape[0], A.shape[1], L
+        st.widths = [A.shape[1] + (0 if A2 is None else A2.shape[1])] + [W.shape[0] for W in Ws]
+        st.acts, st.alpha, st.param_grads = tuple(bool(a) for a in s.acts), float(s.alpha), bool(s.param_grads)
+        st.has_bias, st.has_resid = tuple(b is not None for b in bs), resid is not None
+        ctx.st = st
+        if st.cpu:
+            h = A if A2 is None else torch.cat((A, A2), 1)
+            st.X, st.G = [], []
+            for l in range(L):
+                Z = h @ Ws[l].t()
+                if bs[l] is not None:
+                    Z = Z + bs[l]
+                g = torch.where(Z > 0, torch.ones_like(Z), torch.full_like(Z, st.alpha)) if st.acts[l] else torch.ones_like(Z)
+                if s.keeps is not None and s.keeps[l] is not None:
+                    g = g * s.keeps[l]
+                h = g * Z
+                st.G.append(g)
+                if l < L - 1:
+                    st.X.append(h)
+            out = h if resid is None else h + resid
+            ctx.save_for_backward(A, A2, out, *params)
+            return out
+        _chk(A, "A")
+        dev, M = A.device, st.M
+        st.thr, st.dscale = drop_params(s.p_drop) if s.training else (0, 1.0)
+        st.seed_t, st.tag = seed_tensor(dev), next_tag(dev, "linear_net", st.thr)
+        st.pk = PackedLinearNet(Ws).ensure()
+        A, A2 = _unit_cols(A), None if A2 is None else _unit_cols(A2)
+        r2 = None if resid is None else _unit_cols(resid)
+        X = [torch.empty((M, n), device=dev, dtype=torch.float32) for n in st.widths[1:]]
+        layers = [dict(img=st.pk.ptr(f"W{l}"), K=st.widths[l], N=st.widths[l + 1], bias=bs[l], act=st.acts[l],
+                       drop=(st.tag + 1 + l, st.thr, st.dscale), out=X[l], resid=r2 if l == L - 1 else None) for l in range(L)]
+        run_chain(chain_struct(M, layers, A=A, lda=A.stride(0), K1=st.K1, A2=A2, lda2=0 if A2 is None else A2.stride(0),
+                               alpha=st.alpha, seed_t=st.seed_t, f16=False))
+        st.X = X[:-1]
+        ctx.save_for_backward(A, A2, X[-1], *params)
+        return X[-1]
+
+    @staticmethod
+    def backward(ctx, ybar):
+        A, A2, Y, *params = ctx.saved_tensors
+        need, st = ctx.needs_input_grad, ctx.st
+        again = torch.is_grad_enabled()     # (create_graph=True: this derivative will be differentiated itself)
+        flags = (need[0] or (A2 is not None and need[1]), any(need[4:]) and (st.param_grads or not again), again)
+        out = LinearNetVJPFn.apply(ybar, A, A2, Y.detach(), st, flags, *params)
+        return (out[0] if need[0] else None, out[1] if need[1] else None, ybar if (st.has_resid and need[2]) else None, None, *out[2:])
+
+
+class LinearNetVJPFn(torch.autograd.Function):
+    """The first derivative of ``LinearNetFn`` as a function of (Y_bar, A, A2, parameters): (A_bar, A2_bar, W_bar_1, b_bar_1, ...).
+    Its own backward takes cotangents on A_bar and A2_bar (an absent one is zero) -- one on a parameter gradient raises -- and is
+    once differentiable: a third derivative declines loudly."""
+
+    @staticmethod
+    def forward(ctx, ybar, A, A2, Y, st, flags, *params):
+        need_x, need_w, again = flags
+        Ws = params[0::2]
+        L, K1 = st.L, st.K1
+        ctx.st, ctx.flags = st, flags
+        ctx.set_materialize_grads(False)
+        pg = [None] * (2 * L)
+        ctx.save_for_backward(Y, *Ws)
+        if st.cpu:
+            dZ, d = [None] * L, st.G[L - 1] * ybar
+            for l in range(L - 1, -1, -1):
+                dZ[l] = d
+                if l > 0:
+                    d = st.G[l - 1] * (d @ Ws[l])
+            ctx.dz = dZ
+            xbar = dZ[0] @ Ws[0] if need_x else None
+            if need_w:
+                X0 = A if A2 is None else torch.cat((A, A2), 1)
+                for l in range(L):
+                    pg[2 * l] = dZ[l].t() @ (X0 if l == 0 else st.X[l - 1])
+                    pg[2 * l + 1] = dZ[l].sum(0) if st.has_bias[l] else None
+            return (None if xbar is None else xbar[:, :K1], None if (xbar is None or A2 is None) else xbar[:, K1:], *pg)
+        dev, M, w = ybar.device, st.M, st.widths
+        yb = ybar.reshape(M, w[L]).float().contiguous()
+        A, A2 = _unit_cols(A), None if A2 is None else _unit_cols(A2)
+        keep_dz = need_w or again
+        nchain = L - 1 + int(need_x)     # layers of the input-gradient chain
+        in_gate = in_out = None
+        if st.acts[L - 1] or (st.thr and nchain == 0):
+            dZL = gate(yb, Y if st.acts[L - 1] else None, gate_act=st.acts[L - 1], alpha=st.alpha, seed_t=st.seed_t, tag=st.tag + L,
+                       thr=st.thr, scale=st.dscale)
+        elif st.thr:
+            dZL = torch.empty_like(yb)
+            in_gate, in_out = (st.tag + L, st.thr, st.dscale), dZL
+        else:
+            dZL = yb
+        dZ = [None] * L
+        dZ[L - 1] = dZL
+        xbar = torch.empty((M, w[0]), device=dev, dtype=torch.float32) if need_x else None
+        if nchain:
+            layers = []
+            for l in range(L - 1, 0, -1):
+                if keep_dz:   # (dZ_l leaves the chip only for a weight gradient or the second derivative)
+                    dZ[l - 1] = torch.empty((M, w[l]), device=dev, dtype=torch.float32)
+                layers.append(dict(img=st.pk.ptr(f"W{l}T"), K=w[l + 1], N=w[l], gate=_net_gate(st, l - 1, Y), out=dZ[l - 1]))
+            if need_x:
+                layers.append(dict(img=st.pk.ptr("W0T"), K=w[1], N=w[0], out=xbar))
+            run_chain(chain_struct(M, layers, A=yb if in_gate is not None else dZL, lda=w[L], K1=w[L], in_gate=in_gate, in_out=in_out,
+                                   alpha=st.alpha, seed_t=st.seed_t, f16=False))
+        ctx.dz = dZ if again else None
+        if need_w:
+            wb = WgradBatch()
+            for l in range(L):
+                W = Ws[l]
+                pg[2 * l] = torch.empty_like(W)
+                pg[2 * l + 1] = torch.empty((W.shape[0],), device=dev, dtype=torch.float32) if st.has_bias[l] else None
+                if l == 0:
+                    wb.add(dZ[0], A, out=pg[0], out_col0=0, bias_out=pg[1])
+                    if A2 is not None:
+                        wb.add(dZ[0], A2, out=pg[0], out_col0=K1)
+                else:
+                    wb.add(dZ[l], st.X[l - 1], out=pg[2 * l], bias_out=pg[2 * l + 1])
+            wb.flush()
+        return (None if xbar is None else xbar[:, :K1], None if (xbar is None or A2 is None) else xbar[:, K1:], *pg)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, uA, uA2, *gparams):
+        if any(g is not None for g in gparams):
+            raise RuntimeError("LinearNetVJPFn: a cotangent arrived on a parameter-gradient output; the second-order rule covers the "
+                               "input gradient only")
+        st = ctx.st
+        if ctx.dz is None:
+            raise RuntimeError("LinearNetVJPFn: the first derivative was taken without create_graph=True; there is nothing to differentiate again")
+        L, K1, w, dZ = st.L, st.K1, st.widths, ctx.dz
+        need_w = [ctx.needs_input_grad[6 + 2 * l] for l in range(L)]
+        gW = [None] * L
+        two = w[0] > K1
+        Y, *Ws = ctx.saved_tensors
+        if st.cpu:
+            ref = dZ[0]
+            zero = lambda k: torch.zeros((st.M, k), dtype=ref.dtype)
+            T = torch.cat((zero(K1) if uA is None else uA, *(((zero(w[0] - K1) if uA2 is None else uA2),) if two else ())), 1)
+            for l in range(L):
+                if need_w[l]:
+                    gW[l] = dZ[l].t() @ T
+                T = st.G[l] * (T @ Ws[l].t())
+            return (T, None, None, None, None, None, *(q for g in gW for q in (g, None)))
+        dev, M = dZ[-1].device, st.M
+        zero = lambda k: torch.zeros((M, k), device=dev, dtype=torch.float32)
+        uA = zero(K1) if uA is None else _unit_cols(uA.reshape(M, K1).float())
+        uA2 = None if not two else (zero(w[0] - K1) if uA2 is None else _unit_cols(uA2.reshape(M, w[0] - K1).float()))
+        T = [torch.empty((M, w[l + 1]), device=dev, dtype=torch.float32) if (l == L - 1 or need_w[l + 1]) else None for l in range(L)]
+        layers = [dict(img=st.pk.ptr(f"W{l}"), K=w[l], N=w[l + 1], act=False, gate=_net_gate(st, l, Y), out=T[l]) for l in range(L)]
+        run_chain(chain_struct(M, layers, A=uA, lda=uA.stride(0), K1=K1, A2=uA2, lda2=0 if uA2 is None else uA2.stride(0),
+                               alpha=st.alpha, seed_t=st.seed_t, f16=False))
+        if any(need_w):
+            wb = WgradBatch()
+            for l in range(L):
+                if not need_w[l]:
+                    continue
+                gW[l] = torch.empty((w[l + 1], w[l]), device=dev, dtype=torch.float32)
+                if l == 0:
+                    wb.add(dZ[0], uA, out=gW[0], out_col0=0)
+                    if two:
+                        wb.add(dZ[0], uA2, out=gW[0], out_col0=K1)
+                else:
+                    wb.add(dZ[l], T[l - 1], out=gW[l])
+            wb.flush()
+        return (T[L - 1], None, None, None, None, None, *(q for g in gW for q in (g, None)))
+
+
+def linear_net_dd(A, A2, weights, biases, *, final_linear, alpha, p_drop, training, resid=None, keeps=None, param_grads=False):
+    """A plain LinearNet on rows (A | A2) as consecutive ``LinearNetFn`` ops of up to ``CHAIN_OP_LAYERS`` layers each.  ``resid`` goes
+    into the last op's launch when the last layer has no activation, else it is added behind it."""
+    L = len(weights)
+    acts = [not (final_linear and l == L - 1) for l in range(L)]
+    fuse = resid is not None and not acts[-1]
+    h, h2 = A, A2
+    for i0, i1 in gp_chain_pieces(L):
+        s = LinearNetSettings(tuple(acts[i0:i1]), alpha, p_drop, training, None if keeps is None else keeps[i0:i1], param_grads)
+        prm = [q for W, b in zip(weights[i0:i1], biases[i0:i1]) for q in (W, b)]
+        h, h2 = LinearNetFn.apply(h, h2, resid if (fuse and i1 == L) else None, s, *prm), None
+    return h if (resid is None or fuse) else h + resid
+
+
 class FusedDropoutFn(torch.autograd.Function):
     """Stand-alone inverted dropout on the counter-based mask stream (MAB.dropout, gapt/model.py:132,137)."""
 
@@ -2308,6 +2588,31 @@ class FusedDropoutFn(torch.autograd.Function):
         g2 = g.reshape(-1, shp[-1]).contiguous()
         return gate(g2, None, gate_act=False, alpha=0.0, seed_t=seed_tensor(g.device), tag=tag, thr=thr,
                     scale=scale).reshape(shp), None, None
+
+
+class KeyedDropoutFn(torch.autograd.Function):
+    """``FusedDropoutFn``'s mask stream as an op that can be differentiated to any order: dropout is linear in x, so its backward is
+    the op itself on the cotangent, with the same site tag (the mask is regenerated, never stored)."""
+
+    @staticmethod
+    def forward(ctx, x, tag, thr, scale):
+        _chk(x, "x")
+        ctx.cfg = (tag, thr, scale)
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        return gate(x2, None, gate_act=False, alpha=0.0, seed_t=seed_tensor(x.device), tag=tag, thr=thr, scale=scale).reshape(x.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        return KeyedDropoutFn.apply(g, *ctx.cfg), None, None, None
+
+
+def keyed_dropout(x, p_drop, training):
+    """Stand-alone inverted dropout inside ``double_backward_route`` drawn from the device seed and ``next_tag`` (``OPTIONS["gp_chain"]``:
+    MAB's two dropouts of the gradient penalty), in place of ATen's draw from torch's generator."""
+    thr, scale = drop_params(p_drop) if training else (0, 1.0)
+    if not thr:
+        return x
+    return KeyedDropoutFn.apply(x, next_tag(x.device, "dropout", thr) + TAG_GENERIC, thr, scale)
 
 
 def _attn_struct(q, k, v, ignore, o, P, B, L, S, H, d):
@@ -3085,6 +3390,210 @@ def disc_head_loss(y, mask, w, b, *, mean, sigmoid, p_drop, training, loss, n_re
     h.targets, h.loss_extra = _p(targets), _p(loss_extra)
     check(_lib.lib().mpg_disc_head_loss(C.byref(h), _stream()), "mpg_disc_head_loss")
     return out, dy
+
+
+# ---- the discriminator head, twice differentiable (the gradient penalty; OPTIONS["gp_chain"]) ---------------------------------
+# Per jet, with d = 1 (sum), sum_i m_i + 1e-12 (mean) or N (mean without mask), kappa the output dropout's keep-and-scale:
+#   t_i = <w, y_i> ,  S = sum_i m_i t_i ,  s = S / d + b ,  z = kappa s ,  out = phi(z)
+# The first- and second-order rules are stated with ``mpg_disc_head_dd`` (include/mpgan_amd.h) and derived in DESIGN.md section 4.
+DiscHeadDDSettings = namedtuple("DiscHeadDDSettings", "mean sigmoid p_drop training keep param_grads", defaults=(0.0, True, None, True))
+DD_HEAD_MAX_N = 1024    # mpg_disc_head_dd keeps eight floats per particle of a jet in LDS
+
+
+def gp_head_route(N: int, double_backward: bool, options=None) -> bool:
+    """Does a discriminator's single-launch head (``fused_head()``) run as ``DiscHeadDDFn`` inside ``double_backward_route``?  Only
+    with the option on (``OPTIONS["gp_chain"]``) and a jet that ``mpg_disc_head_dd`` holds in LDS.  Host only."""
+    opt = OPTIONS if options is None else options
+    return bool(opt.get("gp_chain") and double_backward and 1 <= N <= DD_HEAD_MAX_N)
+
+
+class _HeadState:
+    __slots__ = ("cpu", "B", "N", "F", "mean", "sigmoid", "thr", "dscale", "tag", "seed_t", "kappa", "param_grads", "mask_shape",
+                 "w_shape", "has_bias")
+
+
+def _head_dd_terms(st, y, m, wv, b):
+    # (t [B, N], d [B], c [B], phi'(z), phi''(z)) of the plain-torch form
+    t = y @ wv
+    S = (t if m is None else m * t).sum(1)
+    if not st.mean:
+        d = torch.ones_like(S)
+    elif m is None:
+        d = torch.full_like(S, float(st.N))
+    else:
+        d = m.sum(1) + 1e-12
+    c = S / d if (st.mean and m is not None) else torch.zeros_like(S)
+    z = S / d + (0 if b is None else b.reshape(()))
+    if st.kappa is not None:
+        z = st.kappa * z
+    if st.sigmoid:
+        o = torch.sigmoid(z)
+        return t, d, c, z, o * (1 - o), o * (1 - o) * (1 - 2 * o)
+    return t, d, c, z, torch.ones_like(z), torch.zeros_like(z)
+
+
+def _head_dd_pairwise(m, v, d):
+    # v_i d - sum_j m_j v_j as ONE sum of pairwise terms, sum_j m_j (v_i - v_j) + 1e-12 v_i [B, N] (d = sum_j m_j + 1e-12): a jet with one
+    # real particle, where the difference is 1e-12 of its terms, keeps its digits (as the kernel forms it)
+    return (m.unsqueeze(1) * (v.unsqueeze(2) - v.unsqueeze(1))).sum(2) + 1e-12 * v
+
+
+def _head_dd_struct(st, y, m, w, b):
+    h = _lib.MpgDiscHeadDD()
+    h.y, h.ldy, h.mask, h.w, h.bias = _p(y), y.stride(1), _p(m), _p(w), _p(b)
+    h.B, h.N, h.F, h.mean, h.sigmoid = st.B, st.N, st.F, int(st.mean), int(st.sigmoid)
+    h.seed, h.tag, h.thr, h.dscale = _p(st.seed_t), st.tag, st.thr, st.dscale
+    return h
+
+
+class DiscHeadDDFn(torch.autograd.Function):
+    """``DiscHeadFn`` for the gradient penalty: out [B] = phi(kappa (pool_i(m_i <w, y_i>) + b)) with a real-valued mask that takes a
+    gradient, twice differentiable.  y [B, N, F]; ``mask`` [B, N] / [B, N, 1] or None; w [1, F] / [F]; b [1] or None; ``settings``: a
+    ``DiscHeadDDSettings`` (``keep``: the keep-and-scale [B] of a CPU call, None = no dropout; ``param_grads`` as ``LinearNetFn``'s).
+    The forward is ``mpg_disc_head_fwd``; both derivatives are ``mpg_disc_head_dd``.  CPU tensors take the formulas in plain torch."""
+
+    @staticmethod
+    def forward(ctx, y, mask, w, b, settings):
+        s = settings
+        B, N, F = y.shape
+        st = _HeadState()
+        st.cpu, st.B, st.N, st.F, st.mean, st.sigmoid = not y.is_cuda, B, N, F, bool(s.mean), bool(s.sigmoid)
+        st.param_grads, st.mask_shape, st.w_shape, st.has_bias = bool(s.param_grads), None if mask is None else tuple(mask.shape), tuple(w.shape), b is not None
+        ctx.st = st
+        ctx.save_for_backward(y, mask, w, b)
+        if st.cpu:
+            st.kappa = s.keep
+            z = _head_dd_terms(st, y, None if mask is None else mask.reshape(B, N), w.reshape(-1), b)[3]
+            return torch.sigmoid(z) if st.sigmoid else z
+        if N > DD_HEAD_MAX_N:
+            raise ValueError(f"DiscHeadDDFn: at most {DD_HEAD_MAX_N} particles per jet, got {N}")
+        y2, m = _head_inputs(y, mask)
+        dev = y.device
+        st.thr, st.dscale = drop_params(s.p_drop) if s.training else (0, 1.0)
+        st.seed_t, st.tag = seed_tensor(dev), next_tag(dev, "head_dd", st.thr) + TAG_GENERIC
+        out = torch.empty((B,), device=dev, dtype=torch.float32)
+        aux = torch.empty((2 * B,), device=dev, dtype=torch.float32)
+        h = _head_struct(y2, m, w.reshape(-1), b, st.mean, st.sigmoid, s.p_drop, s.training, st.tag, out, None, aux)
+        check(_lib.lib().mpg_disc_head_fwd(C.byref(h), _stream()), "mpg_disc_head_fwd")
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        y, mask, w, b = ctx.saved_tensors
+        need, st = ctx.needs_input_grad, ctx.st
+        again = torch.is_grad_enabled()
+        flags = (need[0], mask is not None and need[1], (need[2] or need[3]) and (st.param_grads or not again), again)
+        return (*DiscHeadVJPFn.apply(g, y, mask, w, b, st, flags), None)
+
+
+class DiscHeadVJPFn(torch.autograd.Function):
+    """The first derivative of ``DiscHeadDDFn`` as a function of (g, y, mask, w, b): (y_bar, m_bar, w_bar, b_bar).  Its own backward
+    takes cotangents U on y_bar and mu on m_bar (an absent one is zero) -- one on a parameter gradient raises -- and is once
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, g, y, mask, w, b, st, flags):
+        need_y, need_m, need_w, again = flags
+        ctx.st, ctx.flags, ctx.g_shape = st, flags, tuple(g.shape)
+        ctx.set_materialize_grads(False)
+        B, N, F = st.B, st.N, st.F
+        if st.cpu:
+            ctx.save_for_backward(g, y, mask, w, b)
+            m = None if mask is None else mask.reshape(B, N)
+            t, d, c, z, d1, _ = _head_dd_terms(st, y, m, w.reshape(-1), b)
+            gh = g.reshape(B) * d1 * (1 if st.kappa is None else st.kappa)
+            cy = (gh / d).unsqueeze(1) * (torch.ones_like(t) if m is None else m)
+            ybar = cy.unsqueeze(2) * w.reshape(-1) if need_y else None
+            mbar = None
+            if need_m:
+                tau = _head_dd_pairwise(m, t, d) / d.unsqueeze(1) if st.mean else t      # t_i - c
+                mbar = ((gh / d).unsqueeze(1) * tau).reshape(st.mask_shape)
+            wbar = (cy.unsqueeze(2) * y).sum((0, 1)).reshape(st.w_shape) if need_w else None
+            bbar = gh.sum().reshape(b.shape) if (need_w and b is not None) else None
+            return ybar, mbar, wbar, bbar
+        dev = y.device
+        y2, m = _head_inputs(y, mask)
+        g1 = g.reshape(B).float().contiguous()
+        wv = w.reshape(-1)
+        ctx.save_for_backward(g1, y2, m, wv, b)
+        h = _head_dd_struct(st, y2, m, wv, b)
+        h.mode, h.g = 0, _p(g1)
+        ybar = torch.empty((B, N, F), device=dev, dtype=torch.float32) if need_y else None
+        mbar = torch.empty((B, N), device=dev, dtype=torch.float32) if need_m else None
+        part = torch.empty((B, F + 1), device=dev, dtype=torch.float32) if need_w else None
+        wbar = torch.empty((F,), device=dev, dtype=torch.float32) if need_w else None
+        bbar = torch.empty((1,), device=dev, dtype=torch.float32) if (need_w and b is not None) else None
+        h.gy, h.ld_gy, h.gm, h.part, h.gw, h.gb = _p(ybar), F, _p(mbar), _p(part), _p(wbar), _p(bbar)
+        check(_lib.lib().mpg_disc_head_dd(C.byref(h), _stream()), "mpg_disc_head_dd")
+        return (ybar, None if mbar is None else mbar.reshape(st.mask_shape), None if wbar is None else wbar.reshape(st.w_shape),
+                None if bbar is None else bbar.reshape(b.shape))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, U, mu, gw_, gb_):
+        if gw_ is not None or gb_ is not None:
+            raise RuntimeError("DiscHeadVJPFn: a cotangent arrived on a parameter-gradient output; the second-order rule covers the "
+                               "input gradient and the mask gradient only")
+        st = ctx.st
+        if not ctx.flags[3]:
+            raise RuntimeError("DiscHeadVJPFn: the first derivative was taken without create_graph=True; there is nothing to differentiate again")
+        B, N, F = st.B, st.N, st.F
+        n_g, n_y, n_m, n_w, n_b = ctx.needs_input_grad[:5]
+        if st.cpu:
+            g, y, mask, w, b = ctx.saved_tensors
+            m = None if mask is None else mask.reshape(B, N)
+            wv = w.reshape(-1)
+            t, d, c, z, d1, d2 = _head_dd_terms(st, y, m, wv, b)
+            kap = torch.ones_like(z) if st.kappa is None else st.kappa
+            mm = st.mean and m is not None
+            m1 = torch.ones_like(t) if m is None else m
+            a = torch.zeros_like(t) if U is None else U @ wv
+            u = torch.zeros_like(t) if mu is None else mu.reshape(B, N)
+            Q = u.sum(1) if mm else torch.zeros_like(z)
+            g1 = g.reshape(B)
+            gh = g1 * d1 * kap
+            col = lambda v: v.unsqueeze(1)
+            # under the mean with a mask the three differences of the rule come as single sums of pairwise terms (_head_dd_pairwise):
+            # tc_i = t_i - c,  al_i = a_i d - sum_j m_j a_j,  be_i = mu_i d - Q m_i
+            tc = _head_dd_pairwise(m, t, d) / col(d) if mm else t
+            Pt = (u * tc).sum(1)                                       # sum_i mu_i (t_i - c)
+            R = ((m1 * a).sum(1) + Pt) / d
+            H = g1 * kap * kap * d2 * R
+            if mm:
+                be = (col(u).transpose(1, 2) * col(m) - col(u) * col(m).transpose(1, 2)).sum(2) + 1e-12 * u
+                cy = col(H / d) * m1 + col(gh / d / d) * be
+                gm = col(H / d) * tc + col(gh / d / d) * (_head_dd_pairwise(m, a, d) - col(Pt) - col(Q) * tc)
+            else:
+                cy = col(H / d) * m1 + col(gh / d) * u
+                gm = col(H / d) * tc + col(gh / d) * a
+            gw = (cy.unsqueeze(2) * y).sum((0, 1))
+            if U is not None:
+                gw = gw + ((col(gh / d) * m1).unsqueeze(2) * U).sum((0, 1))
+            return ((kap * d1 * R).reshape(g.shape), cy.unsqueeze(2) * wv, None if mask is None else gm.reshape(st.mask_shape),
+                    gw.reshape(st.w_shape), None if b is None else H.sum().reshape(b.shape), None, None)
+        g1, y2, m, wv, b = ctx.saved_tensors
+        dev = y2.device
+        h = _head_dd_struct(st, y2, m, wv, b)
+        h.mode, h.g = 1, _p(g1)
+        U2 = None
+        if U is not None:
+            U2 = U.reshape(B, N, F).float()
+            if U2.stride(2) != 1 or U2.stride(0) != N * U2.stride(1):
+                U2 = U2.contiguous()
+        mu1 = None if (mu is None or m is None) else mu.reshape(B, N).float().contiguous()
+        h.U, h.ldu, h.mu = _p(U2), F if U2 is None else U2.stride(1), _p(mu1)
+        want_w = n_w or (n_b and b is not None)
+        gg = torch.empty((B,), device=dev, dtype=torch.float32) if n_g else None
+        gy = torch.empty((B, N, F), device=dev, dtype=torch.float32) if n_y else None
+        gm = torch.empty((B, N), device=dev, dtype=torch.float32) if (n_m and m is not None) else None
+        part = torch.empty((B, F + 1), device=dev, dtype=torch.float32) if want_w else None
+        gw = torch.empty((F,), device=dev, dtype=torch.float32) if n_w else None
+        gb = torch.empty((1,), device=dev, dtype=torch.float32) if (n_b and b is not None) else None
+        h.gy, h.ld_gy, h.gm, h.gg, h.part, h.gw, h.gb = _p(gy), F, _p(gm), _p(gg), _p(part), _p(gw), _p(gb)
+        check(_lib.lib().mpg_disc_head_dd(C.byref(h), _stream()), "mpg_disc_head_dd")
+        return (None if gg is None else gg.reshape(ctx.g_shape), gy, None if gm is None else gm.reshape(st.mask_shape),
+                None if gw is None else gw.reshape(st.w_shape),
+                None if gb is None else gb.reshape(b.shape), None, None)
 
 
 class BatchNormFn(torch.autograd.Function):

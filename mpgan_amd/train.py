@@ -457,7 +457,7 @@ class TrainStep:
                  graph_collectives: Optional[bool] = None, augment=None, loader=None, num_critic: int = 1, num_gen: int = 1,
                  track_epoch_losses: bool = False, label_smoothing: bool = False, label_noise: float = 0.0,
                  ema: Optional[Ema] = None, lr_schedule=None, grad_clip=None, gp_rows: Optional[bool] = None,
-                 gp_attn: Optional[bool] = None, _ada_split: bool = False):
+                 gp_attn: Optional[bool] = None, gp_chain: Optional[bool] = None, _ada_split: bool = False):
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
         self.dev = dev = next(G.parameters()).device
@@ -497,6 +497,9 @@ class TrainStep:
         # (None: as ``ops.OPTIONS["gp_attn"]`` / MPG_GP_ATTN says as the step is built).  The core has no parameters: nothing it
         # hands to autograd meets a gradient of the second stream, so ``wgrad_side`` stays as it is
         self.gp_attn = bool(ops.OPTIONS["gp_attn"]) if gp_attn is None else bool(gp_attn)
+        # ... and the penalty's LinearNets and D's head as one twice-differentiable op each where ``ops.gp_chain_route`` /
+        # ``ops.gp_head_route`` cover them (None: as ``ops.OPTIONS["gp_chain"]`` / MPG_GP_CHAIN says as the step is built)
+        self.gp_chain = bool(ops.OPTIONS["gp_chain"]) if gp_chain is None else bool(gp_chain)
         self.GP = torch.zeros((), device=dev)   # last penalty value (the reference's losses["gp"])
         self.fixed_alpha = None   # tests: the interpolation weights [B, 1, 1] instead of fresh uniform samples
         self.G, self.D = G, D
@@ -604,7 +607,8 @@ class TrainStep:
         # (not beside the penalty on the rows route: there D's edge-network parameters get gradients from two sides in one backward --
         #  added into .grad by the fused layers' launches on that second stream, and handed to autograd by the twice-differentiable
         #  op, whose accumulation runs on the main stream.  On one stream the two are ordered, in eager execution and in a replay alike)
-        if self.gp_lambda and self.gp_rows:
+        # (nor beside the chained LinearNets and the head: their parameter gradients are autograd values as well)
+        if self.gp_lambda and (self.gp_rows or self.gp_chain):
             self.wgrad_side = False
         self._wside = None
         # The generator-ahead branch is forked at the top of the D segment (MPG_GEN_AHEAD_LATE=0: beside the D step's own
@@ -926,12 +930,13 @@ class TrainStep:
         x = (alpha * real + (1 - alpha) * fake.detach()).requires_grad_(True)
         prev, ops.OPTIONS["gp_rows"] = ops.OPTIONS["gp_rows"], self.gp_rows
         prev_attn, ops.OPTIONS["gp_attn"] = ops.OPTIONS["gp_attn"], self.gp_attn
+        prev_chain, ops.OPTIONS["gp_chain"] = ops.OPTIONS["gp_chain"], self.gp_chain
         try:
             with ops.double_backward_route(self.dev):
                 prob = self.D(x)
                 grads = torch.autograd.grad(prob, x, torch.ones_like(prob), create_graph=True, retain_graph=True)[0]
         finally:
-            ops.OPTIONS["gp_rows"], ops.OPTIONS["gp_attn"] = prev, prev_attn
+            ops.OPTIONS["gp_rows"], ops.OPTIONS["gp_attn"], ops.OPTIONS["gp_chain"] = prev, prev_attn, prev_chain
         norm = torch.sqrt((grads.reshape(B, -1) ** 2).sum(1) + 1e-12)
         return self.gp_lambda * ((norm - 1) ** 2).mean()
 

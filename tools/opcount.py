@@ -46,7 +46,42 @@ def count(title):
     print(f"{title}library kernels: {n_ours} launches, {t_ours:.0f} us;  other (ATen) kernels: {n_other} launches, {t_other:.0f} us")
 
 
-if SN:
+def count_gp(title, gp_chain, B=None):
+    """OPC_GP=1: one eager penalty D step (``loss="w"``, ``gp_lambda=10``, the existing switches gp_rows / gp_attn on) with
+    ``gp_chain`` off and on: launches by kind, and -- at B = 16 -- the peak allocation of the step."""
+    torch.manual_seed(0)
+    gapt = bool(os.environ.get("OPC_GAPT"))
+    b = BATCH if B is None else B
+    G, D = train.default_gapt(30, device=dev) if gapt else train.default_mpgan(30, device=dev, loss="w")
+    ts = train.TrainStep(G, D, b, 30, latent=64 if gapt else 32, use_graphs=False, loss="w", gp_lambda=10.0, gp_rows=True, gp_attn=True,
+                         gp_chain=gp_chain)
+    data, labels = synthetic_jets(b, 30, seed=1, dist="gluon")
+    ts.set_batch(data.to(dev), labels.to(dev))
+    for _ in range(2): ts._seg_D()
+    torch.cuda.synchronize()
+    if B is not None:
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        ts._seg_D()
+        torch.cuda.synchronize()
+        print(f"{title}peak allocation of one penalty D step at B = {b}: {torch.cuda.max_memory_allocated() - base} bytes")
+        return
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        ts._seg_D()
+        torch.cuda.synchronize()
+    rows = [(e.key, e.count, e.device_time_total) for e in prof.key_averages() if e.device_time_total > 0]
+    ours = lambda k: any(s in k for s in ("_kernel", "mpg_")) and "at::" not in k and "aten" not in k
+    n_ours = sum(c for k, c, _ in rows if ours(k)); n_other = sum(c for k, c, _ in rows if not ours(k))
+    t_ours = sum(t for k, _, t in rows if ours(k)); t_other = sum(t for k, _, t in rows if not ours(k))
+    print(f"{title}library kernels: {n_ours} launches, {t_ours:.0f} us;  other (ATen) kernels: {n_other} launches, {t_other:.0f} us")
+
+
+if os.environ.get("OPC_GP"):
+    for on in (False, True):
+        count_gp(f"penalty D step, gp_chain={on}: ", on)
+        count_gp(f"penalty D step, gp_chain={on}: ", on, B=16)
+elif SN:
     for on in (True, False):
         ops.OPTIONS["sn_fused"] = on
         count(f"spectral norm, sn_fused={on}: ")

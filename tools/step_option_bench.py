@@ -33,6 +33,9 @@ gp       two steps with ``loss="w", gp_lambda=10``: the penalty's D(x) on the ma
          ``MAB._forward_dd`` as it has always run) and on the twice-differentiable attention kernels (b gp_step_attn:
          ``gp_attn=True``), at N = 30, B = 512 and at N = 150, B = 64.  Held to, per shape: the median of (b) is not above the
          median of (a) by more than (a)'s own run-to-run spread (max - min of its repetitions).
+         Both models: a third step (c gp_step_rows_chain / c gp_step_attn_chain) adds ``gp_chain=True`` to (b) -- the penalty's
+         LinearNets and D's head as one twice-differentiable op each.  Held to, per shape: the median of (c) is not above the
+         median of (b) by more than (b)'s own run-to-run spread.
 
 Every ``step()`` and every lone launch sits between two HIP events of its own -- in all rows alike, so that what an event pair
 costs cancels between them.  A repetition is --batches steps of each kind (critic: two full cycles of the schedule) taken
@@ -273,14 +276,15 @@ def gp_bench(args, emit):
     process, every ``step()`` between two HIP events; at the headline shape and at N = 150, B = 16."""
     if args.model == "gapt":
         return gp_attn_bench(args, emit)
-    rows = ("a gp_step_edges", "b gp_step_rows")
+    rows = ("a gp_step_edges", "b gp_step_rows", "c gp_step_rows_chain")
     for n, b in ((N, B), (150, 16)):
         torch.manual_seed(0)
         steps = []
-        for gp_rows in (False, True):
+        for gp_rows, gp_chain in ((False, False), (True, False), (True, True)):
             G, D = train.default_mpgan(n, loss="w")
             lrs = train.LR["g"]
-            ts = train.TrainStep(G, D, b, n, lr_disc=lrs[0], lr_gen=lrs[1], use_graphs=True, loss="w", gp_lambda=10.0, gp_rows=gp_rows)
+            ts = train.TrainStep(G, D, b, n, lr_disc=lrs[0], lr_gen=lrs[1], use_graphs=True, loss="w", gp_lambda=10.0, gp_rows=gp_rows,
+                                 gp_chain=gp_chain)
             x, labels = mdata.synthetic_jets(b, n, seed=1)
             ts.set_batch(x.cuda(), labels.cuda())
             for _ in range(3):   # warm-up: captures the graph
@@ -299,11 +303,14 @@ def gp_bench(args, emit):
         med = {}
         for name, v in us.items():
             med[name] = float(np.median(v))
-            emit({"model": "mpgan", "B": b, "N": n, "loss": "w", "gp_lambda": 10.0, "gp_rows": name == rows[1], "row": name,
-                  "reps": args.reps, "batches_per_rep": args.batches, "median_us": med[name], "min_us": float(np.min(v)),
+            emit({"model": "mpgan", "B": b, "N": n, "loss": "w", "gp_lambda": 10.0, "gp_rows": name != rows[0], "gp_chain": name == rows[2],
+                  "row": name, "reps": args.reps, "batches_per_rep": args.batches, "median_us": med[name], "min_us": float(np.min(v)),
                   "max_us": float(np.max(v)), "jets_per_s": b / (med[name] * 1e-6)})
+        spread = float(np.max(us[rows[1]]) - np.min(us[rows[1]]))
         emit({"model": "mpgan", "B": b, "N": n, "row": "condition", "rows_minus_edges_us": med[rows[1]] - med[rows[0]],
               "rows_le_edges": bool(med[rows[1]] <= med[rows[0]]),
+              "chain_minus_rows_us": med[rows[2]] - med[rows[1]], "spread_rows_us": spread,
+              "chain_within_spread_of_rows": bool(med[rows[2]] - med[rows[1]] <= spread),
               **{f"{k}_{r[2:]}": float(getattr(ts, k)) for r, ts in zip(rows, steps) for k in ("D_loss", "GP")}})
         del steps
         torch.cuda.empty_cache()
@@ -312,15 +319,15 @@ def gp_bench(args, emit):
 def gp_attn_bench(args, emit):
     """--option gp --model gapt: the captured --gp iteration of GAPT with the penalty's attention cores on the existing route and on
     the attention kernels, alternated in one process, every ``step()`` between two HIP events; at N = 30, B = 512 and N = 150, B = 64."""
-    rows = ("a gp_step_dd", "b gp_step_attn")
+    rows = ("a gp_step_dd", "b gp_step_attn", "c gp_step_attn_chain")
     for n, b in ((30, 512), (150, 64)):
         torch.manual_seed(0)
         steps = []
-        for gp_attn in (False, True):
+        for gp_attn, gp_chain in ((False, False), (True, False), (True, True)):
             G, D = train.default_gapt(n)
             lrs = train.LR_GAPT
             ts = train.TrainStep(G, D, b, n, latent=64, lr_disc=lrs[0], lr_gen=lrs[1], use_graphs=True, loss="w", gp_lambda=10.0,
-                                 gp_attn=gp_attn)
+                                 gp_attn=gp_attn, gp_chain=gp_chain)
             x, labels = mdata.synthetic_jets(b, n, seed=1)
             ts.set_batch(x.cuda(), labels.cuda())
             for _ in range(3):   # warm-up: captures the graph
@@ -338,12 +345,15 @@ def gp_attn_bench(args, emit):
         med = {}
         for name, v in us.items():
             med[name] = float(np.median(v))
-            emit({"model": "gapt", "B": b, "N": n, "loss": "w", "gp_lambda": 10.0, "gp_attn": name == rows[1], "row": name,
-                  "reps": args.reps, "batches_per_rep": args.batches, "median_us": med[name], "min_us": float(np.min(v)),
+            emit({"model": "gapt", "B": b, "N": n, "loss": "w", "gp_lambda": 10.0, "gp_attn": name != rows[0], "gp_chain": name == rows[2],
+                  "row": name, "reps": args.reps, "batches_per_rep": args.batches, "median_us": med[name], "min_us": float(np.min(v)),
                   "max_us": float(np.max(v)), "jets_per_s": b / (med[name] * 1e-6)})
         diff, spread = med[rows[1]] - med[rows[0]], float(np.max(us[rows[0]]) - np.min(us[rows[0]]))
+        spread_b = float(np.max(us[rows[1]]) - np.min(us[rows[1]]))
         emit({"model": "gapt", "B": b, "N": n, "row": "condition", "attn_minus_dd_us": diff, "spread_dd_us": spread,
               "attn_within_spread_of_dd": bool(diff <= spread),
+              "chain_minus_attn_us": med[rows[2]] - med[rows[1]], "spread_attn_us": spread_b,
+              "chain_within_spread_of_attn": bool(med[rows[2]] - med[rows[1]] <= spread_b),
               **{f"{k}_{r[2:]}": float(getattr(ts, k)) for r, ts in zip(rows, steps) for k in ("D_loss", "GP")}})
         del steps
         torch.cuda.empty_cache()
