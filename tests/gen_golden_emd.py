@@ -9,12 +9,21 @@ csrc/jet_emd.hip.  Needs scipy; the tests that run on the GPU read only the file
 Sets: N = 30, 48 x 48, multiplicity laws gluon and top; N = 150, 8 x 8; N in {1, 2, 31, 32, 33}, 6 x 6; and a hand-made set
 (an empty jet, jets of equal pT sums, a jet against itself, a duplicated row).
 
+The "slots" sets (emd_slots_n{N}, 5 x 5, and emd_hand70) fill the node slots and launch shapes that those never reach.
+mpg_jet_emd keeps node v in register slot v / 64 of lane v % 64 and is built for 1, 2 and 6 slots (2N + 2 <= 64, <= 128, more);
+a workgroup runs 4 waves up to N = 60, 3 to 69, 2 to 86, 1 from 87, and needs more than 64 KiB of LDS from N = 125.  The N
+are the two sides of each of those lines and the largest N; every set has two jets per side with pT > 0 in every slot, so
+that a pair of them has all 2N + 2 nodes, which the generator asserts.  These files also hold ``D_R04`` (the same pairs at
+R = 0.4, rounded to fp32 as the C entry receives it) and ``nodes`` [na, nb] (int32): n_a + n_b + 2, the nodes of each pair.
+
 The N = 30 gluon set also decides coverage on the device against coverage on the host, which must agree exactly: nearest
 neighbours must not be near-ties.  For that set the generator asserts that, in every row and every column of D, the
 second-smallest distance is at least 4 x the fp32 bar (2e-5 max S) above the smallest, and moves to the next seed if not
 (seed 7: gap 4.0e-3, 5.5 bars).  The top set is compared distance by distance only; its gap is recorded, not required.
 
-Run:  python tests/gen_golden_emd.py
+Run:  python tests/gen_golden_emd.py            every set
+      python tests/gen_golden_emd.py slots      the emd_slots_* sets and emd_hand70 only
+      python tests/gen_golden_emd.py slots --check   regenerate those and compare with the committed files, writing nothing
 """
 import os
 import sys
@@ -31,6 +40,8 @@ sys.path.insert(0, os.path.dirname(HERE))
 from mpgan_amd import data  # noqa: E402
 
 GPU_BAR = 2e-5
+SLOT_NS = (31, 32, 60, 61, 63, 64, 69, 70, 86, 87, 124, 125, 160)
+R04 = float(np.float32(0.4))   # the C entries take R as a float: the radius they are given is 0.4 rounded to fp32 (1.5e-8 off)
 
 
 def scattered_jets(B, N, law, seed):
@@ -76,8 +87,8 @@ def scale(A, B, R=1.0):
     return s * max(1.0, th)
 
 
-def matrix(a, b):
-    return np.array([[emd_lp(x, y) for y in b] for x in a])
+def matrix(a, b, R=1.0):
+    return np.array([[emd_lp(x, y, R) for y in b] for x in a])
 
 
 def nearest_gap(D):
@@ -107,8 +118,96 @@ def hand_made():
     return jets, jets.copy()
 
 
+def full_jet(rs, N):
+    """pT > 0 in every slot: (eta, phi) uniform in +-0.4, pT a Dirichlet draw times a total in [0.5, 1]."""
+    jet = np.empty((N, 3), np.float32)
+    jet[:, :2] = rs.uniform(-0.4, 0.4, (N, 2))
+    jet[:, 2] = rs.dirichlet(np.ones(N)) * rs.uniform(0.5, 1.0)
+    assert np.all(jet[:, 2] > 0)
+    return jet
+
+
+def slot_side(rs, N):
+    """Five jets: two full, one with about half its slots at pT = 0 (random positions), one particle, an empty jet."""
+    half = full_jet(rs, N)
+    dead = rs.rand(N) < 0.5
+    dead[rs.randint(N)] = False
+    half[dead, 2] = 0
+    one = np.zeros((N, 3), np.float32)
+    one[rs.randint(N)] = (rs.uniform(-0.4, 0.4), rs.uniform(-0.4, 0.4), rs.uniform(0.5, 1.0))
+    return np.stack([full_jet(rs, N), full_jet(rs, N), half, one, np.zeros((N, 3), np.float32)])
+
+
+def slot_set(N):
+    rs = np.random.RandomState(7000 + N)
+    a, b = slot_side(rs, N), slot_side(rs, N)
+    for side in (a, b):
+        assert [(x[:, 2] > 0).sum() for x in side[[0, 1, 3, 4]]] == [N, N, 1, 0]
+        assert side[0, :, 2].sum() != side[1, :, 2].sum()
+    return a, b
+
+
+def hand_made_70():
+    """N = 70, every slot live (142 nodes: register slots 0 to 2 of the six-slot build); a = b = the same five jets.
+    Jets 0 and 1: pT multiples of 2^-10 of equal sum, exact in fp32 in any order, so neither slack takes part.
+    Jets 2 and 3: a jet and its copy (a duplicated row, and the jet against itself).  Jet 4: 35 coincident pairs."""
+    N = 70
+    rs = np.random.RandomState(70)
+    k0, k1 = rs.randint(1, 33, N), rs.randint(1, 33, N)
+    i = 0
+    while k1.sum() != k0.sum():                # move jet 1's sum to jet 0's one unit at a time, every pT staying positive
+        step = 1 if k1.sum() < k0.sum() else -1
+        if k1[i % N] + step >= 1:
+            k1[i % N] += step
+        i += 1
+    jets = np.stack([full_jet(rs, N) for _ in range(5)])
+    jets[0, :, 2], jets[1, :, 2] = k0 / 1024.0, k1 / 1024.0
+    assert not np.array_equal(k0, k1)
+    for order in (slice(None), slice(None, None, -1)):
+        assert jets[0, order, 2].sum(dtype=np.float32) == jets[1, order, 2].sum(dtype=np.float32) == k0.sum() / 1024.0
+    jets[3] = jets[2]
+    jets[4, 35:] = jets[4, :35]
+    assert np.all(jets[..., 2] > 0)
+    return jets, jets.copy()
+
+
+def node_counts(a, b):
+    return ((a[:, None, :, 2] > 0).sum(2) + (b[None, :, :, 2] > 0).sum(2) + 2).astype(np.int32)
+
+
+def save_slots(name, a, b, check):
+    arrays = dict(a=a, b=b, D=matrix(a, b), D_R04=matrix(a, b, R04), nodes=node_counts(a, b))
+    path = os.path.join(OUT, name + ".npz")
+    if check:
+        old = np.load(path, allow_pickle=False)
+        assert sorted(old.files) == sorted(arrays)
+        for k, v in arrays.items():
+            if k.startswith("D"):             # the LP's optimum, not its vertex, is what reproduces: to its own tolerance
+                assert np.allclose(old[k], v, rtol=0, atol=1e-12), (name, k, np.abs(old[k] - v).max())
+            else:
+                assert old[k].dtype == v.dtype and np.array_equal(old[k], v), (name, k)
+        print(f"{name}: reproduced", flush=True)
+        return
+    np.savez_compressed(path, **arrays)
+    print(f"{name}: a {a.shape} nodes max {arrays['nodes'].max()} D mean {arrays['D'].mean():.6f} "
+          f"D_R04 mean {arrays['D_R04'].mean():.6f}", flush=True)
+
+
+def slots(check=False):
+    for N in SLOT_NS:
+        a, b = slot_set(N)
+        nodes = node_counts(a, b)
+        assert np.all(nodes[:2, :2] == 2 * N + 2) and nodes.max() == 2 * N + 2 and nodes[4, 4] == 2 and nodes[3, 3] == 4
+        save_slots(f"emd_slots_n{N}", a, b, check)
+    a, b = hand_made_70()
+    assert np.all(node_counts(a, b) == 142)
+    save_slots("emd_hand70", a, b, check)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
+    if sys.argv[1:2] == ["slots"]:
+        return slots(check="--check" in sys.argv)
     for law, seed0, decides_coverage in (("gluon", 7, True), ("top", 8, False)):
         for seed in range(seed0, seed0 + 20):
             jets = scattered_jets(96, 30, law, seed)
@@ -131,6 +230,7 @@ def main():
         save(f"emd_n{N}", jets[:6], jets[6:], matrix(jets[:6], jets[6:]))
     a, b = hand_made()
     save("emd_hand", a, b, matrix(a, b))
+    slots()
 
 
 if __name__ == "__main__":

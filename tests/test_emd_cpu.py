@@ -11,12 +11,20 @@ from conftest import GOLDEN
 from mpgan_amd import _lib, data, evaluation as ev
 
 GOLDENS = ("emd_n30_gluon", "emd_n30_top", "emd_n150", "emd_n1", "emd_n2", "emd_n31", "emd_n32", "emd_n33", "emd_hand")
+# every node slot and launch shape of the GPU build live (tests/gen_golden_emd.py): also R = 0.4 and the node counts
+SLOT_NS = (31, 32, 60, 61, 63, 64, 69, 70, 86, 87, 124, 125, 160)
+SLOTS = tuple("emd_slots_n%d" % N for N in SLOT_NS) + ("emd_hand70",)
 TOL = 1e-9
 
 
 def golden(name):
     d = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
     return d["a"], d["b"], d["D"]
+
+
+def golden_r04(name):
+    d = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    return d["D_R04"], d["nodes"]
 
 
 def scales(a, b, R=1.0):
@@ -62,7 +70,7 @@ def test_host_solver_matches_linprog_on_a_fresh_sample(N, law, R):
     assert np.array_equal(ev.emds(torch.from_numpy(a), torch.from_numpy(b), R=R).numpy(), got)
 
 
-@pytest.mark.parametrize("name", GOLDENS)
+@pytest.mark.parametrize("name", GOLDENS + SLOTS)
 def test_host_solver_matches_golden(name):
     a, b, D = golden(name)
     got, status, iters = host_emd(a, b)
@@ -73,6 +81,28 @@ def test_host_solver_matches_golden(name):
     check(got, D, scales(a, b))
     # one thread, sixteen threads: the same bits
     assert np.array_equal(host_emd(a, b, threads=1)[0], got)
+    if name in SLOTS:
+        D04, nodes = golden_r04(name)
+        assert np.array_equal(nodes, (a[:, None, :, 2] > 0).sum(2) + (b[None, :, :, 2] > 0).sum(2) + 2)
+        assert nodes.max() == 2 * N + 2                         # a pair that fills every node of the launch
+        got, status, iters = host_emd(a, b, R=0.4)
+        print("R = 0.4 augmentations: mean %.1f max %d" % (iters.mean(), iters.max()))
+        assert np.all(status == 0) and iters.max() < 32 * (N + 1)
+        check(got, D04, scales(a, b, 0.4))
+
+
+@pytest.mark.parametrize("name", ["emd_slots_n63", "emd_slots_n160"])
+def test_scaling_every_pt_by_a_power_of_two_scales_the_distances_exactly(name):
+    """The weights meet only sums, differences, minima and one product with a cost each; the costs and the potentials never
+    see them.  So pT x 2^k gives 2^k times the same bits (no pT here is within 2^10 of the fp32 subnormals)."""
+    a, b, _ = golden(name)
+    pt = np.concatenate([a[..., 2].ravel(), b[..., 2].ravel()])
+    assert pt[pt > 0].min() > 2.0 ** -100 and pt.max() < 2.0 ** 100
+    D, status, iters = host_emd(a, b)
+    for k in (10, -10):
+        f = np.array([1, 1, 2.0 ** k], np.float32)
+        Dk, statusk, itersk = host_emd(a * f, b * f)
+        assert np.array_equal(Dk, D * 2.0 ** k) and np.array_equal(statusk, status) and np.array_equal(itersk, iters)
 
 
 def test_symmetry_self_distance_permutation_and_duplicates():
