@@ -90,6 +90,138 @@ def test_rule_without_a_mask_and_with_one_cotangent_only():
         assert rel(a, b) <= BAR
 
 
+def _ref_agg(c, keeps, alpha):
+    """agg of the case ``c`` of gp_rows_ref with LeakyReLU's own signs: senders weighted by the adjacency and (where there is one) the mask."""
+    import gp_rows_ref as R
+
+    def f(xx, mm, PP):
+        Z3 = R.pre_activations(xx, PP, keeps, torch.float64)[2]
+        E3 = keeps[2] * torch.nn.functional.leaky_relu(Z3, alpha)
+        w = c["adj"].double().unsqueeze(3)
+        return c["s"] * (E3 * (w if mm is None else w * mm.reshape(c["B"], 1, c["N"], 1))).sum(2)
+    return f
+
+
+@pytest.mark.parametrize("what", ["none", "tail", "tail_constant", "k1"])
+def test_rule_with_the_mask_kinds_and_sets_of_the_plan_cases(what):
+    """The CPU statement of the rule against autograd in fp64 on what ``gp_rows_ref.PLAN_CASES`` adds to the case table: no mask,
+    the jet-like mask (its exact zeros take an m_bar and a dPhi/dm; as a constant they take none) and one neighbour per receiver."""
+    import gp_rows_ref as R
+    alpha = R.ALPHA
+    pc = {"none": R.PlanCase(3, 2, 9, 3, "none", 0.5, True, None, False, False, {}),
+          "tail": R.PlanCase(4, 2, 9, 3, "tail", 0.5, False, None, True, False, {}),
+          "tail_constant": R.PlanCase(5, 2, 9, 3, "tail", 0.0, True, None, False, False, {}),
+          "k1": R.PlanCase(6, 2, 9, 3, "frac", 0.5, True, 1, True, False, {})}[what]
+    c = R.make_case(pc)
+    B, N = c["B"], c["N"]
+    assert (c["m"] is None) == (what == "none")
+    if what.startswith("tail"):
+        assert bool((c["m"][:, N - N // 3:] == 0).all()) and bool((c["m"][:, :N - N // 3] > 0).all())
+    if what == "k1":
+        assert bool((c["adj"].sum(2) == 1).all())
+    g = torch.Generator().manual_seed(pc.seed)
+    keeps = [(torch.rand(B, N, N, h, generator=g) >= pc.p).double() / (1 - pc.p) for h in (H1, H2, H3)]
+    st = ops.EdgeRowsSettings(pc.sum_agg, alpha, nbr=None if pc.k is None else c["adj"].double(), k=pc.k or 0, keeps=keeps)
+    got = R.derivatives(lambda xx, mm, PP: ops.EdgeRowsFn.apply(xx, mm, *PP, st), c, pc.mask_grad)
+    ref = R.derivatives(_ref_agg(c, keeps, alpha), c, pc.mask_grad)
+    assert rel(got[0], ref[0]) <= BAR
+    for order, a, b in (("first", got[1], ref[1]), ("second", got[2], ref[2])):
+        assert list(a) == list(b) and ("m" in a) == pc.mask_grad
+        for n in b:
+            assert a[n].shape == b[n].shape and rel(a[n], b[n]) <= BAR, (order, n, rel(a[n], b[n]))
+
+
+def _plan_case_names():
+    import gp_rows_ref as R
+    return R.PLAN_RUNS
+
+
+@pytest.mark.parametrize("name, plan", _plan_case_names(), ids=[f"{n}-{p}" for n, p in _plan_case_names()])
+def test_plan_case_reaches_what_it_is_there_for(name, plan, monkeypatch):
+    """Every ``there_for`` property of a ``gp_rows_ref.PLAN_CASES`` entry, from ``ops.knn_plan`` / ``ops.knn_block_tiles`` as they are
+    (and, where the property is one of the data, from the case's own mask and neighbour sets): after a change of the plan this says
+    which case stopped covering its path.  No launch, no large tensor."""
+    import gp_rows_ref as R
+    pc = R.PLAN_CASES[name]
+    B, N, k = pc.B, pc.N, pc.k or pc.N
+    training_rw = ops.knn_plan(256, N, k, True).RW if "training_rw" in pc.there_for[plan] else None      # (on the chip as it is)
+    if plan == "full_blocks":
+        monkeypatch.setattr(ops, "NUM_CUS", 1)
+    kp = ops.knn_plan(B, N, k, True)
+    RW, NW = kp.RW, (N + 31) // 32
+    wgs = {}      # workgroup of the jet -> its tiles (first edge row, rows)
+    for r0, n in ops.knn_block_tiles(N, k, RW):
+        wgs.setdefault(r0 // (RW * k), []).append((r0, n))
+    wgs = [wgs[i] for i in sorted(wgs)]
+    assert len(wgs) == -(-N // RW) and sum(n for t in wgs for _, n in t) == N * k
+    stage = RW * k * ops.KNN_STAGE_BYTES
+    assert stage <= ops.KNN_LDS_BYTES
+    thr = ops.drop_params(pc.p)[0] if pc.p > 0 else 0
+    assert pc.there_for[plan]
+    for what in pc.there_for[plan]:
+        if what == "tiles_gt4":
+            assert max(len(t) for t in wgs) > 4
+        elif what == "tiles_eq4_short":
+            assert len(wgs[0]) == 4 and wgs[0][-1][1] < 32
+        elif what == "training_rw":
+            assert RW == training_rw
+        elif what == "straddle":
+            assert any(r0 // k != (r0 + n - 1) // k for t in wgs for r0, n in t)
+        elif what == "short_tile":
+            assert any(n < 32 for t in wgs for _, n in t)
+        elif what == "short_workgroup":
+            assert len(wgs) > 1 and N % RW != 0
+        elif what == "receiver_blocks":
+            assert len(wgs) > 1
+        elif what == "one_tile":
+            assert RW == N and all(len(t) == 1 for t in wgs)
+        elif what.startswith("words_"):
+            assert NW == int(what[6:])
+        elif what == "sparse_words":
+            assert k < N and NW > 1
+        elif what == "k_not_dividing_32":
+            assert 32 % k != 0
+        elif what == "k1":
+            assert k == 1
+        elif what == "stage_gt_100k":
+            assert stage > 100 * 1024
+        elif what == "dmask_three_waves":
+            assert N > 128 and pc.mask_grad
+        elif what == "dmask_all_threads":
+            assert N == 192 and pc.mask_grad
+        elif what == "dmask_hits_three_waves":
+            adj = R.make_case(name)["adj"]      # [b, receiver, sender]
+            hit = [adj[:, lo:hi].any(1) for lo, hi in ((0, 64), (64, 128), (128, N))]
+            assert pc.mask_grad and bool((hit[0] & hit[1] & hit[2]).any())
+        elif what == "skipped_tile":
+            m = R.make_case(name)["m"]
+            assert pc.k is None and not pc.mask_grad      # (fully connected: row r of a workgroup has sender r % N; no mu reaches it)
+            assert any(bool((m[b, [(r0 + q) % N for q in range(n)]] == 0).all()) for b in range(B) for t in wgs for r0, n in t[4:])
+        elif what == "byte_drop":      # (edge_drop_mode of csrc/edge_units.h: bit mode at thr = 128 alone)
+            assert thr not in (0, 128)
+        elif what == "bit_drop":
+            assert thr == 128
+        elif what == "no_mask":
+            assert pc.kind == "none" and not pc.mask_grad
+        elif what == "slice_x":
+            assert pc.slice_x
+        else:
+            raise AssertionError(what)
+
+
+def test_the_six_first_cases_are_what_they_were():
+    """``B`` became a field of the case: the six cases of ``CASES`` keep B = 3, their seeds and their draws."""
+    import gp_rows_ref as R
+    assert list(R.CASES) == ["n5_sum", "n33_mean_drop", "n40_sparse_jets_drop", "n40_sparse_jets_skipped", "n9_knn4_drop",
+                             "n30_two_receivers_per_workgroup"]
+    for name in R.CASES:
+        c = R.make_case(name)
+        assert c["B"] == 3 and c["x"].shape[0] == 3 and not c["slice_x"] and c["m"] is not None
+    c = R.make_case("n5_sum")
+    g = torch.Generator().manual_seed(1000)
+    assert torch.equal(c["P"][0], (torch.randn(H1, 6, generator=g, dtype=torch.float64) * 0.5).float().double())
+
+
 def test_third_derivative_and_parameter_gradient_cotangents_raise():
     alpha = 0.2
     P, x, m, keeps, abar, u, mu = _case(9)

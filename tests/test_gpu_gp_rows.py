@@ -1,6 +1,7 @@
 """GPU: the gradient penalty's edge aggregation on the row kernels (``ops.OPTIONS["gp_rows"]``: ``ops.EdgeRowsFn`` /
-``ops.EdgeRowsVJPFn`` over ``mpg_knn_edge_fwd`` / ``_bwd`` / ``_jvp``) -- the op against fp64 under the kernel's own kink decisions, the
---gp D step against the reference's golden and against the existing route, graph replay, and peak memory."""
+``ops.EdgeRowsVJPFn`` over ``mpg_knn_edge_fwd`` / ``_bwd`` / ``_jvp``) -- the op against fp64 under the kernel's own kink decisions (six
+small cases, then every launch plan, word count and N up to 192: ``gp_rows_ref.PLAN_CASES``; what they print is kept in
+profiles/gp_rows_plan_cases.txt), at other cotangent magnitudes, run twice and with another jet beside it, the --gp D step against the reference's golden and against the existing route, graph replay, and peak memory."""
 import itertools
 
 import numpy as np
@@ -40,13 +41,11 @@ def _sign3_bits(sign3):
 _op_cache = {}
 
 
-def _run_op(name):
-    """One case through the op on the GPU and through the gated fp64 statement on the CPU, once per session."""
-    if name in _op_cache:
-        return _op_cache[name]
+def _hip(c):
+    """The case ``c`` through the op on the GPU, from the same device seed and tag every time: ((value, first-order outputs,
+    second-order outputs), the call's ``_RowsState``)."""
     from mpgan_amd import ops
-    c = R.make_case(name)
-    N, F, p = c["N"], c["F"], c["p"]
+    B, N, F, p = c["B"], c["N"], c["F"], c["p"]
     dev = torch.device("cuda:0")
     _reset()
     nbr = None if c["k"] is None else R.adjacency_words(c["adj"]).to(dev)
@@ -54,17 +53,33 @@ def _run_op(name):
     holder = {}
 
     def f(xx, mm, PP):
+        if c["slice_x"]:   # D's own call: the features of a [B, N, F + 1] tensor without its last column, a view of row stride F + 1
+            xx = torch.cat((xx, xx.new_ones(B, N, 1)), 2)[..., :F]
+            assert not xx.is_contiguous() and xx.stride(1) == F + 1
         agg = ops.EdgeRowsFn.apply(xx, mm, *PP, st)
         holder["st"] = agg.grad_fn.st
         return agg
     g = {k: (v.float().to(dev) if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in c.items()}
     g["P"] = [t.float().to(dev) for t in c["P"]]
     got = R.derivatives(f, g, c["mask_grad"])
-    s = holder["st"]
+    torch.cuda.synchronize()
+    assert holder["st"].kp.RW == ops.knn_plan(B, N, c["k"] or N, True).RW
+    return got, holder["st"]
+
+
+def _run_op(name, plan="planned"):
+    """One case through the op on the GPU and through the gated fp64 statement on the CPU, once per session and launch plan (the
+    caller has patched ``ops.NUM_CUS`` for "full_blocks")."""
+    if (name, plan) in _op_cache:
+        return _op_cache[name, plan]
+    from mpgan_amd import ops
+    c = R.make_case(name)
+    B, N, p = c["B"], c["N"], c["p"]
+    got, s = _hip(c)
     thr, dscale = ops.drop_params(p) if p > 0 else (0, 1.0)
-    keeps = [torch.ones(R.B, N, N, h, dtype=torch.float64) for h in (R.H1, R.H2, R.H3)]
+    keeps = [torch.ones(B, N, N, h, dtype=torch.float64) for h in (R.H1, R.H2, R.H3)]
     if thr:
-        keeps = [ops.dropout_mask(R.B * N * N, h, s.tag + t, thr).double().cpu().reshape(R.B, N, N, h) * dscale
+        keeps = [ops.dropout_mask(B * N * N, h, s.tag + t, thr).double().cpu().reshape(B, N, N, h) * dscale
                  for h, t in zip((R.H1, R.H2, R.H3), (ops.TAG_E0, ops.TAG_E1, ops.TAG_E2))]
     torch.cuda.synchronize()
     adj = c["adj"]
@@ -76,8 +91,25 @@ def _run_op(name):
     where = R.live_kept(c, keeps)
     flips = sum(int((((z <= 0) != n) & w).sum()) for z, n, w in zip(z64, neg, where))
     total = sum(int(w.sum()) for w in where)
-    _op_cache[name] = dict(case=c, got=got, ref=ref, flips=flips, total=total, fp32_flips=R.fp32_flips(c, keeps))
-    return _op_cache[name]
+    _op_cache[name, plan] = dict(case=c, got=got, ref=ref, flips=flips, total=total, fp32_flips=R.fp32_flips(c, keeps), RW=s.kp.RW)
+    return _op_cache[name, plan]
+
+
+def _second_errs(second, rsecond):
+    return {"dPhi/d" + k: summary_err(k, second[k], summarize(k, rsecond[k])) for k in rsecond}
+
+
+def _check_against_fp64(r, what):
+    (v, first, second), (rv, rfirst, rsecond) = r["got"], r["ref"]
+    errs = {"agg": summary_err("agg", v, summarize("agg", rv))}
+    errs.update({"d" + k: summary_err(k, first[k], summarize(k, rfirst[k])) for k in rfirst})
+    errs.update(_second_errs(second, rsecond))
+    print(what, {k: f"{e:.2e}" for k, e in errs.items()}, "flips", r["flips"], "of", r["total"], "fp32 flips", r["fp32_flips"])
+    for k in rsecond:
+        assert bool(torch.isfinite(second[k]).all()), k
+    assert max(errs.values()) < BAR, errs
+    assert r["flips"] <= FLIP_SHARE * r["total"], (r["flips"], r["total"])
+    assert r["fp32_flips"] == 0, "the case's seed: torch fp32 on the CPU flips a sign against fp64"
 
 
 @pytest.mark.parametrize("name", list(R.CASES))
@@ -85,17 +117,85 @@ def test_op_against_fp64_under_the_kernels_own_gates(name):
     """Value, first-order outputs and every second-order output of ``EdgeRowsFn`` against the fp64 restatement evaluated with the gates
     the kernels took (read back from the parked E1 / E2 / sign3 and the call's keep masks).  Where the mask takes a gradient its
     exact zeros still have an m_bar and a dPhi/dm -- whole jets of them here --; where it takes none their tiles are skipped."""
-    r = _run_op(name)
-    (v, first, second), (rv, rfirst, rsecond) = r["got"], r["ref"]
-    errs = {"agg": summary_err("agg", v, summarize("agg", rv))}
-    errs.update({"d" + k: summary_err(k, first[k], summarize(k, rfirst[k])) for k in rfirst})
-    errs.update({"dPhi/d" + k: summary_err(k, second[k], summarize(k, rsecond[k])) for k in rsecond})
-    print(name, {k: f"{e:.2e}" for k, e in errs.items()}, "flips", r["flips"], "of", r["total"], "fp32 flips", r["fp32_flips"])
-    for k in rsecond:
+    _check_against_fp64(_run_op(name), name)
+
+
+@pytest.mark.parametrize("name, plan", R.PLAN_RUNS, ids=[f"{n}-{p}" for n, p in R.PLAN_RUNS])
+def test_op_against_fp64_at_every_plan_word_count_and_n_to_192(name, plan, monkeypatch):
+    """The same check, bars included, on ``gp_rows_ref.PLAN_CASES``: the launch shapes the six cases above never take -- more than
+    four tiles per workgroup, the training batch's RW, N = 150 and 192, sparse sets over several words, byte-mode dropout, no mask, x
+    as a strided view.  tests/test_gp_rows_cpu.py asserts from the plan that each case reaches what it is there for."""
+    from mpgan_amd import ops
+    pc = R.PLAN_CASES[name]
+    k = pc.k or pc.N
+    if plan == "full_blocks":
+        monkeypatch.setattr(ops, "NUM_CUS", 1)
+        assert ops.knn_plan(pc.B, pc.N, k, True).RW == max(1, min(pc.N, ops.KNN_WG_ROWS // k))
+    r = _run_op(name, plan)
+    assert r["RW"] == ops.knn_plan(pc.B, pc.N, k, True).RW
+    _check_against_fp64(r, f"{name} {plan} RW {r['RW']}")
+
+
+@pytest.mark.parametrize("exp", [-30, 12])
+@pytest.mark.parametrize("name", ["n33_mean_drop", "n9_knn4_drop"])
+def test_second_order_outputs_at_other_cotangent_magnitudes(name, exp):
+    """``u`` and ``mu`` times 2^exp (a cotangent has no fixed scale: the tangent rows are split hi + lo in a power-of-two unit of
+    their own row).  The first-order outputs do not depend on them and come out bit-identical; Phi is linear in them and the gates
+    are those of the unscaled run, so the fp64 reference is the unscaled one times 2^exp, exactly, and every second-order output meets
+    the same relative bar against it."""
+    base = _run_op(name)
+    c = dict(base["case"])
+    c["u"], c["mu"] = c["u"] * 2.0 ** exp, c["mu"] * 2.0 ** exp
+    assert torch.equal(c["u"].float().double(), c["u"]) and torch.equal(c["mu"].float().double(), c["mu"])   # (fp32-representable)
+    (v, first, second), _ = _hip(c)
+    assert torch.equal(v, base["got"][0])
+    for k, t in base["got"][1].items():
+        assert torch.equal(first[k], t), k
+    errs = _second_errs(second, {k: t * 2.0 ** exp for k, t in base["ref"][2].items()})
+    print(name, "2^%d" % exp, {k: f"{e:.2e}" for k, e in errs.items()})
+    for k in second:
         assert bool(torch.isfinite(second[k]).all()), k
     assert max(errs.values()) < BAR, errs
-    assert r["flips"] <= FLIP_SHARE * r["total"], (r["flips"], r["total"])
-    assert r["fp32_flips"] == 0, "the case's seed: torch fp32 on the CPU flips a sign against fp64"
+
+
+def _all_outputs(got):
+    v, first, second = got
+    return {"agg": v, **{"d" + k: t for k, t in first.items()}, **{"dPhi/d" + k: t for k, t in second.items()}}
+
+
+@pytest.mark.parametrize("name", ["n30_training_plan", "n150_knn20"])
+def test_op_repeats_itself_bit_for_bit(name, monkeypatch):
+    """Two runs from the same seeds and tags under the full-blocks plan: every sum is taken in a fixed order, without atomics."""
+    from mpgan_amd import ops
+    monkeypatch.setattr(ops, "NUM_CUS", 1)
+    c = R.make_case(name)
+    one, two = _all_outputs(_hip(c)[0]), _all_outputs(_hip(c)[0])
+    for k in one:
+        assert torch.equal(one[k], two[k]), k
+
+
+PER_NODE = ("agg", "dx", "dm", "dPhi/dabar", "dPhi/dx", "dPhi/dm")   # (parameter gradients are sums over the jets)
+
+
+@pytest.mark.parametrize("name, plan", [("n150_knn20", "full_blocks"), ("n150_fc", "planned")])
+def test_a_jets_rows_are_unmoved_by_its_neighbour_in_the_launch(name, plan, monkeypatch):
+    """B = 2, then jet 0's x, m, a_bar, u and mu redrawn (with x its neighbour sets) and jet 1 untouched: jet 1's per-node outputs
+    of both orders are bit-identical, jet 0's are not.  HIP against HIP: no reference takes part."""
+    from mpgan_amd import ops
+    if plan == "full_blocks":
+        monkeypatch.setattr(ops, "NUM_CUS", 1)
+    c1, other = R.make_case(name, B=2), R.make_case(name, seed=R.case_fields(name)[0] + 1, B=2)
+    c2 = dict(c1)
+    for key in ("x", "m", "abar", "u", "mu", "adj"):
+        c2[key] = torch.cat((other[key][:1], c1[key][1:]))
+        assert torch.equal(c2[key][1], c1[key][1])
+    assert not torch.equal(c2["x"][0], c1["x"][0])
+    (got1, st1), (got2, st2) = _hip(c1), _hip(c2)
+    assert st1.kp.RW == st2.kp.RW == ops.knn_plan(2, c1["N"], c1["k"] or c1["N"], True).RW
+    one, two = _all_outputs(got1), _all_outputs(got2)
+    for k in PER_NODE:
+        assert torch.equal(one[k][1], two[k][1]), k
+        assert not torch.equal(one[k][0], two[k][0]), k
 
 
 def _gp_step(loss, g, gp_rows):
