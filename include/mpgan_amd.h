@@ -1072,6 +1072,40 @@ int mpg_spectral_norm_bwd(const MpgSpectralBwdJob* jobs, int njobs, void* stream
 int mpg_spectral_norm_host(const MpgSpectralJob* jobs, int njobs, int power_iterations);
 int mpg_spectral_norm_bwd_host(const MpgSpectralBwdJob* jobs, int njobs);
 
+/* ---- set-pooling baselines: the last per-particle layer and the pooling over a jet's particles in one launch ----------------------
+ * mpg_point_pool_fwd replaces  torch.max(sfc(x).reshape(-1, num_hits, C), 1)[0]  of rGAND (ext_models/ext_models.py:70-71) and
+ * pointfc's last layer with  torch.cat((torch.max(x, dim=1)[0], torch.mean(x, dim=1)), dim=1)  of PointNetMixD
+ * (ext_models/ext_models.py:203-206).  For jet b < B, particle n < N, channel c < C:
+ *     z = sum_k x[(b N + n) ldx + k] W[c ldw + k] + bias[c]        (bias NULL = 0),      y = act ? LeakyReLU_alpha(z) : z
+ *     mode bit 0:  pooled[b ld_pooled + c] = max_n y;   argmax[b C + c] (int32, where non-NULL) = the lowest n that attains it
+ *     mode bit 1:  pooled[b ld_pooled + (mode & 1 ? C : 0) + c] = (sum_n y) / N          (torch.cat((max, mean), 1)'s order)
+ *     neg (where non-NULL): bit (c & 31) of word neg[(b N + n) ceil(C / 32) + (c >> 5)] is set where !(z > 0) -- the slope
+ *     torch's leaky_relu_backward takes; bits of columns >= C are clear.
+ * With argmax and neg NULL neither is written.  The [B N, C] activation is never written: it lives in MFMA accumulators (particles
+ * as rows, channels as columns: the pooling is an in-lane reduction).  Products as every forward product: fp16 hi / lo operands,
+ * three terms, fp32 accumulate, no operand scales (mpg_gemm's f16 range); the bias is added in fp32.  Reductions run in a fixed order
+ * (csrc/point_pool.hip): a jet's results depend neither on B nor on the grid nor on the run.  Nothing is read beyond K columns of a
+ * row of x or W.
+ * mpg_point_pool_bwd expands gpooled = dL/dpooled [B, ld_gpooled] into the pre-activation's gradient (element-wise, no reduction):
+ *     dz[(b N + n) ld_dz + c] = slope (gmax[b,c] [n == argmax[b,c]] + gmean[b,c] / N),   slope = act ? (bit ? alpha : 1) : 1
+ * from which dx = dz W, dW = dz^T x and db = colsum dz are ordinary mpg_gemm launches.  It reads argmax (mode bit 0) and neg (act).
+ * Limits: B >= 1, 1 <= N <= MPG_POINT_POOL_MAX_N, 1 <= K <= MPG_POINT_POOL_MAX_K (fwd), 1 <= C <= MPG_POINT_POOL_MAX_C; unit column
+ * stride, ldx, ldw >= K, ld_pooled, ld_gpooled >= the pooled width, ld_dz >= C; 0 <= alpha <= 1; f16 = 1 (the bf16 form is not built).
+ * Errors, before the first HIP call: -1 a size outside the limits, -3 mode not in {1, 2, 3}, -4 alpha, -6 f16 != 1, -2 a NULL
+ * x / W / pooled (fwd), gpooled / dz / needed argmax / needed neg (bwd), -5 a stride below its row. */
+#define MPG_POINT_POOL_MAX_N 160
+#define MPG_POINT_POOL_MAX_K 256
+#define MPG_POINT_POOL_MAX_C 1024
+typedef struct MpgPointPool {
+    const float* x; int ldx; const float* W; int ldw; const float* bias;
+    int B, N, K, C;
+    int act; float alpha; int mode, f16;
+    float* pooled; int ld_pooled; int* argmax; unsigned int* neg;
+    const float* gpooled; int ld_gpooled; float* dz; int ld_dz;
+} MpgPointPool;
+int mpg_point_pool_fwd(const MpgPointPool* p, void* stream);
+int mpg_point_pool_bwd(const MpgPointPool* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

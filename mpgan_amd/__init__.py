@@ -10,6 +10,7 @@ from . import _lib, ops  # noqa: F401
 from . import data, checkpoint, gen, evaluation  # noqa: F401
 from . import mpgan  # noqa: F401
 from . import gapt  # noqa: F401
+from . import ext_models  # noqa: F401  (the paper's baselines: rGANG, rGAND, PointNetMixD)
 from .mpgan import LinearNet, MPLayer, MPNet, MPGenerator, MPDiscriminator  # noqa: F401
 from .gapt import MAB, SAB, PMA, ISAB, GAPT_G, GAPT_D  # noqa: F401
 

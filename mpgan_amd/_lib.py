@@ -266,6 +266,19 @@ class MpgSpectralBwdJob(C.Structure):
     ]
 
 
+class MpgPointPool(C.Structure):
+    _fields_ = [
+        ("x", _fp), ("ldx", C.c_int), ("W", _fp), ("ldw", C.c_int), ("bias", _fp),
+        ("B", C.c_int), ("N", C.c_int), ("K", C.c_int), ("C", C.c_int),
+        ("act", C.c_int), ("alpha", C.c_float), ("mode", C.c_int), ("f16", C.c_int),
+        ("pooled", _fp), ("ld_pooled", C.c_int), ("argmax", _fp), ("neg", _fp),
+        ("gpooled", _fp), ("ld_gpooled", C.c_int), ("dz", _fp), ("ld_dz", C.c_int),
+    ]
+
+
+POINT_POOL_MAX_N, POINT_POOL_MAX_K, POINT_POOL_MAX_C = 160, 256, 1024   # MPG_POINT_POOL_MAX_* of include/mpgan_amd.h
+
+
 class MpgEma(C.Structure):
     _fields_ = [("ema", _fp), ("state", _fp), ("beta", C.c_float), ("start", C.c_int), ("warmup", C.c_int)]
 
@@ -388,6 +401,8 @@ SIGNATURES = {
     "mpg_spectral_norm_bwd": (C.c_int, [C.POINTER(MpgSpectralBwdJob), C.c_int, C.c_void_p]),
     "mpg_spectral_norm_host": (C.c_int, [C.POINTER(MpgSpectralJob), C.c_int, C.c_int]),
     "mpg_spectral_norm_bwd_host": (C.c_int, [C.POINTER(MpgSpectralBwdJob), C.c_int]),
+    "mpg_point_pool_fwd": (C.c_int, [C.POINTER(MpgPointPool), C.c_void_p]),
+    "mpg_point_pool_bwd": (C.c_int, [C.POINTER(MpgPointPool), C.c_void_p]),
 }
 
 

@@ -1,0 +1,168 @@
+"""rGANG, rGAND and PointNetMixD (rkansal47/MPGAN ``ext_models/ext_models.py:14-72``, ``:160-207``).
+
+Both discriminators have one shape: a small per-particle network over the B * N rows, a max (and mean) over each jet's particles,
+a small network over the B pooled rows.  Routes of a call:
+
+  CUDA tensors      every Linear on ``ops.FusedLinearFn`` (mpg_gemm); the LAST point layer together with the pooling on
+                    ``ops.point_pool`` (mpg_point_pool_fwd / _bwd: the widest activation of the net, [B N, 512] / [B N, 1024],
+                    is never written) where ``ops.point_pool_route`` says yes, else ``FusedLinearFn`` followed by torch.max /
+                    torch.mean (``ops.OPTIONS["point_pool"]`` off -- MPG_POINT_POOL=0 -- or a shape beyond the kernel's limits);
+  ... inside ``ops.double_backward_route`` (the gradient penalty; the published baselines were trained with loss "w", gp 10)
+                    every Linear as ``ops.MatMulFn`` + bias, LeakyReLU and the pooling ATen's own: twice differentiable;
+  CPU tensors       of any float dtype: plain ``torch.nn.functional`` formulas (the modules can be checked without a GPU).
+
+``args`` is any object with the reference's attribute names (``latent_dim``, ``rgang_fc``, ``rgand_sfc``, ``rgand_fc``,
+``pointnetd_pointfc``, ``pointnetd_fc``, ``num_hits``, ``node_feat_size``, ``leaky_relu_alpha``, ``mask``).
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F
+from torch import Tensor, nn
+
+from .. import ops
+
+
+def _w2(layer: nn.Module) -> Tensor:
+    """The [out, in] weight of a Linear or of a Conv1d of kernel size 1 ([out, in, 1]: a view, no copy)."""
+    w = layer.weight
+    return w if w.dim() == 2 else w.squeeze(-1)
+
+
+def _linear(x: Tensor, layer: nn.Module, act: bool, alpha: float) -> Tensor:
+    """One Linear (-> LeakyReLU) on the rows of ``x`` by the route of the module docstring."""
+    W, b = _w2(layer), layer.bias
+    if not x.is_cuda:
+        y = F.linear(x, W, b)
+        return F.leaky_relu(y, alpha) if act else y
+    if ops.double_backward_on(x.device):
+        y = ops.MatMulFn.apply(x, W, "nt")
+        if b is not None:
+            y = y + b
+        return F.leaky_relu(y, alpha) if act else y
+    return ops.FusedLinearFn.apply(x, W, b, act, alpha, 0.0, False, None)
+
+
+def _pool(y: Tensor, B: int, N: int, mode: int) -> Tensor:
+    y = y.reshape(B, N, y.shape[-1])
+    parts = ([torch.max(y, dim=1)[0]] if mode & 1 else []) + ([torch.mean(y, dim=1)] if mode & 2 else [])
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+
+def _layer_and_pool(x: Tensor, layer: nn.Module, B: int, N: int, alpha: float, mode: int) -> Tensor:
+    """LeakyReLU(Linear(x)) on the [B N, K] rows and the pooling over each jet's N rows: ``ops.point_pool`` where its route covers
+    the call, else the layer and the pooling one after the other."""
+    W = _w2(layer)
+    if x.is_cuda and ops.point_pool_route(N, W.shape[1], W.shape[0], ops.double_backward_on(x.device)):
+        return ops.point_pool(x, W, layer.bias, B, N, act=True, alpha=alpha, mode=mode)
+    return _pool(_linear(x, layer, True, alpha), B, N, mode)
+
+
+def _stack(widths, alpha, conv=False, last_act=True) -> nn.Sequential:
+    """Linear (Conv1d of kernel 1) -> LeakyReLU pairs as the reference's nn.Sequential numbers them: layer i at index 2 i."""
+    mods = []
+    for i, (a, b) in enumerate(zip(widths[:-1], widths[1:])):
+        mods.append(nn.Conv1d(a, b, 1) if conv else nn.Linear(a, b))
+        if last_act or i < len(widths) - 2:
+            mods.append(nn.LeakyReLU(negative_slope=alpha))
+    return nn.Sequential(*mods)
+
+
+def _linears(seq: nn.Sequential) -> list:
+    return [m for m in seq if isinstance(m, (nn.Linear, nn.Conv1d))]
+
+
+class rGANG(nn.Module):
+    """FC generator (ext_models.py:14-36): Linear -> LeakyReLU over ``[latent_dim] + rgang_fc``, Linear to
+    ``num_hits * node_feat_size``, Tanh; returns ``[B, num_hits, node_feat_size]``.  Keys ``model.{0,2,4,..}.weight|bias``.
+
+    Deliberate difference, results-neutral: ``args.rgang_fc`` is NOT modified.  The reference ``insert(0, latent_dim)``s into the
+    caller's list (ext_models.py:19) and relies on the caller's ``deepcopy``; this class builds its own width list."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        self.alpha = float(args.leaky_relu_alpha)
+        widths = [args.latent_dim] + list(args.rgang_fc)
+        body = _stack(widths, self.alpha)
+        self.model = nn.Sequential(*body, nn.Linear(widths[-1], args.num_hits * args.node_feat_size), nn.Tanh())
+
+    def forward(self, x: Tensor, labels: Tensor = None, epoch=None) -> Tensor:
+        lins = _linears(self.model)
+        for k, lin in enumerate(lins):
+            x = _linear(x, lin, k < len(lins) - 1, self.alpha)
+        return torch.tanh(x).reshape(-1, self.args.num_hits, self.args.node_feat_size)
+
+
+class rGAND(nn.Module):
+    """rGAN discriminator (ext_models.py:39-72): Conv1d(kernel 1) -> LeakyReLU over ``[node_feat_size] + rgand_sfc`` on every
+    particle, max over a jet's ``num_hits`` particles, Linear -> LeakyReLU over ``rgand_fc``, Linear to 1, Sigmoid (always on, as in
+    the reference); returns ``[B, 1]``.  Keys ``sfc.{2i}.weight`` ([out, in, 1]) ``|bias``, ``fc.{2i}.weight|bias``.
+
+    Deliberate difference, results-neutral: ``args.rgand_sfc`` / ``args.rgand_fc`` are NOT modified (the reference inserts the input
+    widths into them, ext_models.py:44, :53)."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        self.alpha = float(args.leaky_relu_alpha)
+        sfc = [args.node_feat_size] + list(args.rgand_sfc)
+        fc = [sfc[-1]] + list(args.rgand_fc)
+        self.sfc = _stack(sfc, self.alpha, conv=True)
+        self.fc = nn.Sequential(*_stack(fc, self.alpha), nn.Linear(fc[-1], 1), nn.Sigmoid())
+
+    def forward(self, x: Tensor, labels: Tensor = None, epoch=None) -> Tensor:
+        N, Fs = self.args.num_hits, self.args.node_feat_size
+        x = x.reshape(-1, Fs)
+        B = x.shape[0] // N
+        point = _linears(self.sfc)
+        for lin in point[:-1]:
+            x = _linear(x, lin, True, self.alpha)
+        x = _layer_and_pool(x, point[-1], B, N, self.alpha, 1)
+        fc = _linears(self.fc)
+        for k, lin in enumerate(fc):
+            x = _linear(x, lin, k < len(fc) - 1, self.alpha)
+        return torch.sigmoid(x)
+
+
+class PointNetMixD(nn.Module):
+    """PointNet-Mix discriminator (ext_models.py:160-207): Linear -> LeakyReLU over ``[node_feat_size] + pointnetd_pointfc`` on
+    every particle, cat(max, mean) over a jet's particles, Linear -> LeakyReLU over ``pointnetd_fc``, Linear to 1, Sigmoid (always
+    on); returns ``[B, 1]``.  With ``args.mask`` the input is ``[B, num_hits, node_feat_size + 1]`` (last column: mask - 0.5) and
+    masked particles enter as (0, 0, -0.5).  Keys ``pointfc.{2i}.weight|bias``, ``fc.{2i}.weight|bias``.
+
+    Two deliberate differences, both results-neutral:
+      * ``args.pointnetd_pointfc`` / ``args.pointnetd_fc`` are NOT modified (the reference inserts and appends widths,
+        ext_models.py:165-168);
+      * ``forward`` does NOT modify the caller's tensor.  The reference adds 0.5 to ``x[:, :, 2]`` in place and takes it off the
+        masked copy only (ext_models.py:199-202), which leaves the caller's third column shifted by +0.5.  Under graph replay on
+        ``TrainStep``'s static batch that would drift by 0.5 per step."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        self.alpha = float(args.leaky_relu_alpha)
+        point = [args.node_feat_size] + list(args.pointnetd_pointfc)
+        fc = [2 * point[-1]] + list(args.pointnetd_fc) + [1]
+        self.pointfc = _stack(point, self.alpha)
+        self.fc = nn.Sequential(*_stack(fc, self.alpha, last_act=False), nn.Sigmoid())
+        # (0, 0, 0.5): the shift of the third feature around the masking; not a state-dict entry
+        self.register_buffer("_shift", torch.tensor([0.0, 0.0, 0.5]), persistent=False)
+
+    def forward(self, x: Tensor, labels: Tensor = None, epoch=None) -> Tensor:
+        N, Fs = self.args.num_hits, self.args.node_feat_size
+        B = x.size(0)
+        if self.args.mask:
+            # ((x + 0.5 e_2) * mask)[..., :3] - 0.5 e_2 of :199-202, out of place
+            keep = (x[:, :, 3:4] >= 0).to(x.dtype)
+            shift = self._shift.to(x.dtype)
+            x = (x[:, :, :3] + shift) * keep - shift
+        x = x.reshape(B * N, Fs)
+        point = _linears(self.pointfc)
+        for lin in point[:-1]:
+            x = _linear(x, lin, True, self.alpha)
+        x = _layer_and_pool(x, point[-1], B, N, self.alpha, 3)
+        fc = _linears(self.fc)
+        for k, lin in enumerate(fc):
+            x = _linear(x, lin, k < len(fc) - 1, self.alpha)
+        return torch.sigmoid(x)

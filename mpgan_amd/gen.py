@@ -28,26 +28,19 @@ def get_gen_noise_shape(model_args: dict, num_samples: int, num_particles: int, 
         return (num_samples, num_particles + int(bool(model_args.get("mask_learn_sep"))), model_args["latent_node_size"])
     if model == "gapt":
         return (num_samples, num_particles, model_args["embed_dim"])
-    raise NotImplementedError(f"mpgan_amd generates for the mpgan and gapt model families only (got {model!r})")
+    if model == "rgan":
+        return (num_samples, model_args["latent_dim"])
+    raise NotImplementedError(f"mpgan_amd generates for the mpgan, gapt and rgan model families only (got {model!r})")
 
 
 def get_gen_noise(model_args: dict, num_samples: int, num_particles: int, model: str = "mpgan", device=None,
                   noise_std: float = 0.2):
     """Generator input noise ~ N(0, noise_std) in the shape the model family takes (train.py:100-140):
     mpgan ``[n, N (+1 with mask_learn_sep), latent_node_size]`` (``[n, lfc_latent_size]`` with ``lfc``),
-    gapt ``[n, N, embed_dim]``.  Returns ``(noise, None)`` like the reference (second slot: PCGAN point noise)."""
+    gapt ``[n, N, embed_dim]``, rgan ``[n, latent_dim]`` (train.py:130-131).  Returns ``(noise, None)`` like the reference (second slot: PCGAN point noise)."""
     if device is None:
         device = "cuda"
-    if model in ("mpgan", "old_mpgan"):
-        if model_args.get("lfc"):
-            shape = (num_samples, model_args["lfc_latent_size"])
-        else:
-            extra = int(bool(model_args.get("mask_learn_sep")))
-            shape = (num_samples, num_particles + extra, model_args["latent_node_size"])
-    elif model == "gapt":
-        shape = (num_samples, num_particles, model_args["embed_dim"])
-    else:
-        raise NotImplementedError(f"mpgan_amd generates for the mpgan and gapt model families only (got {model!r})")
+    shape = get_gen_noise_shape(model_args, num_samples, num_particles, model)
     return torch.empty(shape, device=device).normal_(0.0, noise_std), None
 
 

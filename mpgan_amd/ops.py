@@ -74,6 +74,10 @@ OPTIONS = {
     # discriminator's pooling + fnd_layer + sigmoid on ``DiscHeadDDFn`` (mpg_disc_head_fwd / _dd).  Off unless asked for:
     # MPG_GP_CHAIN=1, or TrainStep(gp_chain=True).
     "gp_chain": os.environ.get("MPG_GP_CHAIN", "0") not in ("", "0"),
+    # the set-pooling baselines (ext_models.rGAND / PointNetMixD): the last per-particle layer and the max / mean over a jet's
+    # particles as one launch (``PointPoolFn``: mpg_point_pool_fwd / _bwd) for the shapes ``point_pool_route`` covers; False
+    # (MPG_POINT_POOL=0) = ``FusedLinearFn`` for the layer, then torch.max / torch.mean on its [B N, C] output
+    "point_pool": os.environ.get("MPG_POINT_POOL", "1") != "0",
 }
 NUM_CUS = 256
 # Forward products (they decide LeakyReLU signs) are split as fp16 hi/lo with the operand scales below (~2^-21 per
@@ -2288,6 +2292,96 @@ class double_backward_route:
 
 def double_backward_on(device) -> bool:
     return dev_state(device).double_backward
+
+
+# ---- a per-particle layer and the pooling over a jet's particles in one launch (ext_models.rGAND / PointNetMixD) ------------------
+POINT_POOL_MAX = (_lib.POINT_POOL_MAX_N, _lib.POINT_POOL_MAX_K, _lib.POINT_POOL_MAX_C)
+POINT_POOL_MODES = {1: "max", 2: "mean", 3: "max | mean"}
+
+
+def point_pool_route(N, K, C, double_backward, options=None) -> bool:
+    """Does a layer-and-pool call run on ``PointPoolFn`` (mpg_point_pool_fwd / _bwd)?  With the option on
+    (``OPTIONS["point_pool"]``), outside the double-backward route (the launch pair is once differentiable) and inside the kernel's
+    limits: 1 <= N <= 160 particles, 1 <= K <= 256 input columns, 1 <= C <= 1024 channels.  Host only."""
+    opt = OPTIONS if options is None else options
+    if not opt.get("point_pool") or double_backward:
+        return False
+    return all(1 <= int(v) <= m for v, m in zip((N, K, C), POINT_POOL_MAX))
+
+
+def _point_pool_desc(x2, W, b, B, N, act, alpha, mode):
+    e = _lib.MpgPointPool()
+    e.x, e.ldx, e.W, e.ldw, e.bias = _p(x2), x2.stride(0), _p(W), W.stride(0), _p(b)
+    e.B, e.N, e.K, e.C = B, N, W.shape[1], W.shape[0]
+    e.act, e.alpha, e.mode, e.f16 = int(act), alpha, mode, 1
+    return e
+
+
+class PointPoolFn(torch.autograd.Function):
+    """pooled [B, C or 2 C] = max and / or mean over the N particles of each jet of  act(x W^T + b),  x [B N, K]: the last point
+    layer of rGAND (ext_models.py:70-71) and PointNetMixD (:203-206) with its pooling, one launch; the [B N, C] activation is not
+    written.  ``mode``: 1 max, 2 mean, 3 cat((max, mean), 1).  The backward expands the cotangent into dz [B N, C] (one element-wise
+    launch on the argmax rows and sign bits the forward kept), dx = dz W on ``linear_bwd_data`` and dW, db through ``ParamGrads`` as
+    ``FusedLinearFn``'s.  Nothing is read back: capturable."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, B, N, act, alpha, mode, grad_mode=True):
+        _chk(x, "x"); _chk(W, "W")
+        if mode not in POINT_POOL_MODES:
+            raise ValueError(f"point_pool: mode must be 1 (max), 2 (mean) or 3 (max | mean), got {mode!r}")
+        x2 = x.reshape(B * N, W.shape[1])
+        if x2.stride(1) != 1 or x2.stride(0) < W.shape[1]:
+            x2 = x2.contiguous()
+        Wc = W if W.stride(1) == 1 else W.contiguous()
+        Cn = W.shape[0]
+        dev = x.device
+        # (``needs_input_grad`` says what the inputs ask for whatever the grad mode: under ``no_grad`` nothing is kept)
+        need = grad_mode and any(ctx.needs_input_grad[:3])
+        argmax = torch.empty((B, Cn), device=dev, dtype=torch.int32) if (need and mode & 1) else None
+        neg = torch.empty((B * N, (Cn + 31) // 32), device=dev, dtype=torch.int32) if (need and act) else None
+        pooled = point_pool_launch(x2, Wc, b, B, N, act=act, alpha=alpha, mode=mode, argmax=argmax, neg=neg)
+        ctx.save_for_backward(x2, Wc, argmax, neg)
+        ctx.wparam, ctx.bias = W, b
+        ctx.cfg = (x.shape, B, N, act, alpha, mode)
+        return pooled
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x2, W, argmax, neg = ctx.saved_tensors
+        shp, B, N, act, alpha, mode = ctx.cfg
+        g2 = g if (g.stride(1) == 1 and g.stride(0) >= g.shape[1]) else g.contiguous()
+        dz = point_pool_bwd_launch(g2, argmax, neg, B, N, W.shape[0], act=act, alpha=alpha, mode=mode)
+        pg = ParamGrads(dev_state(g.device), (ctx.wparam, ctx.bias), ctx.needs_input_grad[1:3])
+        pg.gemm(0, 1, dz, x2)
+        dx = linear_bwd_data(dz, W).reshape(shp) if ctx.needs_input_grad[0] else None
+        return dx, *pg.slots(), None, None, None, None, None, None
+
+
+def point_pool(x, W, b, B, N, *, act=True, alpha=0.2, mode=1):
+    """``PointPoolFn``: [B, C] (mode 1: max; 2: mean) or [B, 2 C] (mode 3: max | mean) of act(x W^T + b) over each jet's N rows."""
+    return PointPoolFn.apply(x, W, b, B, N, bool(act), float(alpha), int(mode), torch.is_grad_enabled())
+
+
+def point_pool_launch(x2, W, b, B, N, *, act, alpha, mode, argmax=None, neg=None):
+    """The forward launch on caller-owned by-product buffers (``argmax`` int32 [B, C], ``neg`` int32 [B N, ceil(C / 32)], or None)."""
+    Cn = W.shape[0]
+    pooled = torch.empty((B, Cn * (2 if mode == 3 else 1)), device=x2.device, dtype=torch.float32)
+    e = _point_pool_desc(x2, W, b, B, N, act, alpha, mode)
+    e.pooled, e.ld_pooled, e.argmax, e.neg = _p(pooled), pooled.stride(0), _p(argmax), _p(neg)
+    check(_lib.lib().mpg_point_pool_fwd(C.byref(e), _stream()), "mpg_point_pool_fwd")
+    return pooled
+
+
+def point_pool_bwd_launch(g, argmax, neg, B, N, Cn, *, act, alpha, mode):
+    """The backward launch alone: dz [B N, C] of the cotangent ``g`` of pooled."""
+    dz = torch.empty((B * N, Cn), device=g.device, dtype=torch.float32)
+    e = _lib.MpgPointPool()
+    e.B, e.N, e.K, e.C, e.act, e.alpha, e.mode, e.f16 = B, N, 1, Cn, int(act), alpha, mode, 1
+    e.argmax, e.neg = _p(argmax), _p(neg)
+    e.gpooled, e.ld_gpooled, e.dz, e.ld_dz = _p(g), g.stride(0), _p(dz), dz.stride(0)
+    check(_lib.lib().mpg_point_pool_bwd(C.byref(e), _stream()), "mpg_point_pool_bwd")
+    return dz
 
 
 # ---- LinearNet as one twice-differentiable op (the gradient penalty; OPTIONS["gp_chain"]) ----------------------------------------

@@ -77,7 +77,44 @@ def count_gp(title, gp_chain, B=None):
     print(f"{title}library kernels: {n_ours} launches, {t_ours:.0f} us;  other (ATen) kernels: {n_other} launches, {t_other:.0f} us")
 
 
-if os.environ.get("OPC_GP"):
+def count_baseline(title, which, fused):
+    """OPC_BASELINE=pointnet | rgan: one eager D step (``loss="ls"``) of the default MP generator against a baseline discriminator of
+    ``mpgan_amd.ext_models`` at its default widths, with ``ops.OPTIONS["point_pool"]`` on and off: launches by kind."""
+    import types
+    from mpgan_amd import ext_models
+    torch.manual_seed(0)
+    args = types.SimpleNamespace(rgand_sfc=[64, 128, 256, 256, 512], rgand_fc=[128, 64], pointnetd_pointfc=[64, 128, 1024],
+                                 pointnetd_fc=[512], num_hits=30, node_feat_size=3, leaky_relu_alpha=0.2, mask=True)
+    G, _ = train.default_mpgan(30, device=dev)
+    D = (ext_models.PointNetMixD if which == "pointnet" else ext_models.rGAND)(args).to(dev)
+    if which == "rgan":    # (rGAND takes the three particle features: the mask column stays outside)
+        inner = D.forward
+        D.forward = lambda x, labels=None, epoch=None: inner(x[..., :3])
+    ops.OPTIONS["point_pool"] = fused
+    ts = train.TrainStep(G, D, BATCH, 30, use_graphs=False)
+    data, labels = synthetic_jets(BATCH, 30, seed=1, dist="gluon")
+    ts.set_batch(data.to(dev), labels.to(dev))
+    for _ in range(2): ts._seg_D()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        ts._seg_D()
+        torch.cuda.synchronize()
+    # (device kernels and copies only: the profiler's rows of the operators and autograd nodes that issued them repeat their time)
+    rows = [(e.key, e.count, e.device_time_total) for e in prof.key_averages()
+            if e.device_time_total > 0 and e.key.startswith(("void ", "(anonymous namespace)::", "Memcpy", "Memset"))]
+    ours = lambda k: "at::native" not in k and not k.startswith(("Memcpy", "Memset"))
+    n_ours = sum(c for k, c, _ in rows if ours(k)); n_other = sum(c for k, c, _ in rows if not ours(k))
+    t_ours = sum(t for k, _, t in rows if ours(k)); t_other = sum(t for k, _, t in rows if not ours(k))
+    if os.environ.get("OPC_ROWS"):
+        for k, c, t in sorted(rows, key=lambda r: -r[2]):
+            print(f"{k[:90]:90s} n={c:4d} dev_us={t:9.1f}")
+    print(f"{title}library kernels: {n_ours} launches, {t_ours:.0f} us;  ATen kernels and copies: {n_other} launches, {t_other:.0f} us")
+
+
+if os.environ.get("OPC_BASELINE"):
+    for on in (True, False):
+        count_baseline(f"D step, {os.environ['OPC_BASELINE']} discriminator, point_pool={on}: ", os.environ["OPC_BASELINE"], on)
+elif os.environ.get("OPC_GP"):
     for on in (False, True):
         count_gp(f"penalty D step, gp_chain={on}: ", on)
         count_gp(f"penalty D step, gp_chain={on}: ", on, B=16)
