@@ -1106,6 +1106,51 @@ typedef struct MpgPointPool {
 int mpg_point_pool_fwd(const MpgPointPool* p, void* stream);
 int mpg_point_pool_bwd(const MpgPointPool* p, void* stream);
 
+/* ---- TreeGAN generator: one TreeGCN layer (ext_models/ext_models.py:211-282) in one launch per direction ---------------------------
+ * Layer d of the tree has P parent nodes of width in, each with g children of width out.  level[i] = tree[i], contiguous
+ * [B, nodes[i], width[i]] for i = 0 .. d (nodes[0] = 1 and level[0] the noise in the generator; nodes[d] = P, width[d] = in); the
+ * ancestor of node p on level i is anc_i(p) = p / (P / nodes[i]) -- the reference's repeat / view.  For jet b < B, node p < P,
+ * child c = p g + j (j < g):
+ *     root[b,p]   = sum_{i<=d} level[i][b, anc_i(p), :] W_root[i]^T                      W_root[i]: [out, width[i]] contiguous
+ *     u[b,c,:]    = LeakyReLU_alpha(level[d][b,p,:] W_branch[p])[j in : (j+1) in]        W_branch: [P, in, g in] contiguous
+ *     h[b,c,:]    = u[b,c,:] Wc^T + root[b,p]                                            Wc = W_loop.1 W_loop.0: [out, in] contiguous
+ *     y[(b P g + c) ld_y + o] = act ? LeakyReLU_alpha(h + bias[j out + o]) : h + bias[j out + o]        (bias [g, out]; NULL = 0)
+ *     u[(b P g + c) ld_u + k]  is written where u != NULL (what the backward reads); with u NULL nothing is written for it.
+ * The reference's [rows, in support] activation of W_loop is never formed: Wc comes from a GEMM in front of this launch.  Products:
+ * fp16 hi / lo operands, three terms, fp32 accumulate (mpg_gemm's f16 range).  Sums run in a fixed order (csrc/tree_gcn.hip; no
+ * atomics): a jet's values depend neither on B, nor on its position in the batch, nor on the grid, nor on the run.  Nothing is read
+ * or written beyond the live rows, columns and k.
+ * mpg_tree_gcn_bwd, given dy = dL/dy [(b P g + c) ld_dy + o], the stored y (act only) and u, writes the data side:
+ *     dz[(b P g + c) ld_dz + o] = dy (act ? (y > 0 ? 1 : alpha) : 1)
+ *     S[(b P + p) out + o]      = sum_j dz[b, p g + j, o]                                 (j ascending)
+ *     du[(b P g + c) in + k]    = (dz[b,c,:] Wc)[k] (u[b,c,k] > 0 ? 1 : alpha)            (bf16 hi / lo, three terms)
+ *     dx[(b P + p) in + k]      = du[b,p,:] W_branch[p]^T                                 (dx != NULL; the branch's share of dtree[d])
+ * from which db = colsum dz, M = dz^T u (dW_loop.0 = W_loop.1^T M, dW_loop.1 = M W_loop.0^T), dW_branch[p] = level[d][:,p]^T du[:,p],
+ * S_i = the sums of S over the descendants of a level-i node, dW_root[i] = S_i^T level[i] and dtree[i] += S_i W_root[i] are mpg_gemm
+ * launches.  It reads no level and no W_root.
+ * Limits: B >= 1; 0 <= d < MPG_TREE_GCN_MAX_LEVELS; 1 <= in, out, width[i] <= MPG_TREE_GCN_MAX_WIDTH; g >= 1, g in <=
+ * MPG_TREE_GCN_MAX_BRANCH; P g <= MPG_TREE_GCN_MAX_NODES; P a multiple of every nodes[i]; ld_y, ld_dy, ld_dz >= out, ld_u >= in;
+ * 0 <= alpha <= 1.
+ * Errors, before the first HIP call: -1 a size outside the limits, -3 node counts that do not nest (or width[d] != in, nodes[d] != P),
+ * -4 alpha, -2 a NULL descriptor / level / W_root / W_branch / Wc / y (fwd), W_branch / Wc / u / dy / dz / S / du / needed y (bwd),
+ * -5 a stride below its row. */
+#define MPG_TREE_GCN_MAX_LEVELS 8
+#define MPG_TREE_GCN_MAX_WIDTH 128
+#define MPG_TREE_GCN_MAX_BRANCH 256
+#define MPG_TREE_GCN_MAX_NODES 160
+typedef struct MpgTreeGcn {
+    const float* level[MPG_TREE_GCN_MAX_LEVELS]; const float* W_root[MPG_TREE_GCN_MAX_LEVELS];
+    int width[MPG_TREE_GCN_MAX_LEVELS]; int nodes[MPG_TREE_GCN_MAX_LEVELS];
+    const float* W_branch; const float* Wc; const float* bias;
+    int B, P, g, in, out, d;
+    int act; float alpha;
+    float* y; int ld_y; float* u; int ld_u;
+    const float* dy; int ld_dy; float* dz; int ld_dz;
+    float* S; float* du; float* dx;
+} MpgTreeGcn;
+int mpg_tree_gcn_fwd(const MpgTreeGcn* p, void* stream);
+int mpg_tree_gcn_bwd(const MpgTreeGcn* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

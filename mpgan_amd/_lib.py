@@ -279,6 +279,22 @@ class MpgPointPool(C.Structure):
 POINT_POOL_MAX_N, POINT_POOL_MAX_K, POINT_POOL_MAX_C = 160, 256, 1024   # MPG_POINT_POOL_MAX_* of include/mpgan_amd.h
 
 
+TREE_GCN_MAX_LEVELS, TREE_GCN_MAX_WIDTH, TREE_GCN_MAX_BRANCH, TREE_GCN_MAX_NODES = 8, 128, 256, 160   # MPG_TREE_GCN_MAX_* of include/mpgan_amd.h
+
+
+class MpgTreeGcn(C.Structure):
+    _fields_ = [
+        ("level", _fp * TREE_GCN_MAX_LEVELS), ("W_root", _fp * TREE_GCN_MAX_LEVELS),
+        ("width", C.c_int * TREE_GCN_MAX_LEVELS), ("nodes", C.c_int * TREE_GCN_MAX_LEVELS),
+        ("W_branch", _fp), ("Wc", _fp), ("bias", _fp),
+        ("B", C.c_int), ("P", C.c_int), ("g", C.c_int), ("in", C.c_int), ("out", C.c_int), ("d", C.c_int),
+        ("act", C.c_int), ("alpha", C.c_float),
+        ("y", _fp), ("ld_y", C.c_int), ("u", _fp), ("ld_u", C.c_int),
+        ("dy", _fp), ("ld_dy", C.c_int), ("dz", _fp), ("ld_dz", C.c_int),
+        ("S", _fp), ("du", _fp), ("dx", _fp),
+    ]
+
+
 class MpgEma(C.Structure):
     _fields_ = [("ema", _fp), ("state", _fp), ("beta", C.c_float), ("start", C.c_int), ("warmup", C.c_int)]
 
@@ -403,6 +419,8 @@ SIGNATURES = {
     "mpg_spectral_norm_bwd_host": (C.c_int, [C.POINTER(MpgSpectralBwdJob), C.c_int]),
     "mpg_point_pool_fwd": (C.c_int, [C.POINTER(MpgPointPool), C.c_void_p]),
     "mpg_point_pool_bwd": (C.c_int, [C.POINTER(MpgPointPool), C.c_void_p]),
+    "mpg_tree_gcn_fwd": (C.c_int, [C.POINTER(MpgTreeGcn), C.c_void_p]),
+    "mpg_tree_gcn_bwd": (C.c_int, [C.POINTER(MpgTreeGcn), C.c_void_p]),
 }
 
 

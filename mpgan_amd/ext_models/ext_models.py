@@ -11,10 +11,22 @@ a small network over the B pooled rows.  Routes of a call:
                     every Linear as ``ops.MatMulFn`` + bias, LeakyReLU and the pooling ATen's own: twice differentiable;
   CPU tensors       of any float dtype: plain ``torch.nn.functional`` formulas (the modules can be checked without a GPU).
 
+``TreeGCN`` / ``TreeGANG`` (ext_models.py:211-333), the TreeGAN generator.  Routes of a layer:
+
+  CUDA tensors      ``ops.tree_gcn`` (mpg_tree_gcn_fwd / _bwd: ancestor sum, branch product, W_loop collapsed to one [out, in]
+                    matrix, bias and activation in one launch; the [B nodes, in support] activation, the widest of the net, is
+                    never formed) where ``ops.tree_gcn_route`` says yes, else the un-fused route: the reference's literal layer
+                    with every Linear on ``FusedLinearFn``, torch.matmul for W_branch and ATen's LeakyReLU
+                    (``ops.OPTIONS["tree_gcn"]`` off -- MPG_TREE_GCN=0 --, a shape beyond the kernel's limits, ``upsample`` off);
+  ... inside ``ops.double_backward_route`` the literal layer with every Linear an ``ops.MatMulFn``: twice differentiable;
+  CPU tensors       of any float dtype: the literal layer in plain torch.
+
 ``args`` is any object with the reference's attribute names (``latent_dim``, ``rgang_fc``, ``rgand_sfc``, ``rgand_fc``,
 ``pointnetd_pointfc``, ``pointnetd_fc``, ``num_hits``, ``node_feat_size``, ``leaky_relu_alpha``, ``mask``).
 """
 from __future__ import annotations
+
+import math
 
 import torch
 import torch.nn.functional as F
@@ -166,3 +178,105 @@ class PointNetMixD(nn.Module):
         for k, lin in enumerate(fc):
             x = _linear(x, lin, k < len(fc) - 1, self.alpha)
         return torch.sigmoid(x)
+
+
+def _plain_linear(x: Tensor, W: Tensor) -> Tensor:
+    """x W^T, no bias, by the route of the module docstring."""
+    if not x.is_cuda:
+        return F.linear(x, W)
+    if ops.double_backward_on(x.device):
+        return ops.MatMulFn.apply(x.reshape(-1, x.shape[-1]), W, "nt").reshape(*x.shape[:-1], W.shape[0])
+    return ops.FusedLinearFn.apply(x, W, None, False, 0.2, 0.0, False, None)
+
+
+class TreeGCN(nn.Module):
+    """One tree graph-convolution layer (ext_models.py:211-282): level ``depth`` ([B, node, features[depth]]) to level
+    ``depth + 1`` ([B, node * degrees[depth], features[depth + 1]]).  Keys ``W_root.{i}.weight`` (i <= depth), ``W_branch``
+    ([node, in, degree * in]; with ``upsample``), ``W_loop.{0,1}.weight``, ``bias`` ([1, degree, out]; read only with
+    ``activation``).  Initialisation as the reference: W_branch xavier-uniform with relu gain, bias uniform in +-1 / sqrt(out), the
+    Linears torch's default.
+
+    Deliberate difference, results-neutral: ``forward`` returns a NEW list (the caller's levels and the new one) and does not
+    append to the caller's (the reference does, ext_models.py:280)."""
+
+    def __init__(self, depth, features, degrees, support=10, node=1, upsample=False, activation=True):
+        super().__init__()
+        self.depth, self.node, self.degree = depth, node, degrees[depth]
+        self.in_feature, self.out_feature = features[depth], features[depth + 1]
+        self.upsample, self.activation = upsample, activation
+        self.features, self.degrees = [int(f) for f in features], [int(g) for g in degrees]
+        self.W_root = nn.ModuleList([nn.Linear(features[i], self.out_feature, bias=False) for i in range(depth + 1)])
+        if upsample:
+            self.W_branch = nn.Parameter(torch.empty(node, self.in_feature, self.degree * self.in_feature))
+        self.W_loop = nn.Sequential(nn.Linear(self.in_feature, self.in_feature * support, bias=False),
+                                    nn.Linear(self.in_feature * support, self.out_feature, bias=False))
+        self.bias = nn.Parameter(torch.empty(1, self.degree, self.out_feature))
+        self.leaky_relu = nn.LeakyReLU(negative_slope=0.2)
+        self.init_param()
+
+    def init_param(self):
+        if self.upsample:
+            nn.init.xavier_uniform_(self.W_branch.data, gain=nn.init.calculate_gain("relu"))
+        stdv = 1.0 / math.sqrt(self.out_feature)
+        self.bias.data.uniform_(-stdv, stdv)
+
+    def _literal(self, tree) -> Tensor:
+        """The reference's layer as written (ext_models.py:254-279)."""
+        batch, out = tree[0].size(0), self.out_feature
+        root = 0
+        for i in range(self.depth + 1):
+            repeat_num = self.node // tree[i].size(1)
+            root = root + _plain_linear(tree[i], self.W_root[i].weight).repeat(1, 1, repeat_num).view(batch, -1, out)
+        if self.upsample:
+            branch = F.leaky_relu(tree[-1].unsqueeze(2) @ self.W_branch, 0.2).view(batch, self.node * self.degree, self.in_feature)
+            branch = _plain_linear(_plain_linear(branch, self.W_loop[0].weight), self.W_loop[1].weight)
+            branch = root.repeat(1, 1, self.degree).view(batch, -1, out) + branch
+        else:
+            branch = root + _plain_linear(_plain_linear(tree[-1], self.W_loop[0].weight), self.W_loop[1].weight)
+        if self.activation:
+            branch = F.leaky_relu(branch + self.bias.repeat(1, self.node, 1), 0.2)
+        return branch
+
+    def next_level(self, tree) -> Tensor:
+        """Level ``depth + 1`` from the levels 0 .. depth, by the route of the module docstring."""
+        x = tree[-1]
+        if (x.is_cuda and self.upsample and len(tree) == self.depth + 1
+                and ops.tree_gcn_route(self.features, self.degrees, self.depth, ops.double_backward_on(x.device))):
+            return ops.tree_gcn(tree, [m.weight for m in self.W_root], self.W_branch, self.W_loop[0].weight, self.W_loop[1].weight,
+                                self.bias if self.activation else None, act=self.activation, alpha=0.2)
+        return self._literal(tree)
+
+    def forward(self, tree):
+        tree = list(tree)
+        return tree + [self.next_level(tree)]
+
+
+class TreeGANG(nn.Module):
+    """TreeGAN generator (ext_models.py:286-333): ``len(degrees)`` TreeGCN layers with ``upsample``, the last without bias and
+    activation; ``forward(tree)`` takes the one-element list ``[noise [B, 1, features[0]]]`` and returns
+    ``[B, prod(degrees), features[-1]]``, kept in ``pointcloud`` as well.  Keys ``gcn.TreeGCN_{d}.*``.
+
+    Deliberate difference, results-neutral: ``forward`` does NOT append to the caller's list.  The reference grows the list it is
+    given (ext_models.py:280), so a noise list passed twice would run on a tree of 1 + 2 * len(degrees) levels."""
+
+    def __init__(self, features, degrees, support):
+        super().__init__()
+        self.layer_num = len(features) - 1
+        assert self.layer_num == len(degrees), "Number of features should be one more than number of degrees."
+        self.pointcloud = None
+        vertex_num = 1
+        self.gcn = nn.Sequential()
+        for inx in range(self.layer_num):
+            self.gcn.add_module("TreeGCN_" + str(inx), TreeGCN(inx, features, degrees, support=support, node=vertex_num, upsample=True,
+                                                               activation=inx != self.layer_num - 1))
+            vertex_num = int(vertex_num * degrees[inx])
+
+    def forward(self, tree, labels=None):
+        levels = list(tree)
+        for layer in self.gcn:
+            levels.append(layer.next_level(levels))
+        self.pointcloud = levels[-1]
+        return self.pointcloud
+
+    def getPointcloud(self):
+        return self.pointcloud[-1]

@@ -30,16 +30,21 @@ def get_gen_noise_shape(model_args: dict, num_samples: int, num_particles: int, 
         return (num_samples, num_particles, model_args["embed_dim"])
     if model == "rgan":
         return (num_samples, model_args["latent_dim"])
-    raise NotImplementedError(f"mpgan_amd generates for the mpgan, gapt and rgan model families only (got {model!r})")
+    raise NotImplementedError(f"mpgan_amd has a single noise shape for the mpgan, gapt and rgan model families only (got {model!r}; "
+                              "treegan's noise is a list: get_gen_noise)")
 
 
 def get_gen_noise(model_args: dict, num_samples: int, num_particles: int, model: str = "mpgan", device=None,
                   noise_std: float = 0.2):
     """Generator input noise ~ N(0, noise_std) in the shape the model family takes (train.py:100-140):
     mpgan ``[n, N (+1 with mask_learn_sep), latent_node_size]`` (``[n, lfc_latent_size]`` with ``lfc``),
-    gapt ``[n, N, embed_dim]``, rgan ``[n, latent_dim]`` (train.py:130-131).  Returns ``(noise, None)`` like the reference (second slot: PCGAN point noise)."""
+    gapt ``[n, N, embed_dim]``, rgan ``[n, latent_dim]`` (train.py:130-131), treegan the ONE-ELEMENT LIST
+    ``[[n, 1, treegang_features[0]]]`` that ``ext_models.TreeGANG`` takes (train.py:132-133; a list has no single shape:
+    ``get_gen_noise_shape`` declines it).  Returns ``(noise, None)`` like the reference (second slot: PCGAN point noise)."""
     if device is None:
         device = "cuda"
+    if model == "treegan":
+        return [torch.empty((num_samples, 1, model_args["treegang_features"][0]), device=device).normal_(0.0, noise_std)], None
     shape = get_gen_noise_shape(model_args, num_samples, num_particles, model)
     return torch.empty(shape, device=device).normal_(0.0, noise_std), None
 

@@ -78,6 +78,10 @@ OPTIONS = {
     # particles as one launch (``PointPoolFn``: mpg_point_pool_fwd / _bwd) for the shapes ``point_pool_route`` covers; False
     # (MPG_POINT_POOL=0) = ``FusedLinearFn`` for the layer, then torch.max / torch.mean on its [B N, C] output
     "point_pool": os.environ.get("MPG_POINT_POOL", "1") != "0",
+    # the TreeGAN generator (ext_models.TreeGANG): a TreeGCN layer as one launch per direction (``TreeGcnFn``: mpg_tree_gcn_fwd /
+    # _bwd, W_loop collapsed to one [out, in] matrix) for the shapes ``tree_gcn_route`` covers; False (MPG_TREE_GCN=0) = the
+    # reference's literal layer on ``FusedLinearFn``, torch.matmul and ATen's LeakyReLU, its [rows, in support] activation included
+    "tree_gcn": os.environ.get("MPG_TREE_GCN", "1") != "0",
 }
 NUM_CUS = 256
 # Forward products (they decide LeakyReLU signs) are split as fp16 hi/lo with the operand scales below (~2^-21 per
@@ -2382,6 +2386,166 @@ def point_pool_bwd_launch(g, argmax, neg, B, N, Cn, *, act, alpha, mode):
     e.gpooled, e.ld_gpooled, e.dz, e.ld_dz = _p(g), g.stride(0), _p(dz), dz.stride(0)
     check(_lib.lib().mpg_point_pool_bwd(C.byref(e), _stream()), "mpg_point_pool_bwd")
     return dz
+
+
+# ---- one TreeGCN layer of the TreeGAN generator in one launch per direction (ext_models.TreeGANG) ---------------------------------
+TREE_GCN_MAX = (_lib.TREE_GCN_MAX_LEVELS, _lib.TREE_GCN_MAX_WIDTH, _lib.TREE_GCN_MAX_BRANCH, _lib.TREE_GCN_MAX_NODES)
+
+
+def tree_gcn_route(features, degrees, depth, double_backward, options=None) -> bool:
+    """Does layer ``depth`` of a tree with these ``features`` / ``degrees`` run on ``TreeGcnFn`` (mpg_tree_gcn_fwd / _bwd)?  With
+    the option on (``OPTIONS["tree_gcn"]``), outside the double-backward route (the launch pair is once differentiable) and inside
+    the kernel's limits: depth < 8, every width of levels 0 .. depth + 1 in 1 .. 128, degree * in <= 256, nodes * degree <= 160,
+    every degree >= 1.  Host only."""
+    opt = OPTIONS if options is None else options
+    if not opt.get("tree_gcn") or double_backward:
+        return False
+    levels, width, branch, nodes = TREE_GCN_MAX
+    d = int(depth)
+    if not 0 <= d < levels or len(features) < d + 2 or len(degrees) < d + 1:
+        return False
+    if any(not 1 <= int(f) <= width for f in features[:d + 2]) or any(int(g) < 1 for g in degrees[:d + 1]):
+        return False
+    P = 1
+    for g in degrees[:d]:
+        P *= int(g)
+    return int(degrees[d]) * int(features[d]) <= branch and P * int(degrees[d]) <= nodes
+
+
+def _tree_gcn_desc(shapes, W_branch, Wc, act, alpha):
+    """``shapes``: (nodes, width) of the levels 0 .. d.  The sizes both directions check."""
+    e = _lib.MpgTreeGcn()
+    for i, (nodes, width) in enumerate(shapes):
+        e.nodes[i], e.width[i] = nodes, width
+    e.d, e.P = len(shapes) - 1, shapes[-1][0]
+    setattr(e, "in", Wc.shape[1])
+    e.out, e.g = Wc.shape[0], W_branch.shape[2] // Wc.shape[1]
+    e.W_branch, e.Wc, e.act, e.alpha = _p(W_branch), _p(Wc), int(act), alpha
+    return e
+
+
+def tree_gcn_launch(levels, W_roots, W_branch, Wc, bias, *, act, alpha, y=None, u=None):
+    """The forward launch: tree[d + 1] as rows [B P g, out] from the contiguous levels 0 .. d ([B, P_i, width_i]), the root weights
+    ([out, width_i]), W_branch [P, in, g in], Wc [out, in] and bias [g out] (or None).  ``y`` / ``u``: caller-owned row views (unit
+    column stride) to write into; ``u`` None: u is not written."""
+    B, P = levels[-1].shape[:2]
+    g, out = W_branch.shape[2] // Wc.shape[1], Wc.shape[0]
+    if y is None:
+        y = torch.empty((B * P * g, out), device=Wc.device, dtype=torch.float32)
+    e = _tree_gcn_desc([t.shape[1:] for t in levels], W_branch, Wc, act, alpha)
+    for i, (t, W) in enumerate(zip(levels, W_roots)):
+        e.level[i], e.W_root[i] = t.data_ptr(), W.data_ptr()
+    e.B, e.bias = B, _p(bias)
+    e.y, e.ld_y, e.u, e.ld_u = _p(y), y.stride(0), _p(u), 0 if u is None else u.stride(0)
+    check(_lib.lib().mpg_tree_gcn_fwd(C.byref(e), _stream()), "mpg_tree_gcn_fwd")
+    return y
+
+
+def tree_gcn_bwd_launch(dy, y, u, shapes, W_branch, Wc, *, act, alpha, need_dx=True):
+    """The backward launch alone, on rows: (dz [B P g, out], S [B P, out], du [B P g, in], dx [B P, in] or None) of the cotangent
+    ``dy`` [B P g, out]; ``y`` the stored output (read with ``act``), ``u`` the stored branch activation."""
+    P, inn, out = shapes[-1][0], Wc.shape[1], Wc.shape[0]
+    g = W_branch.shape[2] // inn
+    B = dy.shape[0] // (P * g)
+    new = lambda *s: torch.empty(s, device=dy.device, dtype=torch.float32)
+    dz, S, du, dx = new(B * P * g, out), new(B * P, out), new(B * P * g, inn), (new(B * P, inn) if need_dx else None)
+    e = _tree_gcn_desc(shapes, W_branch, Wc, act, alpha)
+    e.B = B
+    e.y, e.ld_y, e.u, e.ld_u = _p(y), 0 if y is None else y.stride(0), _p(u), u.stride(0)
+    e.dy, e.ld_dy, e.dz, e.ld_dz = _p(dy), dy.stride(0), _p(dz), dz.stride(0)
+    e.S, e.du, e.dx = _p(S), _p(du), _p(dx)
+    check(_lib.lib().mpg_tree_gcn_bwd(C.byref(e), _stream()), "mpg_tree_gcn_bwd")
+    return dz, S, du, dx
+
+
+class TreeGcnFn(torch.autograd.Function):
+    """tree[d + 1] [B, P g, out] of one TreeGCN layer (ext_models.py:254-282, ``upsample``) from the levels 0 .. d: the ancestor
+    sum, the per-node branch product, its LeakyReLU, the loop product, bias and activation in one launch.  W_loop's two bias-free
+    Linears have nothing between them, so their product Wc = W_loop.1 W_loop.0 [out, in] (one ``mpg_gemm`` in front of the launch,
+    every forward: nothing is cached on the host, the op stays right under graph replay with weights updated in place) gives the
+    same forward, and the [rows, in support] activation is never formed; the gradients of both factors follow from M = dz^T u as
+    dW_loop.0 = W_loop.1^T M, dW_loop.1 = M W_loop.0^T.  Saved: the levels, u [B P g, in] and (with ``act``) the output.
+    Arguments behind the flags: W_branch, W_loop.0, W_loop.1, bias ([1, g, out] or None: the last layer's bias is not read and
+    gets no gradient), the d + 1 levels, the d + 1 root weights.  Nothing is read back: capturable."""
+
+    @staticmethod
+    def forward(ctx, act, alpha, grad_mode, W_branch, W0, W1, bias, *rest):
+        n = len(rest) // 2
+        for t in rest + (W_branch, W0, W1):
+            _chk(t, "tree_gcn")
+        levels, roots = [t.contiguous() for t in rest[:n]], [t.contiguous() for t in rest[n:]]
+        Wb, W0c, W1c = W_branch.contiguous(), W0.contiguous(), W1.contiguous()
+        Wc = linear_bwd_data(W1c, W0c)   # [out, in] = W_loop.1 W_loop.0
+        B, P, inn = levels[-1].shape
+        g, out = Wb.shape[2] // inn, W1.shape[0]
+        # (``needs_input_grad`` says what the inputs ask for whatever the grad mode: under ``no_grad`` nothing is kept)
+        need = grad_mode and any(ctx.needs_input_grad)
+        u = torch.empty((B * P * g, inn), device=Wc.device, dtype=torch.float32) if need else None
+        y = tree_gcn_launch(levels, roots, Wb, Wc, None if bias is None else bias.reshape(-1), act=act, alpha=alpha, u=u)
+        ctx.save_for_backward(y if act else None, u, Wc, Wb, W0c, W1c, *levels, *roots)
+        ctx.params = (W_branch, W0, W1, bias) + tuple(rest[n:])   # (only their .grad buffers are touched: ``ParamGrads``)
+        ctx.cfg = (act, alpha, n, g)
+        return y.view(B, P * g, out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        y, u, Wc, Wb, W0, W1, *rest = ctx.saved_tensors
+        act, alpha, n, g = ctx.cfg
+        levels, roots = rest[:n], rest[n:]
+        B, P, inn = levels[-1].shape
+        out = Wc.shape[0]
+        need_lv = ctx.needs_input_grad[7:7 + n]
+        dz, S, du, dx = tree_gcn_bwd_launch(gy.reshape(B * P * g, out).contiguous(), y, u, [t.shape[1:] for t in levels], Wb, Wc,
+                                            act=act, alpha=alpha, need_dx=need_lv[-1])
+        pg = ParamGrads(dev_state(gy.device), ctx.params, ctx.needs_input_grad[3:7] + ctx.needs_input_grad[7 + n:])
+        if pg.wanted[3]:
+            pg.colsum(3, dz.view(B * P, g * out))
+            if pg.out[3] is not None:
+                pg.out[3] = pg.out[3].view(1, g, out)
+        # every GEMM-shaped gradient of the layer is one job: of the collecting batch when queued (``pg.gemm``), else of ONE grouped
+        # launch of this node's own into fresh tensors
+        own = WgradBatch()
+
+        def wgrad(i, dy, x, rows=None):
+            if not pg.wanted[i]:
+                return
+            if pg.batch is not None:
+                return pg.gemm(i, None, dy, x, rows=rows)
+            if pg.out[i] is None:
+                pg.out[i] = torch.empty_like(ctx.params[i], memory_format=torch.contiguous_format)
+            own.add(dy, x, out=pg.out[i] if rows is None else pg.out[i][rows])
+
+        if pg.wanted[1] or pg.wanted[2]:
+            M = linear_bwd_weight(dz, u)                             # [out, in]
+            wgrad(1, W1, M)                                          # W_loop.1^T M
+            if pg.wanted[2]:
+                wgrad(2, M.t().contiguous(), W0.t().contiguous())    # M W_loop.0^T
+        du3 = du.view(B, P, g * inn)
+        for p in range(P if pg.wanted[0] else 0):                    # dW_branch[p] = tree[d][:, p]^T du[:, p]
+            wgrad(0, levels[-1][:, p], du3[:, p], rows=p)
+        # the root terms, from the finest level up: S_i sums S over the descendants of a level-i node (node order)
+        dlev, Si = [None] * n, S.view(B, P, out)
+        for i in reversed(range(n)):
+            Pi = levels[i].shape[1]
+            if Si.shape[1] != Pi:
+                Si = Si.view(B, Pi, Si.shape[1] // Pi, out).sum(2)
+            rows = Si.reshape(B * Pi, out)
+            wgrad(4 + i, rows, levels[i].view(B * Pi, -1))
+            if need_lv[i]:
+                if i == n - 1:
+                    dlev[i] = linear_bwd_data(rows, roots[i], out=dx, accumulate=True).view(B, P, inn)
+                else:
+                    dlev[i] = linear_bwd_data(rows, roots[i]).view(B, Pi, -1)
+        own.flush()
+        slots = pg.slots()
+        return (None, None, None, *slots[:4], *dlev, *slots[4:])
+
+
+def tree_gcn(levels, W_roots, W_branch, W0, W1, bias, *, act=True, alpha=0.2):
+    """``TreeGcnFn``: tree[d + 1] [B, P g, out] from the levels 0 .. d, their root weights, W_branch [P, in, g in], W_loop's two
+    weights and bias [1, g, out] (None: no bias)."""
+    return TreeGcnFn.apply(bool(act), float(alpha), torch.is_grad_enabled(), W_branch, W0, W1, bias, *levels, *W_roots)
 
 
 # ---- LinearNet as one twice-differentiable op (the gradient penalty; OPTIONS["gp_chain"]) ----------------------------------------

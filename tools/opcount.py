@@ -111,7 +111,36 @@ def count_baseline(title, which, fused):
     print(f"{title}library kernels: {n_ours} launches, {t_ours:.0f} us;  ATen kernels and copies: {n_other} launches, {t_other:.0f} us")
 
 
-if os.environ.get("OPC_BASELINE"):
+def count_treegan(title, fused):
+    """OPC_BASELINE=treegan: one eager forward + backward of ``ext_models.TreeGANG`` at its default configuration, B = 256, with
+    ``ops.OPTIONS["tree_gcn"]`` on and off: launches by kind."""
+    from mpgan_amd import ext_models
+    torch.manual_seed(0)
+    G = ext_models.TreeGANG([96, 64, 64, 64, 64, 3], [2, 2, 2, 2, 2], 10).to(dev)
+    noise = torch.randn(BATCH, 1, 96, device=dev) * 0.2
+    up = torch.randn(BATCH, 32, 3, device=dev)
+    ops.OPTIONS["tree_gcn"] = fused
+    go = lambda: (G([noise]) * up).sum().backward()
+    for _ in range(2): go()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        go()
+        torch.cuda.synchronize()
+    rows = [(e.key, e.count, e.device_time_total) for e in prof.key_averages()
+            if e.device_time_total > 0 and e.key.startswith(("void ", "(anonymous namespace)::", "Memcpy", "Memset", "Cijk_"))]
+    ours = lambda k: k.startswith(("void ", "(anonymous namespace)::")) and "at::native" not in k
+    n_ours = sum(c for k, c, _ in rows if ours(k)); n_other = sum(c for k, c, _ in rows if not ours(k))
+    t_ours = sum(t for k, _, t in rows if ours(k)); t_other = sum(t for k, _, t in rows if not ours(k))
+    if os.environ.get("OPC_ROWS"):
+        for k, c, t in sorted(rows, key=lambda r: -r[2]):
+            print(f"{k[:90]:90s} n={c:4d} dev_us={t:9.1f}")
+    print(f"{title}library kernels: {n_ours} launches, {t_ours:.0f} us;  ATen kernels and copies: {n_other} launches, {t_other:.0f} us")
+
+
+if os.environ.get("OPC_BASELINE") == "treegan":
+    for on in (True, False):
+        count_treegan(f"TreeGANG forward + backward, tree_gcn={on}: ", on)
+elif os.environ.get("OPC_BASELINE"):
     for on in (True, False):
         count_baseline(f"D step, {os.environ['OPC_BASELINE']} discriminator, point_pool={on}: ", os.environ["OPC_BASELINE"], on)
 elif os.environ.get("OPC_GP"):
