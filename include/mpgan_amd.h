@@ -1151,6 +1151,37 @@ typedef struct MpgTreeGcn {
 int mpg_tree_gcn_fwd(const MpgTreeGcn* p, void* stream);
 int mpg_tree_gcn_bwd(const MpgTreeGcn* p, void* stream);
 
+/* ---- PCGAN's set encoder: the equivariant stack phi and the max over a jet's particles in one launch ------------------------------
+ * (ext_models/pcgan_model.py:4-42 PermEqui1_max / PermEqui2_max / PermEqui2_mean behind a Tanh or a Softplus, :89-91 / :140-142 the
+ * max.)  For jet b < B with particles n < N: h_0 = x[(b N + n) ldx + k], k < K[0]; for layer l < L, with Gamma[l] [D[l], K[l]] and
+ * Lambda[l] [D[l], K[l]] contiguous (the modules' raw fp32 weights: nothing is cached on the host, a captured launch follows
+ * in-place weight updates), bias[l] [D[l]] (NULL = 0), and m = the column-wise max_n h_l (pool 1, 2) or (sum_n h_l) / N (pool 3;
+ * the sum in ascending n):
+ *     pool 1 (max1):            z = (h_l - m) Gamma[l]^T + bias[l]         (the subtraction in fp32, in front of the operand split)
+ *     pool 2 (max), 3 (mean):   z = h_l Gamma[l]^T + bias[l] - m Lambda[l]^T
+ *     h_{l+1} = act(z):  act 2 tanh, act 3 torch's Softplus (z > 20 ? z : log1p(exp(z)))
+ *     pooled[b ld_pooled + c] = max_n h_L[n, c],  c < D[L-1]
+ * No [B N, D] activation is written: a group of jets (128 / (32 ceil(N / 32)) of them) stays in LDS for the whole stack
+ * (csrc/set_encode.hip).  Products: fp16 hi / lo operands, three terms, fp32 accumulate.  Reductions run in fixed orders without
+ * atomics: a jet's bits depend neither on B, nor on its position in the batch, nor on the grid, nor on the run.  Nothing is read
+ * beyond K[0] columns of a row of x, beyond N rows of a jet or beyond the weights' extents; only pooled[b, c < D[L-1]] is written.
+ * Forward only (the reference runs this encoder frozen, train.py:837-839).
+ * Limits: B >= 1; 1 <= N <= MPG_SET_ENC_MAX_N (a jet's rows of 256 fp32 columns must fit the CU's LDS beside the other jets' --
+ * 128 rows are 130 KiB of 160); 1 <= L <= MPG_SET_ENC_MAX_LAYERS; 1 <= K[0], D[l] <= MPG_SET_ENC_MAX_D; K[l+1] == D[l].
+ * Errors, before the first HIP call: -1 a size outside the limits or widths that do not chain, -3 pool not in {1, 2, 3} or act not in
+ * {2, 3}, -2 a NULL descriptor / x / pooled / Gamma[l] / (pool 2, 3) Lambda[l], -5 ldx < K[0] or ld_pooled < D[L-1]. */
+#define MPG_SET_ENC_MAX_N 128
+#define MPG_SET_ENC_MAX_D 256
+#define MPG_SET_ENC_MAX_LAYERS 4
+typedef struct MpgSetEncode {
+    const float* x; int ldx;
+    int B, N, L, pool, act;
+    int K[MPG_SET_ENC_MAX_LAYERS]; int D[MPG_SET_ENC_MAX_LAYERS];
+    const float* Gamma[MPG_SET_ENC_MAX_LAYERS]; const float* bias[MPG_SET_ENC_MAX_LAYERS]; const float* Lambda[MPG_SET_ENC_MAX_LAYERS];
+    float* pooled; int ld_pooled;
+} MpgSetEncode;
+int mpg_set_encode_fwd(const MpgSetEncode* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -295,6 +295,19 @@ class MpgTreeGcn(C.Structure):
     ]
 
 
+SET_ENC_MAX_N, SET_ENC_MAX_D, SET_ENC_MAX_LAYERS = 128, 256, 4   # MPG_SET_ENC_MAX_* of include/mpgan_amd.h
+
+
+class MpgSetEncode(C.Structure):
+    _fields_ = [
+        ("x", _fp), ("ldx", C.c_int),
+        ("B", C.c_int), ("N", C.c_int), ("L", C.c_int), ("pool", C.c_int), ("act", C.c_int),
+        ("K", C.c_int * SET_ENC_MAX_LAYERS), ("D", C.c_int * SET_ENC_MAX_LAYERS),
+        ("Gamma", _fp * SET_ENC_MAX_LAYERS), ("bias", _fp * SET_ENC_MAX_LAYERS), ("Lambda", _fp * SET_ENC_MAX_LAYERS),
+        ("pooled", _fp), ("ld_pooled", C.c_int),
+    ]
+
+
 class MpgEma(C.Structure):
     _fields_ = [("ema", _fp), ("state", _fp), ("beta", C.c_float), ("start", C.c_int), ("warmup", C.c_int)]
 
@@ -421,6 +434,7 @@ SIGNATURES = {
     "mpg_point_pool_bwd": (C.c_int, [C.POINTER(MpgPointPool), C.c_void_p]),
     "mpg_tree_gcn_fwd": (C.c_int, [C.POINTER(MpgTreeGcn), C.c_void_p]),
     "mpg_tree_gcn_bwd": (C.c_int, [C.POINTER(MpgTreeGcn), C.c_void_p]),
+    "mpg_set_encode_fwd": (C.c_int, [C.POINTER(MpgSetEncode), C.c_void_p]),
 }
 
 

@@ -31,7 +31,7 @@ def get_gen_noise_shape(model_args: dict, num_samples: int, num_particles: int, 
     if model == "rgan":
         return (num_samples, model_args["latent_dim"])
     raise NotImplementedError(f"mpgan_amd has a single noise shape for the mpgan, gapt and rgan model families only (got {model!r}; "
-                              "treegan's noise is a list: get_gen_noise)")
+                              "treegan's noise is a list and pcgan has two noises: get_gen_noise)")
 
 
 def get_gen_noise(model_args: dict, num_samples: int, num_particles: int, model: str = "mpgan", device=None,
@@ -40,9 +40,16 @@ def get_gen_noise(model_args: dict, num_samples: int, num_particles: int, model:
     mpgan ``[n, N (+1 with mask_learn_sep), latent_node_size]`` (``[n, lfc_latent_size]`` with ``lfc``),
     gapt ``[n, N, embed_dim]``, rgan ``[n, latent_dim]`` (train.py:130-131), treegan the ONE-ELEMENT LIST
     ``[[n, 1, treegang_features[0]]]`` that ``ext_models.TreeGANG`` takes (train.py:132-133; a list has no single shape:
-    ``get_gen_noise_shape`` declines it).  Returns ``(noise, None)`` like the reference (second slot: PCGAN point noise)."""
+    ``get_gen_noise_shape`` declines it), pcgan ``[n, pcgan_latent_dim]`` for ``ext_models.latent_G`` (train.py:134-139).
+    Returns ``(noise, point_noise)`` like the reference: the second slot is None except for pcgan with
+    ``model_args["sample_points"]``, where it is the decoder's per-particle noise ``[n, N, pcgan_z2_dim]`` ~ N(0, 1)."""
     if device is None:
         device = "cuda"
+    if model == "pcgan":
+        noise = torch.empty((num_samples, model_args["pcgan_latent_dim"]), device=device).normal_(0.0, noise_std)
+        if not model_args["sample_points"]:
+            return noise, None
+        return noise, torch.empty((num_samples, num_particles, model_args["pcgan_z2_dim"]), device=device).normal_(0.0, 1.0)
     if model == "treegan":
         return [torch.empty((num_samples, 1, model_args["treegang_features"][0]), device=device).normal_(0.0, noise_std)], None
     shape = get_gen_noise_shape(model_args, num_samples, num_particles, model)
@@ -51,16 +58,24 @@ def get_gen_noise(model_args: dict, num_samples: int, num_particles: int, model:
 
 def gen(model_args: dict, G: torch.nn.Module, num_samples: int, num_particles: int, model: str = "mpgan",
         noise: Tensor = None, labels: Tensor = None, noise_std: float = 0.2, **extra_args) -> Tensor:
-    """``num_samples`` jets in one go (train.py:143-215): ``G(noise, labels)``, then the optional manual pT mask."""
+    """``num_samples`` jets in one go (train.py:143-215): ``G(noise, labels)``, then the optional manual pT mask.  pcgan with
+    ``model_args["sample_points"]``: the latent rows go through the decoder ``model_args["G_pc"]`` with per-particle noise
+    (train.py:212-213); with a caller's ``noise`` that is ``extra_args["point_noise"]`` where given, else drawn here (the
+    reference leaves it undefined there: a NameError)."""
     device = next(G.parameters()).device
     if labels is not None:
         assert labels.shape[0] == num_samples, "number of labels doesn't match num_samples"
         labels = labels.to(device)
+    point_noise = extra_args.get("point_noise")
     if noise is None:
-        noise, _ = get_gen_noise(model_args, num_samples, num_particles, model, device, noise_std)
+        noise, point_noise = get_gen_noise(model_args, num_samples, num_particles, model, device, noise_std)
+    elif model == "pcgan" and model_args["sample_points"] and point_noise is None:
+        _, point_noise = get_gen_noise(model_args, num_samples, num_particles, model, device, noise_std)
     gen_data = G(noise, labels)
     if extra_args.get("mask_manual"):
         gen_data = mask_manual(model_args, gen_data, extra_args["pt_cutoff"])
+    if model == "pcgan" and model_args["sample_points"]:
+        gen_data = model_args["G_pc"](gen_data.unsqueeze(1), point_noise)
     logging.debug(gen_data[0, :10])
     return gen_data
 

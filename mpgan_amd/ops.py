@@ -82,6 +82,11 @@ OPTIONS = {
     # _bwd, W_loop collapsed to one [out, in] matrix) for the shapes ``tree_gcn_route`` covers; False (MPG_TREE_GCN=0) = the
     # reference's literal layer on ``FusedLinearFn``, torch.matmul and ATen's LeakyReLU, its [rows, in support] activation included
     "tree_gcn": os.environ.get("MPG_TREE_GCN", "1") != "0",
+    # PCGAN's set encoder (ext_models.G_inv_Tanh / G_inv): the equivariant stack ``phi`` and the max over a jet's particles as one
+    # forward-only launch (``set_encode_launch``: mpg_set_encode_fwd, the [B N, d_dim] activations stay in LDS) where
+    # ``set_encode_route`` says yes; False (MPG_SET_ENCODE=0) = layer by layer on ``FusedLinearFn`` and ATen's max / mean / tanh /
+    # softplus, which is also the differentiable route
+    "set_encode": os.environ.get("MPG_SET_ENCODE", "1") != "0",
 }
 NUM_CUS = 256
 # Forward products (they decide LeakyReLU signs) are split as fp16 hi/lo with the operand scales below (~2^-21 per
@@ -2546,6 +2551,57 @@ def tree_gcn(levels, W_roots, W_branch, W0, W1, bias, *, act=True, alpha=0.2):
     """``TreeGcnFn``: tree[d + 1] [B, P g, out] from the levels 0 .. d, their root weights, W_branch [P, in, g in], W_loop's two
     weights and bias [1, g, out] (None: no bias)."""
     return TreeGcnFn.apply(bool(act), float(alpha), torch.is_grad_enabled(), W_branch, W0, W1, bias, *levels, *W_roots)
+
+
+# ---- PCGAN's set encoder: equivariant stack and max over particles in one forward-only launch (ext_models.G_inv_Tanh / G_inv) ------
+SET_ENC_MAX = (_lib.SET_ENC_MAX_N, _lib.SET_ENC_MAX_D, _lib.SET_ENC_MAX_LAYERS)
+SET_ENC_POOLS = {"max1": 1, "max": 2, "mean": 3}      # PermEqui1_max, PermEqui2_max, PermEqui2_mean
+SET_ENC_ACTS = {"tanh": 2, "softplus": 3}
+
+
+def set_encode_route(N, widths, pool, act, needs_grad, double_backward, options=None) -> bool:
+    """Does the stack ``phi`` with the max behind it run on ``set_encode_launch`` (mpg_set_encode_fwd)?  ``widths`` = [K_0, D_0, ..,
+    D_{L-1}]; ``pool`` in 1 .. 3 (or a name of ``SET_ENC_POOLS``), ``act`` in 2, 3 (or a name of ``SET_ENC_ACTS``).  With the
+    option on (``OPTIONS["set_encode"]``), when nothing in the call needs a gradient (``needs_grad``: grad mode is on and the input
+    or a parameter of the stack requires grad -- the launch is forward only, the reference runs this encoder frozen), outside the
+    double-backward route, and inside the kernel's limits: 1 <= N <= 128, 1 <= L <= 4, every width in 1 .. 256.  Host only."""
+    opt = OPTIONS if options is None else options
+    if not opt.get("set_encode") or needs_grad or double_backward:
+        return False
+    max_n, max_d, max_l = SET_ENC_MAX
+    if SET_ENC_POOLS.get(pool, pool) not in (1, 2, 3) or SET_ENC_ACTS.get(act, act) not in (2, 3):
+        return False
+    return 1 <= int(N) <= max_n and 2 <= len(widths) <= max_l + 1 and all(1 <= int(w) <= max_d for w in widths)
+
+
+def set_encode_launch(x, gammas, biases, lambdas, *, pool, act, pooled=None):
+    """The launch: pooled [B, D_{L-1}] from ``x`` [B, N, K_0] (unit column stride, rows ``x.stride(1)`` apart, jets N rows apart),
+    the layers' ``gammas`` [D_l, K_l], ``biases`` [D_l] (entries may be None) and, for pools 2 and 3, ``lambdas`` [D_l, K_l] -- the
+    parameters themselves where they are contiguous.  ``pooled``: a caller-owned [B, >= D] row view to write into."""
+    _chk(x, "x")
+    B, N, K0 = x.shape
+    if x.stride(2) != 1 or x.stride(1) < K0 or x.stride(0) != N * x.stride(1):
+        x = x.contiguous()
+    pool, act = SET_ENC_POOLS.get(pool, pool), SET_ENC_ACTS.get(act, act)
+    L = len(gammas)
+    if L > SET_ENC_MAX[2]:
+        raise ValueError(f"set_encode: at most {SET_ENC_MAX[2]} layers, got {L}")
+    if pooled is None:
+        pooled = torch.empty((B, gammas[-1].shape[0]), device=x.device, dtype=torch.float32)
+    e = _lib.MpgSetEncode()
+    e.x, e.ldx, e.B, e.N, e.L, e.pool, e.act = _p(x), x.stride(1), B, N, L, pool, act
+    keep = []      # (contiguous copies live until the launch is enqueued; the stream orders their release)
+    for l in range(L):
+        G = gammas[l]
+        _chk(G, "Gamma")
+        e.K[l], e.D[l] = G.shape[1], G.shape[0]
+        ws = [G, biases[l], lambdas[l] if pool != 1 else None]
+        ws = [None if w is None else (w if w.is_contiguous() else w.contiguous()) for w in ws]
+        keep.append(ws)
+        e.Gamma[l], e.bias[l], e.Lambda[l] = (None if w is None else w.data_ptr() for w in ws)
+    e.pooled, e.ld_pooled = _p(pooled), pooled.stride(0)
+    check(_lib.lib().mpg_set_encode_fwd(C.byref(e), _stream()), "mpg_set_encode_fwd")
+    return pooled
 
 
 # ---- LinearNet as one twice-differentiable op (the gradient penalty; OPTIONS["gp_chain"]) ----------------------------------------
