@@ -1182,6 +1182,48 @@ typedef struct MpgSetEncode {
 } MpgSetEncode;
 int mpg_set_encode_fwd(const MpgSetEncode* p, void* stream);
 
+/* ---- GraphCNN-GAN generator: one edge-conditioned convolution (PyG's NNConv, aggr = "mean", root_weight, bias; ----------------------
+ * ext_models/ext_models.py:75-157) on a k-nearest-neighbour graph, without a weight matrix per edge.
+ * x is [B N, Cin] with row stride ld_x; nbr the [B N][ceil(N / 32)] words of mpg_knn_sets (bit j of row (b, i) set <=> node j of
+ * jet b is a neighbour of receiver i; bits beyond N are ignored); nn_weight [Cin Cout, Cin], nn_bias [Cin Cout], root [Cin, Cout],
+ * bias [Cout] are the module's raw contiguous fp32 parameters (PyG 1.x layouts: nothing is repacked or cached on the host, a
+ * captured launch follows in-place weight updates).  With N(i) the set bits of row i in ascending j, n_i their number:
+ *     P_i[c,d] = (1 / n_i) sum_{j in N(i)} x_j[c] (x_j[d] - x_i[d])        m_i[c] = (1 / n_i) sum_{j in N(i)} x_j[c]
+ *     y[(b N + i) ld_y + o] = sum_{c,d} P_i[c,d] nn_weight[(c Cout + o) Cin + d] + sum_c m_i[c] nn_bias[c Cout + o]
+ *                             + sum_c x_i[c] root[c Cout + o] + bias[o]
+ * which equals mean_j x_j ((nn_weight (x_j - x_i) + nn_bias).view(Cin, Cout)) + x_i root + bias.  A row without a set bit has
+ * P = m = 0 (a zero message).  The differences are taken in fp32 in front of every product and of the operand split; the product
+ * with [W3 ; Bn ; root] takes fp16 hi / lo operands, three terms, fp32 accumulate (mpg_gemm's f16 range, for |P| as for x).
+ *     pm[(b N + i) Cin (Cin + 1) + c Cin + d] = P_i[c,d],  pm[.. + Cin Cin + c] = m_i[c]   where pm != NULL (fwd), else not written.
+ * mpg_nnconv_bwd, given dy = dL/dy [(b N + i) ld_dy + o] and the parked pm, writes into the workspace g [B N, Cin (Cin + 1)]
+ *     G_i[c,d] = sum_o dy_i[o] nn_weight[(c Cout + o) Cin + d]   and   dm_i[c] = sum_o dy_i[o] nn_bias[c Cout + o]   (behind G_i)
+ * and from them, in a second launch behind the first,
+ *     dx[(b N + j) ld_dx + c] = sum_o dy_j[o] root[c Cout + o] - sum_c' G_j[c',c] m_j[c']
+ *                               + sum_{i : j in N(i)} (1 / n_i) (dm_i[c] + sum_d G_i[c,d] (x_j[d] - x_i[d]) + sum_c' x_j[c'] G_i[c',c])
+ * in fp32 (the listing receivers i ascending).  The parameter gradients are GEMMs of pm, x and dy: d nn_weight[c Cout + o, d] =
+ * sum_i P_i[c,d] dy_i[o], d nn_bias[c Cout + o] = sum_i m_i[c] dy_i[o], d root = x^T dy, d bias = colsum dy.  The neighbour
+ * sets carry no gradient.  Every sum runs in a fixed order without atomics (csrc/nnconv.hip): a jet's values depend neither on
+ * B, nor on its position in the batch, nor on the run.  Nothing is read or written beyond the live rows and columns.
+ * Limits: 1 <= B <= MPG_NNCONV_MAX_B; 1 <= N <= MPG_NNCONV_MAX_N; 1 <= Cin, Cout <= MPG_NNCONV_MAX_C.
+ * Errors, before the first HIP call: -1 a size outside the limits, -2 a NULL descriptor / x / nbr / parameter / y (fwd) / pm, dy,
+ * g, dx (bwd), -5 a stride below its row. */
+#define MPG_NNCONV_MAX_N 160
+#define MPG_NNCONV_MAX_C 64
+#define MPG_NNCONV_MAX_B (1 << 20)
+typedef struct MpgNNConv {
+    const float* x; int ld_x;
+    const unsigned int* nbr;
+    const float* nn_weight; const float* nn_bias; const float* root; const float* bias;
+    int B, N, Cin, Cout;
+    float* y; int ld_y;
+    float* pm;
+    const float* dy; int ld_dy;
+    float* g;
+    float* dx; int ld_dx;
+} MpgNNConv;
+int mpg_nnconv_fwd(const MpgNNConv* p, void* stream);
+int mpg_nnconv_bwd(const MpgNNConv* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -308,6 +308,23 @@ class MpgSetEncode(C.Structure):
     ]
 
 
+NNCONV_MAX_N, NNCONV_MAX_C, NNCONV_MAX_B = 160, 64, 1 << 20   # MPG_NNCONV_MAX_* of include/mpgan_amd.h
+
+
+class MpgNNConv(C.Structure):
+    _fields_ = [
+        ("x", _fp), ("ld_x", C.c_int),
+        ("nbr", _fp),
+        ("nn_weight", _fp), ("nn_bias", _fp), ("root", _fp), ("bias", _fp),
+        ("B", C.c_int), ("N", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
+        ("y", _fp), ("ld_y", C.c_int),
+        ("pm", _fp),
+        ("dy", _fp), ("ld_dy", C.c_int),
+        ("g", _fp),
+        ("dx", _fp), ("ld_dx", C.c_int),
+    ]
+
+
 class MpgEma(C.Structure):
     _fields_ = [("ema", _fp), ("state", _fp), ("beta", C.c_float), ("start", C.c_int), ("warmup", C.c_int)]
 
@@ -435,6 +452,8 @@ SIGNATURES = {
     "mpg_tree_gcn_fwd": (C.c_int, [C.POINTER(MpgTreeGcn), C.c_void_p]),
     "mpg_tree_gcn_bwd": (C.c_int, [C.POINTER(MpgTreeGcn), C.c_void_p]),
     "mpg_set_encode_fwd": (C.c_int, [C.POINTER(MpgSetEncode), C.c_void_p]),
+    "mpg_nnconv_fwd": (C.c_int, [C.POINTER(MpgNNConv), C.c_void_p]),
+    "mpg_nnconv_bwd": (C.c_int, [C.POINTER(MpgNNConv), C.c_void_p]),
 }
 
 

@@ -21,6 +21,17 @@ a small network over the B pooled rows.  Routes of a call:
   ... inside ``ops.double_backward_route`` the literal layer with every Linear an ``ops.MatMulFn``: twice differentiable;
   CPU tensors       of any float dtype: the literal layer in plain torch.
 
+``NNConv`` / ``GraphBatchNorm`` / ``GraphCNNGANG`` (ext_models.py:75-157), the GraphCNN-GAN generator, without PyG or
+torch_cluster.  The k-nearest-neighbour graph is ``ops.knn_sets`` (bit words; Euclidean distance over all features of the layer's
+input, self excluded unless ``loop``, ties in index order).  Routes of a convolution:
+
+  CUDA tensors      ``ops.nnconv``: ``ops.NNConvFn`` (mpg_nnconv_fwd / _bwd, the factorised form: no weight matrix per edge) where
+                    ``ops.nnconv_route`` says yes, else the literal layer (``ops.nnconv_literal``: gather, per-edge weights on
+                    ``FusedLinearFn``, torch.bmm, mean; ``ops.OPTIONS["nnconv"]`` off -- MPG_NNCONV=0 -- or beyond the limits);
+                    batch norm on ``ops.BatchNormFn`` / ``ops.batchnorm_eval``;
+  ... inside ``ops.double_backward_route`` the literal layer with every Linear an ``ops.MatMulFn`` and ATen's batch norm;
+  CPU tensors       of any float dtype: the literal layer and the graph in plain torch.
+
 ``args`` is any object with the reference's attribute names (``latent_dim``, ``rgang_fc``, ``rgand_sfc``, ``rgand_fc``,
 ``pointnetd_pointfc``, ``pointnetd_fc``, ``num_hits``, ``node_feat_size``, ``leaky_relu_alpha``, ``mask``).
 """
@@ -280,3 +291,116 @@ class TreeGANG(nn.Module):
 
     def getPointcloud(self):
         return self.pointcloud[-1]
+
+
+def knn_adjacency(x: Tensor, k: int, loop: bool) -> Tensor:
+    """``torch_cluster.knn_graph`` per jet as a 0 / 1 adjacency [B, N, N] (receiver, sender) in plain torch: the senders of node i
+    are the ``k`` nearest nodes of its jet in Euclidean distance over all features, self excluded unless ``loop``, equal distances
+    in index order (a stable sort); with fewer than ``k`` candidates, all of them."""
+    B, N, _ = x.shape
+    d = (x.unsqueeze(1) - x.unsqueeze(2)).pow(2).sum(-1)              # [B, i, j]
+    order = torch.sort(d, dim=2, stable=True).indices
+    first = 0 if loop else 1
+    adj = torch.zeros(B, N, N, dtype=x.dtype, device=x.device)
+    return adj.scatter_(2, order[:, :, first:first + k], 1.0)
+
+
+class NNConv(nn.Module):
+    """PyG 1.x's ``NNConv`` in the one configuration the reference uses (ext_models.py:94-121): ``aggr="mean"``, ``root_weight``,
+    ``bias``, the edge attribute x_j - x_i of a k-nearest-neighbour graph.  Keys ``root`` [in, out], ``bias`` [out] and ``nn.*``
+    (the edge network, a Linear in -> in * out that keeps its own initialisation); ``root`` and ``bias`` are uniform in
+    +-1 / sqrt(in) as PyG's ``reset_parameters`` leaves them.  ``forward(x [B, N, in], graph, k)`` takes the graph as the bit words
+    of ``ops.knn_sets`` (CUDA) or as the adjacency of ``knn_adjacency`` (CPU) and returns the rows [B N, out]."""
+
+    def __init__(self, in_channels, out_channels, nn, aggr="mean", root_weight=True, bias=True, **kwargs):
+        super().__init__()
+        if aggr != "mean":
+            raise NotImplementedError(f"NNConv: aggr={aggr!r} is not built (the reference uses aggr='mean' only)")
+        if not root_weight:
+            raise NotImplementedError("NNConv: root_weight=False is not built (the reference uses root_weight=True only)")
+        if not bias:
+            raise NotImplementedError("NNConv: bias=False is not built (the reference uses bias=True only)")
+        if kwargs:
+            raise NotImplementedError(f"NNConv: {sorted(kwargs)} are not built")
+        self.in_channels, self.out_channels, self.aggr = in_channels, out_channels, aggr
+        self.nn = nn
+        self.root = torch.nn.Parameter(torch.empty(in_channels, out_channels))
+        self.bias = torch.nn.Parameter(torch.empty(out_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.in_channels)
+        self.root.data.uniform_(-bound, bound)
+        self.bias.data.uniform_(-bound, bound)
+
+    def forward(self, x: Tensor, graph: Tensor, k: int) -> Tensor:
+        B, N, _ = x.shape
+        if x.is_cuda:
+            return ops.nnconv(x, graph, self.nn.weight, self.nn.bias, self.root, self.bias, k=k)
+        return ops.nnconv_literal(x, graph, self.nn.weight, self.nn.bias, self.root, self.bias, B, N, k)
+
+
+class GraphBatchNorm(nn.Module):
+    """``torch_geometric.nn.BatchNorm`` over the rows [B N, F]: a wrapper whose ``module`` is an ``nn.BatchNorm1d`` (keys
+    ``module.weight|bias|running_mean|running_var|num_batches_tracked``).  CUDA: ``ops.BatchNormFn`` in training mode, with the
+    running statistics kept as ``nn.BatchNorm1d`` keeps them, ``ops.batchnorm_eval`` in eval mode without a gradient; ATen's
+    batch norm inside ``ops.double_backward_route``, in eval mode with a gradient, and on the CPU."""
+
+    def __init__(self, in_channels, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True):
+        super().__init__()
+        self.module = nn.BatchNorm1d(in_channels, eps, momentum, affine, track_running_stats)
+
+    def forward(self, x: Tensor) -> Tensor:
+        bn = self.module
+        batch_stats = self.training or not bn.track_running_stats
+        if not x.is_cuda or ops.double_backward_on(x.device) or not bn.affine or (
+                not batch_stats and torch.is_grad_enabled() and x.requires_grad):
+            return bn(x)
+        if not batch_stats:
+            return ops.batchnorm_eval(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+        y, mean, var = ops.BatchNormFn.apply(x, bn.weight, bn.bias, bn.eps)
+        if bn.track_running_stats:   # running statistics as nn.BatchNorm1d keeps them (unbiased variance, momentum 0.1)
+            with torch.no_grad():
+                M = x.shape[0]
+                bn.num_batches_tracked += 1
+                mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+                bn.running_mean.mul_(1 - mom).add_(mean, alpha=mom)
+                bn.running_var.mul_(1 - mom).add_(var, alpha=mom * M / max(M - 1, 1))
+        return y
+
+
+class GraphCNNGANG(nn.Module):
+    """GraphCNN-GAN generator (ext_models.py:75-157): Linear ``latent_dim -> num_hits * graphcnng_layers[0]`` and LeakyReLU, then
+    per layer a k-nearest-neighbour graph (``num_knn``) of the CURRENT features, ``NNConv``, batch norm and (but for the last, which
+    ends in ``node_feat_size`` columns) LeakyReLU; Tanh with ``graphcnng_tanh``.  Returns ``[B, num_hits, node_feat_size]``.  Keys
+    ``dense.*``, ``layers.{i}.{root,bias,nn.weight,nn.bias}``, ``edge_weights.{i}.{weight,bias}``, ``bn_layers.{i}.module.*``;
+    ``edge_weights[i]`` IS ``layers[i].nn`` (one module under two names, as in the reference: ``parameters()`` yields it once).
+    ``loop = (num_knn == num_hits)`` as in the reference."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        self.alpha = float(args.leaky_relu_alpha)
+        widths = list(args.graphcnng_layers) + [args.node_feat_size]
+        self.dense = nn.Linear(args.latent_dim, args.num_hits * widths[0])
+        self.layers, self.edge_weights, self.bn_layers = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
+        for a, b in zip(widths[:-1], widths[1:]):
+            self.edge_weights.append(nn.Linear(a, a * b))
+            self.layers.append(NNConv(a, b, self.edge_weights[-1], aggr="mean", root_weight=True, bias=True))
+            self.bn_layers.append(GraphBatchNorm(b))
+
+    def forward(self, x: Tensor, labels: Tensor = None, epoch=None) -> Tensor:
+        N, k = self.args.num_hits, self.args.num_knn
+        loop = k == N
+        x = _linear(x, self.dense, True, self.alpha)
+        B = x.size(0)
+        for i, (conv, bn) in enumerate(zip(self.layers, self.bn_layers)):
+            x3 = x.reshape(B, N, conv.in_channels)
+            with torch.no_grad():
+                graph = ops.knn_sets(x3.detach(), None, k, self_loops=loop) if x.is_cuda else knn_adjacency(x3.detach(), k, loop)
+            x = bn(conv(x3, graph, min(k, N if loop else N - 1)))
+            if i < len(self.layers) - 1:
+                x = F.leaky_relu(x, self.alpha)
+        if self.args.graphcnng_tanh:
+            x = torch.tanh(x)
+        return x.reshape(B, N, self.args.node_feat_size)

@@ -40,7 +40,8 @@ def get_gen_noise(model_args: dict, num_samples: int, num_particles: int, model:
     mpgan ``[n, N (+1 with mask_learn_sep), latent_node_size]`` (``[n, lfc_latent_size]`` with ``lfc``),
     gapt ``[n, N, embed_dim]``, rgan ``[n, latent_dim]`` (train.py:130-131), treegan the ONE-ELEMENT LIST
     ``[[n, 1, treegang_features[0]]]`` that ``ext_models.TreeGANG`` takes (train.py:132-133; a list has no single shape:
-    ``get_gen_noise_shape`` declines it), pcgan ``[n, pcgan_latent_dim]`` for ``ext_models.latent_G`` (train.py:134-139).
+    ``get_gen_noise_shape`` declines it), pcgan ``[n, pcgan_latent_dim]`` for ``ext_models.latent_G`` (train.py:134-139),
+    graphcnngan ``[n, latent_dim]`` for ``ext_models.GraphCNNGANG`` (train.py:130-131; no extra noise).
     Returns ``(noise, point_noise)`` like the reference: the second slot is None except for pcgan with
     ``model_args["sample_points"]``, where it is the decoder's per-particle noise ``[n, N, pcgan_z2_dim]`` ~ N(0, 1)."""
     if device is None:
@@ -52,6 +53,8 @@ def get_gen_noise(model_args: dict, num_samples: int, num_particles: int, model:
         return noise, torch.empty((num_samples, num_particles, model_args["pcgan_z2_dim"]), device=device).normal_(0.0, 1.0)
     if model == "treegan":
         return [torch.empty((num_samples, 1, model_args["treegang_features"][0]), device=device).normal_(0.0, noise_std)], None
+    if model == "graphcnngan":
+        return torch.empty((num_samples, model_args["latent_dim"]), device=device).normal_(0.0, noise_std), None
     shape = get_gen_noise_shape(model_args, num_samples, num_particles, model)
     return torch.empty(shape, device=device).normal_(0.0, noise_std), None
 

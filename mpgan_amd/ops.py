@@ -87,6 +87,11 @@ OPTIONS = {
     # ``set_encode_route`` says yes; False (MPG_SET_ENCODE=0) = layer by layer on ``FusedLinearFn`` and ATen's max / mean / tanh /
     # softplus, which is also the differentiable route
     "set_encode": os.environ.get("MPG_SET_ENCODE", "1") != "0",
+    # the GraphCNN-GAN generator (ext_models.GraphCNNGANG): an NNConv layer (mean aggregation, root weight, bias) as one launch per
+    # direction (``NNConvFn``: mpg_nnconv_fwd / _bwd, the factorised form [P | m | x] [W3 ; Bn ; root]: no weight matrix per edge)
+    # for the shapes ``nnconv_route`` covers; False (MPG_NNCONV=0) = the literal layer: gather, a [B N k, Cin Cout] per-edge weight
+    # tensor from ``FusedLinearFn``, torch.bmm, the mean over the listed neighbours
+    "nnconv": os.environ.get("MPG_NNCONV", "1") != "0",
 }
 NUM_CUS = 256
 # Forward products (they decide LeakyReLU signs) are split as fp16 hi/lo with the operand scales below (~2^-21 per
@@ -2551,6 +2556,164 @@ def tree_gcn(levels, W_roots, W_branch, W0, W1, bias, *, act=True, alpha=0.2):
     """``TreeGcnFn``: tree[d + 1] [B, P g, out] from the levels 0 .. d, their root weights, W_branch [P, in, g in], W_loop's two
     weights and bias [1, g, out] (None: no bias)."""
     return TreeGcnFn.apply(bool(act), float(alpha), torch.is_grad_enabled(), W_branch, W0, W1, bias, *levels, *W_roots)
+
+
+# ---- NNConv (edge-conditioned convolution, mean aggregation) of the GraphCNN-GAN generator in one launch per direction ---------------
+NNCONV_MAX = (_lib.NNCONV_MAX_N, _lib.NNCONV_MAX_C, _lib.NNCONV_MAX_C)
+
+
+def nnconv_route(N, Cin, Cout, double_backward, options=None) -> bool:
+    """Does an NNConv call run on ``NNConvFn`` (mpg_nnconv_fwd / _bwd)?  With the option on (``OPTIONS["nnconv"]``), outside the
+    double-backward route (the launch pair is once differentiable) and inside the kernel's limits: 1 <= N <= 160 nodes per jet,
+    1 <= Cin, Cout <= 64.  Host only."""
+    opt = OPTIONS if options is None else options
+    if not opt.get("nnconv") or double_backward:
+        return False
+    return all(1 <= int(v) <= m for v, m in zip((N, Cin, Cout), NNCONV_MAX))
+
+
+def _nnconv_desc(x2, nbr, nn_weight, nn_bias, root, B, N):
+    e = _lib.MpgNNConv()
+    e.x, e.ld_x, e.nbr = _p(x2), x2.stride(0), C.c_void_p(nbr.data_ptr())
+    e.nn_weight, e.nn_bias, e.root = _p(nn_weight), _p(nn_bias), _p(root)
+    e.B, e.N, e.Cin, e.Cout = B, N, root.shape[0], root.shape[1]
+    return e
+
+
+def nnconv_launch(x2, nbr, nn_weight, nn_bias, root, bias, B, N, *, y=None, pm=None):
+    """The forward launch: y [B N, Cout] from the rows x2 [B N, Cin] (unit column stride), the neighbour words ``nbr`` of
+    ``knn_sets`` ([B N, ceil(N / 32)] int32) and the four contiguous parameters.  ``y``: a caller-owned row view to write into;
+    ``pm``: a contiguous [B N, Cin (Cin + 1)] array that receives [P | m], or None: not written."""
+    Cin, Cout = root.shape
+    if y is None:
+        y = torch.empty((B * N, Cout), device=x2.device, dtype=torch.float32)
+    e = _nnconv_desc(x2, nbr, nn_weight, nn_bias, root, B, N)
+    e.bias, e.y, e.ld_y, e.pm = _p(bias), _p(y), y.stride(0), _p(pm)
+    check(_lib.lib().mpg_nnconv_fwd(C.byref(e), _stream()), "mpg_nnconv_fwd")
+    return y
+
+
+def nnconv_bwd_launch(dy, x2, nbr, pm, nn_weight, nn_bias, root, B, N, *, dx=None, g=None):
+    """The backward launch alone: dx [B N, Cin] (all three shares) of the cotangent rows ``dy`` [B N, Cout] from the parked
+    ``pm``; ``g``: the [B N, Cin (Cin + 1)] workspace that receives [G | dm] (allocated when None).  ``dx``: a caller-owned row
+    view to write into."""
+    Cin = root.shape[0]
+    if dx is None:
+        dx = torch.empty((B * N, Cin), device=dy.device, dtype=torch.float32)
+    if g is None:
+        g = torch.empty((B * N, Cin * (Cin + 1)), device=dy.device, dtype=torch.float32)
+    e = _nnconv_desc(x2, nbr, nn_weight, nn_bias, root, B, N)
+    e.pm, e.dy, e.ld_dy, e.g, e.dx, e.ld_dx = _p(pm), _p(dy), dy.stride(0), _p(g), _p(dx), dx.stride(0)
+    check(_lib.lib().mpg_nnconv_bwd(C.byref(e), _stream()), "mpg_nnconv_bwd")
+    return dx
+
+
+class NNConvFn(torch.autograd.Function):
+    """y [B N, Cout] of PyG's NNConv (aggr "mean", root weight, bias; ext_models.py:94-121) on the neighbour sets ``nbr`` of
+    ``knn_sets``, edge attribute x_j - x_i, in the factorised form of csrc/nnconv.hip: no weight matrix per edge, forward or
+    backward.  With a gradient wanted the forward parks [P | m] [B N, Cin (Cin + 1)]; the backward launch writes dx, and the
+    four parameter gradients are GEMM jobs through ``ParamGrads`` that land in the parameters' own layouts (nn.weight's row block
+    c Cout .. (c + 1) Cout from columns c Cin .. of P: one job per c).  The raw parameters are read by every launch: nothing is
+    cached on the host, the op stays right under graph replay with weights updated in place.  ``nbr`` carries no gradient.
+    Nothing is read back: capturable."""
+
+    @staticmethod
+    def forward(ctx, x, nbr, nn_weight, nn_bias, root, bias, B, N, grad_mode=True):
+        for t in (x, nn_weight, nn_bias, root, bias):
+            _chk(t, "nnconv")
+        Cin, Cout = root.shape
+        x2 = x.reshape(B * N, Cin)
+        if x2.stride(1) != 1 or x2.stride(0) < Cin:
+            x2 = x2.contiguous()
+        Wn, bn, rt, bs = nn_weight.contiguous(), nn_bias.contiguous(), root.contiguous(), bias.contiguous()
+        nbr = nbr.contiguous()
+        # (``needs_input_grad`` says what the inputs ask for whatever the grad mode: under ``no_grad`` nothing is kept)
+        need = grad_mode and any(ctx.needs_input_grad)
+        pm = torch.empty((B * N, Cin * (Cin + 1)), device=x.device, dtype=torch.float32) if need else None
+        y = nnconv_launch(x2, nbr, Wn, bn, rt, bs, B, N, pm=pm)
+        ctx.save_for_backward(x2, nbr, pm, Wn, bn, rt)
+        ctx.params = (nn_weight, nn_bias, root, bias)   # (only their .grad buffers are touched: ``ParamGrads``)
+        ctx.cfg = (x.shape, B, N)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x2, nbr, pm, Wn, bn, rt = ctx.saved_tensors
+        shp, B, N = ctx.cfg
+        Cin, Cout = rt.shape
+        dy = gy if (gy.stride(1) == 1 and gy.stride(0) >= Cout) else gy.contiguous()
+        dx = nnconv_bwd_launch(dy, x2, nbr, pm, Wn, bn, rt, B, N).reshape(shp) if ctx.needs_input_grad[0] else None
+        pg = ParamGrads(dev_state(gy.device), ctx.params, ctx.needs_input_grad[2:6])
+        pg.colsum(3, dy)
+        own = WgradBatch()
+
+        def wgrad(i, a, b, view, rows=None):
+            """``view(target)[rows] = a^T b``: a job of the collecting batch when queued, else of this node's own grouped launch"""
+            if pg.batch is not None:
+                out = view(pg.targets[i])
+                return pg.batch.add(a, b, out=out if rows is None else out[rows], accumulate=True)
+            if pg.out[i] is None:
+                pg.out[i] = torch.empty_like(ctx.params[i], memory_format=torch.contiguous_format)
+            out = view(pg.out[i])
+            own.add(a, b, out=out if rows is None else out[rows])
+
+        if pg.wanted[0]:     # d nn.weight[c Cout + o, d] = sum_i dy_i[o] P_i[c,d]
+            for c in range(Cin):
+                wgrad(0, dy, pm[:, c * Cin:(c + 1) * Cin], lambda t: t.view(Cin, Cout, Cin), rows=c)
+        if pg.wanted[1]:     # d nn.bias[c Cout + o] = sum_i m_i[c] dy_i[o]
+            wgrad(1, pm[:, Cin * Cin:], dy, lambda t: t.view(Cin, Cout))
+        if pg.wanted[2]:     # d root = x^T dy
+            wgrad(2, x2, dy, lambda t: t)
+        own.flush()
+        return (dx, None, *pg.slots(), None, None, None)
+
+
+def _nbr_dense(nbr, B, N):
+    """The neighbour words as a 0 / 1 float adjacency [B, N, N] (receiver, sender) and the rows' counts [B, N]; on the device."""
+    W = nbr.shape[-1]
+    bits = (nbr.view(B, N, W, 1) >> torch.arange(32, device=nbr.device, dtype=torch.int32)) & 1
+    adj = bits.reshape(B, N, W * 32)[:, :, :N].to(torch.float32)
+    return adj, adj.sum(2)
+
+
+def nnconv_literal(x, adj, nn_weight, nn_bias, root, bias, B, N, k, *, double_backward=False):
+    """The un-fused route, PyG's layer as written: gather the ``k`` listed neighbours of every node (``adj`` [B, N, N], 0 / 1; a
+    row with fewer takes part with weight 0 in the slots left over), a weight matrix per edge from the Linear on x_j - x_i, the
+    per-edge product, the mean over the listed neighbours, root and bias.  Every Linear a ``FusedLinearFn`` (``MatMulFn`` with
+    ``double_backward``: twice differentiable), the rest ATen.  CPU tensors: plain torch."""
+    Cin, Cout = root.shape
+    x3 = x.reshape(B, N, Cin)
+    val, idx = adj.topk(k, dim=2)                                     # [B, N, k]: the set bits first
+    cnt = adj.sum(2).clamp(min=1.0)
+    xj = x3.gather(1, idx.reshape(B, N * k, 1).expand(B, N * k, Cin)).reshape(B, N, k, Cin)
+    ea = (xj - x3.unsqueeze(2)).reshape(B * N * k, Cin)
+    if not x.is_cuda:
+        We = torch.nn.functional.linear(ea, nn_weight, nn_bias)
+        own = x3.reshape(B * N, Cin) @ root
+    elif double_backward:
+        We = MatMulFn.apply(ea, nn_weight, "nt") + nn_bias
+        own = MatMulFn.apply(x3.reshape(B * N, Cin), root, "nn")
+    else:
+        We = FusedLinearFn.apply(ea, nn_weight, nn_bias, False, 0.2, 0.0, False, None)
+        own = MatMulFn.apply(x3.reshape(B * N, Cin), root, "nn")
+    msg = torch.bmm(xj.reshape(B * N * k, 1, Cin), We.view(B * N * k, Cin, Cout)).view(B, N, k, Cout)
+    agg = (msg * val.unsqueeze(3).to(msg.dtype)).sum(2) / cnt.unsqueeze(2).to(msg.dtype)
+    return agg.reshape(B * N, Cout) + own + bias
+
+
+def nnconv(x, nbr, nn_weight, nn_bias, root, bias, *, k=None):
+    """NNConv (mean aggregation, root weight, bias) of the rows ``x`` [B, N, Cin] on the neighbour words ``nbr`` [B N, ceil(N / 32)]
+    of ``knn_sets``: [B N, Cout].  ``NNConvFn`` where ``nnconv_route`` says yes, else ``nnconv_literal`` (``k``: the largest
+    number of neighbours a row lists; None: read back from the words)."""
+    B, N, Cin = x.shape
+    dd = double_backward_on(x.device)
+    if nnconv_route(N, Cin, root.shape[1], dd):
+        return NNConvFn.apply(x, nbr, nn_weight, nn_bias, root, bias, B, N, torch.is_grad_enabled())
+    adj, cnt = _nbr_dense(nbr, B, N)
+    if k is None:
+        k = int(cnt.max())
+    return nnconv_literal(x, adj, nn_weight, nn_bias, root, bias, B, N, max(1, min(int(k), N)), double_backward=dd)
 
 
 # ---- PCGAN's set encoder: equivariant stack and max over particles in one forward-only launch (ext_models.G_inv_Tanh / G_inv) ------

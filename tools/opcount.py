@@ -137,9 +137,40 @@ def count_treegan(title, fused):
     print(f"{title}library kernels: {n_ours} launches, {t_ours:.0f} us;  ATen kernels and copies: {n_other} launches, {t_other:.0f} us")
 
 
+def count_graphcnn(title, fused):
+    """OPC_BASELINE=graphcnn: one eager forward + backward of ``ext_models.GraphCNNGANG`` at the published configuration, B = 256,
+    with ``ops.OPTIONS["nnconv"]`` on and off: launches by kind."""
+    import types
+    from mpgan_amd import ext_models
+    torch.manual_seed(0)
+    G = ext_models.GraphCNNGANG(types.SimpleNamespace(latent_dim=128, num_hits=30, graphcnng_layers=[32, 24], node_feat_size=3, num_knn=20,
+                                                      leaky_relu_alpha=0.2, graphcnng_tanh=False, device=dev)).to(dev)
+    noise = torch.randn(BATCH, 128, device=dev) * 0.2
+    up = torch.randn(BATCH, 30, 3, device=dev)
+    ops.OPTIONS["nnconv"] = fused
+    go = lambda: (G(noise) * up).sum().backward()
+    for _ in range(2): go()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        go()
+        torch.cuda.synchronize()
+    rows = [(e.key, e.count, e.device_time_total) for e in prof.key_averages()
+            if e.device_time_total > 0 and e.key.startswith(("void ", "(anonymous namespace)::", "Memcpy", "Memset", "Cijk_"))]
+    ours = lambda k: k.startswith(("void ", "(anonymous namespace)::")) and "at::native" not in k
+    n_ours = sum(c for k, c, _ in rows if ours(k)); n_other = sum(c for k, c, _ in rows if not ours(k))
+    t_ours = sum(t for k, _, t in rows if ours(k)); t_other = sum(t for k, _, t in rows if not ours(k))
+    if os.environ.get("OPC_ROWS"):
+        for k, c, t in sorted(rows, key=lambda r: -r[2]):
+            print(f"{k[:90]:90s} n={c:4d} dev_us={t:9.1f}")
+    print(f"{title}library kernels: {n_ours} launches, {t_ours:.0f} us;  ATen kernels and copies: {n_other} launches, {t_other:.0f} us")
+
+
 if os.environ.get("OPC_BASELINE") == "treegan":
     for on in (True, False):
         count_treegan(f"TreeGANG forward + backward, tree_gcn={on}: ", on)
+elif os.environ.get("OPC_BASELINE") == "graphcnn":
+    for on in (True, False):
+        count_graphcnn(f"GraphCNNGANG forward + backward, nnconv={on}: ", on)
 elif os.environ.get("OPC_BASELINE"):
     for on in (True, False):
         count_baseline(f"D step, {os.environ['OPC_BASELINE']} discriminator, point_pool={on}: ", os.environ["OPC_BASELINE"], on)
